@@ -9,8 +9,16 @@ Metric (BASELINE.json): Mpixel-labels/s per CRF mean-field iter = H*W*L / t(step
 Default workload = the volume the north-star target is quoted on: 2048 x 1536 x 256, d = 5
 bilateral features (SURVEY.md section 8d synthetic recipe).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5|c1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5|c1] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the headline line (`value`, `ms_per_step`, ...).
+`--full` adds everything else the benchmark measures or checks: warm rebuild times and the step on the lattice
+built the other way, per-stage times and the roofline, the mean-field iteration, the backward pass, the regime
+sweep, the Tsukuba-sized extra, the CPU baseline (with its bit-for-bit check against the reference engine) and,
+for N > 1, the run's own correctness check (`check`).
+`--dump-outputs DIR` writes what the last timed step computed (a fixed, seeded sample of its rows plus per-label
+sums over all rows) as .npy files into DIR; the inputs are seeded, so two builds can be compared output for output.
 
 N > 1 shards the image by row bands over the ranks (strong scaling, same total volume); see
 depth-estimation_amd/phl/rowtile.py for the halo exchange over RCCL.  `--workload c5` instead
@@ -189,6 +197,28 @@ def stage_times(torch, lat, src, out, kw, reps):
             acc[name] += e[k].elapsed_time(e[k + 1])
         del v, a
     return {k: v / reps for k, v in acc.items()}
+
+
+DUMP_ROWS = 16384       # rows of the sampled output: 16 MB at L = 256
+
+
+def dump_outputs(torch, path, out, pixel0, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, the filtered volume `out` [pixels, L] (this rank's
+    pixels, the first of them being image pixel `pixel0`), as DIR/*.npy:
+      filter_out_rows.npy      float32 [k, L]  the rows of a fixed, seeded sample of k <= DUMP_ROWS pixels, ascending;
+      filter_out_pixels.npy    float64 [k]     their pixel indices in the image;
+      filter_out_label_sums.npy float64 [L]    the sum of every label's column over ALL of this rank's pixels.
+    With more than one rank every rank writes its own set, file names prefixed rank<r>_."""
+    n, L = out.shape
+    k = min(n, DUMP_ROWS)
+    rows = np.sort(np.random.default_rng(20261016).choice(n, size=k, replace=False))
+    sample = out[torch.from_numpy(rows).to(out.device)].cpu().numpy().astype(np.float32)
+    sums = torch.sum(out, dim=0, dtype=torch.float64).cpu().numpy()
+    prefix = f"rank{rank}_" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, prefix + "filter_out_rows.npy"), sample)
+    np.save(os.path.join(path, prefix + "filter_out_pixels.npy"), (rows + pixel0).astype(np.float64))
+    np.save(os.path.join(path, prefix + "filter_out_label_sums.npy"), sums)
 
 
 def algorithmic_bytes(n, M, L, d):
@@ -461,7 +491,7 @@ def dry_rank(args, rank, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=40, help="number of timed steps (>= 1)")
     # (tools/step_seq.py: from an idle GPU the clocks take ~8 steps to come up; 3 warm-up steps left 1 % on the table)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
@@ -481,12 +511,19 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph (launch-bound sizes)")
     ap.add_argument("--force-rowtile", action="store_true", help="debug: run the row-band driver even with one rank")
     ap.add_argument("--mean-field", dest="mean_field", action="store_true", default=True,
-                    help="also time one full mean-field iteration and its fused compatibility kernel (extra key; default on)")
+                    help="with --full: also time one full mean-field iteration and its fused compatibility kernel (extra key; default on)")
     ap.add_argument("--no-mean-field", dest="mean_field", action="store_false")
     ap.add_argument("--no-small-image", action="store_true", help="skip the Tsukuba-sized extra (key c1_small_image)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (extra keys; see the module docstring); "
+                         "--no-cpu-baseline, --no-regimes, --no-mean-field and --no-small-image leave parts of it out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/*.npy (float32 / float64, well under 64 MB)")
     ap.add_argument("--dry-launch", action="store_true", help="launcher / rendezvous plumbing only, gloo on CPU, no filter")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_worker:
         return cpu_worker(args.cpu_worker)
@@ -556,6 +593,7 @@ def main():
         if world > 1 and not os.environ.get("PHL_ROWTILE_MODE"):
             job.autotune(src, out_rt)
         extra = job.describe()
+        out_step = out_rt
     else:
         ref = torch.from_numpy(feat.reshape(-1, d)).to(device)
         src = synthetic_values(torch, H, W, L, 1000 * rank, device)      # every rank its own volume
@@ -577,16 +615,19 @@ def main():
                 lat_warm.close()
             return best
 
-        build_warm_ms = warm_build(ref_table)
-        build_warm_other_ms = warm_build(not ref_table)
+        extra = {}
+        if args.full:
+            build_warm_ms = warm_build(ref_table)
+            build_warm_other_ms = warm_build(not ref_table)
+            extra = {"tiles": lat.tile_stats(L), "lattice_build_warm_ms": round(build_warm_ms, 2),
+                     ("lattice_build_warm_ms_reference_table" if args.clean_table else "lattice_build_warm_ms_clean_table"):
+                         round(build_warm_other_ms, 2)}
         lat.reserve(L)
         out = torch.empty_like(src)
         kw = dict(exact=args.exact, no_tiles=args.no_tiles)
         step = lambda: lat.filter(src, out=out, **kw)
         M, n_local = lat.M, n_total
-        extra = {"tiles": lat.tile_stats(L), "lattice_build_warm_ms": round(build_warm_ms, 2),
-                 ("lattice_build_warm_ms_reference_table" if args.clean_table else "lattice_build_warm_ms_clean_table"):
-                     round(build_warm_other_ms, 2)}
+        out_step = out
 
     def sync_all():
         torch.cuda.synchronize()
@@ -616,6 +657,43 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     volumes = world if (world > 1 and not rowtiled) else 1     # independent volumes: one per rank
     value = volumes * n_total * L / (dt / args.steps) / 1e6
+    # before anything else reuses the output buffer
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, out_step, job.row0 * W if rowtiled else 0, rank, world)
+
+    if rank == 0:
+        line = {
+            "metric": "Mpixel-labels/s per CRF mean-field iter (splat+blur+slice)",
+            "value": round(value, 1), "unit": "Mpixel-labels/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "strong" if (world > 1 and rowtiled) else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.workload}: {desc}", "H": H, "W": W, "L": L, "d": d, "features": feat_desc,
+                       "sigma_xy": None if tsu else args.sigma_xy, "sigma_c": tsu[0] if tsu else args.sigma_c, "n": n_total, "M": int(M), "M_over_n": round(M / n_local, 4),
+                       "parallelism": ("single GPU" if world == 1 and not rowtiled else
+                                       f"row bands x{world} + RCCL boundary-vertex exchange" if rowtiled else
+                                       f"{world} independent volumes, one per GPU, no collective"),
+                       "launch": "hip graph replay" if (args.graph and not rowtiled) else "eager",
+                       "arithmetic": "reference-exact (bit-identical to the CPU path)" if args.exact else "default (fp32-rounding-equivalent, ~1e-7 rel)",
+                       # "reference": vertices, duplicates included, are the reference's (its hash table files the key in
+                       # flight at every doubling from a stale slot, permutohedral.h:59-62,101-103) -- with --exact the
+                       # output is bit-identical to the reference engine at this size (cpu_baseline.gpu_bit_equal_to_reference
+                       # checks it in a --full run); "clean": one vertex per key.  Row bands are cut out of the whole image's
+                       # reference-table lattice (phl_sub_lattice): "reference" too, checked by `check` in a --full run.
+                       "table": (job.band.table if rowtiled else ("clean" if args.clean_table else "reference"))},
+            "ranks": world, "backend": backend, "devices_visible": ndev,
+            "launched_by": "bench.py launcher" if os.environ.get("PHL_BENCH_LAUNCHED") else ("torchrun" if "TORCHELASTIC_RUN_ID" in os.environ else "direct"),
+            "lattice_build_ms": round(build_ms, 2), "full": bool(args.full),
+        }
+    if not args.full:
+        if rank == 0:
+            line.update(extra)
+            print(json.dumps(line), file=JSON_OUT, flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything beyond the headline figure ---------------------------------------
 
     # the same step on the lattice built the other way (clean <-> reference table): same kernels, a handful of
     # duplicate vertices more or fewer
@@ -748,32 +826,10 @@ def main():
         cpu = cpu_baseline(feat, H, W, L, d)
 
     if rank == 0:
-        line = {
-            "metric": "Mpixel-labels/s per CRF mean-field iter (splat+blur+slice)",
-            "value": round(value, 1), "unit": "Mpixel-labels/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "strong" if (world > 1 and rowtiled) else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.workload}: {desc}", "H": H, "W": W, "L": L, "d": d, "features": feat_desc,
-                       "sigma_xy": None if tsu else args.sigma_xy, "sigma_c": tsu[0] if tsu else args.sigma_c, "n": n_total, "M": int(M), "M_over_n": round(M / n_local, 4),
-                       "parallelism": ("single GPU" if world == 1 and not rowtiled else
-                                       f"row bands x{world} + RCCL boundary-vertex exchange" if rowtiled else
-                                       f"{world} independent volumes, one per GPU, no collective"),
-                       "launch": "hip graph replay" if (args.graph and not rowtiled) else "eager",
-                       "arithmetic": "reference-exact (bit-identical to the CPU path)" if args.exact else "default (fp32-rounding-equivalent, ~1e-7 rel)",
-                       # "reference": vertices, duplicates included, are the reference's (its hash table files the key in
-                       # flight at every doubling from a stale slot, permutohedral.h:59-62,101-103) -- with --exact the
-                       # output is bit-identical to the reference engine at this size (cpu_baseline.gpu_bit_equal_to_reference
-                       # checks it in this run); "clean": one vertex per key.  Row bands are cut out of the whole image's
-                       # reference-table lattice (phl_sub_lattice): "reference" too, checked by `check` in the same run.
-                       "table": (job.band.table if rowtiled else ("clean" if args.clean_table else "reference"))},
-            "ranks": world, "backend": backend, "devices_visible": ndev,
-            "launched_by": "bench.py launcher" if os.environ.get("PHL_BENCH_LAUNCHED") else ("torchrun" if "TORCHELASTIC_RUN_ID" in os.environ else "direct"),
-            "lattice_build_ms": round(build_ms, 2),
-            # the reference rebuilds its lattice in every filter call: the same metric with a (steady-state, warm
-            # scratch) build added to every step -- SURVEY 8d asks for both
-            "value_rebuild_each_iter": round(volumes * n_total * L / ((ms_per_step + extra.get("lattice_build_warm_ms", build_ms)) * 1e-3) / 1e6, 1),
-            "roofline": roofline, "cpu_baseline": cpu,
-        }
+        # the reference rebuilds its lattice in every filter call: the same metric with a (steady-state, warm
+        # scratch) build added to every step -- SURVEY 8d asks for both
+        line["value_rebuild_each_iter"] = round(volumes * n_total * L / ((ms_per_step + extra.get("lattice_build_warm_ms", build_ms)) * 1e-3) / 1e6, 1)
+        line.update(roofline=roofline, cpu_baseline=cpu)
         if mean_field is not None:
             line["mean_field_iteration"] = mean_field
         if backward is not None:

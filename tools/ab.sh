@@ -2,7 +2,7 @@
 # A/B of environment settings with repetitions: tools/ab.sh REPS "ENV=a" "ENV=b" ...   (prints min/median of each stage)
 reps=$1; shift
 for cfg in "$@"; do
-  for i in $(seq $reps); do env $cfg python bench.py --no-cpu-baseline 2>/dev/null; done | python -c "
+  for i in $(seq $reps); do env $cfg python bench.py --full --no-cpu-baseline 2>/dev/null; done | python -c "
 import json,sys,statistics as st
 rows=[json.loads(l) for l in sys.stdin if l.startswith('{')]
 f=lambda k:[r['roofline']['per_stage'][k]['ms'] for r in rows]

@@ -1,4 +1,6 @@
-"""Condense rocprofv3 outputs under gpurun_out/ into the committed summaries under profiles/."""
+"""Condense the rocprofv3 outputs that tools/profile_round.sh wrote under OUTDIR into the committed summaries under profiles/.
+
+usage: python tools/save_profiles.py TAG STATS_DIR EXACT_DIR PMC_PREFIX OUTDIR"""
 import collections
 import csv
 import glob
@@ -10,11 +12,11 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import bench  # noqa: E402  (hot_source_sha)
 
-tag, stats_dir, exact_dir, pmc_prefix = sys.argv[1:5]
+tag, stats_dir, exact_dir, pmc_prefix, run = sys.argv[1:6]
 
 
 def newest(pattern):
-    """gpurun_out/ keeps the files of earlier calls with the same tag: take the latest run's"""
+    """OUTDIR may keep the files of earlier runs with the same tag: take the latest run's"""
     return max(glob.glob(pattern), key=os.path.getmtime)
 
 
@@ -24,7 +26,7 @@ def short(n):
 
 
 def stats(dirn, out):
-    f = newest(f'gpurun_out/{dirn}/*/*kernel_stats.csv')
+    f = newest(f'{run}/{dirn}/*/*kernel_stats.csv')
     rows = list(csv.DictReader(open(f)))
     with open(out, 'w') as fo:
         w = csv.writer(fo)
@@ -40,7 +42,7 @@ for x in stats(exact_dir, f'profiles/{tag}_bench_c3_exact_kernel_stats.csv')[:3]
     print('exact', short(x['Name']), x['Calls'], round(float(x['AverageNs']) / 1e3, 1), 'us')
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for d in ('FETCH_SIZE', 'WRITE_SIZE', 'TCC_HIT_sum'):
-    f = newest(f'gpurun_out/{pmc_prefix}_{d}/*/*counter_collection.csv')
+    f = newest(f'{run}/{pmc_prefix}_{d}/*/*counter_collection.csv')
     for row in csv.DictReader(open(f)):
         n = short(row['Kernel_Name'])
         if n.startswith('k_'):
@@ -60,18 +62,18 @@ json.dump({'note': 'rocprofv3 --pmc, separate passes (FETCH_SIZE | WRITE_SIZE | 
            'kernels': pm}, open(f'profiles/{tag}_pmc_traffic.json', 'w'), indent=1)
 for k, v in pm.items():
     print(k, v['hbm_bytes_per_launch'], v['L2_hit_rate'])
-shutil.copy('gpurun_out/bench_final.log', f'profiles/{tag}_bench_c3.log')
-shutil.copy('gpurun_out/bench_final_prof.log', f'profiles/{tag}_bench_c3_under_rocprof.log')
-open(f'profiles/{tag}_bench_c3_exact.log', 'w').write(''.join(l for l in open('gpurun_out/bench_final_exact.log') if l.startswith('{')))
+shutil.copy(f'{run}/bench_final.log', f'profiles/{tag}_bench_c3.log')
+shutil.copy(f'{run}/bench_final_prof.log', f'profiles/{tag}_bench_c3_under_rocprof.log')
+open(f'profiles/{tag}_bench_c3_exact.log', 'w').write(''.join(l for l in open(f'{run}/bench_final_exact.log') if l.startswith('{')))
 
 # mean-field iteration (k_compat_softmax): kernel stats + HBM traffic of the fused compatibility kernel
 import os
-if glob.glob(f'gpurun_out/prof_{tag}_mf/*/*kernel_stats.csv'):
+if glob.glob(f'{run}/prof_{tag}_mf/*/*kernel_stats.csv'):
     for x in stats(f'prof_{tag}_mf', f'profiles/{tag}_meanfield_kernel_stats.csv')[:4]:
         print('mean-field', short(x['Name']), x['Calls'], round(float(x['AverageNs']) / 1e3, 1), 'us')
     mf = collections.defaultdict(lambda: collections.defaultdict(list))
     for d in ('FETCH_SIZE', 'WRITE_SIZE'):
-        for f in [newest(f'gpurun_out/pmc_{tag}_mf_{d}/*/*counter_collection.csv')]:
+        for f in [newest(f'{run}/pmc_{tag}_mf_{d}/*/*counter_collection.csv')]:
             for row in csv.DictReader(open(f)):
                 n = short(row['Kernel_Name'])
                 if n.startswith('k_compat'):
@@ -84,6 +86,6 @@ if glob.glob(f'gpurun_out/prof_{tag}_mf/*/*kernel_stats.csv'):
                   'hbm_bytes_per_launch': int(fk * 2048 + wk * 1024)}
     json.dump({'note': 'rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes), bench.py c3 mean-field extras; FETCH_SIZE doubled (gfx950)',
                'kernels': out}, open(f'profiles/{tag}_meanfield_pmc_traffic.json', 'w'), indent=1)
-    open(f'profiles/{tag}_bench_c3_mean_field.log', 'w').write(''.join(l for l in open('gpurun_out/bench_final_mf.log') if l.startswith('{')))
-if os.path.exists(f'gpurun_out/regimes_{tag}.json'):
-    shutil.copy(f'gpurun_out/regimes_{tag}.json', f'profiles/{tag}_regimes.json')
+    open(f'profiles/{tag}_bench_c3_mean_field.log', 'w').write(''.join(l for l in open(f'{run}/bench_final_mf.log') if l.startswith('{')))
+if os.path.exists(f'{run}/regimes_{tag}.json'):
+    shutil.copy(f'{run}/regimes_{tag}.json', f'profiles/{tag}_regimes.json')
