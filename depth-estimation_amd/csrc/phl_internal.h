@@ -258,3 +258,10 @@ int phl_launch_slice(const phl_lattice *lat, const float *vert, int vd, float *o
 // generic strided 2-D copy dst[r*drs + c*dcs] = src[r*srs + c*scs], rows x cols
 int phl_launch_copy2d(const float *src, int64_t srs, int64_t scs, float *dst, int64_t drs, int64_t dcs,
                       int64_t rows, int cols, hipStream_t st);
+
+// ---- the fused compatibility + softmax step for 256 < L <= 512 (phl_compat_wide.hip), behind phl_compat_planes_bytes /
+// phl_compat_prepare / phl_compat_softmax_split; arguments are checked there
+size_t phl_compat_wide_planes_bytes(int L);   // 0 unless 256 < L <= 512, L % 4 == 0
+int phl_compat_wide_prepare(const float *mu_t, int L, void *planes, hipStream_t st);
+int phl_compat_wide_softmax(const float *E0, int64_t e_rs, const float *X, int64_t x_rs, const float *mu_t, const void *planes,
+                            float *out, int64_t o_rs, int64_t n, int L, bool logits, hipStream_t st);

@@ -12,6 +12,7 @@
 #include <atomic>
 
 #include "phl_internal.h"
+#include "phl_compat_common.h"
 
 namespace {
 
@@ -235,37 +236,8 @@ __global__ __launch_bounds__(256) void k_stream_copy(const vf4 *__restrict__ src
 // Mu^T[16T+i][16q+4g .. +3] -- 16 contiguous bytes of the TRANSPOSED compatibility matrix, which is what the caller
 // passes (MuT[c][k]).  Both LDS images are [row][32 k] with 128-byte rows whose 16-byte slots are XOR-swizzled (see
 // the feeder).  16 bytes global -> LDS without a register in between (global_load_lds_dwordx4): the LDS address is
-// wave-uniform (M0) plus lane*16, the global address is per lane.
-//
-// The DMA is issued through inline assembly, NOT __builtin_amdgcn_global_load_lds: with the builtin the compiler
-// knows an LDS write is in flight, cannot tell it from the buffer the ds_reads use, and puts `s_waitcnt vmcnt(0)`
-// in front of the first ds_read after every prefetch.  The kernel's own protocol makes that wait unnecessary (a
-// buffer is only read behind the barrier that follows the counted wait for its DMA).
-// Addressing: scalar base (SGPR pair) + 32-bit per-lane byte offset, so that a whole chunk's DMAs share two VGPRs.
-__device__ __forceinline__ void glds16(const float *sbase, unsigned voff, unsigned lds_addr)
-{
-    unsigned keep;                              // m0 is the compiler's: hand it back as found
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_addr));
-}
-__device__ __forceinline__ void dma_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// VALU helpers of the epilogue.  f32 MFMAs and ordinary VALU instructions do NOT overlap on gfx950
-// (tools/mfma_probe.hip: every v_fma slipped between two MFMAs costs its own issue time plus a ~10-cycle bubble,
-// SQ_VALU_MFMA_COEXEC_CYCLES reads 0), so every epilogue instruction is paid for in matrix-pipe time: minima
-// three at a time and without the compiler's NaN canonicalisation (v_max x,x before every v_min), the one
-// cross-lane step as a lane-half swap instead of a ds_bpermute round trip.  (The swap is inline assembly because
-// __builtin_amdgcn_permlane16/32_swap hands back its FIRST result twice in this compiler -- ROCm 7.2, checked with
-// tools/dpp_probe.hip.)
-__device__ __forceinline__ float vmin3(float a, float b, float c)
-{
-    float r;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-// v_permlane32_swap_b32 a, b: the upper 32 lanes of a trade places with the lower 32 lanes of b (checked on the GPU:
-// with a = b = x on entry, a holds x[lane & 31] and b holds x[32 + (lane & 31)] in every lane afterwards)
-#define PHL_HALF_SWAP(a, b) asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b))
+// wave-uniform (M0) plus lane*16, the global address is per lane (glds16, phl_compat_common.h, with the helpers of the
+// epilogue).
 #ifdef PHL_COMPAT_TIMELINE
 // debug build only (make EXTRA=-DPHL_COMPAT_TIMELINE): per wave group, 100 MHz stamps of the first 16 phase starts
 __device__ unsigned long long *g_cs_timeline;
@@ -280,18 +252,6 @@ __device__ unsigned long long *g_cs_timeline;
 #define CS_ARRIVE(k) do { } while (0)
 #endif
 
-// compile-time loop: f(integral_constant<int, I>) for I = 0 .. N-1 (slot-dependent wait counts must be immediates)
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>());
-        static_for<N, I + 1>(f);
-    }
-}
-
-// v_permlane16_swap_b32 a, b: the odd 16-lane rows of a trade places with the even rows of b
-#define PHL_ROW_SWAP(a, b) asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b))
 template <int NT, bool LOGITS, bool PAD>
 __global__ __launch_bounds__(512) void k_compat_softmax(const float *__restrict__ E0, int64_t e_rs,
                                                         const float *__restrict__ X, int64_t x_rs,
@@ -673,21 +633,6 @@ __global__ __launch_bounds__(512) void k_compat_softmax(const float *__restrict_
 //    that it is not hoisted out of the slot loop (its registers would spill).
 //  * a wave that goes from its epilogue half to the matrix cores still has the DMAs of its last two slots in flight
 //    (they feed slots 1 and 2 of the half it enters): counted waits at the end of its first two slots there.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// two f32 -> the packed bf16 pairs of their three addends (truncation: top 8 significant bits, the next 8, the last 8)
-__device__ __forceinline__ void split3(float x0, float x1, unsigned &h, unsigned &m, unsigned &l)
-{
-    const unsigned b0 = __float_as_uint(x0), b1 = __float_as_uint(x1);
-    const float r0 = x0 - __uint_as_float(b0 & 0xFFFF0000u), r1 = x1 - __uint_as_float(b1 & 0xFFFF0000u);
-    const unsigned c0 = __float_as_uint(r0), c1 = __float_as_uint(r1);
-    const float s0 = r0 - __uint_as_float(c0 & 0xFFFF0000u), s1 = r1 - __uint_as_float(c1 & 0xFFFF0000u);
-    h = __builtin_amdgcn_perm(b1, b0, 0x07060302u);        // {hi16(x1), hi16(x0)}
-    m = __builtin_amdgcn_perm(c1, c0, 0x07060302u);
-    l = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
-}
-
 constexpr int CSP_PIECE = 24576;                 // bytes of one slot's piece of the planes
 #ifndef PHL_CSP_XR
 #define PHL_CSP_XR 3
@@ -1074,7 +1019,6 @@ __global__ __launch_bounds__(512) void k_compat_split(const float *__restrict__ 
 #undef PHL_E0_LOAD_UNIT
 #undef PHL_E0_LOAD_HIDDEN
 #undef PHL_VMCNT
-#undef PHL_ROW_SWAP
 
 // The last n % 128 pixels of phl_compat_softmax (the tile kernel takes whole tiles only): one workgroup per pixel,
 // thread c owns label c -- an fmaf chain over k straight from the transposed compatibility matrix, then the row
@@ -1244,13 +1188,15 @@ int phl_compat_softmax(const float *E0, int64_t e_rs, const float *X, int64_t x_
 
 size_t phl_compat_planes_bytes(int L)
 {
+    if (L > 256) return phl_compat_wide_planes_bytes(L);     // 256 < L <= 512: k_compat_wide (phl_compat_wide.hip)
     return (L > 128 && L <= 256 && L % 4 == 0) ? (size_t)CSP_PLANES_BYTES : 0;
 }
 
 int phl_compat_prepare(const float *MuT, int L, void *planes, phl_stream stream)
 {
-    if (!phl_compat_planes_bytes(L)) { phl_set_error("phl_compat_prepare: the split kernel takes 128 < L <= 256, L %% 4 == 0 (L=%d)", L); return PHL_ERR_UNSUPPORTED; }
+    if (!phl_compat_planes_bytes(L)) { phl_set_error("phl_compat_prepare: the split kernels take 128 < L <= 512, L %% 4 == 0 (L=%d)", L); return PHL_ERR_UNSUPPORTED; }
     if (!MuT || !planes || ((reinterpret_cast<uintptr_t>(MuT) | reinterpret_cast<uintptr_t>(planes)) & 15)) { phl_set_error("phl_compat_prepare: bad arguments"); return PHL_ERR_INVALID; }
+    if (L > 256) return phl_compat_wide_prepare(MuT, L, planes, (hipStream_t)stream);
     k_compat_planes<<<dim3(16 * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream>>>(MuT, (L + 31) / 32 * 32, reinterpret_cast<u32x4 *>(planes));
     PHL_HIP(hipGetLastError());
     return PHL_OK;
@@ -1264,9 +1210,11 @@ int phl_compat_softmax_split(const float *E0, int64_t e_rs, const float *X, int6
     if (!phl_compat_planes_bytes(L) || x_rs % 4 || e_rs % 4 || o_rs % 4 || x_rs >= (1 << 24) || e_rs >= (1 << 24) || o_rs >= (1 << 24) ||
         ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(MuT) | reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(E0) |
           reinterpret_cast<uintptr_t>(out)) & 15)) {
-        phl_set_error("phl_compat_softmax_split: needs 128 < L <= 256, L %% 4 == 0 and 16-byte aligned E0 / X / out rows (L=%d)", L);
+        phl_set_error("phl_compat_softmax_split: needs 128 < L <= 512, L %% 4 == 0 and 16-byte aligned E0 / X / out rows (L=%d)", L);
         return PHL_ERR_UNSUPPORTED;
     }
+    if (L > 256)                                 // 256 < L <= 512: k_compat_wide (phl_compat_wide.hip)
+        return phl_compat_wide_softmax(E0, e_rs, X, x_rs, MuT, planes, out, o_rs, n, L, (flags & PHL_COMPAT_LOGITS) != 0, (hipStream_t)stream);
     const bool pad = L != 256;
     hipStream_t st = (hipStream_t)stream;
     const int64_t n_main = n / 128 * 128, npairs = (n / 128 + 1) / 2;

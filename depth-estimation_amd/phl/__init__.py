@@ -602,13 +602,15 @@ def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None
     """softmax(-(E0 + X @ Mu), dim=1): the whole non-lattice half of a mean-field iteration
     (crf/crf_module.py:51-52) for fp32 CUDA E0, X [n, L] and Mu [L, L], in one fused MFMA kernel
     (phl_compat_softmax) when L % 4 == 0 and L <= 256 (label counts that are not a multiple of 32 run on a padded
-    tile); other label counts take a library GEMM followed by the fused add + softmax pass.  A Mu of the Potts family
+    tile), or for 256 < L <= 512 with arith="split"; other label counts take a library GEMM followed by the fused
+    add + softmax pass.  A Mu of the Potts family
     (alpha * ones + beta * eye, detected once per Mu; ``structure=False`` switches that off) needs no product at all:
     phl_uniform_compat_softmax streams E0, X and Q once.  logits=True returns -(E0 + X @ Mu) instead (CRFasRNN's output).
     arith: "f32" = the f32-input matrix cores (bitwise an fma chain in k order), "split" = bf16 matrix cores on operands
-    split three ways, six partial products, f32 accumulation (phl_compat_softmax_split: a 256-label tile, 128 < L <= 256;
-    the same accuracy against float64, 3/8 of the matrix time).  Default: "split" for L > 176 -- below that the f32 kernel
-    is bound by its bytes as well and computes no padding -- unless PHL_COMPAT_ARITH names one of the two."""
+    split three ways, six partial products, f32 accumulation (phl_compat_softmax_split: a 256-label tile for
+    128 < L <= 256, a row of L rounded up to 32 for 256 < L <= 512; the same accuracy against float64, 3/8 of the matrix
+    time).  Default: "split" for L > 176 -- below that the f32 kernel is bound by its bytes as well and computes no
+    padding -- unless PHL_COMPAT_ARITH names one of the two.  Above 256 labels "f32" keeps the library GEMM route."""
     if arith is None:
         arith = os.environ.get("PHL_COMPAT_ARITH") or ("split" if E0.shape[-1] > 176 else "f32")
     if arith not in ("f32", "split"):
@@ -631,9 +633,10 @@ def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None
                 C.c_void_p(E0.data_ptr()), E0.stride(0), C.c_void_p(X.data_ptr()), X.stride(0), C.c_float(uniform[0]),
                 C.c_float(uniform[1]), C.c_void_p(out.data_ptr()), out.stride(0), n, L, 1 if logits else 0, _stream(E0.device)))
         return out
-    if aligned and L <= 256:
+    split = aligned and L <= 512 and arith == "split" and bool(load_library().phl_compat_planes_bytes(L))
+    if split or (aligned and L <= 256):
         mu_t = _mu_transposed(Mu, E0.device)
-        if arith == "split" and hasattr(load_library(), "phl_compat_softmax_split") and load_library().phl_compat_planes_bytes(L):
+        if split:
             planes = _mu_planes(Mu, mu_t, E0.device)
             with torch.cuda.device(E0.device):
                 _check(load_library().phl_compat_softmax_split(
