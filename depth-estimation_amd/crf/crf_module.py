@@ -108,14 +108,18 @@ def mean_field_step(E_0, W, Mu, Q, out=None):
     return phl.compat_softmax(E_0, X, Mu, out=out)
 
 
-def mean_field_infer(E_0, W, Mu, niters=10):
+def mean_field_infer(E_0, W, Mu, niters=10, fused_grad=False):
     """[E_0] n x L unaries, [W] n x n operator, [Mu] L x L compatibility -> Q n x L (crf_module.py:41-53).
 
     On the GPU inference path everything of an iteration outside the lattice filter -- the compatibility
     product, the add, the negation and the softmax -- is ONE fused HIP kernel (phl.compat_softmax: fp32 MFMA
     tiles of X @ Mu with the softmax as epilogue, so neither G nor E ever exists in HBM).  With autograd
     (E_0, Mu, or anything W carries -- e.g. a LatticeGaussian whose ``ref`` requires grad) or CPU tensors
-    the plain, differentiable torch ops run."""
+    the plain, differentiable torch ops run -- unless ``fused_grad=True``: then CUDA fp32 inputs keep the fused
+    kernels under autograd too (phl.CompatSoftmax / phl.SoftmaxNegAdd, whose backward runs on the library's own
+    kernels), and ``W @ Q`` keeps its own graph.  Without any gradient, ``fused_grad`` changes nothing."""
+    if fused_grad and _fused_grad_ok(E_0, Mu):
+        return _mean_field_infer_grad(E_0, W, Mu, niters)
     if _fused_ok(E_0, Mu):
         import phl
 
@@ -126,13 +130,16 @@ def mean_field_infer(E_0, W, Mu, niters=10):
             Mu, uniform = _padded_mu(Mu, Lp, E_0.device)
         Q = phl.softmax_neg_add(E_0)
         fused = True
-        for _ in range(niters):
+        for it in range(niters):
             if fused:
                 X = W @ Q
                 if torch.is_grad_enabled() and X.requires_grad:
                     # W itself is being differentiated: the raw-pointer kernels would drop its graph (and
                     # overwrite a tensor LatticeFilter saved for backward) -> differentiable path from here on
                     fused = False
+                    if fused_grad and E_0.shape[1] <= 512:      # (the Functions write fresh tensors: nothing saved is overwritten)
+                        Q = _mean_field_infer_grad_loop(E_0, W, Mu, niters - it, uniform, X)
+                        break
                     Q = F.softmax(-(E_0 + X @ Mu), dim=1)
                     continue
                 if not (X.is_cuda and X.dtype == torch.float32 and X.stride(1) == 1):
@@ -147,6 +154,48 @@ def mean_field_infer(E_0, W, Mu, niters=10):
     for _ in range(niters):
         Q = F.softmax(-(E_0 + (W @ Q) @ Mu), dim=1)
     return Q
+
+
+def _fused_grad_ok(E_0, Mu):
+    """The differentiable device loop: CUDA fp32 [n, L] unaries (at most 512 labels: the backward kernels' range), a fp32
+    Mu, and a gradient asked of E_0 or Mu (a gradient that only W asks for is found in the loop of mean_field_infer, at its
+    first ``W @ Q``)."""
+    return (E_0.is_cuda and E_0.dtype == torch.float32 and E_0.dim() == 2 and torch.is_tensor(Mu) and Mu.dtype == torch.float32
+            and Mu.is_cuda and _label_pad(E_0.shape[1]) <= 512 and torch.is_grad_enabled() and (E_0.requires_grad or Mu.requires_grad))
+
+
+def _mean_field_infer_grad_loop(E_0, W, Mu, niters, uniform, X=None):
+    """``niters`` iterations on the differentiable fused Functions from the Q behind X = W @ Q (X given) or from
+    softmax(-E_0).  E_0, Mu: already padded to the label count the kernels take."""
+    import phl
+
+    Q = None if X is not None else phl.softmax_neg_add_fn(E_0)
+    for _ in range(niters):
+        if X is None:
+            X = W @ Q
+        if not (X.is_cuda and X.dtype == torch.float32 and X.stride(1) == 1):
+            X = X.to(E_0.device, torch.float32).contiguous()
+        Q = phl.compat_softmax_fn(E_0, X, Mu, False, uniform)
+        X = None
+    return Q
+
+
+def _mean_field_infer_grad(E_0, W, Mu, niters):
+    """mean_field_infer with autograd on the fused kernels: label padding through differentiable ops (F.pad of E_0 with
+    _PAD_ENERGY, of Mu with zeros), Q = phl.SoftmaxNegAdd, then per iteration X = W @ Q with W's own graph and
+    Q = phl.CompatSoftmax.  Every tensor is fresh: nothing autograd saved is written again."""
+    import phl
+
+    L = E_0.shape[1]
+    Lp, uniform = _label_pad(L), None
+    if E_0.stride(1) != 1:
+        E_0 = E_0.contiguous()
+    if Lp != L:
+        uniform = phl._mu_uniform(Mu.detach()) or False
+        E_0 = F.pad(E_0, (0, Lp - L), value=_PAD_ENERGY)
+        Mu = F.pad(Mu, (0, Lp - L, 0, Lp - L))
+    Q = _mean_field_infer_grad_loop(E_0, W, Mu, niters, uniform)
+    return Q if Lp == L else Q[:, :L].contiguous()
 
 
 def _staged_ok(E_0, W, Mu):
@@ -192,13 +241,15 @@ def potts(num_classes):
     return conv
 
 
-def _compat_matrix(mu, L, labels, device):
+def _compat_matrix(mu, L, labels, device, detach=True):
     """[L, L] matrix M with ``mu(Q)[:, c] = sum_b M[b, c] Q[:, b]`` for the compatibility modules CRFasRNN is
-    used with (``charb``, or a bias-free 1x1 conv such as ``potts``); None for anything else."""
+    used with (``charb``, or a bias-free 1x1 conv such as ``potts``); None for anything else.  detach=False keeps
+    the graph to the module's parameters (the differentiable path of CRFasRNN)."""
     if isinstance(mu, charb):
-        return mu.matrix(L, labels, device)
+        return mu.matrix(L, labels, device, detach=detach)
     if isinstance(mu, nn.Conv2d) and mu.kernel_size == (1, 1) and mu.bias is None and mu.groups == 1 and mu.weight.shape[:2] == (L, L):
-        return mu.weight.detach()[:, :, 0, 0].t().to(device, torch.float32)      # conv: out[c] = sum_b w[c, b] q[b]
+        w = mu.weight.detach() if detach else mu.weight
+        return w[:, :, 0, 0].t().to(device, torch.float32)      # conv: out[c] = sum_b w[c, b] q[b]
     return None
 
 
@@ -227,12 +278,14 @@ class charb(nn.Module):
         weight = compatibility_matrix(lambda p, q: charbonneir(q, p, self.gamma), labels)     # symmetric in (p, q)
         return F.conv2d(x, weight[..., None, None]) * self._scale()
 
-    def matrix(self, L, labels=None, device=None):
-        """The same compatibility as a dense [L, L] matrix for pixel-major data: forward(x)[:, c] = (x @ M)[:, c]."""
+    def matrix(self, L, labels=None, device=None, detach=True):
+        """The same compatibility as a dense [L, L] matrix for pixel-major data: forward(x)[:, c] = (x @ M)[:, c].
+        detach=False keeps the graph to ``gamma`` and ``s``."""
         if labels is None:
             labels = torch.arange(L, dtype=torch.float32, device=device)
         weight = compatibility_matrix(lambda p, q: charbonneir(q, p, self.gamma), labels.to(device))
-        return (weight * self._scale()).detach().t().contiguous()
+        M = weight * self._scale()
+        return (M.detach() if detach else M).t().contiguous()
 
     def get_energies_from_scalar(self, x, labels):
         return charbonneir(labels, x, self.gamma * labels.max()) * self._scale()
@@ -310,29 +363,67 @@ def _mean_field_nchw_fused(E0, refs, M, niters):
     return out
 
 
+def _mean_field_nchw_grad(E0, refs, M, niters):
+    """The NCHW iteration of CRFasRNN under autograd on the library's kernels, image by image pixel-major on the current
+    stream: e0 = E0[b] as [n, L] (padded by F.pad where L is off the kernels' grid), Q = phl.SoftmaxNegAdd, then per
+    iteration, in the reference's order E = E0 + W(Mu(Q)) (crf_module.py:97-99): Y = Q @ M (phl.CompatProduct, matrix
+    cores), G = LatticeFilter(Y, ref_b) - Y with the guide's graph kept, Q = phl.SoftmaxNegAdd(e0, G) -- the logits
+    -(e0 + G) on the last one -- and back to NCHW.  M is the differentiable compatibility matrix (gradients reach the Mu
+    module).  W and Mu commute in the forward, not in the backward: the lattice filter is not exactly symmetric, its
+    backward is the filter itself (LatticeFilter, as the reference's), so only this order gives Mu the reference's
+    gradient; the (W Q) Mu order of mean_field_infer would give the exact gradient of the forward instead."""
+    import phl
+    from crf.gaussian_matrix import LatticeFilter
+
+    bs, L, h, w = E0.shape
+    d, n = refs.shape[1], h * w
+    Lp = _label_pad(L)
+    Mp = M if Lp == L else F.pad(M, (0, Lp - L, 0, Lp - L))
+    outs = []
+    for b in range(bs):
+        e0 = E0[b].reshape(L, n).t().contiguous()
+        if Lp != L:
+            e0 = F.pad(e0, (0, Lp - L), value=_PAD_ENERGY)
+        ref_b = refs[b].reshape(d, n).t().contiguous()
+        Q = phl.softmax_neg_add_fn(e0)
+        for it in range(niters):
+            Y = phl.compat_product_fn(Q, Mp)
+            G = LatticeFilter.apply(Y, ref_b) - Y
+            Q = -(e0 + G) if it == niters - 1 else phl.softmax_neg_add_fn(e0, G)
+        outs.append(Q[:, :L].t().reshape(L, h, w))
+    return torch.stack(outs)
+
+
 class CRFasRNN(nn.Module):
     """Batched NCHW mean field (crf_module.py:81-104); returns logits -E of the LAST iteration.
 
     ``lattice=True`` selects the permutohedral W (BatchedAdjacency, the MI355X path); the default
     stays the reference's guided-filter W."""
 
-    def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False):
+    def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
+                 fused_grad=False):
         super().__init__()
         self.Mu, self.niters = mu_init, niters
         if notrain_mu:
             self.Mu.requires_grad_(False)
         self.W = BatchedAdjacency() if lattice else BatchedGuidedAdjacency(gchannels, r, eps, gaussian=gaussian)
+        self.fused_grad = fused_grad
 
     def forward(self, refs, logits, confidence=None, labels=None):
         """refs [B, C, H, W], logits [B, L, H, W]."""
         E0 = -logits if confidence is None else -logits * confidence
         extra = () if labels is None else (labels,)
-        if (isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda and E0.dtype == torch.float32
-                and not (torch.is_grad_enabled() and (E0.requires_grad or refs.requires_grad
-                                                      or any(p.requires_grad for p in self.Mu.parameters())))):
-            M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device)
-            if M is not None:
-                return _mean_field_nchw_fused(E0.contiguous(), refs, M, self.niters)      # already -E
+        if isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda and E0.dtype == torch.float32:
+            grad = torch.is_grad_enabled() and (E0.requires_grad or refs.requires_grad
+                                                or any(p.requires_grad for p in self.Mu.parameters()))
+            if not grad:
+                M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device)
+                if M is not None:
+                    return _mean_field_nchw_fused(E0.contiguous(), refs, M, self.niters)      # already -E
+            elif self.fused_grad and refs.is_cuda and refs.dtype == torch.float32 and _label_pad(E0.shape[1]) <= 512:
+                M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device, detach=False)
+                if M is not None:
+                    return _mean_field_nchw_grad(E0, refs, M, self.niters)                    # already -E
         return -_mean_field_nchw(E0, lambda Q: self.W(self.Mu(Q, *extra), refs), self.niters)
 
 

@@ -101,6 +101,13 @@ def load_library():
             lib.phl_compat_planes_bytes.restype = C.c_size_t
             lib.phl_compat_prepare.argtypes = [vp, i32, vp, vp]
             lib.phl_compat_softmax_split.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, u32, vp]
+        if hasattr(lib, "phl_compat_grad_x"):          # (an older build loaded through PHL_LIB lacks the backward)
+            lib.phl_softmax_neg_grad.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, vp]
+            lib.phl_uniform_compat_grad.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, vp, i64, vp, i64, i64, i32, vp]
+            lib.phl_compat_grad_x.argtypes = [vp, i64, vp, C.c_float, vp, i64, i64, i32, vp]
+            lib.phl_compat_mu_grad_workspace_bytes.argtypes = [i64, i32]
+            lib.phl_compat_mu_grad_workspace_bytes.restype = C.c_size_t
+            lib.phl_compat_mu_grad.argtypes = [vp, i64, vp, i64, C.c_float, i64, i32, vp, vp, i32, vp]
         lib.phl_stream_copy.argtypes = [vp, vp, i64, vp]
         lib.phl_copy2d.argtypes = [vp, i64, i64, vp, i64, i64, i64, i32, vp]
         lib.phl_cost_volume.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
@@ -653,6 +660,218 @@ def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None
     if logits:
         return out.copy_(-(E0 + G))
     return softmax_neg_add(E0, G, out=out)
+
+
+# ---------------------------------------------------------------------------------------------
+# backward of the compatibility + softmax step (CRF training; include/phl.h, phl_compat_grad.hip)
+def _grad_operand(t, n, L):
+    """fp32 CUDA [n, L] with unit channel stride and 16-byte aligned rows, as the backward kernels read it."""
+    if not (_rowmajor(t) and t.shape == (n, L) and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0):
+        t = t.to(torch.float32).clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def _mu_operand(Mu, L, device):
+    """Mu as phl_compat_grad_x reads it: a dense fp32 [L][L] with row stride L (the ABI takes no stride for Mu), 16-byte
+    aligned -- a row-padded or offset view is copied."""
+    if tuple(Mu.shape) != (L, L):
+        raise TypeError(f"compat_grad_x: Mu must be [{L}, {L}], got {tuple(Mu.shape)}")
+    m = Mu.detach().to(device, torch.float32)
+    if not (m.shape == (L, L) and m.stride() == (L, 1) and m.data_ptr() % 16 == 0):
+        m = m.clone(memory_format=torch.contiguous_format)
+    return m
+
+
+def _check_grad_domain(name, L, *tensors):
+    """The backward kernels take fp32 CUDA operands with L % 4 == 0 and 4 <= L <= 512: checked when the forward records
+    a graph, so that an input the backward cannot take fails there, with this message, not at backward time."""
+    for t in tensors:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32):
+            raise TypeError(f"{name}: the differentiable form takes fp32 CUDA tensors, got {t.dtype} on {t.device}")
+    if not (L % 4 == 0 and 4 <= L <= 512):
+        raise ValueError(f"{name}: the backward kernels take L % 4 == 0 and 4 <= L <= 512 labels, got L = {L} "
+                         "(pad the labels, as crf_module._label_pad does, or use the plain torch ops)")
+
+
+def softmax_neg_grad(Q, gQ, out=None):
+    """dE = Q * (sum_c gQ Q - gQ): the gradient of Q = softmax(-E) with respect to E, one pass (phl_softmax_neg_grad)."""
+    n, L = Q.shape
+    Q, gQ = _grad_operand(Q, n, L), _grad_operand(gQ, n, L)
+    if out is None:
+        out = torch.empty((n, L), dtype=torch.float32, device=Q.device)
+    with torch.cuda.device(Q.device):
+        _check(load_library().phl_softmax_neg_grad(C.c_void_p(Q.data_ptr()), Q.stride(0), C.c_void_p(gQ.data_ptr()), gQ.stride(0),
+                                                   C.c_void_p(out.data_ptr()), out.stride(0), n, L, _stream(Q.device)))
+    return out
+
+
+def uniform_compat_grad(Q, gQ, alpha, beta):
+    """(dE, gX) for Mu = alpha * ones + beta * eye in one pass (phl_uniform_compat_grad).  Q = None: logits mode,
+    dE = -gQ."""
+    n, L = gQ.shape
+    gQ = _grad_operand(gQ, n, L)
+    if Q is not None:
+        Q = _grad_operand(Q, n, L)
+    dE = torch.empty((n, L), dtype=torch.float32, device=gQ.device)
+    gX = torch.empty_like(dE)
+    with torch.cuda.device(gQ.device):
+        _check(load_library().phl_uniform_compat_grad(
+            C.c_void_p(Q.data_ptr()) if Q is not None else None, Q.stride(0) if Q is not None else 0, C.c_void_p(gQ.data_ptr()),
+            gQ.stride(0), C.c_float(alpha), C.c_float(beta), C.c_void_p(dE.data_ptr()), dE.stride(0), C.c_void_p(gX.data_ptr()),
+            gX.stride(0), n, L, _stream(gQ.device)))
+    return dE, gX
+
+
+def compat_grad_x(dE, Mu, scale=1.0):
+    """scale * dE @ Mu^T on the f32-input matrix cores (phl_compat_grad_x); Mu is [L, L] as the forward takes it."""
+    n, L = dE.shape
+    dE = _grad_operand(dE, n, L)
+    Mu = _mu_operand(Mu, L, dE.device)
+    gX = torch.empty((n, L), dtype=torch.float32, device=dE.device)
+    with torch.cuda.device(dE.device):
+        _check(load_library().phl_compat_grad_x(C.c_void_p(dE.data_ptr()), dE.stride(0), C.c_void_p(Mu.data_ptr()), C.c_float(scale),
+                                                C.c_void_p(gX.data_ptr()), gX.stride(0), n, L, _stream(dE.device)))
+    return gX
+
+
+def compat_mu_grad(X, dE, scale=1.0, out=None, accumulate=False):
+    """scale * X^T @ dE as a dense [L, L] (phl_compat_mu_grad): per-range fp32 partials in a workspace, summed in a fixed
+    order in fp64 -- the same bits on every run.  accumulate=True adds to ``out``."""
+    n, L = dE.shape
+    X, dE = _grad_operand(X, n, L), _grad_operand(dE, n, L)
+    lib = load_library()
+    if out is None:
+        out = torch.empty((L, L), dtype=torch.float32, device=dE.device)
+        accumulate = False
+    elif not (out.is_contiguous() and out.dtype == torch.float32 and out.shape == (L, L)):
+        raise TypeError("compat_mu_grad: out must be a contiguous fp32 [L, L] tensor")
+    ws = torch.empty((max(1, lib.phl_compat_mu_grad_workspace_bytes(n, L)),), dtype=torch.uint8, device=dE.device)
+    with torch.cuda.device(dE.device):
+        _check(lib.phl_compat_mu_grad(C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(dE.data_ptr()), dE.stride(0), C.c_float(scale),
+                                      n, L, C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()), 1 if accumulate else 0,
+                                      _stream(dE.device)))
+    return out
+
+
+class SoftmaxNegAdd(torch.autograd.Function):
+    """Q = softmax(-(E0 + G)) (phl_softmax_neg_add; G optional) with its backward on phl_softmax_neg_grad: the first
+    step of a differentiable mean-field loop, and the step of one that applies W after Mu (CRFasRNN)."""
+
+    @staticmethod
+    def forward(ctx, E0, G=None):
+        if any(ctx.needs_input_grad):
+            _check_grad_domain("SoftmaxNegAdd", E0.shape[-1], E0, G)
+        E0 = E0 if _rowmajor(E0) else E0.contiguous()
+        if G is not None and not _rowmajor(G):
+            G = G.contiguous()
+        Q = softmax_neg_add(E0, G)
+        ctx.save_for_backward(Q)
+        return Q
+
+    @staticmethod
+    def backward(ctx, g):
+        Q, = ctx.saved_tensors
+        dE = softmax_neg_grad(Q, g) if any(ctx.needs_input_grad[:2]) else None
+        return (dE if ctx.needs_input_grad[0] else None), (dE if ctx.needs_input_grad[1] else None)
+
+
+class CompatProduct(torch.autograd.Function):
+    """Y = Q @ M on the f32 matrix cores (phl_compat_grad_x with M^T), backward gQ = gY M^T (phl_compat_grad_x) and
+    gM = Q^T gY (phl_compat_mu_grad), each only when asked for.  The compatibility applied BEFORE W, as CRFasRNN does
+    (``W(Mu(Q))``, crf_module.py:98): with a W whose backward is taken to be W itself (the lattice filter), the gradient
+    of M then is the one the reference computes."""
+
+    @staticmethod
+    def forward(ctx, Q, M):
+        _check_grad_domain("CompatProduct", Q.shape[-1], Q, M)
+        ctx.save_for_backward(Q, M)
+        return compat_grad_x(Q, M.detach().t().contiguous())
+
+    @staticmethod
+    def backward(ctx, gY):
+        Q, M = ctx.saved_tensors
+        gQ = compat_grad_x(gY, M) if ctx.needs_input_grad[0] else None
+        gM = compat_mu_grad(Q, gY) if ctx.needs_input_grad[1] else None
+        return gQ, gM
+
+
+class CompatSoftmax(torch.autograd.Function):
+    """softmax(-(E0 + X @ Mu)) (or its logits -(E0 + X @ Mu)) on the fused forward kernels of ``compat_softmax``, with
+    the backward on the library's kernels: dE in one pass over Q and the incoming gradient (phl_softmax_neg_grad),
+    gX = dE Mu^T and gMu = X^T dE on the f32 matrix cores (phl_compat_grad_x, phl_compat_mu_grad).  A Mu of the Potts
+    family detected on Mu itself gets dE and gX from one streaming pass (phl_uniform_compat_grad).  Only the gradients
+    autograd asks for are computed.  The forward writes a fresh tensor; it saves Q (not in logits mode), X and Mu.
+
+    uniform: as for ``compat_softmax``; a structure the caller asserts for the labels that matter (a padded Mu) serves
+    the forward only -- the backward then takes the dense product, whose padding columns are exactly 0.
+
+    Domain when a gradient is recorded: fp32 CUDA E0, X, Mu and L % 4 == 0, 4 <= L <= 512 (else TypeError / ValueError in
+    the forward); without one, everything ``compat_softmax`` takes."""
+
+    @staticmethod
+    def forward(ctx, E0, X, Mu, logits=False, uniform=None):
+        if any(ctx.needs_input_grad[:3]):
+            _check_grad_domain("CompatSoftmax", E0.shape[-1], E0, X, Mu)
+        E0 = E0 if _rowmajor(E0) else E0.contiguous()
+        X = X if _rowmajor(X) else X.contiguous()
+        n, L = E0.shape
+        detected = None
+        if uniform is None:
+            aligned = L % 4 == 0 and all(t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in (X, E0))
+            detected = _mu_uniform(Mu) if (aligned and L <= 1024) else None
+            uniform = detected if detected is not None else False
+        out = compat_softmax(E0, X, Mu, logits=logits, uniform=uniform)
+        ctx.logits, ctx.uniform = bool(logits), detected
+        ctx.save_for_backward(None if logits else out, X, Mu)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        Q, X, Mu = ctx.saved_tensors
+        need_e0, need_x, need_mu = ctx.needs_input_grad[:3]
+        n, L = g.shape
+        g = _grad_operand(g, n, L)
+        gE0 = gX = gMu = None
+        uni = ctx.uniform if need_x else None
+        if ctx.logits:                           # out = -E: dE = -g; the products take g with scale -1
+            if uni is not None:
+                dE, gX = uniform_compat_grad(None, g, *uni)
+                gE0 = dE if need_e0 else None
+            else:
+                gE0 = -g if need_e0 else None
+                if need_x:
+                    gX = compat_grad_x(g, Mu, -1.0)
+            if need_mu:
+                gMu = compat_mu_grad(X, g, -1.0)
+        else:
+            if uni is not None:
+                dE, gX = uniform_compat_grad(Q, g, *uni)
+            else:
+                dE = softmax_neg_grad(Q, g)
+                if need_x:
+                    gX = compat_grad_x(dE, Mu, 1.0)
+            gE0 = dE if need_e0 else None
+            if need_mu:
+                gMu = compat_mu_grad(X, dE, 1.0)
+        if gMu is not None and gMu.dtype != Mu.dtype:
+            gMu = gMu.to(Mu.dtype)
+        return gE0, gX, gMu, None, None
+
+
+def compat_softmax_fn(E0, X, Mu, logits=False, uniform=None):
+    """Differentiable ``compat_softmax``: CompatSoftmax.apply(E0, X, Mu, logits, uniform).  With a gradient recorded it
+    takes fp32 CUDA tensors and L % 4 == 0, 4 <= L <= 512 (the backward kernels' range), and says so in the forward."""
+    return CompatSoftmax.apply(E0, X, Mu, logits, uniform)
+
+
+def softmax_neg_add_fn(E0, G=None):
+    """Differentiable ``softmax_neg_add(E0, G)``: SoftmaxNegAdd.apply(E0, G)."""
+    return SoftmaxNegAdd.apply(E0, G)
+
+
+def compat_product_fn(Q, M):
+    """Differentiable Q @ M on the library's kernels: CompatProduct.apply(Q, M)."""
+    return CompatProduct.apply(Q, M)
 
 
 CRITERIA = {"AD": 0, "SD": 1, "nprod": 2}

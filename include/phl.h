@@ -292,6 +292,32 @@ int phl_compat_softmax_split(const float *E0_dev, int64_t e0_row_stride, const f
 int phl_uniform_compat_softmax(const float *E0_dev, int64_t e0_row_stride, const float *X_dev, int64_t x_row_stride,
                                float alpha, float beta, float *out_dev, int64_t out_row_stride, int64_t n, int L,
                                unsigned flags, phl_stream stream);
+/* ---- backward of the compatibility + softmax step (CRF training) ---------------------------------------------
+ * Forward: Q = softmax(-E), E = E0 + X Mu.  With the upstream gradient gQ: dE = Q (s - gQ), s[p] = sum_c gQ[p,c] Q[p,c];
+ * gE0 = dE, gX = dE Mu^T, gMu = X^T dE.  All entry points: fp32 rows with unit channel stride, row strides % 4 == 0,
+ * 16-byte aligned pointers, L % 4 == 0, 4 <= L <= 512 (else PHL_ERR_UNSUPPORTED), any n.
+ *   phl_softmax_neg_grad      dE from Q and gQ in one pass (the backward of phl_softmax_neg_add as well).
+ *   phl_uniform_compat_grad   the same pass for Mu = alpha*J + beta*I, which also writes gX = alpha*rowsum(dE) + beta*dE;
+ *                             Q == NULL: logits mode (the step returned -E), dE = -gQ.
+ *   phl_compat_grad_x         gX = scale * dE Mu^T on the f32-input matrix cores (exact f32); Mu is the [L][L] matrix
+ *                             itself, row stride L, NOT transposed.  scale = -1 with dE = g_out serves logits mode.
+ *   phl_compat_mu_grad        gMu = scale * X^T dE (+ gMu if accumulate) into a dense [L][L]: one fp32 partial per pixel
+ *                             range into the workspace, then the partials summed in range order in fp64 -- no atomics,
+ *                             the result is the same bit for bit on every run.
+ *   phl_compat_mu_grad_workspace_bytes(n, L) = R * L * L * 4 with R = max(1, min(ceil(n / 64), C, floor(2^24 / L^2)))
+ *                             pixel ranges, C = floor(256 * max(1, floor(16 / (c * min(c, floor(16 / c))))) / slabs),
+ *                             c = ceil(L / 64), slabs = ceil(L / (64 min(c, floor(16 / c)))); where slabs > 1 and R >= 8,
+ *                             R is rounded down to a multiple of 8.  At most 64 MiB; 0 for an L the kernels do not take. */
+int phl_softmax_neg_grad(const float *Q_dev, int64_t q_row_stride, const float *gQ_dev, int64_t gq_row_stride, float *dE_dev,
+                         int64_t de_row_stride, int64_t n, int L, phl_stream stream);
+int phl_uniform_compat_grad(const float *Q_dev, int64_t q_row_stride, const float *gQ_dev, int64_t gq_row_stride, float alpha,
+                            float beta, float *dE_dev, int64_t de_row_stride, float *gX_dev, int64_t gx_row_stride, int64_t n,
+                            int L, phl_stream stream);
+int phl_compat_grad_x(const float *dE_dev, int64_t de_row_stride, const float *mu_dev, float scale, float *gX_dev,
+                      int64_t gx_row_stride, int64_t n, int L, phl_stream stream);
+size_t phl_compat_mu_grad_workspace_bytes(int64_t n, int L);
+int phl_compat_mu_grad(const float *X_dev, int64_t x_row_stride, const float *dE_dev, int64_t de_row_stride, float scale,
+                       int64_t n, int L, void *workspace_dev, float *gMu_dev, int accumulate, phl_stream stream);
 /* out[p] = sum_c Q[p,c]*labels[c] : the expected disparity `mf @ labels`
  * (Experiments/DenseCrf.ipynb cell 11). */
 int phl_expected_value(const float *Q_dev, int64_t q_row_stride, const float *labels_dev, float *out_dev,
