@@ -57,7 +57,6 @@ def compatibility_matrix(compat, labels):
 # iteration (exp underflows), their rows and columns of Mu are 0, W maps a zero column to a zero column -- the first L
 # columns evolve exactly as without them.  One padded copy of E_0 on entry, one slice on exit.
 _PAD_ENERGY = 1.0e30
-_mu_pad_cache = {}
 
 
 def _label_pad(L):
@@ -66,33 +65,47 @@ def _label_pad(L):
     return 256 if 224 < L < 256 else (L + 3) // 4 * 4
 
 
-def _padded_mu(Mu, Lp, device):
-    """Mu with zero rows / columns up to Lp, cached per (storage, version) like the kernels' own forms of it, plus the
-    Potts-family structure of the ORIGINAL matrix (the padded one no longer shows it)."""
+def _pad_labels(E_0, Mu, differentiable=False, channel_major=False, structure=True):
+    """(E_0, Mu, uniform) on the label count of the device loop (_label_pad): the energies of the extra labels are
+    _PAD_ENERGY, Mu gets zero rows / columns, and uniform is the Potts-family structure of the ORIGINAL Mu (or False) for
+    phl.compat_softmax -- None when nothing is padded.  E_0 [..., n, L] and Mu [L, L].
+    differentiable: through autograd (F.pad: fresh tensors, Mu's graph kept); structure=False then skips the
+    Potts-family test and its device -> host read (uniform None), for a caller that does not run phl.compat_softmax.
+    Otherwise one padded copy of E_0 and the padded Mu cached per Mu (phl._mu_forms); channel_major: E_0 is an image's
+    [L, n] (NCHW) plane, always transposed into a fresh pixel-major buffer by phl.copy2d."""
     import phl
 
-    key = (Mu.data_ptr(), Mu._version, tuple(Mu.shape), tuple(Mu.stride()), Lp, str(device))
-    hit = _mu_pad_cache.get(key)
-    if hit is None:
-        if len(_mu_pad_cache) > 8:
-            _mu_pad_cache.clear()
-        L = Mu.shape[0]
-        mp = torch.zeros((Lp, Lp), dtype=torch.float32, device=device)
-        mp[:L, :L] = Mu.detach().to(device, torch.float32)
-        hit = _mu_pad_cache[key] = (mp, phl._mu_uniform(Mu.detach()) or False, Mu)
-    return hit[0], hit[1]
-
-
-def _pad_energies(E_0, Lp):
-    n, L = E_0.shape
-    E0p = torch.full((n, Lp), _PAD_ENERGY, dtype=torch.float32, device=E_0.device)
-    E0p[:, :L] = E_0
-    return E0p
+    L = E_0.shape[0] if channel_major else E_0.shape[-1]
+    Lp = _label_pad(L)
+    if differentiable:
+        if Lp == L:
+            return E_0, Mu, None
+        uniform = (phl._mu_uniform(Mu.detach()) or False) if structure else None
+        return F.pad(E_0, (0, Lp - L), value=_PAD_ENERGY), F.pad(Mu, (0, Lp - L, 0, Lp - L)), uniform
+    if Lp == L and not channel_major:
+        return E_0, Mu, None
+    n = E_0.shape[1] if channel_major else E_0.shape[0]
+    E0p = torch.empty((n, L), dtype=torch.float32, device=E_0.device) if Lp == L else \
+        torch.full((n, Lp), _PAD_ENERGY, dtype=torch.float32, device=E_0.device)
+    if channel_major:
+        phl.copy2d(E0p[:, :L], E_0.t())
+    else:
+        E0p[:, :L] = E_0
+    if Lp == L:
+        return E0p, Mu, None
+    return (E0p,) + phl._mu_forms(Mu).padded(Lp, E_0.device)
 
 
 def _fused_ok(E_0, Mu):
     return (E_0.is_cuda and E_0.dtype == torch.float32 and E_0.dim() == 2 and E_0.stride(1) == 1
             and not (torch.is_grad_enabled() and (E_0.requires_grad or Mu.requires_grad)))
+
+
+def _kernel_operand(X, device):
+    """X as the fused kernels read it: a fp32 [n, L] device tensor with unit channel stride."""
+    if X.is_cuda and X.dtype == torch.float32 and X.stride(1) == 1:
+        return X
+    return X.to(device, torch.float32).contiguous()
 
 
 def mean_field_step(E_0, W, Mu, Q, out=None):
@@ -103,9 +116,42 @@ def mean_field_step(E_0, W, Mu, Q, out=None):
     import phl
 
     X = W(Q) if callable(W) and not hasattr(W, "__matmul__") else W @ Q
-    if not (X.is_cuda and X.dtype == torch.float32 and X.stride(1) == 1):
-        X = X.to(E_0.device, torch.float32).contiguous()
-    return phl.compat_softmax(E_0, X, Mu, out=out)
+    return phl.compat_softmax(E_0, _kernel_operand(X, E_0.device), Mu, out=out)
+
+
+def _device_loop(E_0, apply_W, Mu, niters, uniform=None, differentiable=False, logits=False, fused_grad=False):
+    """``niters`` iterations Q <- softmax(-(E_0 + X @ Mu)), X = apply_W(Q), on the fused kernels from Q = softmax(-E_0).
+    E_0, Mu, uniform: from _pad_labels.  logits: the last iteration returns -(E_0 + X @ Mu) instead.
+
+    differentiable=False: the raw-pointer kernels, in place (out=Q): nothing is allocated per iteration.  When X first
+    carries a graph (W itself is being differentiated), the raw-pointer kernels would drop it and overwrite a tensor W
+    saved for backward: from there on the loop continues on the differentiable Functions (fused_grad) or on plain torch
+    ops.  differentiable=True: phl.SoftmaxNegAdd / phl.CompatSoftmax, every tensor fresh -- nothing autograd saved is
+    written again."""
+    import phl
+
+    plain = False
+    Q = phl.softmax_neg_add_fn(E_0) if differentiable else phl.softmax_neg_add(E_0)
+    for it in range(niters):
+        X = apply_W(Q)
+        if not differentiable and torch.is_grad_enabled() and X.requires_grad:
+            differentiable, plain = True, not fused_grad
+        last = logits and it == niters - 1
+        if plain:
+            Q = -(E_0 + X @ Mu) if last else F.softmax(-(E_0 + X @ Mu), dim=1)
+        elif differentiable:
+            Q = phl.compat_softmax_fn(E_0, _kernel_operand(X, E_0.device), Mu, last, uniform)
+        else:
+            Q = phl.compat_softmax(E_0, _kernel_operand(X, E_0.device), Mu, out=Q, logits=last, uniform=uniform)
+    return Q
+
+
+def _fused_infer(E_0, apply_W, Mu, niters, differentiable=False, fused_grad=False):
+    """_device_loop on the padded label count, Q [n, L] back."""
+    L = E_0.shape[1]
+    E0p, Mp, uniform = _pad_labels(E_0, Mu, differentiable)
+    Q = _device_loop(E0p, apply_W, Mp, niters, uniform, differentiable, fused_grad=fused_grad and E0p.shape[1] <= 512)
+    return Q if E0p.shape[1] == L else Q[:, :L].contiguous()
 
 
 def mean_field_infer(E_0, W, Mu, niters=10, fused_grad=False):
@@ -118,36 +164,10 @@ def mean_field_infer(E_0, W, Mu, niters=10, fused_grad=False):
     the plain, differentiable torch ops run -- unless ``fused_grad=True``: then CUDA fp32 inputs keep the fused
     kernels under autograd too (phl.CompatSoftmax / phl.SoftmaxNegAdd, whose backward runs on the library's own
     kernels), and ``W @ Q`` keeps its own graph.  Without any gradient, ``fused_grad`` changes nothing."""
-    if fused_grad and _fused_grad_ok(E_0, Mu):
-        return _mean_field_infer_grad(E_0, W, Mu, niters)
-    if _fused_ok(E_0, Mu):
-        import phl
-
-        L = E_0.shape[1]
-        Lp, uniform = _label_pad(L), None
-        if Lp != L:                          # (see _label_pad: w // 6 labels are rarely a multiple of 4)
-            E_0 = _pad_energies(E_0, Lp)
-            Mu, uniform = _padded_mu(Mu, Lp, E_0.device)
-        Q = phl.softmax_neg_add(E_0)
-        fused = True
-        for it in range(niters):
-            if fused:
-                X = W @ Q
-                if torch.is_grad_enabled() and X.requires_grad:
-                    # W itself is being differentiated: the raw-pointer kernels would drop its graph (and
-                    # overwrite a tensor LatticeFilter saved for backward) -> differentiable path from here on
-                    fused = False
-                    if fused_grad and E_0.shape[1] <= 512:      # (the Functions write fresh tensors: nothing saved is overwritten)
-                        Q = _mean_field_infer_grad_loop(E_0, W, Mu, niters - it, uniform, X)
-                        break
-                    Q = F.softmax(-(E_0 + X @ Mu), dim=1)
-                    continue
-                if not (X.is_cuda and X.dtype == torch.float32 and X.stride(1) == 1):
-                    X = X.to(E_0.device, torch.float32).contiguous()
-                Q = phl.compat_softmax(E_0, X, Mu, out=Q, uniform=uniform)
-            else:
-                Q = F.softmax(-(E_0 + (W @ Q) @ Mu), dim=1)
-        return Q if Lp == L else Q[:, :L].contiguous()
+    differentiable = fused_grad and _fused_grad_ok(E_0, Mu)
+    if differentiable or _fused_ok(E_0, Mu):
+        return _fused_infer(E_0 if E_0.stride(1) == 1 else E_0.contiguous(), lambda Q: W @ Q, Mu, niters, differentiable,
+                            fused_grad)
     if _staged_ok(E_0, W, Mu):
         return _mean_field_infer_staged(E_0, W, Mu, niters)
     Q = F.softmax(-E_0, dim=1)
@@ -158,44 +178,10 @@ def mean_field_infer(E_0, W, Mu, niters=10, fused_grad=False):
 
 def _fused_grad_ok(E_0, Mu):
     """The differentiable device loop: CUDA fp32 [n, L] unaries (at most 512 labels: the backward kernels' range), a fp32
-    Mu, and a gradient asked of E_0 or Mu (a gradient that only W asks for is found in the loop of mean_field_infer, at its
-    first ``W @ Q``)."""
+    Mu, and a gradient asked of E_0 or Mu (a gradient that only W asks for is found in the device loop, at its first
+    ``W @ Q``)."""
     return (E_0.is_cuda and E_0.dtype == torch.float32 and E_0.dim() == 2 and torch.is_tensor(Mu) and Mu.dtype == torch.float32
             and Mu.is_cuda and _label_pad(E_0.shape[1]) <= 512 and torch.is_grad_enabled() and (E_0.requires_grad or Mu.requires_grad))
-
-
-def _mean_field_infer_grad_loop(E_0, W, Mu, niters, uniform, X=None):
-    """``niters`` iterations on the differentiable fused Functions from the Q behind X = W @ Q (X given) or from
-    softmax(-E_0).  E_0, Mu: already padded to the label count the kernels take."""
-    import phl
-
-    Q = None if X is not None else phl.softmax_neg_add_fn(E_0)
-    for _ in range(niters):
-        if X is None:
-            X = W @ Q
-        if not (X.is_cuda and X.dtype == torch.float32 and X.stride(1) == 1):
-            X = X.to(E_0.device, torch.float32).contiguous()
-        Q = phl.compat_softmax_fn(E_0, X, Mu, False, uniform)
-        X = None
-    return Q
-
-
-def _mean_field_infer_grad(E_0, W, Mu, niters):
-    """mean_field_infer with autograd on the fused kernels: label padding through differentiable ops (F.pad of E_0 with
-    _PAD_ENERGY, of Mu with zeros), Q = phl.SoftmaxNegAdd, then per iteration X = W @ Q with W's own graph and
-    Q = phl.CompatSoftmax.  Every tensor is fresh: nothing autograd saved is written again."""
-    import phl
-
-    L = E_0.shape[1]
-    Lp, uniform = _label_pad(L), None
-    if E_0.stride(1) != 1:
-        E_0 = E_0.contiguous()
-    if Lp != L:
-        uniform = phl._mu_uniform(Mu.detach()) or False
-        E_0 = F.pad(E_0, (0, Lp - L), value=_PAD_ENERGY)
-        Mu = F.pad(Mu, (0, Lp - L, 0, Lp - L))
-    Q = _mean_field_infer_grad_loop(E_0, W, Mu, niters, uniform)
-    return Q if Lp == L else Q[:, :L].contiguous()
 
 
 def _staged_ok(E_0, W, Mu):
@@ -220,17 +206,9 @@ def _mean_field_infer_staged(E_0, W, Mu, niters):
     dev = W.ref.device if W.ref.is_cuda else torch.device("cuda", torch.cuda.current_device())
     lat = phl.lattice_for(W.ref.detach())                 # CPU ref: built on the current device; GPU ref: where it lives
     E0d = phl.to_device(E_0.detach().contiguous(), dev)
-    L = E0d.shape[1]
-    Lp, uniform, Mu = _label_pad(L), None, Mu.detach()
-    if Lp != L:
-        E0d = _pad_energies(E0d, Lp)
-        Mu, uniform = _padded_mu(Mu, Lp, dev)
-    Q = phl.softmax_neg_add(E0d)
-    X = torch.empty_like(Q) if niters > 0 else None
-    for _ in range(niters):
-        lat.filter(Q, subtract_input=True, out=X)
-        Q = phl.compat_softmax(E0d, X, Mu, out=Q, uniform=uniform)   # (Mu^T is cached per Mu tensor, wherever it lives)
-    return phl.to_host(Q if Lp == L else Q[:, :L].contiguous())
+    X = torch.empty((E0d.shape[0], _label_pad(E0d.shape[1])), dtype=torch.float32, device=dev)
+    Q = _fused_infer(E0d, lambda Q: lat.filter(Q, subtract_input=True, out=X), Mu.detach(), niters)
+    return phl.to_host(Q)
 
 
 def potts(num_classes):
@@ -334,21 +312,12 @@ def _mean_field_nchw_fused(E0, refs, M, niters):
             st = _nchw_streams[(dev, lane)] = torch.cuda.Stream(device=dev)
         st.wait_stream(cur)
         with torch.cuda.device(dev), torch.cuda.stream(st):
-            e_b, r_b = E0[b], refs[b].detach()
+            e_b, r_b, Mb = E0[b], refs[b].detach(), M
             if dev != home:
-                e_b, r_b = e_b.to(dev, non_blocking=True), r_b.to(dev, non_blocking=True)
-            Lp = _label_pad(L)               # (label counts that are not a multiple of 4 run padded: see _label_pad)
-            e0 = torch.empty((n, L), dtype=torch.float32, device=dev) if Lp == L else \
-                torch.full((n, Lp), _PAD_ENERGY, dtype=torch.float32, device=dev)
-            phl.copy2d(e0[:, :L], e_b.reshape(L, n).t())                  # [L, n] channel-major -> [n, L]
+                e_b, r_b, Mb = e_b.to(dev, non_blocking=True), r_b.to(dev, non_blocking=True), M.to(dev)
+            e0, Mb, uniform = _pad_labels(e_b.reshape(L, n), Mb, channel_major=True)   # [L, n] channel-major -> [n, Lp]
             lat = phl.lattice_for(r_b.reshape(d, n).t(), device=dev)      # strided [n, d] view, no copy
-            Mb, uniform = (M if M.device == dev else M.to(dev)), None
-            if Lp != L:
-                Mb, uniform = _padded_mu(M, Lp, dev)
-            Q = phl.softmax_neg_add(e0)
-            for it in range(niters):
-                X = lat.filter(Q, subtract_input=True)
-                Q = phl.compat_softmax(e0, X, Mb, out=Q, logits=it == niters - 1, uniform=uniform)
+            Q = _device_loop(e0, lambda Q: lat.filter(Q, subtract_input=True), Mb, niters, uniform, logits=True)
             if dev == home:
                 phl.copy2d(out[b].reshape(L, n).t(), Q[:, :L])
             else:
@@ -365,7 +334,7 @@ def _mean_field_nchw_fused(E0, refs, M, niters):
 
 def _mean_field_nchw_grad(E0, refs, M, niters):
     """The NCHW iteration of CRFasRNN under autograd on the library's kernels, image by image pixel-major on the current
-    stream: e0 = E0[b] as [n, L] (padded by F.pad where L is off the kernels' grid), Q = phl.SoftmaxNegAdd, then per
+    stream: e0 = E0[b] as [n, L] (padded by _pad_labels where L is off the kernels' grid), Q = phl.SoftmaxNegAdd, then per
     iteration, in the reference's order E = E0 + W(Mu(Q)) (crf_module.py:97-99): Y = Q @ M (phl.CompatProduct, matrix
     cores), G = LatticeFilter(Y, ref_b) - Y with the guide's graph kept, Q = phl.SoftmaxNegAdd(e0, G) -- the logits
     -(e0 + G) on the last one -- and back to NCHW.  M is the differentiable compatibility matrix (gradients reach the Mu
@@ -377,13 +346,10 @@ def _mean_field_nchw_grad(E0, refs, M, niters):
 
     bs, L, h, w = E0.shape
     d, n = refs.shape[1], h * w
-    Lp = _label_pad(L)
-    Mp = M if Lp == L else F.pad(M, (0, Lp - L, 0, Lp - L))
+    E0p, Mp, _ = _pad_labels(E0.reshape(bs, L, n).transpose(1, 2), M, differentiable=True, structure=False)   # [bs, n, Lp]
     outs = []
     for b in range(bs):
-        e0 = E0[b].reshape(L, n).t().contiguous()
-        if Lp != L:
-            e0 = F.pad(e0, (0, Lp - L), value=_PAD_ENERGY)
+        e0 = E0p[b].contiguous()
         ref_b = refs[b].reshape(d, n).t().contiguous()
         Q = phl.softmax_neg_add_fn(e0)
         for it in range(niters):

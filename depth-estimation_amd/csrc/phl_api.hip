@@ -384,6 +384,22 @@ int phl_hip_fail(hipError_t e, const char *what, const char *file, int line)
     return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? PHL_ERR_NO_DEVICE : PHL_ERR_HIP;
 }
 
+int phl_raise_lds_limit(const void *kernel, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return PHL_OK;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> allowed;
+    int dev = 0;
+    PHL_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu);
+    size_t &have = allowed[std::make_pair(dev, kernel)];
+    if (bytes > have) {
+        PHL_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        have = bytes;
+    }
+    return PHL_OK;
+}
+
 // an empty handle (phl_sub_lattice fills it): same initial state phl_build_ex gives one
 int phl_lattice_blank(phl_lattice **out, int device, int d, int64_t n)
 {

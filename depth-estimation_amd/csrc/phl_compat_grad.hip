@@ -262,8 +262,6 @@ inline unsigned grad_rows_grid(int64_t n)
     return (unsigned)(b < 1 ? 1 : b);
 }
 
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // the slab geometry of k_compat_grad_mu for L labels: waves per row band (NWC), row bands per slab (NWR), slabs
 struct MuGeom {
     int nwc, nwr, S, nslabs;
@@ -306,8 +304,7 @@ int phl_uniform_compat_grad(const float *Q, int64_t q_rs, const float *gQ, int64
                             int64_t d_rs, float *gX, int64_t x_rs, int64_t n, int L, phl_stream stream)
 {
     if (n < 0 || L < 1 || (n > 0 && (!gQ || !dE))) { phl_set_error("phl_uniform_compat_grad: bad arguments"); return PHL_ERR_INVALID; }
-    if (!grad_l_ok(L) || g_rs % 4 || d_rs % 4 || (Q && q_rs % 4) || (gX && x_rs % 4) || !al16(Q) || !al16(gQ) || !al16(dE) ||
-        !al16(gX)) {
+    if (!grad_l_ok(L) || !phl_rows16(gQ, g_rs) || !phl_rows16(dE, d_rs) || (Q && !phl_rows16(Q, q_rs)) || (gX && !phl_rows16(gX, x_rs))) {
         phl_set_error("phl_uniform_compat_grad / phl_softmax_neg_grad: needs L %% 4 == 0, L <= 512 and 16-byte aligned rows (L=%d)", L);
         return PHL_ERR_UNSUPPORTED;
     }
@@ -335,7 +332,7 @@ int phl_compat_grad_x(const float *dE, int64_t de_rs, const float *Mu, float sca
                       phl_stream stream)
 {
     if (n < 0 || L < 1 || (n > 0 && (!dE || !Mu || !gX))) { phl_set_error("phl_compat_grad_x: bad arguments"); return PHL_ERR_INVALID; }
-    if (!grad_l_ok(L) || de_rs % 4 || gx_rs % 4 || !al16(dE) || !al16(Mu) || !al16(gX)) {
+    if (!grad_l_ok(L) || !phl_rows16(dE, de_rs) || !phl_rows16(gX, gx_rs) || !phl_al16(Mu)) {
         phl_set_error("phl_compat_grad_x: needs L %% 4 == 0, L <= 512 and 16-byte aligned rows (L=%d)", L);
         return PHL_ERR_UNSUPPORTED;
     }
@@ -358,7 +355,7 @@ int phl_compat_mu_grad(const float *X, int64_t x_rs, const float *dE, int64_t de
                        float *gMu, int accumulate, phl_stream stream)
 {
     if (n < 0 || L < 1 || !gMu || !workspace || (n > 0 && (!X || !dE))) { phl_set_error("phl_compat_mu_grad: bad arguments"); return PHL_ERR_INVALID; }
-    if (!grad_l_ok(L) || x_rs % 4 || de_rs % 4 || !al16(X) || !al16(dE) || !al16(workspace)) {
+    if (!grad_l_ok(L) || !phl_rows16(X, x_rs) || !phl_rows16(dE, de_rs) || !phl_al16(workspace)) {
         phl_set_error("phl_compat_mu_grad: needs L %% 4 == 0, L <= 512 and 16-byte aligned rows (L=%d)", L);
         return PHL_ERR_UNSUPPORTED;
     }

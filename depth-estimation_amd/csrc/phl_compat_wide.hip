@@ -28,7 +28,6 @@
 //    consumed, nothing stored (only the last K chunk and the last two label tiles can hold padding: Lp - L < 32).
 //  * the last n % 64 rows go to k_compat_wide_tail (one workgroup per pixel, f64 dot product from mu_t).
 #include <math.h>
-#include <atomic>
 
 #include "phl_internal.h"
 #include "phl_compat_common.h"
@@ -303,19 +302,9 @@ int phl_compat_wide_softmax(const float *E0, int64_t e_rs, const float *X, int64
     const int Lp = (L + 31) / 32 * 32;
     const int64_t ntiles = n / CW_TILE, n_main = ntiles * CW_TILE;
     const size_t lds = (size_t)3 * CW_PIECE;     // ring of three pieces: 72 KiB, two workgroups per CU
-    int dev = 0;
-    PHL_HIP(hipGetDevice(&dev));
-    // more than 64 KiB of dynamic LDS needs the attribute, once per device and instance (not per launch: the call is
-    // not a stream operation, and a launch may sit inside a stream capture)
 #define PHL_CW_LAUNCH(NT_, LG_)                                                                                           \
     do {                                                                                                                  \
-        static std::atomic<unsigned long long> ready{0};                                                                  \
-        const unsigned long long bit = 1ull << (dev & 63);                                                                \
-        if (!(ready.load(std::memory_order_acquire) & bit)) {                                                             \
-            PHL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_compat_wide<NT_, LG_>),                         \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-            ready.fetch_or(bit, std::memory_order_release);                                                               \
-        }                                                                                                                 \
+        if (const int rc = phl_allow_lds(&k_compat_wide<NT_, LG_>, lds)) return rc;                                       \
         k_compat_wide<NT_, LG_><<<dim3((unsigned)ntiles), dim3(256), lds, st>>>(                                          \
             E0, e_rs, X, x_rs, reinterpret_cast<const unsigned char *>(planes), out, o_rs, L);                            \
     } while (0)

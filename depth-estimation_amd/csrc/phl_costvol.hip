@@ -122,8 +122,7 @@ int launch(const float *img1, const float *img2, int h, int w, int C, int L, flo
 {
     constexpr int ROWS = TY + 2 * R, COLS = TX + 2 * R, W2 = COLS + DC;
     const size_t lds = sizeof(float) * (4 * (size_t)ROWS * COLS + 4 * (size_t)ROWS * W2 + COLS + (size_t)ROWS * TX * DC);
-    if (lds > 64 * 1024)
-        PHL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_cost_volume<R, CRIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (const int rc = phl_allow_lds(k_cost_volume<R, CRIT>, lds)) return rc;
     const dim3 grid((unsigned)((w + TX - 1) / TX), (unsigned)((h + TY - 1) / TY), (unsigned)((L + DC - 1) / DC));
     k_cost_volume<R, CRIT><<<grid, dim3(ROWS * DC), lds, st>>>(img1, img2, h, w, C, L, out, out_rs);
     PHL_HIP(hipGetLastError());

@@ -205,6 +205,21 @@ int phl_hip_fail(hipError_t e, const char *what, const char *file, int line);
         if (e__ != hipSuccess) return phl_hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
 
+// Raise kernel K's dynamic-LDS limit on the current device to at least `bytes` (phl_api.hip).  A no-op at or below the
+// default 64 KiB; at most one attribute call per (device, kernel, larger size), never per launch: the call is not a stream
+// operation, and a launch may sit inside a stream capture.
+int phl_raise_lds_limit(const void *kernel, size_t bytes);
+template <typename K>
+inline int phl_allow_lds(K kernel, size_t bytes)
+{
+    return phl_raise_lds_limit(reinterpret_cast<const void *>(kernel), bytes);
+}
+
+// argument checks of the entry points: a 16-byte aligned address (null counts as aligned), and fp32 rows of 16-byte
+// pieces (aligned base, row stride a multiple of 4 floats)
+inline bool phl_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool phl_rows16(const void *p, int64_t rs) { return rs % 4 == 0 && phl_al16(p); }
+
 // cached device blocks for the arrays a lattice owns (phl_api.hip)
 hipError_t phl_dev_malloc(void **p, size_t bytes);
 hipError_t phl_dev_free(void *p);

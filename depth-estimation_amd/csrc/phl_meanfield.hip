@@ -9,7 +9,6 @@
 //   k_expected_value    out[p] = sum_c Q[p,c] * labels[c]                (Experiments/DenseCrf.ipynb cell 11)
 #include <math.h>
 #include <type_traits>
-#include <atomic>
 
 #include "phl_internal.h"
 #include "phl_compat_common.h"
@@ -1078,8 +1077,7 @@ int phl_softmax_neg_add(const float *E0, int64_t e_rs, const float *G, int64_t g
     if (n < 0 || L < 1 || (n > 0 && (!E0 || !out))) { phl_set_error("phl_softmax_neg_add: bad arguments"); return PHL_ERR_INVALID; }
     if (n == 0) return PHL_OK;
     hipStream_t st = (hipStream_t)stream;
-    const bool v4 = L % 4 == 0 && e_rs % 4 == 0 && o_rs % 4 == 0 && (!G || g_rs % 4 == 0) &&
-                    ((reinterpret_cast<uintptr_t>(E0) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(G)) & 15) == 0;
+    const bool v4 = L % 4 == 0 && phl_rows16(E0, e_rs) && phl_rows16(out, o_rs) && (!G || phl_rows16(G, g_rs));
     const unsigned grid = rows_grid(n);
     if (v4 && L <= 256) k_softmax_neg_add<1><<<dim3(grid), dim3(256), 0, st>>>(E0, e_rs, G, g_rs, out, o_rs, n, L);
     else if (v4 && L <= 512) k_softmax_neg_add<2><<<dim3(grid), dim3(256), 0, st>>>(E0, e_rs, G, g_rs, out, o_rs, n, L);
@@ -1094,8 +1092,7 @@ int phl_uniform_compat_softmax(const float *E0, int64_t e_rs, const float *X, in
 {
     if (n < 0 || L < 1 || (n > 0 && (!E0 || !X || !out))) { phl_set_error("phl_uniform_compat_softmax: bad arguments"); return PHL_ERR_INVALID; }
     if (n == 0) return PHL_OK;
-    if (L % 4 || L > 1024 || x_rs % 4 || e_rs % 4 || o_rs % 4 ||
-        ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(E0) | reinterpret_cast<uintptr_t>(out)) & 15)) {
+    if (L % 4 || L > 1024 || !phl_rows16(X, x_rs) || !phl_rows16(E0, e_rs) || !phl_rows16(out, o_rs)) {
         phl_set_error("phl_uniform_compat_softmax: needs L %% 4 == 0, L <= 1024 and 16-byte aligned E0 / X / out rows (L=%d)", L);
         return PHL_ERR_UNSUPPORTED;
     }
@@ -1120,8 +1117,8 @@ int phl_compat_softmax(const float *E0, int64_t e_rs, const float *X, int64_t x_
 {
     if (n < 0 || L < 1 || (n > 0 && (!E0 || !X || !MuT || !out))) { phl_set_error("phl_compat_softmax: bad arguments"); return PHL_ERR_INVALID; }
     if (n == 0) return PHL_OK;
-    if (L % 4 || L > 256 || x_rs % 4 || e_rs % 4 || o_rs % 4 || x_rs >= (1 << 24) || e_rs >= (1 << 24) || o_rs >= (1 << 24) ||
-        ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(MuT) | reinterpret_cast<uintptr_t>(E0) | reinterpret_cast<uintptr_t>(out)) & 15)) {
+    if (L % 4 || L > 256 || !phl_rows16(X, x_rs) || !phl_rows16(E0, e_rs) || !phl_rows16(out, o_rs) || !phl_al16(MuT) ||
+        x_rs >= (1 << 24) || e_rs >= (1 << 24) || o_rs >= (1 << 24)) {
         phl_set_error("phl_compat_softmax: needs L %% 4 == 0, L <= 256 and 16-byte aligned E0 / X / out rows (L=%d)", L);
         return PHL_ERR_UNSUPPORTED;
     }
@@ -1149,19 +1146,9 @@ int phl_compat_softmax(const float *E0, int64_t e_rs, const float *X, int64_t x_
         hipMemset(tl_buf, 0, 512 * 64 * 8);
     }
 #endif
-    // more than 64 KiB of dynamic LDS needs the attribute, once per device and instance (not per launch: the call is
-    // not a stream operation, and a launch may sit inside a stream capture)
-    int dev = 0;
-    PHL_HIP(hipGetDevice(&dev));
 #define PHL_CS_LAUNCH(NT_, LG_, PD_)                                                                                    \
     do {                                                                                                                  \
-        static std::atomic<unsigned long long> ready{0};                                                                  \
-        const unsigned long long bit = 1ull << (dev & 63);                                                                \
-        if (lds > 64 * 1024 && !(ready.load(std::memory_order_acquire) & bit)) {                                          \
-            PHL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_compat_softmax<NT_, LG_, PD_>),                 \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-            ready.fetch_or(bit, std::memory_order_release);                                                               \
-        }                                                                                                                 \
+        if (const int rc = phl_allow_lds(&k_compat_softmax<NT_, LG_, PD_>, lds)) return rc;                             \
         k_compat_softmax<NT_, LG_, PD_><<<dim3(grid), dim3(512), lds, st>>>(E0, e_rs, X, x_rs, MuT, out, o_rs, n, L);     \
     } while (0)
 #define PHL_CS(NT_)                                                                                                       \
@@ -1195,7 +1182,7 @@ size_t phl_compat_planes_bytes(int L)
 int phl_compat_prepare(const float *MuT, int L, void *planes, phl_stream stream)
 {
     if (!phl_compat_planes_bytes(L)) { phl_set_error("phl_compat_prepare: the split kernels take 128 < L <= 512, L %% 4 == 0 (L=%d)", L); return PHL_ERR_UNSUPPORTED; }
-    if (!MuT || !planes || ((reinterpret_cast<uintptr_t>(MuT) | reinterpret_cast<uintptr_t>(planes)) & 15)) { phl_set_error("phl_compat_prepare: bad arguments"); return PHL_ERR_INVALID; }
+    if (!MuT || !planes || !phl_al16(MuT) || !phl_al16(planes)) { phl_set_error("phl_compat_prepare: bad arguments"); return PHL_ERR_INVALID; }
     if (L > 256) return phl_compat_wide_prepare(MuT, L, planes, (hipStream_t)stream);
     k_compat_planes<<<dim3(16 * 8 * 64 / 256), dim3(256), 0, (hipStream_t)stream>>>(MuT, (L + 31) / 32 * 32, reinterpret_cast<u32x4 *>(planes));
     PHL_HIP(hipGetLastError());
@@ -1207,9 +1194,8 @@ int phl_compat_softmax_split(const float *E0, int64_t e_rs, const float *X, int6
 {
     if (n < 0 || L < 1 || (n > 0 && (!E0 || !X || !MuT || !planes || !out))) { phl_set_error("phl_compat_softmax_split: bad arguments"); return PHL_ERR_INVALID; }
     if (n == 0) return PHL_OK;
-    if (!phl_compat_planes_bytes(L) || x_rs % 4 || e_rs % 4 || o_rs % 4 || x_rs >= (1 << 24) || e_rs >= (1 << 24) || o_rs >= (1 << 24) ||
-        ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(MuT) | reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(E0) |
-          reinterpret_cast<uintptr_t>(out)) & 15)) {
+    if (!phl_compat_planes_bytes(L) || !phl_rows16(X, x_rs) || !phl_rows16(E0, e_rs) || !phl_rows16(out, o_rs) || !phl_al16(MuT) ||
+        !phl_al16(planes) || x_rs >= (1 << 24) || e_rs >= (1 << 24) || o_rs >= (1 << 24)) {
         phl_set_error("phl_compat_softmax_split: needs 128 < L <= 512, L %% 4 == 0 and 16-byte aligned E0 / X / out rows (L=%d)", L);
         return PHL_ERR_UNSUPPORTED;
     }
@@ -1221,17 +1207,9 @@ int phl_compat_softmax_split(const float *E0, int64_t e_rs, const float *X, int6
     const unsigned grid = (unsigned)(npairs < 256 ? npairs : 256);
     const size_t lds = (size_t)4 * CSP_PIECE + CSP_XR * 4 * 1024 * sizeof(float);     // ring of four pieces + X ring: 144 KiB
     const bool logits = (flags & PHL_COMPAT_LOGITS) != 0;
-    int dev = 0;
-    PHL_HIP(hipGetDevice(&dev));
 #define PHL_CSP_LAUNCH(LG_, PD_)                                                                                          \
     do {                                                                                                                  \
-        static std::atomic<unsigned long long> ready{0};                                                                  \
-        const unsigned long long bit = 1ull << (dev & 63);                                                                \
-        if (!(ready.load(std::memory_order_acquire) & bit)) {                                                             \
-            PHL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_compat_split<LG_, PD_>),                        \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-            ready.fetch_or(bit, std::memory_order_release);                                                               \
-        }                                                                                                                 \
+        if (const int rc = phl_allow_lds(&k_compat_split<LG_, PD_>, lds)) return rc;                                      \
         k_compat_split<LG_, PD_><<<dim3(grid), dim3(512), lds, st>>>(E0, e_rs, X, x_rs, reinterpret_cast<const unsigned char *>(planes), out, o_rs, n, L); \
     } while (0)
     if (n_main > 0) {
@@ -1252,7 +1230,7 @@ int phl_compat_softmax_split(const float *E0, int64_t e_rs, const float *X, int6
 
 int phl_stream_copy(const float *src, float *dst, int64_t n_floats, phl_stream stream)
 {
-    if (n_floats < 0 || n_floats % 4 || ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15)) { phl_set_error("phl_stream_copy: needs 16-byte aligned buffers, n % 4 == 0"); return PHL_ERR_INVALID; }
+    if (n_floats < 0 || n_floats % 4 || !phl_al16(src) || !phl_al16(dst)) { phl_set_error("phl_stream_copy: needs 16-byte aligned buffers, n % 4 == 0"); return PHL_ERR_INVALID; }
     if (n_floats == 0) return PHL_OK;
     int64_t blocks = (n_floats / 4 + 256 * 4 - 1) / (256 * 4);
     if (blocks > 65536) blocks = 65536;

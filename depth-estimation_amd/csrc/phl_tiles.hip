@@ -1746,20 +1746,8 @@ inline slice_cfg plan_slice(const phl_lattice *lat, int vd)
 template <typename K>
 inline int allow_lds(K kernel, size_t bytes, int threads = 512)
 {
-    if (bytes > 64 * 1024) {
-        // once per (device, kernel, size): the attribute call is not free and this runs on every launch
-        static std::mutex mu;
-        static std::map<std::pair<int, const void *>, size_t> allowed;
-        int dev = 0;
-        PHL_HIP(hipGetDevice(&dev));
-        const void *fn = reinterpret_cast<const void *>(kernel);
-        std::lock_guard<std::mutex> lk(mu);
-        size_t &have = allowed[std::make_pair(dev, fn)];
-        if (bytes > have) {
-            PHL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-            have = bytes;
-        }
-    }
+    const int rc = phl_allow_lds(kernel, bytes);
+    if (rc != PHL_OK) return rc;
     static const bool dbg = getenv("PHL_DEBUG") != nullptr;
     if (dbg) {
         int nb = -1;

@@ -526,6 +526,22 @@ def _rowmajor(t):
     return t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1
 
 
+def _aligned(t):
+    """A row operand the compat kernels take as it is: fp32 CUDA [n, L], unit channel stride, 16-byte aligned rows."""
+    return _rowmajor(t) and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _launch(device, name, *args):
+    """Library function ``name`` on ``device`` with its current stream as the last argument; raises on a failed status.
+    Looked up on every call, so that a replaced attribute of the library (a test's spy) is the one that runs."""
+    with torch.cuda.device(device):
+        _check(getattr(load_library(), name)(*args, _stream(device)))
+
+
 def softmax_neg_add(E0, G=None, out=None):
     """softmax(-(E0 + G), dim=1) in one pass over HBM (G optional).  CUDA fp32 [n, L] only."""
     if not _rowmajor(E0) or (G is not None and (not _rowmajor(G) or G.shape != E0.shape)):
@@ -533,76 +549,113 @@ def softmax_neg_add(E0, G=None, out=None):
     n, L = E0.shape
     if out is None:
         out = torch.empty((n, L), dtype=torch.float32, device=E0.device)
-    with torch.cuda.device(E0.device):
-        _check(load_library().phl_softmax_neg_add(
-            C.c_void_p(E0.data_ptr()), E0.stride(0), C.c_void_p(G.data_ptr()) if G is not None else None,
-            G.stride(0) if G is not None else 0, C.c_void_p(out.data_ptr()), out.stride(0), n, L, _stream(E0.device)))
+    _launch(E0.device, "phl_softmax_neg_add", _ptr(E0), E0.stride(0), _ptr(G), G.stride(0) if G is not None else 0, _ptr(out),
+            out.stride(0), n, L)
     return out
 
 
-_mu_t_cache = {}
-
-
-def _mu_transposed(Mu, device):
-    """Mu^T as a dense fp32 device tensor padded to the MFMA tile width, cached per (storage, version): Mu is
-    fixed during inference."""
-    key = (Mu.data_ptr(), Mu._version, tuple(Mu.shape), tuple(Mu.stride()), str(device))
-    hit = _mu_t_cache.get(key)
-    if hit is None:
-        if len(_mu_t_cache) > 8:
-            _mu_t_cache.clear()
-        L = Mu.shape[0]
-        Lp = (L + 31) // 32 * 32                 # the kernel's tile width: zero padding beyond L
-        mt = torch.zeros((Lp, Lp), dtype=torch.float32, device=device)
-        mt[:L, :L] = Mu.detach().to(device, torch.float32).t()
-        if not torch.cuda.is_current_stream_capturing():     # cached across calls: complete before another stream can use it
-            torch.cuda.current_stream(device).synchronize()
-        hit = _mu_t_cache[key] = (mt, Mu)        # keeps Mu alive
-    return hit[0]
-
-
-_mu_planes_cache = {}
-
-
-def _mu_planes(Mu, mu_t, device):
-    """The compatibility matrix as the split kernel reads it (phl_compat_prepare), cached like Mu^T."""
-    key = (Mu.data_ptr(), Mu._version, tuple(Mu.shape), tuple(Mu.stride()), str(device))
-    hit = _mu_planes_cache.get(key)
-    if hit is None:
-        if len(_mu_planes_cache) > 8:
-            _mu_planes_cache.clear()
-        lib = load_library()
-        planes = torch.empty((lib.phl_compat_planes_bytes(Mu.shape[0]),), dtype=torch.uint8, device=device)
-        with torch.cuda.device(device):
-            _check(lib.phl_compat_prepare(C.c_void_p(mu_t.data_ptr()), Mu.shape[0], C.c_void_p(planes.data_ptr()), _stream(device)))
-            # cached across calls, and a later call may come on another stream: finished before anyone else can see it
-            if not torch.cuda.is_current_stream_capturing():
-                torch.cuda.current_stream(device).synchronize()
-        hit = _mu_planes_cache[key] = (planes, Mu, mu_t)
-    return hit[0]
-
-
-_mu_uniform_cache = {}
-
-
-def _mu_uniform(Mu):
+def _potts_family(Mu):
     """(alpha, beta) if Mu == alpha * ones + beta * eye exactly (the Potts family: the reference's ``potts`` layer is
-    (1, -1), crf_module.py:55-64), else None.  One device -> host read per (storage, version) of Mu."""
-    key = (Mu.data_ptr(), Mu._version, tuple(Mu.shape), tuple(Mu.stride()))
-    if key in _mu_uniform_cache:
-        return _mu_uniform_cache[key][0]
-    if len(_mu_uniform_cache) > 8:
-        _mu_uniform_cache.clear()
+    (1, -1), crf_module.py:55-64), else None.  One device -> host read."""
     L = Mu.shape[0]
-    res = None
     m = Mu.detach().to(torch.float32)
     if L >= 2:
         alpha = m[0, 1]
         beta = m[0, 0] - alpha
         if bool(((m - alpha) - beta * torch.eye(L, dtype=torch.float32, device=m.device) == 0).all()) and bool(torch.isfinite(m).all()):
-            res = (float(alpha), float(beta))
-    _mu_uniform_cache[key] = (res, Mu)           # keeps Mu alive
-    return res
+            return (float(alpha), float(beta))
+    return None
+
+
+class _MuForms:
+    """The forms of one compatibility matrix Mu the kernels read, each made on first use: Mu is fixed during inference.
+    Holds Mu, so that its storage address cannot be recycled while the record is cached."""
+
+    def __init__(self, Mu):
+        self.Mu = Mu.detach()
+        self._forms = {}
+
+    def _form(self, key, device, make):
+        hit = self._forms.get(key)
+        if hit is None:
+            with torch.cuda.device(device):
+                hit = make()
+                # cached across calls, and a later call may come on another stream: finished before anyone else can see it
+                if not torch.cuda.is_current_stream_capturing():
+                    torch.cuda.current_stream(device).synchronize()
+            self._forms[key] = hit
+        return hit
+
+    def uniform(self):
+        """_potts_family(Mu), on Mu's own device."""
+        if "uniform" not in self._forms:
+            self._forms["uniform"] = _potts_family(self.Mu)
+        return self._forms["uniform"]
+
+    def mu_t(self, device):
+        """Mu^T as a dense fp32 device tensor padded to the MFMA tile width (zero beyond L)."""
+        def make():
+            L = self.Mu.shape[0]
+            Lp = (L + 31) // 32 * 32
+            mt = torch.zeros((Lp, Lp), dtype=torch.float32, device=device)
+            mt[:L, :L] = self.Mu.to(device, torch.float32).t()
+            return mt
+        return self._form(("mu_t", str(device)), device, make)
+
+    def planes(self, device):
+        """Mu as the split kernels read it (phl_compat_prepare)."""
+        def make():
+            L = self.Mu.shape[0]
+            planes = torch.empty((load_library().phl_compat_planes_bytes(L),), dtype=torch.uint8, device=device)
+            _launch(device, "phl_compat_prepare", _ptr(self.mu_t(device)), L, _ptr(planes))
+            return planes
+        return self._form(("planes", str(device)), device, make)
+
+    def padded(self, Lp, device):
+        """(Mu with zero rows / columns up to Lp, the Potts-family structure of the ORIGINAL matrix or False): the padded
+        matrix no longer shows it (crf_module._pad_labels)."""
+        def make():
+            L = self.Mu.shape[0]
+            mp = torch.zeros((Lp, Lp), dtype=torch.float32, device=device)
+            mp[:L, :L] = self.Mu.to(device, torch.float32)
+            return mp
+        return self._form(("padded", Lp, str(device)), device, make), self.uniform() or False
+
+
+_mu_cache = {}
+
+
+def _mu_forms(Mu):
+    """The _MuForms record of Mu, one per (storage, version, shape, strides)."""
+    key = (Mu.data_ptr(), Mu._version, tuple(Mu.shape), tuple(Mu.stride()))
+    hit = _mu_cache.get(key)
+    if hit is None:
+        if len(_mu_cache) > 8:
+            _mu_cache.clear()
+        hit = _mu_cache[key] = _MuForms(Mu)
+    return hit
+
+
+def _mu_uniform(Mu):
+    """(alpha, beta) if Mu == alpha * ones + beta * eye exactly, else None; read once per (storage, version) of Mu."""
+    return _mu_forms(Mu).uniform()
+
+
+def _compat_route(L, operands, Mu, uniform=None, structure=True, arith="f32"):
+    """(route, uniform) of the compatibility + softmax step for these operands: "uniform" (Potts family, one streaming
+    pass), "split", "f32" (the fused MFMA kernels) or "gemm" (library GEMM + fused add / softmax).
+    uniform: None = look at Mu; (alpha, beta) = the caller knows it is alpha * ones + beta * eye on the labels that matter
+    (a Mu padded with zero rows / columns for labels of probability 0: crf_module._pad_labels); False = it is not."""
+    aligned = L % 4 == 0 and all(_aligned(t) for t in operands)
+    if uniform is None:
+        uniform = _mu_uniform(Mu) if (structure and aligned and L <= 1024) else None
+    elif uniform is False or not (structure and aligned and L <= 1024):
+        uniform = None
+    if uniform is not None:
+        return "uniform", uniform
+    if aligned and L <= 512 and arith == "split" and load_library().phl_compat_planes_bytes(L):
+        return "split", None
+    return ("f32" if aligned and L <= 256 else "gemm"), None
 
 
 def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None, uniform=None):
@@ -617,7 +670,8 @@ def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None
     split three ways, six partial products, f32 accumulation (phl_compat_softmax_split: a 256-label tile for
     128 < L <= 256, a row of L rounded up to 32 for 256 < L <= 512; the same accuracy against float64, 3/8 of the matrix
     time).  Default: "split" for L > 176 -- below that the f32 kernel is bound by its bytes as well and computes no
-    padding -- unless PHL_COMPAT_ARITH names one of the two.  Above 256 labels "f32" keeps the library GEMM route."""
+    padding -- unless PHL_COMPAT_ARITH names one of the two.  Above 256 labels "f32" keeps the library GEMM route.
+    uniform: see _compat_route."""
     if arith is None:
         arith = os.environ.get("PHL_COMPAT_ARITH") or ("split" if E0.shape[-1] > 176 else "f32")
     if arith not in ("f32", "split"):
@@ -627,46 +681,31 @@ def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None
     n, L = E0.shape
     if out is None:
         out = torch.empty((n, L), dtype=torch.float32, device=E0.device)
-    aligned = L % 4 == 0 and all(t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in (X, E0, out))
-    # uniform: None = look at Mu; (alpha, beta) = the caller knows it is alpha * ones + beta * eye on the labels that matter
-    # (a Mu padded with zero rows / columns for labels of probability 0: crf_module._padded_mu); False = it is not
-    if uniform is None:
-        uniform = _mu_uniform(Mu) if (structure and aligned and L <= 1024) else None
-    elif uniform is False or not (structure and aligned and L <= 1024):
-        uniform = None
-    if uniform is not None:                      # Potts family: X @ Mu = alpha rowsum(X) + beta X, one streaming pass
-        with torch.cuda.device(E0.device):
-            _check(load_library().phl_uniform_compat_softmax(
-                C.c_void_p(E0.data_ptr()), E0.stride(0), C.c_void_p(X.data_ptr()), X.stride(0), C.c_float(uniform[0]),
-                C.c_float(uniform[1]), C.c_void_p(out.data_ptr()), out.stride(0), n, L, 1 if logits else 0, _stream(E0.device)))
-        return out
-    split = aligned and L <= 512 and arith == "split" and bool(load_library().phl_compat_planes_bytes(L))
-    if split or (aligned and L <= 256):
-        mu_t = _mu_transposed(Mu, E0.device)
-        if split:
-            planes = _mu_planes(Mu, mu_t, E0.device)
-            with torch.cuda.device(E0.device):
-                _check(load_library().phl_compat_softmax_split(
-                    C.c_void_p(E0.data_ptr()), E0.stride(0), C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(mu_t.data_ptr()),
-                    C.c_void_p(planes.data_ptr()), C.c_void_p(out.data_ptr()), out.stride(0), n, L, 1 if logits else 0,
-                    _stream(E0.device)))
-            return out
-        with torch.cuda.device(E0.device):
-            _check(load_library().phl_compat_softmax(
-                C.c_void_p(E0.data_ptr()), E0.stride(0), C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(mu_t.data_ptr()),
-                C.c_void_p(out.data_ptr()), out.stride(0), n, L, 1 if logits else 0, _stream(E0.device)))
-        return out
-    G = X @ Mu.to(E0.device, torch.float32)
-    if logits:
-        return out.copy_(-(E0 + G))
-    return softmax_neg_add(E0, G, out=out)
+    route, uniform = _compat_route(L, (X, E0, out), Mu, uniform, structure, arith)
+    dev, flags = E0.device, 1 if logits else 0
+    if route == "uniform":                       # Potts family: X @ Mu = alpha rowsum(X) + beta X, one streaming pass
+        _launch(dev, "phl_uniform_compat_softmax", _ptr(E0), E0.stride(0), _ptr(X), X.stride(0), C.c_float(uniform[0]),
+                C.c_float(uniform[1]), _ptr(out), out.stride(0), n, L, flags)
+    elif route == "split":
+        forms = _mu_forms(Mu)
+        _launch(dev, "phl_compat_softmax_split", _ptr(E0), E0.stride(0), _ptr(X), X.stride(0), _ptr(forms.mu_t(dev)),
+                _ptr(forms.planes(dev)), _ptr(out), out.stride(0), n, L, flags)
+    elif route == "f32":
+        _launch(dev, "phl_compat_softmax", _ptr(E0), E0.stride(0), _ptr(X), X.stride(0), _ptr(_mu_forms(Mu).mu_t(dev)),
+                _ptr(out), out.stride(0), n, L, flags)
+    else:
+        G = X @ Mu.to(dev, torch.float32)
+        if logits:
+            return out.copy_(-(E0 + G))
+        return softmax_neg_add(E0, G, out=out)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------
 # backward of the compatibility + softmax step (CRF training; include/phl.h, phl_compat_grad.hip)
 def _grad_operand(t, n, L):
     """fp32 CUDA [n, L] with unit channel stride and 16-byte aligned rows, as the backward kernels read it."""
-    if not (_rowmajor(t) and t.shape == (n, L) and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0):
+    if not (t.shape == (n, L) and _aligned(t)):
         t = t.to(torch.float32).clone(memory_format=torch.contiguous_format)
     return t
 
@@ -699,9 +738,7 @@ def softmax_neg_grad(Q, gQ, out=None):
     Q, gQ = _grad_operand(Q, n, L), _grad_operand(gQ, n, L)
     if out is None:
         out = torch.empty((n, L), dtype=torch.float32, device=Q.device)
-    with torch.cuda.device(Q.device):
-        _check(load_library().phl_softmax_neg_grad(C.c_void_p(Q.data_ptr()), Q.stride(0), C.c_void_p(gQ.data_ptr()), gQ.stride(0),
-                                                   C.c_void_p(out.data_ptr()), out.stride(0), n, L, _stream(Q.device)))
+    _launch(Q.device, "phl_softmax_neg_grad", _ptr(Q), Q.stride(0), _ptr(gQ), gQ.stride(0), _ptr(out), out.stride(0), n, L)
     return out
 
 
@@ -714,11 +751,8 @@ def uniform_compat_grad(Q, gQ, alpha, beta):
         Q = _grad_operand(Q, n, L)
     dE = torch.empty((n, L), dtype=torch.float32, device=gQ.device)
     gX = torch.empty_like(dE)
-    with torch.cuda.device(gQ.device):
-        _check(load_library().phl_uniform_compat_grad(
-            C.c_void_p(Q.data_ptr()) if Q is not None else None, Q.stride(0) if Q is not None else 0, C.c_void_p(gQ.data_ptr()),
-            gQ.stride(0), C.c_float(alpha), C.c_float(beta), C.c_void_p(dE.data_ptr()), dE.stride(0), C.c_void_p(gX.data_ptr()),
-            gX.stride(0), n, L, _stream(gQ.device)))
+    _launch(gQ.device, "phl_uniform_compat_grad", _ptr(Q), Q.stride(0) if Q is not None else 0, _ptr(gQ), gQ.stride(0),
+            C.c_float(alpha), C.c_float(beta), _ptr(dE), dE.stride(0), _ptr(gX), gX.stride(0), n, L)
     return dE, gX
 
 
@@ -728,9 +762,7 @@ def compat_grad_x(dE, Mu, scale=1.0):
     dE = _grad_operand(dE, n, L)
     Mu = _mu_operand(Mu, L, dE.device)
     gX = torch.empty((n, L), dtype=torch.float32, device=dE.device)
-    with torch.cuda.device(dE.device):
-        _check(load_library().phl_compat_grad_x(C.c_void_p(dE.data_ptr()), dE.stride(0), C.c_void_p(Mu.data_ptr()), C.c_float(scale),
-                                                C.c_void_p(gX.data_ptr()), gX.stride(0), n, L, _stream(dE.device)))
+    _launch(dE.device, "phl_compat_grad_x", _ptr(dE), dE.stride(0), _ptr(Mu), C.c_float(scale), _ptr(gX), gX.stride(0), n, L)
     return gX
 
 
@@ -739,17 +771,14 @@ def compat_mu_grad(X, dE, scale=1.0, out=None, accumulate=False):
     order in fp64 -- the same bits on every run.  accumulate=True adds to ``out``."""
     n, L = dE.shape
     X, dE = _grad_operand(X, n, L), _grad_operand(dE, n, L)
-    lib = load_library()
     if out is None:
         out = torch.empty((L, L), dtype=torch.float32, device=dE.device)
         accumulate = False
     elif not (out.is_contiguous() and out.dtype == torch.float32 and out.shape == (L, L)):
         raise TypeError("compat_mu_grad: out must be a contiguous fp32 [L, L] tensor")
-    ws = torch.empty((max(1, lib.phl_compat_mu_grad_workspace_bytes(n, L)),), dtype=torch.uint8, device=dE.device)
-    with torch.cuda.device(dE.device):
-        _check(lib.phl_compat_mu_grad(C.c_void_p(X.data_ptr()), X.stride(0), C.c_void_p(dE.data_ptr()), dE.stride(0), C.c_float(scale),
-                                      n, L, C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()), 1 if accumulate else 0,
-                                      _stream(dE.device)))
+    ws = torch.empty((max(1, load_library().phl_compat_mu_grad_workspace_bytes(n, L)),), dtype=torch.uint8, device=dE.device)
+    _launch(dE.device, "phl_compat_mu_grad", _ptr(X), X.stride(0), _ptr(dE), dE.stride(0), C.c_float(scale), n, L, _ptr(ws), _ptr(out),
+            1 if accumulate else 0)
     return out
 
 
@@ -803,7 +832,8 @@ class CompatSoftmax(torch.autograd.Function):
     autograd asks for are computed.  The forward writes a fresh tensor; it saves Q (not in logits mode), X and Mu.
 
     uniform: as for ``compat_softmax``; a structure the caller asserts for the labels that matter (a padded Mu) serves
-    the forward only -- the backward then takes the dense product, whose padding columns are exactly 0.
+    the forward only -- the backward then takes the dense product, whose padding columns are exactly 0.  The backward
+    takes the Potts-family shortcut only for a structure detected on Mu itself.
 
     Domain when a gradient is recorded: fp32 CUDA E0, X, Mu and L % 4 == 0, 4 <= L <= 512 (else TypeError / ValueError in
     the forward); without one, everything ``compat_softmax`` takes."""
@@ -814,14 +844,9 @@ class CompatSoftmax(torch.autograd.Function):
             _check_grad_domain("CompatSoftmax", E0.shape[-1], E0, X, Mu)
         E0 = E0 if _rowmajor(E0) else E0.contiguous()
         X = X if _rowmajor(X) else X.contiguous()
-        n, L = E0.shape
-        detected = None
-        if uniform is None:
-            aligned = L % 4 == 0 and all(t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in (X, E0))
-            detected = _mu_uniform(Mu) if (aligned and L <= 1024) else None
-            uniform = detected if detected is not None else False
-        out = compat_softmax(E0, X, Mu, logits=logits, uniform=uniform)
-        ctx.logits, ctx.uniform = bool(logits), detected
+        _, found = _compat_route(E0.shape[1], (X, E0), Mu, uniform)
+        out = compat_softmax(E0, X, Mu, logits=logits, uniform=found or False)
+        ctx.logits, ctx.uniform = bool(logits), (found if uniform is None else None)
         ctx.save_for_backward(None if logits else out, X, Mu)
         return out
 
@@ -895,19 +920,14 @@ def cost_volume(img1, img2, max_disp=None, window_size=9, criterion="AD", out=No
     crit = CRITERIA[getattr(criterion, "__name__", criterion)]
     res = torch.empty((h * w, L), dtype=torch.float32, device=dev) if out is None else out
     assert res.shape == (h * w, L) and res.stride(1) == 1 and res.dtype == torch.float32
-    with torch.cuda.device(dev):
-        _check(load_library().phl_cost_volume(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), h, w, c, L,
-                                              int(window_size), crit, C.c_void_p(res.data_ptr()), res.stride(0) if L else 0,
-                                              _stream(dev)))
+    _launch(dev, "phl_cost_volume", _ptr(a), _ptr(b), h, w, c, L, int(window_size), crit, _ptr(res), res.stride(0) if L else 0)
     return res
 
 
 def stream_copy(dst, src):
     """float4 streaming copy (HBM ceiling probe for bench.py)."""
     assert dst.is_contiguous() and src.is_contiguous() and dst.numel() == src.numel()
-    with torch.cuda.device(src.device):
-        _check(load_library().phl_stream_copy(C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), src.numel(),
-                                              _stream(src.device)))
+    _launch(src.device, "phl_stream_copy", _ptr(src), _ptr(dst), src.numel())
     return dst
 
 
@@ -916,9 +936,8 @@ def copy2d(dst, src):
     transpose (phl_copy2d): the NCHW <-> pixel-major hops of the batched API."""
     assert dst.shape == src.shape and dst.dim() == 2 and dst.is_cuda and src.device == dst.device
     assert dst.dtype == torch.float32 and src.dtype == torch.float32
-    with torch.cuda.device(dst.device):
-        _check(load_library().phl_copy2d(C.c_void_p(src.data_ptr()), src.stride(0), src.stride(1), C.c_void_p(dst.data_ptr()),
-                                         dst.stride(0), dst.stride(1), int(dst.shape[0]), int(dst.shape[1]), _stream(dst.device)))
+    _launch(dst.device, "phl_copy2d", _ptr(src), src.stride(0), src.stride(1), _ptr(dst), dst.stride(0), dst.stride(1),
+            int(dst.shape[0]), int(dst.shape[1]))
     return dst
 
 
@@ -928,9 +947,7 @@ def expected_value(Q, labels):
         raise TypeError("expected_value: expects fp32 CUDA Q [n, L] and labels [L]")
     labels = labels.to(Q.device).contiguous()
     out = torch.empty((Q.shape[0],), dtype=torch.float32, device=Q.device)
-    with torch.cuda.device(Q.device):
-        _check(load_library().phl_expected_value(C.c_void_p(Q.data_ptr()), Q.stride(0), C.c_void_p(labels.data_ptr()),
-                                                 C.c_void_p(out.data_ptr()), Q.shape[0], Q.shape[1], _stream(Q.device)))
+    _launch(Q.device, "phl_expected_value", _ptr(Q), Q.stride(0), _ptr(labels), _ptr(out), Q.shape[0], Q.shape[1])
     return out
 
 
