@@ -8,8 +8,9 @@ Mirrored names (reference line numbers in crf/gaussian_matrix.py):
     batched_filter :370    LatticeGaussian :292-303    RbfLaplacian :305-319
     RbfLaplacianC :321-338 BatchedAdjacency :341-352
 The guided-filter siblings (GuidedFilter, FastGuidedFilter, BatchedGuidedAdjacency,
-GuidedAdjacency; :161-287) are a different, dense-torch kernel outside the lattice hot path;
-they are provided in crf.guided as plain torch ops for API completeness.
+GuidedAdjacency; :161-287) are a different, dense kernel outside the lattice hot path; they
+live in crf.guided, together with the separable Gaussian (box_filter :86, gaussian_blur :107,
+GaussianBlur :110) that GuidedFilter(gaussian=True) is built on (HIP for fp32 CUDA tensors).
 """
 import os
 
@@ -247,6 +248,6 @@ class BatchedAdjacency(nn.Module):
         return out.permute(0, 2, 1).reshape(src_imgs.shape) - src_imgs
 
 
-# guided-filter family: API surface only, implemented in crf.guided
-from crf.guided import (BatchedGuidedAdjacency, FastGuidedFilter, GuidedAdjacency,  # noqa: E402,F401
-                        GuidedFilter)
+# guided-filter family and the separable Gaussian, implemented in crf.guided
+from crf.guided import (BatchedGuidedAdjacency, FastGuidedFilter, GaussianBlur, GuidedAdjacency,  # noqa: E402,F401
+                        GuidedFilter, box_filter, gaussian_blur)

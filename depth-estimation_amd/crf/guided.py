@@ -1,16 +1,124 @@
-"""Guided-filter adjacency operators -- API surface only.
+"""Guided-filter adjacency operators and the separable Gaussian blur behind GuidedFilter(gaussian=True).
 
-The reference's CRFasRNN defaults to a guided-filter W (crf/gaussian_matrix.py:161-287,
-crf_module.py:91).  That is a different kernel from the lattice hot path (box sums over dense
-NCHW tensors, already GPU-resident torch ops) and is OUT OF SCOPE for the HIP work
-(SURVEY.md section 2.1).  These classes keep the constructor / call signatures so that code
-written against the reference imports and runs; they are plain torch and their numerics are
-"parity unpinned": the reference builds on the pip package ``guided_filter_pytorch`` (BoxFilter),
-which is absent from this image, so no reference output exists to pin them against.
+The reference's CRFasRNN defaults to a guided-filter W (crf/gaussian_matrix.py:161-287, crf_module.py:91).  The
+box-window classes keep the reference's constructor / call signatures and are plain torch; their numerics are "parity
+unpinned": the reference builds them on the pip package ``guided_filter_pytorch`` (BoxFilter), which is absent here.
+
+The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
+(gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
+    box_filter(x, r, dim)            one normalised box pass (window of 2r samples, divisor of 2r+1: see _box_torch)
+    gaussian_blur(x, sigma, dim)     three box passes, r = floor(sqrt(4 sigma^2 + 1)) // 2, with a sigma gradient
+    GaussianBlur                     the autograd Function behind it
+fp32 CUDA tensors run on the HIP kernels (phl.box_blur / phl.box_blur_grad: one fused pass over the data per blur and
+per gradient); anything else (CPU tensors, float64) runs the plain-torch transcription below.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+import phl
+
+
+def _box_torch(x, r, dim):
+    """B_r along dim, from the formula: out[i] = (P[min(h, i+r+1)] - P[max(0, i-r+1)]) / c(i), P the exclusive prefix
+    sum, c(i) = min(i, r) + min(h-1-i, r) + 1.  The window holds at most 2r samples (i-r+1 .. i+r) while c counts the
+    symmetric 2r+1 -- the reference's cumsum slices, kept as they are."""
+    h = x.shape[dim]
+    P = torch.cat([torch.zeros_like(x.narrow(dim, 0, 1)), x.cumsum(dim)], dim)
+    i = torch.arange(h, device=x.device)
+    hi = torch.clamp(i + r + 1, max=h)
+    lo = torch.clamp(i - r + 1, min=0)
+    c = (torch.clamp(i, max=r) + torch.clamp(h - 1 - i, max=r) + 1).to(x.dtype)
+    shape = (1,) * dim + (h,) + (1,) * (x.dim() - dim - 1)
+    return (P.index_select(dim, hi) - P.index_select(dim, lo)) / c.reshape(shape)
+
+
+def _hip_ok(x):
+    return x.is_cuda and x.dtype == torch.float32
+
+
+def _cascade(x, r, dim, passes=3):
+    if _hip_ok(x):
+        return phl.box_blur(x, r, dim, passes=passes)
+    for _ in range(passes):
+        x = _box_torch(x, r, dim)
+    return x
+
+
+def box_filter(array, r, dim):
+    """One normalised box pass of radius r >= 1 along ``dim`` (gaussian_matrix.py:86-105)."""
+    r = int(r)
+    if r < 1:
+        raise ValueError(f"box_filter: r must be >= 1, got {r}")
+    return _cascade(array, r, dim, passes=1)
+
+
+def sigma_radius(sigma, niters=3):
+    """The box radius of the reference: floor(sqrt(12 sigma^2 / niters + 1)) // 2, computed with torch ops in sigma's
+    own dtype on the CPU (float32 and float64 differ where 4 sigma^2 + 1 = (2k)^2).  One device read for a GPU sigma."""
+    s = sigma.detach().cpu() if torch.is_tensor(sigma) else torch.as_tensor(sigma)
+    return int(torch.floor(torch.sqrt(12 * s ** 2 / niters + 1)) // 2)
+
+
+def gaussian_blur(array, sigma, dim):
+    return GaussianBlur.apply(array, sigma, dim)
+
+
+class GaussianBlur(torch.autograd.Function):
+    """Three box passes along ``dim`` approximating a Gaussian of width sigma (gaussian_matrix.py:110-156).  sigma is a
+    number or a 0-d tensor; only a tensor that requires grad receives a gradient.  The backward is the reference's:
+        grad_x     = B(g)                      (the forward operator, not its transpose)
+        grad_sigma = -sum(grad_f f) / sigma - sum(B(g) v) / sigma,  f[i] = i / sigma,
+        grad_f     = -(v f B(g) - v B(g f) + g f B(v) - g B(v f))
+    the continuous Gaussian's sigma-derivative, not that of the (piecewise constant in sigma) discrete operator -- so
+    gradcheck does not apply.  No double backward, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, array, sigma, dim, niters=3):
+        r = sigma_radius(sigma, niters)
+        if r < 1:
+            raise ValueError(f"gaussian_blur: sigma = {float(sigma)} gives box radius {r}; needs r >= 1")
+        ctx.dim, ctx.r = dim, r
+        ctx.sigma_is_tensor = torch.is_tensor(sigma)
+        if ctx.sigma_is_tensor:
+            ctx.save_for_backward(array, sigma)
+        else:
+            ctx.save_for_backward(array)
+            ctx.sigma = sigma
+        with torch.no_grad():
+            return _cascade(array, r, dim, niters)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        if ctx.sigma_is_tensor:
+            v, sigma = ctx.saved_tensors
+        else:
+            (v,), sigma = ctx.saved_tensors, ctx.sigma
+        need_x = ctx.needs_input_grad[0]
+        need_s = ctx.sigma_is_tensor and ctx.needs_input_grad[1]
+        dim, r = ctx.dim, ctx.r
+        g = grad_output
+        grad_x = grad_sigma = None
+        if not (need_x or need_s):
+            return None, None, None, None
+        if _hip_ok(v) and _hip_ok(g):
+            grad_x, grad_sigma = phl.box_blur_grad(v, g, r, dim, float(sigma), need_x=need_x, need_sigma=need_s)
+        else:
+            g = g.to(v.dtype)
+            Bg = _cascade(g, r, dim)
+            grad_x = Bg if need_x else None
+            if need_s:
+                h = v.shape[dim]
+                shape = (1,) * dim + (h,) + (1,) * (v.dim() - dim - 1)
+                f = (torch.arange(h) / sigma.detach().cpu()).reshape(shape).to(v.dtype).to(v.device)
+                gf, vf = g * f, v * f
+                grad_f = -(vf * Bg - v * _cascade(gf, r, dim) + gf * _cascade(v, r, dim) - g * _cascade(vf, r, dim))
+                s = sigma.detach().to(v.device)
+                grad_sigma = -(grad_f * f).sum() / s - (Bg * v).sum() / s
+        if grad_sigma is not None:
+            grad_sigma = grad_sigma.to(dtype=sigma.dtype, device=sigma.device).reshape(sigma.shape)
+        return grad_x, grad_sigma, None, None
 
 
 def _box_sum(x, r):
@@ -26,14 +134,19 @@ class GuidedFilter(nn.Module):
 
     def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False):
         super().__init__()
-        if gaussian:
-            raise NotImplementedError("gaussian=True (learned-sigma box cascade) is outside the lattice scope")
         self.omega = nn.Parameter(torch.log(torch.expm1(torch.tensor(float(eps)))).expand(channels).clone())
-        self._r = r
-        self.gaussian = False
+        if gaussian:
+            # pinned to the reference (tests/golden/blur_guided.npz): its fp32 log(exp(eps) - 1), not expm1 (:166)
+            with torch.no_grad():
+                self.omega.copy_(torch.log(torch.exp(torch.tensor(float(eps))) - 1).expand(channels))
+            # learned window: the Gaussian's sigma is exp(omega2), initialised at r (:169-170)
+            self.omega2 = nn.Parameter(torch.log(torch.tensor(r).float()))
+        else:
+            self._r = r
+        self.gaussian = gaussian
 
     def r(self):
-        return self._r
+        return torch.exp(self.omega2) if self.gaussian else self._r
 
     @property
     def eps(self):
@@ -45,9 +158,16 @@ class GuidedFilter(nn.Module):
     def get_coeffs(self, y, x):
         n, cx, h, w = x.shape
         cy = y.shape[1]
-        r = self._window()
-        N = _box_sum(torch.ones((1, 1, h, w), dtype=x.dtype, device=x.device), r)
-        mean = lambda t: _box_sum(t, r) / N
+        if self.gaussian:
+            s = self.r()
+            assert h > 2 * s + 1 and w > 2 * s + 1
+            blur = lambda t: gaussian_blur(gaussian_blur(t, s, 2), s, 3)  # noqa: E731
+        else:
+            r = self._window()
+            blur = lambda t: _box_sum(t, r)  # noqa: E731
+        # N: the window weight of every pixel; in the Gaussian form it depends on sigma and is differentiated too
+        N = blur(torch.ones((1, 1, h, w), dtype=x.dtype, device=x.device))
+        mean = lambda t: blur(t) / N  # noqa: E731
         mx, my = mean(x), mean(y)
         cov = mean((y[:, :, None] * x[:, None]).reshape(n, cy * cx, h, w)).reshape(n, cy, cx, h, w) - my[:, :, None] * mx[:, None]
         var = mean(x * x) - mx * mx
@@ -66,6 +186,9 @@ class FastGuidedFilter(GuidedFilter):
 
     def __init__(self, *args, subsample_ratio=2, mode="nearest", **kwargs):
         super().__init__(*args, **kwargs)
+        if self.gaussian:
+            # the reference's constructor reads self._r, which its gaussian form never sets (AttributeError, :238)
+            raise NotImplementedError("FastGuidedFilter(gaussian=True) does not construct in the reference either")
         self.subsample_ratio = subsample_ratio
         self.mode = mode
 

@@ -108,6 +108,10 @@ def load_library():
             lib.phl_compat_mu_grad_workspace_bytes.argtypes = [i64, i32]
             lib.phl_compat_mu_grad_workspace_bytes.restype = C.c_size_t
             lib.phl_compat_mu_grad.argtypes = [vp, i64, vp, i64, C.c_float, i64, i32, vp, vp, i32, vp]
+        if hasattr(lib, "phl_box_blur"):               # (an older build loaded through PHL_LIB lacks the blur)
+            lib.phl_box_blur.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp]
+            lib.phl_box_blur_grad.argtypes = [vp, vp, i64, i64, i64, i32, C.c_double, vp, vp, vp]
+            lib.phl_box_blur_fused_max_r.argtypes = [i32, i32, i32]
         lib.phl_stream_copy.argtypes = [vp, vp, i64, vp]
         lib.phl_copy2d.argtypes = [vp, i64, i64, vp, i64, i64, i64, i32, vp]
         lib.phl_cost_volume.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
@@ -922,6 +926,71 @@ def cost_volume(img1, img2, max_disp=None, window_size=9, criterion="AD", out=No
     assert res.shape == (h * w, L) and res.stride(1) == 1 and res.dtype == torch.float32
     _launch(dev, "phl_cost_volume", _ptr(a), _ptr(b), h, w, c, L, int(window_size), crit, _ptr(res), res.stride(0) if L else 0)
     return res
+
+
+# ---------------------------------------------------------------------------------------------
+# separable Gaussian of the guided filter (crf/guided.py; include/phl.h, phl_blur.hip)
+def _blur_view(x, dim):
+    """(outer, h, inner) of a contiguous tensor along ``dim`` (non-negative, as the reference takes it)."""
+    if not 0 <= dim < x.dim():
+        raise ValueError(f"box_blur: dim must be in 0..{x.dim() - 1}, got {dim}")
+    shape = tuple(int(s) for s in x.shape)
+    outer = int(np.prod(shape[:dim], dtype=np.int64))
+    inner = int(np.prod(shape[dim + 1:], dtype=np.int64))
+    return outer, shape[dim], inner
+
+
+def _blur_operand(t):
+    if not (t.is_cuda and t.dtype == torch.float32):
+        raise TypeError(f"box_blur: takes fp32 CUDA tensors, got {t.dtype} on {t.device}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def box_blur(x, r, dim, passes=3, out=None):
+    """``passes`` normalised box passes of radius r along ``dim`` (phl_box_blur): one kernel for the whole cascade while
+    its LDS fits, one launch per pass above that.  fp32 CUDA; any strides (copied contiguous)."""
+    x = _blur_operand(x)
+    outer, h, inner = _blur_view(x, dim)
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    elif not (out.is_contiguous() and out.dtype == torch.float32 and out.shape == x.shape and out.device == x.device):
+        raise TypeError("box_blur: out must be a contiguous fp32 tensor of the input's shape and device")
+    _launch(x.device, "phl_box_blur", _ptr(x), _ptr(out), outer, h, inner, int(r), int(passes))
+    return out
+
+
+def box_blur_fused_max_r(inner_is_one, passes=3, grad=False):
+    """Largest r that the fused cascade kernel (grad=True: the fused sigma-gradient) takes."""
+    return int(load_library().phl_box_blur_fused_max_r(1 if inner_is_one else 0, int(passes), 1 if grad else 0))
+
+
+def box_blur_grad(v, g, r, dim, sigma, need_x=True, need_sigma=True):
+    """Backward of the 3-pass Gaussian (phl_box_blur_grad): (grad_x = B(g) or None, grad_sigma as a 0-d fp32 device
+    tensor or None).  Without need_sigma only the plain cascade on g runs.  Above the fused kernel's radius the four
+    cascades g, g f, v, v f run as box_blur calls and the contraction as fp64 torch ops."""
+    v, g = _blur_operand(v), _blur_operand(g)
+    if v.shape != g.shape or v.device != g.device:
+        raise ValueError("box_blur_grad: v and g must have the same shape and device")
+    if not need_sigma:
+        return (box_blur(g, r, dim) if need_x else None), None
+    outer, h, inner = _blur_view(v, dim)
+    gx = torch.empty_like(v) if need_x else None
+    gs = torch.empty((), dtype=torch.float32, device=v.device)
+    try:
+        _launch(v.device, "phl_box_blur_grad", _ptr(v), _ptr(g), outer, h, inner, int(r), C.c_double(float(sigma)), _ptr(gx),
+                _ptr(gs))
+        return gx, gs
+    except PhlError as e:
+        if e.status != 7:          # PHL_ERR_UNSUPPORTED: r above the fused kernel's limit
+            raise
+    shape = (1,) * dim + (h,) + (1,) * (v.dim() - dim - 1)
+    f = (torch.arange(h, device=v.device, dtype=torch.float64) / float(sigma)).reshape(shape)
+    Bg, Bv = box_blur(g, r, dim), box_blur(v, r, dim)
+    Bgf, Bvf = box_blur((g * f).float(), r, dim), box_blur((v * f).float(), r, dim)
+    vd, gd = v.double(), g.double()
+    D = vd * f * Bg - vd * Bgf + gd * f * Bv - gd * Bvf
+    gs = ((D * f).sum() - (Bg.double() * vd).sum()) / float(sigma)
+    return (Bg if need_x else None), gs.float()
 
 
 def stream_copy(dst, src):

@@ -335,6 +335,32 @@ int phl_expected_value(const float *Q_dev, int64_t q_row_stride, const float *la
 int phl_cost_volume(const float *img1_dev, const float *img2_dev, int h, int w, int channels, int max_disp,
                     int window, int criterion, float *out_dev, int64_t out_row_stride, phl_stream stream);
 
+/* ---- separable Gaussian of the guided filter (crf/guided.py: box_filter, gaussian_blur) -------------------------
+ * Dense contiguous fp32 viewed as [outer][h][inner]; every (outer, inner) line is filtered along h by `passes` box
+ * passes  B_r(x)[i] = sum(x[max(0, i-r+1) .. min(h-1, i+r)]) / (min(i, r) + min(h-1-i, r) + 1).
+ *   phl_box_blur        dst = B_r^passes(src), all passes in one kernel while its LDS fits (r up to
+ *                       phl_box_blur_fused_max_r), else one launch per pass through stream-ordered temporaries.
+ *                       src and dst must not overlap.
+ *   phl_box_blur_grad   the backward of the 3-pass Gaussian with f[i] = i / sigma:
+ *                         grad_x     = B(g)                                     (written if grad_x != NULL)
+ *                         grad_sigma = -sum(grad_f f) / sigma - sum(B(g) v) / sigma,
+ *                         grad_f     = -(v f B(g) - v B(g f) + g f B(v) - g B(v f))
+ *                       as one fp32 on the device (written if grad_sigma_dev != NULL; per-workgroup fp64 partials in
+ *                       a stream-ordered temporary, summed in a fixed order: the same bits on every run).  Without
+ *                       grad_sigma_dev it is phl_box_blur(g, grad_x, ..., 3).
+ * Status, checked before any HIP call: PHL_ERR_INVALID for negative sizes, r < 1, passes outside 1..8, sigma not
+ * > 0, NULL data pointers (when there is at least one element), src == dst, grad_x aliasing v / g, or neither grad_x
+ * nor grad_sigma_dev; PHL_ERR_TOO_LARGE when outer*h*inner*4 bytes leave int64 or the lines make more than 2^31-1
+ * workgroups; PHL_ERR_UNSUPPORTED from phl_box_blur_grad with grad_sigma_dev when min(r, h) exceeds
+ * phl_box_blur_fused_max_r(inner == 1, 3, 1) (the caller then composes it from phl_box_blur calls).
+ * Zero elements: PHL_OK (grad_sigma_dev set to 0). */
+int phl_box_blur(const float *src_dev, float *dst_dev, int64_t outer, int64_t h, int64_t inner, int r, int passes,
+                 phl_stream stream);
+int phl_box_blur_grad(const float *v_dev, const float *g_dev, int64_t outer, int64_t h, int64_t inner, int r, double sigma,
+                      float *grad_x_dev, float *grad_sigma_dev, phl_stream stream);
+/* largest r the single fused kernel takes for these passes (grad != 0: phl_box_blur_grad's); INT32_MAX for one pass */
+int phl_box_blur_fused_max_r(int inner_is_one, int passes, int grad);
+
 /* Plain float4 streaming copy dst <- src (n_floats % 4 == 0, 16-byte aligned): measures the
  * HBM read+write ceiling of the box that the roofline fractions are compared with. */
 int phl_stream_copy(const float *src_dev, float *dst_dev, int64_t n_floats, phl_stream stream);
