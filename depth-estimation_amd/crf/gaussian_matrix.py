@@ -10,7 +10,8 @@ Mirrored names (reference line numbers in crf/gaussian_matrix.py):
 The guided-filter siblings (GuidedFilter, FastGuidedFilter, BatchedGuidedAdjacency,
 GuidedAdjacency; :161-287) are a different, dense kernel outside the lattice hot path; they
 live in crf.guided, together with the separable Gaussian (box_filter :86, gaussian_blur :107,
-GaussianBlur :110) that GuidedFilter(gaussian=True) is built on (HIP for fp32 CUDA tensors).
+GaussianBlur :110) that GuidedFilter(gaussian=True) is built on (HIP for fp32 CUDA tensors).  The
+box-window forward runs on phl.guided_filter for fp32 CUDA tensors outside autograd.
 """
 import os
 

@@ -1,8 +1,12 @@
 """Guided-filter adjacency operators and the separable Gaussian blur behind GuidedFilter(gaussian=True).
 
 The reference's CRFasRNN defaults to a guided-filter W (crf/gaussian_matrix.py:161-287, crf_module.py:91).  The
-box-window classes keep the reference's constructor / call signatures and are plain torch; their numerics are "parity
-unpinned": the reference builds them on the pip package ``guided_filter_pytorch`` (BoxFilter), which is absent here.
+box-window classes (GuidedFilter, FastGuidedFilter, BatchedGuidedAdjacency, GuidedAdjacency) keep the reference's
+constructor / call signatures.  Their torch form below is pinned to the reference run in float64 with its own
+``mBoxFilter`` as the box sum (tests/golden/generate_guided.py, tests/test_guided_cpu.py).  A forward on fp32 CUDA tensors
+that autograd does not record runs on the HIP kernels instead (phl.guided_filter, phl_guided.hip: fp64 window sums over
+LDS tiles, the ``* k - src`` of the adjacency fused); CPU tensors, float64, training, ``mode != 'nearest'`` and
+``gaussian=True`` stay on the torch form.
 
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
@@ -176,9 +180,30 @@ class GuidedFilter(nn.Module):
         mean_A = mean(A.reshape(n, cy * cx, h, w)).reshape(n, cy, cx, h, w)
         return mean_A, mean(b)
 
-    def forward(self, y, x):
+    def _fused(self, y, x, subsample=1, scale=1.0, subtract=None):
+        """The forward on the HIP kernels (phl.guided_filter), or None where the torch form has to run: a Gaussian
+        window, an interpolation other than nearest, tensors that are not fp32 CUDA, autograd recording, or a shape the
+        kernels do not take (PHL_ERR_UNSUPPORTED: more than 16 guide channels)."""
+        if self.gaussian or getattr(self, "mode", "nearest") != "nearest" or not (_hip_ok(y) and _hip_ok(x)):
+            return None
+        if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
+            return None
+        if torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad):
+            return None
+        try:
+            return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract)
+        except phl.PhlError as e:
+            if e.status != 7:
+                raise
+        return None
+
+    def _torch_forward(self, y, x):
         mean_A, mean_b = self.get_coeffs(y, x)
         return (mean_A * x[:, None]).sum(2) + mean_b
+
+    def forward(self, y, x):
+        out = self._fused(y, x, subsample=getattr(self, "subsample_ratio", 1))
+        return out if out is not None else self._torch_forward(y, x)
 
 
 class FastGuidedFilter(GuidedFilter):
@@ -195,7 +220,7 @@ class FastGuidedFilter(GuidedFilter):
     def _window(self):
         return self._r // self.subsample_ratio
 
-    def forward(self, y, x):
+    def _torch_forward(self, y, x):
         s = self.subsample_ratio
         n, cx, h, w = x.shape
         cy = y.shape[1]
@@ -210,7 +235,11 @@ class BatchedGuidedAdjacency(FastGuidedFilter):
     """W(src) = guided(src) * (2r+1)^2 / 2 - src  (:285-287)."""
 
     def forward(self, src_imgs, guide_imgs):
-        return super().forward(src_imgs, guide_imgs) * 0.5 * (2 * self.r() + 1) ** 2 - src_imgs
+        out = self._fused(src_imgs, guide_imgs, subsample=self.subsample_ratio, scale=0.5 * (2 * self._r + 1) ** 2,
+                          subtract=src_imgs)
+        if out is not None:
+            return out
+        return self._torch_forward(src_imgs, guide_imgs) * 0.5 * (2 * self.r() + 1) ** 2 - src_imgs
 
 
 class GuidedAdjacency(GuidedFilter):
@@ -222,7 +251,10 @@ class GuidedAdjacency(GuidedFilter):
 
     def __matmul__(self, U):
         h, w = self.guide_img.shape[-2:]
-        img = U.t().reshape(1, -1, h, w).float().to(self.guide_img.device)
+        # the guide's dtype: fp32 as constructed; a guide_img set to float64 keeps the whole product in float64
+        img = U.t().reshape(1, -1, h, w).to(self.guide_img.dtype).to(self.guide_img.device)
         with torch.no_grad():
-            out = self(img, self.guide_img) * 0.5 * (2 * self._r + 1) ** 2 - img
+            out = self._fused(img, self.guide_img, scale=0.5 * (2 * self._r + 1) ** 2, subtract=img)
+            if out is None:
+                out = self._torch_forward(img, self.guide_img) * 0.5 * (2 * self._r + 1) ** 2 - img
         return out[0].reshape(U.shape[1], -1).t().to(U.device)

@@ -1,0 +1,498 @@
+// phl_guided.hip -- the box-window guided filter (crf/guided.py: GuidedFilter, FastGuidedFilter, BatchedGuidedAdjacency,
+// GuidedAdjacency), forward only, NCHW fp32.
+//
+// S_r(t) = sum of t over the (2r+1)^2 window clipped to the image, N = S_r(1), mean(t) = S_r(t) / N.  At the solving
+// resolution h x w (the nearest-sampled H x W image; h = H, w = W for the plain filter), per guide channel c and label l:
+//   mx_c = mean(x_c)   var_c = mean(x_c^2) - mx_c^2   my_l = mean(y_l)   cov_lc = mean(y_l x_c) - my_l mx_c
+//   A_lc = cov_lc / (var_c + eps_c)       b_l = my_l - sum_c A_lc mx_c
+//   out_l = (sum_c mean(A_lc)[lo(p)] x_c[p] + mean(b_l)[lo(p)]) * scale - src_l[p]      at every full-resolution pixel p
+// The nearest index maps (low -> full for sampling, full -> low for the upsampling) come from the caller.
+//
+// Three kernels, all built on one tile routine (tile_fill + tile_sums): a workgroup of 256 owns a 32 x 64 tile of one low-resolution
+// plane, fills the tile plus a halo of r (zero outside the image) into LDS as fp32, forms the horizontal window sums of
+// every halo row by a sliding fp64 sum (work item = row x column segment, lanes across rows, odd row strides: no bank
+// conflict) into an fp64 LDS plane, then the vertical window sums by a second sliding fp64 sum (lane = column, wave =
+// 8 rows), which leaves the 8 window sums of a thread's pixels in registers.  No image-long prefix sums, no atomics:
+// a window sum is exact to fp64 rounding whatever the image size, and every run gives the same bits.
+//   k_guide_stats   per (image, tile), channels in a loop: mx_c (fp64 plane) and 1 / (var_c + eps_c) (fp32 plane)
+//   k_guide_coef    per (image x label, tile): the sums of y and y x_c -> A_lc (rounded to fp32 once; b_l uses the
+//                   rounded value, so the model stays consistent) and b_l, as cx + 1 low-resolution fp32 planes
+//   k_guide_apply   per (image x label, tile): window means of the cx + 1 planes into LDS, four planes at a time, then
+//                   the full-resolution pixels that map into the tile: fp64 sum over the channels, * scale - src, one
+//                   rounding into out (with more than four planes the partial sum passes through out between groups)
+// Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
+// routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.
+// The coefficient planes are a stream-ordered temporary; labels are processed in chunks whose planes stay within
+// kChunkBytes, so that k_guide_apply finds them in the Infinity Cache.
+#include <math.h>
+
+#include "phl_internal.h"
+
+namespace {
+
+constexpr int TH = 32, TW = 64;     // tile of low-resolution pixels per workgroup
+constexpr int NT = 256;             // threads: lane = tile column, wave = 8 tile rows
+constexpr int RPT = TH / 4;         // rows per thread
+constexpr int HSP = TW + 1;         // row stride of the fp64 plane: 16 consecutive rows hit 16 different bank pairs
+constexpr int NCO = 3;              // halo columns per lane: a halo row is at most 64 * NCO words
+constexpr int FU = 8;               // halo rows per wave whose loads tile_fill issues together
+constexpr int SR = 64;               // rows per strip of the streamed form
+constexpr int GRP = 4;              // coefficient planes per pass of k_guide_apply
+constexpr size_t kMaxLds = 160 << 10;
+constexpr size_t kChunkBytes = (size_t)96 << 20;
+
+__host__ __device__ inline int halo_rows(int r) { return TH + 2 * r; }
+__host__ __device__ inline int halo_stride(int r) { return (TW + 2 * r) | 1; }   // odd: lanes across rows, distinct banks
+// LDS of a workgroup: the fp64 plane, `ntiles` fp32 halo tiles, and k_guide_apply's window means
+inline size_t tile_lds(int r, int ntiles, bool apply)
+{
+    return (size_t)halo_rows(r) * HSP * sizeof(double) + (size_t)ntiles * halo_rows(r) * halo_stride(r) * sizeof(float) +
+           (apply ? (size_t)GRP * TH * TW * sizeof(float) : 0) + (size_t)halo_rows(r) * sizeof(int);
+}
+inline size_t max_lds(int r) { return max(tile_lds(r, 2, false), tile_lds(r, 1, true)); }
+// ... of the streamed form (any radius): a strip of the fp64 plane, and k_guide_apply's window means
+inline size_t stream_lds(bool apply) { return (size_t)SR * HSP * sizeof(double) + (apply ? (size_t)GRP * TH * TW * sizeof(float) : 0); }
+enum { KIND_STATS = 0, KIND_COEF = 1, KIND_APPLY = 2 };
+
+struct Tile {
+    double *hs;     // [TH + 2r][HSP] horizontal window sums
+    float *in;      // [TH + 2r][halo_stride] the tile and its halo
+    float *in2;     // a second one (k_guide_coef: the guide channel beside y); k_guide_apply keeps its means here
+    int *rowoff;    // [TH + 2r] offset of every halo row in a source plane, -1 outside the image
+    int co[NCO];    // this lane's halo columns lane, lane + 64, ...: offset in a source row, -1 outside the image
+    int r, ti, tj, h, w;
+    const int *rmap, *cmap;     // low-resolution row / column -> row / column of a source plane (null: the identity)
+    int ph, pw;                 // source planes are ph x pw
+    // element (i, j) of the low-resolution image in a source plane, straight from memory (the streamed form)
+    __device__ __forceinline__ float ld(const float *__restrict__ plane, int i, int j) const
+    {
+        const int I = rmap ? min(max(rmap[i], 0), ph - 1) : i, J = cmap ? min(max(cmap[j], 0), pw - 1) : j;
+        return plane[(int64_t)I * pw + J];
+    }
+};
+
+// in[ih][jh] = plane[rowoff[ih] + co] at the low-resolution pixel (ti - r + ih, tj - r + jh), 0 outside the image; the
+// row's padding word is filled as well.  The loads of FU rows are issued before the first store: a fill costs a few
+// memory latencies, not one per row.
+__device__ __forceinline__ void tile_fill(const Tile &t, float *__restrict__ in, const float *__restrict__ plane)
+{
+    const int HH = halo_rows(t.r), st = halo_stride(t.r);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int ih0 = wave; ih0 < HH; ih0 += 4 * FU) {
+        float v[FU][NCO];
+#pragma unroll
+        for (int u = 0; u < FU; u++) {
+            const int ih = ih0 + 4 * u;
+            const int ro = ih < HH ? t.rowoff[ih] : -1;
+#pragma unroll
+            for (int m = 0; m < NCO; m++) v[u][m] = ro >= 0 && t.co[m] >= 0 ? plane[(int64_t)ro + t.co[m]] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < FU; u++) {
+            const int ih = ih0 + 4 * u;
+#pragma unroll
+            for (int m = 0; m < NCO; m++)
+                if (ih < HH && lane + 64 * m < st) in[ih * st + lane + 64 * m] = v[u][m];
+        }
+    }
+}
+
+// window sums of val(e), e the element's index in a filled tile: res[k] = S_r at pixel (ti + wave * RPT + k, tj + lane).
+// val runs in fp64, so a product of two fp32 tiles enters the sums exactly.  Two barriers inside; the caller's next
+// tile_fill may follow at once (nobody reads a tile after the second barrier).
+template <typename V>
+__device__ __forceinline__ void tile_sums(const Tile &t, double (&res)[RPT], V val)
+{
+    const int r = t.r, HH = halo_rows(r), st = halo_stride(r);
+    __syncthreads();
+    const int nseg = HH >= NT ? 1 : min(TW, NT / HH);
+    const int seglen = (TW + nseg - 1) / nseg;
+    for (int it = threadIdx.x; it < HH * nseg; it += NT) {
+        const int ih = it % HH, j0 = (it / HH) * seglen, j1 = min(TW, j0 + seglen);
+        const int row = ih * st;
+        double *o = t.hs + ih * HSP;
+        double s = 0.0;
+        int jh = j0, j = j0;
+        for (; jh + 3 <= j0 + 2 * r; jh += 4) {          // four loads in flight, not one
+            const double a0 = val(row + jh), a1 = val(row + jh + 1), a2 = val(row + jh + 2), a3 = val(row + jh + 3);
+            s += (a0 + a1) + (a2 + a3);
+        }
+        for (; jh <= j0 + 2 * r; jh++) s += val(row + jh);
+        for (; j + 4 <= j1; j += 4) {                    // (the last step of a row reads its padding word at most)
+            const int e = row + j + 2 * r + 1;
+            const double d0 = val(e) - val(row + j), d1 = val(e + 1) - val(row + j + 1), d2 = val(e + 2) - val(row + j + 2),
+                         d3 = val(e + 3) - val(row + j + 3);
+            const double s1 = s + d0, s2 = s1 + d1, s3 = s2 + d2;
+            o[j] = s, o[j + 1] = s1, o[j + 2] = s2, o[j + 3] = s3;
+            s = s3 + d3;
+        }
+        for (; j < j1; j++) {
+            o[j] = s;
+            if (j + 1 < j1) s += val(row + j + 2 * r + 1) - val(row + j);
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, i0 = (threadIdx.x >> 6) * RPT;
+    const double *col = t.hs + lane;
+    double s = 0.0;
+    int ih = i0;
+    for (; ih + 3 <= i0 + 2 * r; ih += 4) s += (col[ih * HSP] + col[(ih + 1) * HSP]) + (col[(ih + 2) * HSP] + col[(ih + 3) * HSP]);
+    for (; ih <= i0 + 2 * r; ih++) s += col[ih * HSP];
+#pragma unroll
+    for (int k = 0; k < RPT; k++) {
+        res[k] = s;
+        if (k + 1 < RPT) s += col[(i0 + k + 2 * r + 1) * HSP] - col[(i0 + k) * HSP];
+    }
+}
+
+// The same sums for any radius, with LDS that does not grow with it: g(i, j) reads element (i, j) of the low-resolution
+// image from memory.  The image rows that the tile's windows reach are taken in strips of SR; per strip every row's
+// horizontal window sums (clipped to the image) go into the fp64 plane, and every thread adds the part of its pixels'
+// vertical windows that lies in the strip, again as a sliding sum.  Slower than the tiled form (no staging, one memory
+// latency per step of a chain); taken only where the tiled form's LDS would not fit.
+template <typename G>
+__device__ __forceinline__ void tile_sums_stream(const Tile &t, double (&res)[RPT], G g)
+{
+    constexpr int SEG = TW / (NT / SR);
+    const int r = t.r, lane = threadIdx.x & 63, i0 = t.ti + (threadIdx.x >> 6) * RPT;
+    const int lo = max(0, t.ti - r), hi = min(t.h, t.ti + TH + r);
+#pragma unroll
+    for (int k = 0; k < RPT; k++) res[k] = 0.0;
+    for (int a = lo; a < hi; a += SR) {
+        const int b = min(hi, a + SR);
+        __syncthreads();
+        const int i = a + (int)(threadIdx.x % SR), j0 = (int)(threadIdx.x / SR) * SEG;
+        if (i < b) {
+            int jl = t.tj + j0 - r, jr = t.tj + j0 + r;
+            double s = 0.0;
+            for (int jj = max(0, jl); jj <= min(t.w - 1, jr); jj++) s += g(i, jj);
+            double *o = t.hs + (i - a) * HSP + j0;
+            for (int j = 0; j < SEG; j++) {
+                o[j] = s;
+                ++jr;
+                if (jr >= 0 && jr < t.w) s += g(i, jr);
+                if (jl >= 0 && jl < t.w) s -= g(i, jl);
+                ++jl;
+            }
+        }
+        __syncthreads();
+        const double *col = t.hs + lane;
+        double s = 0.0;
+        for (int ii = max(a, i0 - r); ii < min(b, i0 + r + 1); ii++) s += col[(ii - a) * HSP];
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            res[k] += s;
+            const int e = i0 + k + r + 1, l = i0 + k - r;
+            if (e >= a && e < b) s += col[(e - a) * HSP];
+            if (l >= a && l < b) s -= col[(l - a) * HSP];
+        }
+    }
+}
+
+// samples in the window of pixel i along an axis of length n
+__device__ __forceinline__ int win_count(int i, int r, int n) { return min(i + r, n - 1) - max(i - r, 0) + 1; }
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
+// The workgroup's tile over dynamic LDS (ST: the streamed form, which keeps no halo tile).  Source planes are ph x pw;
+// low-resolution row i / column j is their row rmap[i] / column cmap[j] (null maps: the identity).  Ends with a barrier
+// (rowoff is read by every wave).
+template <bool ST>
+__device__ __forceinline__ Tile make_tile(int r, int h, int w, const int *__restrict__ rmap, const int *__restrict__ cmap, int ph,
+                                          int pw, int kind)
+{
+    extern __shared__ double lds_d[];
+    Tile t;
+    t.hs = lds_d;
+    t.r = r, t.h = h, t.w = w;
+    t.ti = blockIdx.y * TH, t.tj = blockIdx.x * TW;
+    t.rmap = rmap, t.cmap = cmap, t.ph = ph, t.pw = pw;
+    if (ST) {
+        t.in = nullptr;
+        t.in2 = reinterpret_cast<float *>(lds_d + (size_t)SR * HSP);
+        t.rowoff = nullptr;
+        return t;
+    }
+    const int HH = halo_rows(r), st = halo_stride(r);
+    t.in = reinterpret_cast<float *>(lds_d + (size_t)HH * HSP);
+    t.in2 = t.in + (size_t)HH * st;
+    t.rowoff = reinterpret_cast<int *>(t.in2 + (kind == KIND_APPLY ? (size_t)GRP * TH * TW : kind == KIND_COEF ? (size_t)HH * st : 0));
+    for (int ih = threadIdx.x; ih < HH; ih += NT) {
+        const int i = t.ti - r + ih;
+        t.rowoff[ih] = i >= 0 && i < h ? clampi(rmap ? rmap[i] : i, 0, ph - 1) * pw : -1;
+    }
+#pragma unroll
+    for (int m = 0; m < NCO; m++) {
+        const int jh = (threadIdx.x & 63) + 64 * m, j = t.tj - r + jh;
+        t.co[m] = jh < st && j >= 0 && j < w ? clampi(cmap ? cmap[j] : j, 0, pw - 1) : -1;
+    }
+    __syncthreads();
+    return t;
+}
+
+// ---- guide statistics ----------------------------------------------------------------------------------------------
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_guide_stats(const float *__restrict__ x, const int *__restrict__ rmap,
+                                                   const int *__restrict__ cmap, const float *__restrict__ eps,
+                                                   double *__restrict__ mx, float *__restrict__ inv, int cx, int H, int W, int h,
+                                                   int w, int r)
+{
+    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_STATS);
+    const int b = blockIdx.z, lane = threadIdx.x & 63, i0 = t.ti + (threadIdx.x >> 6) * RPT, j = t.tj + lane;
+    const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
+    const int cj = j < w ? win_count(j, r, w) : 1;
+    for (int c = 0; c < cx; c++) {
+        const float *xp = x + ((int64_t)b * cx + c) * HWf;
+        double s1[RPT], s2[RPT];
+        if constexpr (ST) {
+            tile_sums_stream(t, s1, [&](int i, int jj) { return (double)t.ld(xp, i, jj); });
+            tile_sums_stream(t, s2, [&](int i, int jj) { const double v = t.ld(xp, i, jj); return v * v; });
+        } else {
+            tile_fill(t, t.in, xp);
+            tile_sums(t, s1, [&](int e) { return (double)t.in[e]; });
+            tile_sums(t, s2, [&](int e) { const double v = t.in[e]; return v * v; });
+        }
+        const double e = (double)eps[c];
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            const int i = i0 + k;
+            if (i < h && j < w) {
+                const double n = (double)win_count(i, r, h) * (double)cj;
+                const double m = s1[k] / n, var = s2[k] / n - m * m;
+                const int64_t o = ((int64_t)b * cx + c) * hw + (int64_t)i * w + j;
+                mx[o] = m;
+                inv[o] = (float)(1.0 / (var + e));
+            }
+        }
+    }
+}
+
+// ---- coefficients --------------------------------------------------------------------------------------------------
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_guide_coef(const float *__restrict__ y, const float *__restrict__ x,
+                                                  const int *__restrict__ rmap, const int *__restrict__ cmap,
+                                                  const double *__restrict__ mx, const float *__restrict__ inv,
+                                                  float *__restrict__ coef, int n0, int cy, int cx, int H, int W, int h, int w, int r)
+{
+    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_COEF);
+    const int n = n0 + blockIdx.z, b = n / cy;                     // n = image * cy + label
+    const int lane = threadIdx.x & 63, i0 = t.ti + (threadIdx.x >> 6) * RPT, j = t.tj + lane;
+    const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
+    const float *yp = y + (int64_t)n * HWf;
+    float *cp = coef + (int64_t)blockIdx.z * (cx + 1) * hw;
+    const int cj = j < w ? win_count(j, r, w) : 1;
+
+    double my[RPT], bacc[RPT], rn[RPT], s[RPT];
+#pragma unroll
+    for (int k = 0; k < RPT; k++) rn[k] = 1.0 / ((double)(i0 + k < h ? win_count(i0 + k, r, h) : 1) * (double)cj);
+    if constexpr (ST) {
+        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(yp, i, jj); });
+    } else {
+        tile_fill(t, t.in, yp);
+        tile_sums(t, s, [&](int e) { return (double)t.in[e]; });
+    }
+#pragma unroll
+    for (int k = 0; k < RPT; k++) bacc[k] = my[k] = s[k] * rn[k];
+    for (int c = 0; c < cx; c++) {
+        const float *xp = x + ((int64_t)b * cx + c) * HWf;
+        if constexpr (ST) {
+            tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(yp, i, jj) * (double)t.ld(xp, i, jj); });
+        } else {
+            tile_fill(t, t.in2, xp);
+            tile_sums(t, s, [&](int e) { return (double)t.in[e] * (double)t.in2[e]; });      // exact: 24 + 24 bits
+        }
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            const int i = i0 + k;
+            if (i < h && j < w) {
+                const int64_t o = (int64_t)i * w + j, g = ((int64_t)b * cx + c) * hw + o;
+                const double m = mx[g];
+                const float a = (float)((s[k] * rn[k] - my[k] * m) * (double)inv[g]);
+                cp[(int64_t)c * hw + o] = a;
+                bacc[k] -= (double)a * m;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < RPT; k++) {
+        const int i = i0 + k;
+        if (i < h && j < w) cp[(int64_t)cx * hw + (int64_t)i * w + j] = (float)bacc[k];
+    }
+}
+
+// ---- apply ---------------------------------------------------------------------------------------------------------
+// first index I in [0, n) with map[I] >= v (map is non-decreasing)
+__device__ __forceinline__ int lower_bound(const int *__restrict__ map, int n, int v)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (map[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_guide_apply(const float *__restrict__ coef, const float *__restrict__ x,
+                                                   const float *__restrict__ src, float *__restrict__ out,
+                                                   const int *__restrict__ rlow, const int *__restrict__ clow, int n0, int cy, int cx,
+                                                   int H, int W, int h, int w, int r, float scale)
+{
+    Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_APPLY);
+    float *M = t.in2;                                               // [GRP][TH][TW] window means (both forms)
+    const int n = n0 + blockIdx.z, b = n / cy;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i0 = t.ti + wave * RPT, j = t.tj + lane;
+    const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
+    const float *cp = coef + (int64_t)blockIdx.z * (cx + 1) * hw;
+    const int cj = j < w ? win_count(j, r, w) : 1;
+    double rn[RPT];
+#pragma unroll
+    for (int k = 0; k < RPT; k++) rn[k] = 1.0 / ((double)(i0 + k < h ? win_count(i0 + k, r, h) : 1) * (double)cj);
+    // the full-resolution rows and columns whose low-resolution pixel lies in this tile
+    const int I0 = lower_bound(rlow, H, t.ti), I1 = lower_bound(rlow, H, t.ti + TH);
+    const int J0 = lower_bound(clow, W, t.tj), J1 = lower_bound(clow, W, t.tj + TW);
+    const float *xb = x + (int64_t)b * cx * HWf;
+    const float *sp = src ? src + (int64_t)n * HWf : nullptr;
+    float *op = out + (int64_t)n * HWf;
+    const int np = cx + 1;
+
+    for (int q0 = 0; q0 < np; q0 += GRP) {
+        const int nq = min(GRP, np - q0);
+        for (int q = 0; q < nq; q++) {
+            const float *pl = cp + (int64_t)(q0 + q) * hw;
+            double s[RPT];
+            if constexpr (ST) {
+                tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(pl, i, jj); });
+            } else {
+                tile_fill(t, t.in, pl);
+                tile_sums(t, s, [&](int e) { return (double)t.in[e]; });
+            }
+#pragma unroll
+            for (int k = 0; k < RPT; k++) M[(q * TH + wave * RPT + k) * TW + lane] = (float)(s[k] * rn[k]);
+        }
+        __syncthreads();
+        const bool first = q0 == 0, last = q0 + GRP >= np;
+        for (int I = I0 + wave; I < I1; I += 4) {
+            const int li = clampi(rlow[I] - t.ti, 0, TH - 1);
+            for (int J = J0 + lane; J < J1; J += 64) {
+                const int lj = clampi(clow[J] - t.tj, 0, TW - 1);
+                const int64_t o = (int64_t)I * W + J;
+                double acc = first ? 0.0 : (double)op[o];
+                for (int q = 0; q < nq; q++) {
+                    const double m = M[(q * TH + li) * TW + lj];
+                    acc += q0 + q < cx ? m * (double)xb[(int64_t)(q0 + q) * HWf + o] : m;
+                }
+                if (last) {
+                    acc *= (double)scale;
+                    if (sp) acc -= (double)sp[o];
+                }
+                op[o] = (float)acc;
+            }
+        }
+        // (the next group's first write to M comes after the two barriers of its tile_sums)
+    }
+}
+
+// the three kernels in the tiled form while its LDS fits the radius, else in the streamed form
+int run(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h, int w, int re,
+        const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col, const float *eps, float scale,
+        hipStream_t st)
+{
+    const bool tiled = max_lds(re) <= kMaxLds && halo_stride(re) <= 64 * NCO;
+    const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
+    const dim3 tiles((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH));
+    const size_t lds_stats = tiled ? tile_lds(re, 1, false) : stream_lds(false);
+    const size_t lds_coef = tiled ? tile_lds(re, 2, false) : stream_lds(false);
+    const size_t lds_apply = tiled ? tile_lds(re, 1, true) : stream_lds(true);
+    auto stats = tiled ? k_guide_stats<false> : k_guide_stats<true>;
+    auto coefk = tiled ? k_guide_coef<false> : k_guide_coef<true>;
+    auto apply = tiled ? k_guide_apply<false> : k_guide_apply<true>;
+    if (int rc = phl_allow_lds(stats, lds_stats)) return rc;
+    if (int rc = phl_allow_lds(coefk, lds_coef)) return rc;
+    if (int rc = phl_allow_lds(apply, lds_apply)) return rc;
+
+    // labels per chunk: the coefficient planes of a chunk stay within kChunkBytes (and gridDim.z)
+    const int64_t per = (int64_t)(cx + 1) * hw * (int64_t)sizeof(float);
+    const int64_t chunk = max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per));
+    const size_t nstat = (size_t)B * cx * hw;
+    void *tmp[3] = {nullptr, nullptr, nullptr};          // mx, inv, coef: every one that was allocated is freed below
+    const size_t bytes[3] = {nstat * sizeof(double), nstat * sizeof(float), (size_t)chunk * per};
+    int rc = PHL_OK;
+    for (int i = 0; i < 3 && rc == PHL_OK; i++) {
+        hipError_t e = hipMallocAsync(&tmp[i], bytes[i], st);
+        if (e != hipSuccess) tmp[i] = nullptr, rc = phl_hip_fail(e, "hipMallocAsync", __FILE__, __LINE__);
+    }
+    double *mx = (double *)tmp[0];
+    float *inv = (float *)tmp[1], *coef = (float *)tmp[2];
+    if (rc == PHL_OK) {
+        stats<<<dim3(tiles.x, tiles.y, (unsigned)B), dim3(NT), lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = phl_hip_fail(e, "k_guide_stats", __FILE__, __LINE__);
+    }
+    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
+        const unsigned nz = (unsigned)min(chunk, nimg - n0);
+        coefk<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_coef, st>>>(y, x, row_of_low, col_of_low, mx, inv, coef, (int)n0, cy, cx, H, W, h,
+                                                                     w, re);
+        apply<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_apply, st>>>(coef, x, src, out, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h,
+                                                                      w, re, scale);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = phl_hip_fail(e, "k_guide_coef / k_guide_apply", __FILE__, __LINE__);
+    }
+    for (int i = 2; i >= 0; i--) {
+        if (!tmp[i]) continue;
+        hipError_t e = hipFreeAsync(tmp[i], st);
+        if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, "hipFreeAsync", __FILE__, __LINE__);
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int phl_guided_filter_max_r(void)
+{
+    int r = 0;
+    while (max_lds(r + 1) <= kMaxLds && halo_stride(r + 1) <= 64 * NCO) r++;
+    return r;
+}
+
+int phl_guided_filter(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h, int w,
+                      int r, const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col,
+                      const float *eps, float scale, phl_stream stream)
+{
+    if (B < 0 || cy < 0 || cx < 1 || H < 0 || W < 0 || h < 0 || w < 0 || r < 0 || h > H || w > W || !isfinite(scale)) {
+        phl_set_error("phl_guided_filter: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", B, cy, cx, H, W, h, w,
+                      r, (double)scale);
+        return PHL_ERR_INVALID;
+    }
+    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
+    if (h == 0 || w == 0) {
+        phl_set_error("phl_guided_filter: empty solving resolution %d x %d for a %d x %d image", h, w, H, W);
+        return PHL_ERR_INVALID;
+    }
+    if (!y || !x || !out || !eps || !row_of_low || !col_of_low || !low_of_row || !low_of_col) {
+        phl_set_error("phl_guided_filter: null y / x / out / eps / index map");
+        return PHL_ERR_INVALID;
+    }
+    if (out == y || out == x || out == src) {
+        phl_set_error("phl_guided_filter: out aliases an input");
+        return PHL_ERR_INVALID;
+    }
+    const int64_t HWf = (int64_t)H * W, lim = INT64_MAX / 16;
+    const int64_t nimg = (int64_t)B * cy;
+    if (HWf > INT32_MAX || nimg > INT32_MAX || HWf > lim / nimg || HWf > lim / ((int64_t)B * cx) || (h + TH - 1) / TH > 65535 ||
+        B > 65535 || max(H, W) > (1 << 30)) {
+        phl_set_error("phl_guided_filter: %d x %d x (%d | %d) x %d x %d elements are too many", B, cy, cx, cy, H, W);
+        return PHL_ERR_TOO_LARGE;
+    }
+    if (cx > PHL_GUIDED_MAX_CX) {
+        phl_set_error("phl_guided_filter: %d guide channels, at most %d", cx, PHL_GUIDED_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    const int re = min(r, max(h, w));            // a window beyond the image on both axes sums the same pixels
+    return run(y, x, src, out, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps, scale,
+                      (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -112,6 +112,8 @@ def load_library():
             lib.phl_box_blur.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp]
             lib.phl_box_blur_grad.argtypes = [vp, vp, i64, i64, i64, i32, C.c_double, vp, vp, vp]
             lib.phl_box_blur_fused_max_r.argtypes = [i32, i32, i32]
+        if hasattr(lib, "phl_guided_filter"):          # (an older build loaded through PHL_LIB lacks the guided filter)
+            lib.phl_guided_filter.argtypes = [vp, vp, vp, vp] + [i32] * 8 + [vp, vp, vp, vp, vp, C.c_float, vp]
         lib.phl_stream_copy.argtypes = [vp, vp, i64, vp]
         lib.phl_copy2d.argtypes = [vp, i64, i64, vp, i64, i64, i64, i32, vp]
         lib.phl_cost_volume.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
@@ -991,6 +993,77 @@ def box_blur_grad(v, g, r, dim, sigma, need_x=True, need_sigma=True):
     D = vd * f * Bg - vd * Bgf + gd * f * Bv - gd * Bvf
     gs = ((D * f).sum() - (Bg.double() * vd).sum()) / float(sigma)
     return (Bg if need_x else None), gs.float()
+
+
+# ---------------------------------------------------------------------------------------------
+# box-window guided filter (crf/guided.py; include/phl.h, phl_guided.hip)
+_nearest_maps = OrderedDict()
+
+
+def _nearest_index_maps(H, W, s, device):
+    """int32 device maps of F.interpolate(mode='nearest') between (H, W) and (H // s, W // s): (row_of_low [h], col_of_low
+    [w], low_of_row [H], low_of_col [W]).  torch interpolates an arange itself, on the tensors' own device, so the kernel
+    cannot disagree with torch's float rounding of floor(dst * in / out).  Cached per (H, W, s, device)."""
+    key = (H, W, s, str(device))
+    maps = _nearest_maps.get(key)
+    if maps is None:
+        def nearest(n_in, n_out):
+            if n_in == n_out:
+                return torch.arange(n_in, dtype=torch.int32, device=device)
+            src = torch.arange(n_in, dtype=torch.float32, device=device).reshape(1, 1, n_in, 1)
+            return torch.nn.functional.interpolate(src, size=(n_out, 1), mode="nearest").reshape(n_out).to(torch.int32)
+
+        h, w = H // s, W // s
+        maps = (nearest(H, h), nearest(W, w), nearest(h, H), nearest(w, W))
+        _nearest_maps[key] = maps
+        while len(_nearest_maps) > 16:
+            _nearest_maps.popitem(last=False)
+    return maps
+
+
+def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=None):
+    """The box-window guided filter of ``y`` [B, cy, H, W] by the guide ``x`` [B, cx, H, W] (phl_guided_filter; forward
+    only): ``out = guided(y, x) * scale - subtract``.  ``r`` is the full-resolution radius; with ``subsample = s > 1`` the
+    linear model is solved on nearest samples at (H // s, W // s) with radius r // s and upsampled by nearest
+    (FastGuidedFilter).  ``eps``: a number or a tensor of cx values (softplus(omega) stays on the device).  fp32 CUDA
+    tensors of any strides (copied contiguous); any radius (above phl_guided_filter_max_r at the solving resolution the
+    kernels read the image from memory instead of LDS tiles); PhlError status 7 for more than 16 guide channels."""
+    for t in (y, x) + (() if subtract is None else (subtract,)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise TypeError(f"guided_filter: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+    if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:] or x.device != y.device:
+        raise ValueError(f"guided_filter: y [B, cy, H, W] and x [B, cx, H, W] on one device, got {tuple(y.shape)} and {tuple(x.shape)}")
+    if subtract is not None and (subtract.shape != y.shape or subtract.device != y.device):
+        raise ValueError("guided_filter: subtract must have y's shape and device")
+    s, r = int(subsample), int(r)
+    if s < 1 or r < 0:
+        raise ValueError(f"guided_filter: needs subsample >= 1 and r >= 0, got {subsample} and {r}")
+    B, cy, H, W = (int(v) for v in y.shape)
+    cx = int(x.shape[1])
+    yc, xc = y.contiguous(), x.contiguous()
+    sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
+    if out is None:
+        out = torch.empty((B, cy, H, W), dtype=torch.float32, device=y.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == y.shape
+              and out.device == y.device):
+        raise TypeError("guided_filter: out must be a contiguous fp32 tensor of y's shape and device")
+    if torch.is_tensor(eps):
+        e = eps.detach().to(device=y.device, dtype=torch.float32).reshape(-1)
+        if e.numel() == 1 and cx != 1:
+            e = e.expand(cx)
+        if e.numel() != cx:
+            raise ValueError(f"guided_filter: eps has {e.numel()} values for {cx} guide channels")
+        e = e.contiguous()
+    else:
+        e = torch.full((cx,), float(eps), dtype=torch.float32, device=y.device)
+    if out.numel() == 0:
+        return out
+    if H // s == 0 or W // s == 0:
+        raise ValueError(f"guided_filter: a {H} x {W} image has no pixels at subsample {s}")
+    maps = _nearest_index_maps(H, W, s, y.device)
+    _launch(y.device, "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), B, cy, cx, H, W, H // s, W // s, r // s,
+            *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)))
+    return out
 
 
 def stream_copy(dst, src):

@@ -361,6 +361,32 @@ int phl_box_blur_grad(const float *v_dev, const float *g_dev, int64_t outer, int
 /* largest r the single fused kernel takes for these passes (grad != 0: phl_box_blur_grad's); INT32_MAX for one pass */
 int phl_box_blur_fused_max_r(int inner_is_one, int passes, int grad);
 
+/* ---- box-window guided filter (crf/guided.py: GuidedFilter, FastGuidedFilter, BatchedGuidedAdjacency) -------------
+ * Forward only.  Contiguous NCHW fp32: y [B][cy][H][W] (filtered), x [B][cx][H][W] (guide), out [B][cy][H][W], src NULL
+ * or [B][cy][H][W].  S_r(t) = sum of t over the (2r+1)^2 window clipped to the image, mean(t) = S_r(t) / S_r(1).  The
+ * linear model is solved at the resolution h x w <= H x W on nearest samples (FastGuidedFilter; h = H, w = W and
+ * identity maps give the plain filter), with r the radius AT THAT RESOLUTION:
+ *   yl = y[.., row_of_low[i], col_of_low[j]], xl likewise
+ *   A_lc = (mean(yl_l xl_c) - mean(yl_l) mean(xl_c)) / (mean(xl_c^2) - mean(xl_c)^2 + eps[c])
+ *   b_l  = mean(yl_l) - sum_c A_lc mean(xl_c)
+ *   out_l[I][J] = (sum_c mean(A_lc)[i][j] x_c[I][J] + mean(b_l)[i][j]) * scale - src_l[I][J],  i = low_of_row[I], j = low_of_col[J]
+ * Index maps are int32 on the device: row_of_low [h], col_of_low [w] (values in 0..H-1 / 0..W-1) and low_of_row [H],
+ * low_of_col [W] (non-decreasing, values in 0..h-1 / 0..w-1) -- torch's own nearest maps, see phl.guided_filter.
+ * eps: [cx] fp32 on the device.  Window sums are kept in fp64 over direct sliding windows (no image-long prefix sums);
+ * no atomics: the same bits on every run.  Temporaries are stream-ordered allocations.
+ * Status, checked before any HIP call: PHL_ERR_INVALID for negative sizes, cx < 1, r < 0, h > H, w > W, an empty solving
+ * resolution of a non-empty image, a non-finite scale, NULL pointers (src may be NULL) or out aliasing an input;
+ * PHL_ERR_TOO_LARGE when H*W or B*cy leave int32, a side exceeds 2^30 or the byte counts leave int64;
+ * PHL_ERR_UNSUPPORTED for cx > PHL_GUIDED_MAX_CX (the caller keeps its torch path).  Any r: while
+ * min(r, max(h, w)) <= phl_guided_filter_max_r() a workgroup keeps its tile and halo in LDS; above it the same kernels
+ * run their streamed form, which reads the image from memory in strips and needs no LDS that grows with r (slower).
+ * Zero elements: PHL_OK. */
+#define PHL_GUIDED_MAX_CX 16
+int phl_guided_filter(const float *y_dev, const float *x_dev, const float *src_dev, float *out_dev, int B, int cy, int cx, int H,
+                      int W, int h, int w, int r, const int *row_of_low_dev, const int *col_of_low_dev, const int *low_of_row_dev,
+                      const int *low_of_col_dev, const float *eps_dev, float scale, phl_stream stream);
+int phl_guided_filter_max_r(void);   /* largest window radius (at the solving resolution) of the LDS-tiled form */
+
 /* Plain float4 streaming copy dst <- src (n_floats % 4 == 0, 16-byte aligned): measures the
  * HBM read+write ceiling of the box that the roofline fractions are compared with. */
 int phl_stream_copy(const float *src_dev, float *dst_dev, int64_t n_floats, phl_stream stream);
