@@ -364,7 +364,9 @@ class CRFasRNN(nn.Module):
     """Batched NCHW mean field (crf_module.py:81-104); returns logits -E of the LAST iteration.
 
     ``lattice=True`` selects the permutohedral W (BatchedAdjacency, the MI355X path); the default
-    stays the reference's guided-filter W."""
+    stays the reference's guided-filter W.  ``fused_grad=True`` keeps W on the library's kernels under autograd: the
+    lattice W through _mean_field_nchw_grad, the guided W through phl.GuidedFilterFn inside the plain NCHW loop (Mu and
+    the softmax stay torch ops there)."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
                  fused_grad=False):
@@ -372,7 +374,10 @@ class CRFasRNN(nn.Module):
         self.Mu, self.niters = mu_init, niters
         if notrain_mu:
             self.Mu.requires_grad_(False)
-        self.W = BatchedAdjacency() if lattice else BatchedGuidedAdjacency(gchannels, r, eps, gaussian=gaussian)
+        # (fused_grad and the guided W: its box-window filter trains on phl.GuidedFilterFn; the Gaussian window has its own
+        # backward, crf.guided.GaussianBlur, and ignores the flag)
+        self.W = BatchedAdjacency() if lattice else BatchedGuidedAdjacency(gchannels, r, eps, gaussian=gaussian,
+                                                                             fused_grad=fused_grad and not gaussian)
         self.fused_grad = fused_grad
 
     def forward(self, refs, logits, confidence=None, labels=None):

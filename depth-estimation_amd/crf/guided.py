@@ -6,7 +6,9 @@ constructor / call signatures.  Their torch form below is pinned to the referenc
 ``mBoxFilter`` as the box sum (tests/golden/generate_guided.py, tests/test_guided_cpu.py).  A forward on fp32 CUDA tensors
 that autograd does not record runs on the HIP kernels instead (phl.guided_filter, phl_guided.hip: fp64 window sums over
 LDS tiles, the ``* k - src`` of the adjacency fused); CPU tensors, float64, training, ``mode != 'nearest'`` and
-``gaussian=True`` stay on the torch form.
+``gaussian=True`` stay on the torch form.  Training leaves it only on request: with the keyword ``fused_grad=True`` a forward
+that autograd records goes through phl.GuidedFilterFn, whose backward runs on the library's kernels as well
+(phl.guided_filter_grad: y, x and eps are all that is saved) and gives y, x and omega their gradients.
 
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
@@ -136,8 +138,9 @@ class GuidedFilter(nn.Module):
     """y filtered by guide x with per-guide-channel (diagonal covariance) linear model,
     eps = softplus(omega) as in the reference's parametrisation (:161-232)."""
 
-    def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False):
+    def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False, *, fused_grad=False):
         super().__init__()
+        self.fused_grad = fused_grad
         self.omega = nn.Parameter(torch.log(torch.expm1(torch.tensor(float(eps)))).expand(channels).clone())
         if gaussian:
             # pinned to the reference (tests/golden/blur_guided.npz): its fp32 log(exp(eps) - 1), not expm1 (:166)
@@ -182,15 +185,20 @@ class GuidedFilter(nn.Module):
 
     def _fused(self, y, x, subsample=1, scale=1.0, subtract=None):
         """The forward on the HIP kernels (phl.guided_filter), or None where the torch form has to run: a Gaussian
-        window, an interpolation other than nearest, tensors that are not fp32 CUDA, autograd recording, or a shape the
-        kernels do not take (PHL_ERR_UNSUPPORTED: more than 16 guide channels)."""
+        window, an interpolation other than nearest, tensors that are not fp32 CUDA, autograd recording without
+        ``fused_grad``, or a shape the kernels do not take (PHL_ERR_UNSUPPORTED: more than 16 guide channels).  With
+        ``fused_grad`` a recorded forward is phl.GuidedFilterFn (eps = softplus(omega) keeps its graph); ``subtract`` is
+        None or y itself."""
         if self.gaussian or getattr(self, "mode", "nearest") != "nearest" or not (_hip_ok(y) and _hip_ok(x)):
             return None
         if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
             return None
-        if torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad):
+        recording = torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad)
+        if recording and not self.fused_grad:
             return None
         try:
+            if recording:
+                return phl.GuidedFilterFn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract)
         except phl.PhlError as e:
             if e.status != 7:

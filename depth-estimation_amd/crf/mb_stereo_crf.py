@@ -35,9 +35,10 @@ class _CoordConv(nn.Module):
 
 
 class CRFdepthRefiner(nn.Module):
-    def __init__(self, d_in=64, d_guide=16, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False):
+    def __init__(self, d_in=64, d_guide=16, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False):
         super().__init__()
-        self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice)
+        self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
+                            fused_grad=fused_grad)
         self.projection = nn.Conv2d(d_in, d_guide - 3, kernel_size=1)
 
     def _guide(self, imgrgb, features):
@@ -63,9 +64,10 @@ class CRFwUncertainty(CRFdepthRefiner):
 
 
 class CRFdepthUpsampler(nn.Module):
-    def __init__(self, d_in=64, d_guide=3, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False):
+    def __init__(self, d_in=64, d_guide=3, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False):
         super().__init__()
-        self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice)
+        self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
+                            fused_grad=fused_grad)
 
     def forward(self, inputs):
         disp_lowres, img_highres, _ = inputs

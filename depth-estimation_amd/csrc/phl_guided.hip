@@ -1,5 +1,5 @@
 // phl_guided.hip -- the box-window guided filter (crf/guided.py: GuidedFilter, FastGuidedFilter, BatchedGuidedAdjacency,
-// GuidedAdjacency), forward only, NCHW fp32.
+// GuidedAdjacency), forward and backward, NCHW fp32.
 //
 // S_r(t) = sum of t over the (2r+1)^2 window clipped to the image, N = S_r(1), mean(t) = S_r(t) / N.  At the solving
 // resolution h x w (the nearest-sampled H x W image; h = H, w = W for the plain filter), per guide channel c and label l:
@@ -8,7 +8,7 @@
 //   out_l = (sum_c mean(A_lc)[lo(p)] x_c[p] + mean(b_l)[lo(p)]) * scale - src_l[p]      at every full-resolution pixel p
 // The nearest index maps (low -> full for sampling, full -> low for the upsampling) come from the caller.
 //
-// Three kernels, all built on one tile routine (tile_fill + tile_sums): a workgroup of 256 owns a 32 x 64 tile of one low-resolution
+// The forward is three kernels (the backward follows further down), all built on one tile routine (tile_fill + tile_sums): a workgroup of 256 owns a 32 x 64 tile of one low-resolution
 // plane, fills the tile plus a halo of r (zero outside the image) into LDS as fp32, forms the horizontal window sums of
 // every halo row by a sliding fp64 sum (work item = row x column segment, lanes across rows, odd row strides: no bank
 // conflict) into an fp64 LDS plane, then the vertical window sums by a second sliding fp64 sum (lane = column, wave =
@@ -446,6 +446,437 @@ int run(const float *y, const float *x, const float *src, float *out, int B, int
     return rc;
 }
 
+// ---- backward ------------------------------------------------------------------------------------------------------
+// With g the gradient of out [B][cy][H][W], N = S(1), and the forward's mx_c, my_l, inv_c = 1 / (var_c + eps_c), A_lc
+// recomputed (nothing but y, x, eps and g comes in):
+//   gAbar_lc[q] = scale sum_{p: lo(p) = q} g_l[p] x_c[p]      gbbar_l[q] = scale sum_{p: lo(p) = q} g_l[p]
+//   gA_lc = S(gAbar_lc / N)    gb_l = S(gbbar_l / N)                        (the adjoint of mean is u -> S(u / N))
+//   gA'_lc = gA_lc - gb_l mx_c   gcov_lc = gA'_lc inv_c   gvar_c = -inv_c sum_l gA'_lc A_lc   gmy_l = gb_l - sum_c gcov_lc mx_c
+//   gmx_c = -sum_l gb_l A_lc - sum_l gcov_lc my_l - 2 mx_c gvar_c
+//   U_l0 = S(gmy_l / N)   U_lc = S(gcov_lc / N)
+//   gys_l = U_l0 + sum_c xs_c U_lc          gxs_c = sum_l ys_l U_lc + S(gmx_c / N) + 2 xs_c S(gvar_c / N)
+//   grad_y = gys at the sampled pixels (0 elsewhere) - g where the subtracted source is y
+//   grad_x[p] = scale sum_l g_l[p] mean(A_lc)[lo(p)] + gxs at the sampled pixels        grad_eps_c = sum gvar_c
+// Kernels, per chunk of labels (planes are low-resolution, fp32 where a window sum reads them, fp64 where labels are summed):
+//   k_grad_gather   the nearest samples ys / xs as planes of their own (skipped at full resolution: y and x are those
+//                   planes), so that every tile below has identity maps
+//   k_grad_down     gAbar / N and gbbar / N: one thread per low-resolution pixel sums its pre-image rectangle in fp64
+//   k_grad_coef     per (label, tile): the forward's sums of ys and ys xs_c again -> my, A in fp64; the sums gA, gb; the
+//                   pointwise step; writes gcov_lc / N and gmy_l / N, A_lc (for grad_x) and this label's terms of
+//                   gvar_c / N and gmx_c / N
+//   k_grad_apply    per (label, tile): U_l0, U_lc -> gys into LDS -> grad_y over the tile's full-resolution pixels;
+//                   for grad_x also this label's ys_l U_lc and mean(A_lc)
+//   k_grad_reduce   the per-label terms summed over the chunk's labels in index order into fp64 planes [B][cx][h][w]
+//   k_grad_direct   sum_l g_l[p] mean(A_lc)[lo(p)] into an fp64 plane [B][cx][H][W], labels in index order
+// (chunks follow each other in stream order), and then once:
+//   k_grad_finish   gmx_c / N with its - 2 mx_c gvar_c term, and gvar_c / N, as fp32 planes for the tile routine
+//   k_grad_x        per (image, tile), channels in a loop: gxs into LDS -> grad_x over the tile's full-resolution pixels
+//   k_grad_eps1/2   grad_eps: a fixed-order two-stage fp64 reduction of gvar_c
+// No atomics anywhere; every gradient is rounded to fp32 once.
+constexpr int NE = 256;             // threads of the pointwise kernels
+constexpr int NEB = 128;            // first-stage workgroups per channel of the grad_eps reduction
+enum { PART_VAR = 0, PART_MX = 1, PART_YU = 2, NPART = 3 };
+
+__global__ __launch_bounds__(NE) void k_grad_gather(const float *__restrict__ src, float *__restrict__ dst,
+                                                   const int *__restrict__ rmap, const int *__restrict__ cmap, int H, int W, int h,
+                                                   int w)
+{
+    const int64_t hw = (int64_t)h * w, q = (int64_t)blockIdx.x * NE + threadIdx.x;
+    if (q >= hw) return;
+    const int64_t pl = (int64_t)blockIdx.z * gridDim.y + blockIdx.y;
+    const int i = (int)(q / w), j = (int)(q % w);
+    dst[pl * hw + q] = src[pl * H * W + (int64_t)clampi(rmap[i], 0, H - 1) * W + clampi(cmap[j], 0, W - 1)];
+}
+
+__global__ __launch_bounds__(NE) void k_grad_down(const float *__restrict__ g, const float *__restrict__ x, float *__restrict__ P,
+                                                 const int *__restrict__ rlow, const int *__restrict__ clow, int n0, int cy, int cx,
+                                                 int H, int W, int h, int w, int r, float scale)
+{
+    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, q = (int64_t)blockIdx.x * NE + threadIdx.x;
+    if (q >= hw) return;
+    const int z = blockIdx.y, n = n0 + z, b = n / cy;
+    const int i = (int)(q / w), j = (int)(q % w);
+    const int I0 = lower_bound(rlow, H, i), I1 = lower_bound(rlow, H, i + 1);
+    const int J0 = lower_bound(clow, W, j), J1 = lower_bound(clow, W, j + 1);
+    const double k = (double)scale / ((double)win_count(i, r, h) * (double)win_count(j, r, w));
+    const float *gp = g + (int64_t)n * HWf;
+    for (int c = 0; c <= cx; c++) {
+        const float *xp = c < cx ? x + ((int64_t)b * cx + c) * HWf : nullptr;
+        double acc = 0.0;
+        for (int I = I0; I < I1; I++)
+            for (int J = J0; J < J1; J++) {
+                const int64_t o = (int64_t)I * W + J;
+                acc += xp ? (double)gp[o] * (double)xp[o] : (double)gp[o];
+            }
+        P[((int64_t)z * (cx + 1) + c) * hw + q] = (float)(acc * k);
+    }
+}
+
+// window sums of a low-resolution plane (identity maps) in either form
+template <bool ST>
+__device__ __forceinline__ void plane_sums(const Tile &t, float *__restrict__ in, const float *__restrict__ pl, double (&s)[RPT])
+{
+    if constexpr (ST) {
+        tile_sums_stream(t, s, [&](int i, int jj) { return (double)pl[(int64_t)i * t.w + jj]; });
+    } else {
+        tile_fill(t, in, pl);
+        tile_sums(t, s, [&](int e) { return (double)in[e]; });
+    }
+}
+
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_grad_coef(const float *__restrict__ ys, const float *__restrict__ xs,
+                                                 const float *__restrict__ P, const double *__restrict__ mx,
+                                                 const float *__restrict__ inv, float *__restrict__ Q, float *__restrict__ A,
+                                                 double *__restrict__ part, int n0, int cy, int cx, int h, int w, int r)
+{
+    Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_COEF);
+    const int z = blockIdx.z, b = (n0 + z) / cy;
+    const int lane = threadIdx.x & 63, i0 = t.ti + (threadIdx.x >> 6) * RPT, j = t.tj + lane;
+    const int64_t hw = (int64_t)h * w;
+    const float *yp = ys + (int64_t)z * hw, *pp = P + (int64_t)z * (cx + 1) * hw;
+    float *qp = Q + (int64_t)z * (cx + 1) * hw, *ap = A ? A + (int64_t)z * cx * hw : nullptr;
+    double *tp = part ? part + (int64_t)z * NPART * cx * hw : nullptr;
+    const int cj = j < w ? win_count(j, r, w) : 1;
+
+    double my[RPT], gb[RPT], gmy[RPT], rn[RPT], a[RPT], s[RPT];
+#pragma unroll
+    for (int k = 0; k < RPT; k++) rn[k] = 1.0 / ((double)(i0 + k < h ? win_count(i0 + k, r, h) : 1) * (double)cj);
+    plane_sums<ST>(t, t.in, yp, s);                                 // (tiled form: ys stays in LDS for the products below)
+#pragma unroll
+    for (int k = 0; k < RPT; k++) my[k] = s[k] * rn[k];
+    plane_sums<ST>(t, t.in2, pp + (int64_t)cx * hw, gb);
+#pragma unroll
+    for (int k = 0; k < RPT; k++) gmy[k] = gb[k];
+    for (int c = 0; c < cx; c++) {
+        const float *xp = xs + ((int64_t)b * cx + c) * hw;
+        if constexpr (ST) {
+            tile_sums_stream(t, s, [&](int i, int jj) { const int64_t o = (int64_t)i * w + jj; return (double)yp[o] * (double)xp[o]; });
+        } else {
+            tile_fill(t, t.in2, xp);
+            tile_sums(t, s, [&](int e) { return (double)t.in[e] * (double)t.in2[e]; });
+        }
+#pragma unroll
+        for (int k = 0; k < RPT; k++) a[k] = s[k] * rn[k];            // mean(y x_c) for now
+        plane_sums<ST>(t, t.in2, pp + (int64_t)c * hw, s);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            const int i = i0 + k;
+            if (i < h && j < w) {
+                const int64_t o = (int64_t)i * w + j, gi = ((int64_t)b * cx + c) * hw + o;
+                const double m = mx[gi], iv = (double)inv[gi];
+                const double alc = (a[k] - my[k] * m) * iv;
+                const double gap = s[k] - gb[k] * m, gcov = gap * iv;
+                gmy[k] -= gcov * m;
+                qp[(int64_t)c * hw + o] = (float)(gcov * rn[k]);
+                if (ap) ap[(int64_t)c * hw + o] = (float)alc;
+                if (tp) {
+                    tp[((int64_t)PART_VAR * cx + c) * hw + o] = -(iv * (gap * alc)) * rn[k];
+                    tp[((int64_t)PART_MX * cx + c) * hw + o] = -(gb[k] * alc + gcov * my[k]) * rn[k];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < RPT; k++) {
+        const int i = i0 + k;
+        if (i < h && j < w) qp[(int64_t)cx * hw + (int64_t)i * w + j] = (float)(gmy[k] * rn[k]);
+    }
+}
+
+// f(o, value) for every full-resolution pixel of the tile's share: G[li][lj] of the tile's LDS plane at the pixel that is
+// the sample (rmapS[i], cmapS[j]) of the tile's low-resolution pixel (i, j), 0 at the others.  The shares partition the
+// image: the rows from the sample row of the tile's first row up to that of the next tile's (strictly increasing maps),
+// columns likewise -- a sample need not lie in the pre-image of its own low-resolution pixel under the upsampling maps.
+template <typename F>
+__device__ __forceinline__ void scatter_tile(const Tile &t, const double *__restrict__ G, const int *__restrict__ rmapS,
+                                             const int *__restrict__ cmapS, int H, int W, F f)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int I0 = t.ti == 0 ? 0 : clampi(rmapS[t.ti], 0, H), I1 = t.ti + TH >= t.h ? H : clampi(rmapS[t.ti + TH], 0, H);
+    const int J0 = t.tj == 0 ? 0 : clampi(cmapS[t.tj], 0, W), J1 = t.tj + TW >= t.w ? W : clampi(cmapS[t.tj + TW], 0, W);
+    for (int I = I0 + wave; I < I1; I += 4) {
+        const int i = lower_bound(rmapS, t.h, I);
+        const bool ri = i < t.h && i >= t.ti && i < t.ti + TH && rmapS[i] == I;
+        for (int J = J0 + lane; J < J1; J += 64) {
+            const int j = lower_bound(cmapS, t.w, J);
+            const bool hit = ri && j < t.w && j >= t.tj && j < t.tj + TW && cmapS[j] == J;
+            f((int64_t)I * W + J, hit ? G[(i - t.ti) * TW + (j - t.tj)] : 0.0);
+        }
+    }
+}
+
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_grad_apply(const float *__restrict__ Q, const float *__restrict__ A,
+                                                  const float *__restrict__ ys, const float *__restrict__ xs,
+                                                  const float *__restrict__ g, float *__restrict__ grad_y, float *__restrict__ mA,
+                                                  double *__restrict__ part, const int *__restrict__ rmapS,
+                                                  const int *__restrict__ cmapS, int n0, int cy, int cx, int H, int W, int h, int w,
+                                                  int r, int subtract_is_y)
+{
+    Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_APPLY);
+    double *G = reinterpret_cast<double *>(t.in2);                  // [TH][TW] gys (both forms; 8-byte aligned)
+    const int z = blockIdx.z, n = n0 + z, b = n / cy;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i0 = t.ti + wave * RPT, j = t.tj + lane;
+    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W;
+    const float *qp = Q + (int64_t)z * (cx + 1) * hw, *yp = ys + (int64_t)z * hw;
+    const int cj = j < w ? win_count(j, r, w) : 1;
+    double gys[RPT], s[RPT];
+    plane_sums<ST>(t, t.in, qp + (int64_t)cx * hw, gys);
+    for (int c = 0; c < cx; c++) {
+        const float *xp = xs + ((int64_t)b * cx + c) * hw;
+        plane_sums<ST>(t, t.in, qp + (int64_t)c * hw, s);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            const int i = i0 + k;
+            if (i < h && j < w) {
+                const int64_t o = (int64_t)i * w + j;
+                gys[k] += (double)xp[o] * s[k];
+                if (part) part[((int64_t)z * NPART * cx + (int64_t)PART_YU * cx + c) * hw + o] = (double)yp[o] * s[k];
+            }
+        }
+        if (mA) {
+            plane_sums<ST>(t, t.in, A + ((int64_t)z * cx + c) * hw, s);
+#pragma unroll
+            for (int k = 0; k < RPT; k++) {
+                const int i = i0 + k;
+                if (i < h && j < w)
+                    mA[((int64_t)z * cx + c) * hw + (int64_t)i * w + j] =
+                        (float)(s[k] / ((double)win_count(i, r, h) * (double)cj));
+            }
+        }
+    }
+    if (!grad_y) return;
+#pragma unroll
+    for (int k = 0; k < RPT; k++) G[(wave * RPT + k) * TW + lane] = gys[k];
+    __syncthreads();
+    const float *gp = g + (int64_t)n * HWf;
+    float *op = grad_y + (int64_t)n * HWf;
+    scatter_tile(t, G, rmapS, cmapS, H, W,
+                 [&](int64_t o, double v) { op[o] = (float)(subtract_is_y ? v - (double)gp[o] : v); });
+}
+
+// acc[sel][b][c] (+)= sum over the chunk's labels of image b, in index order, of part[label][sel][c]
+__global__ __launch_bounds__(NE) void k_grad_reduce(const double *__restrict__ part, double *__restrict__ acc, int n0, int nz, int cy,
+                                                   int cx, int B, int nsel, int64_t hw)
+{
+    const int64_t q = (int64_t)blockIdx.x * NE + threadIdx.x;
+    if (q >= hw) return;
+    const int c = blockIdx.y, b = n0 / cy + blockIdx.z;
+    const int na = max(n0, b * cy), nb = min(n0 + nz, (b + 1) * cy);
+    for (int sel = 0; sel < nsel; sel++) {
+        double s = 0.0;
+        for (int n = na; n < nb; n++) s += part[(((int64_t)(n - n0) * NPART + sel) * cx + c) * hw + q];
+        double *d = acc + (((int64_t)sel * B + b) * cx + c) * hw + q;
+        *d = na == b * cy ? s : *d + s;
+    }
+}
+
+// D[b][c][p] (+)= sum over the chunk's labels of image b, in index order, of g_l[p] mean(A_lc)[lo(p)]
+__global__ __launch_bounds__(NE) void k_grad_direct(const float *__restrict__ g, const float *__restrict__ mA, double *__restrict__ D,
+                                                   const int *__restrict__ rlow, const int *__restrict__ clow, int n0, int nz, int cy,
+                                                   int cx, int H, int W, int h, int w)
+{
+    const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w, p = (int64_t)blockIdx.x * NE + threadIdx.x;
+    if (p >= HWf) return;
+    const int c = blockIdx.y, b = n0 / cy + blockIdx.z;
+    const int na = max(n0, b * cy), nb = min(n0 + nz, (b + 1) * cy);
+    const int64_t lo = (int64_t)clampi(rlow[p / W], 0, h - 1) * w + clampi(clow[p % W], 0, w - 1);
+    double s = 0.0;
+    for (int n = na; n < nb; n++) s += (double)g[(int64_t)n * HWf + p] * (double)mA[((int64_t)(n - n0) * cx + c) * hw + lo];
+    double *d = D + ((int64_t)b * cx + c) * HWf + p;
+    *d = na == b * cy ? s : *d + s;
+}
+
+__global__ __launch_bounds__(NE) void k_grad_finish(const double *__restrict__ acc, const double *__restrict__ mx,
+                                                   float *__restrict__ F, int B, int cx, int64_t hw)
+{
+    const int64_t q = (int64_t)blockIdx.x * NE + threadIdx.x;
+    if (q >= hw) return;
+    const int64_t bc = (int64_t)blockIdx.z * cx + blockIdx.y, o = bc * hw + q;
+    const double gv = acc[(int64_t)PART_VAR * B * cx * hw + o];
+    F[(bc * 2 + 0) * hw + q] = (float)(acc[(int64_t)PART_MX * B * cx * hw + o] - 2.0 * mx[o] * gv);
+    F[(bc * 2 + 1) * hw + q] = (float)gv;
+}
+
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_grad_x(const float *__restrict__ F, const double *__restrict__ YU,
+                                              const float *__restrict__ xs, const double *__restrict__ D, float *__restrict__ grad_x,
+                                              const int *__restrict__ rmapS, const int *__restrict__ cmapS, int cx, int H, int W,
+                                              int h, int w, int r, float scale)
+{
+    Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_APPLY);
+    double *G = reinterpret_cast<double *>(t.in2);
+    const int b = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i0 = t.ti + wave * RPT, j = t.tj + lane;
+    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W;
+    for (int c = 0; c < cx; c++) {
+        const int64_t bc = (int64_t)b * cx + c;
+        double s1[RPT], s2[RPT];
+        plane_sums<ST>(t, t.in, F + (bc * 2 + 0) * hw, s1);
+        plane_sums<ST>(t, t.in, F + (bc * 2 + 1) * hw, s2);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            const int i = i0 + k;
+            double v = 0.0;
+            if (i < h && j < w) {
+                const int64_t o = bc * hw + (int64_t)i * w + j;
+                v = YU[o] + s1[k] + 2.0 * (double)xs[o] * s2[k];
+            }
+            G[(wave * RPT + k) * TW + lane] = v;
+        }
+        __syncthreads();
+        const double *dp = D + bc * HWf;
+        float *op = grad_x + bc * HWf;
+        scatter_tile(t, G, rmapS, cmapS, H, W, [&](int64_t o, double v) { op[o] = (float)((double)scale * dp[o] + v); });
+        // (the next channel's first write to G comes after the barriers of its plane_sums)
+    }
+}
+
+// grad_eps_c = sum over images and pixels of gvar_c = (gvar_c / N) N: stage 1, NEB workgroups per channel, each thread a
+// fixed strided share in index order, then a fixed tree in LDS; stage 2 adds the NEB partial sums in index order
+__global__ __launch_bounds__(NE) void k_grad_eps1(const double *__restrict__ gvn, double *__restrict__ partial, int B, int cx, int h,
+                                                 int w, int r)
+{
+    __shared__ double sh[NE];
+    const int c = blockIdx.y;
+    const int64_t hw = (int64_t)h * w, total = (int64_t)B * hw;
+    double s = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * NE + threadIdx.x; e < total; e += (int64_t)NEB * NE) {
+        const int64_t b = e / hw, q = e % hw;
+        const double n = (double)win_count((int)(q / w), r, h) * (double)win_count((int)(q % w), r, w);
+        s += gvn[(b * cx + c) * hw + q] * n;
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = NE / 2; d > 0; d >>= 1) {
+        if ((int)threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(int64_t)c * NEB + blockIdx.x] = sh[0];
+}
+
+__global__ void k_grad_eps2(const double *__restrict__ partial, float *__restrict__ grad_eps, int cx)
+{
+    const int c = threadIdx.x;
+    if (c >= cx) return;
+    double s = 0.0;
+    for (int k = 0; k < NEB; k++) s += partial[(int64_t)c * NEB + k];
+    grad_eps[c] = (float)s;
+}
+
+struct Temps {                       // stream-ordered temporaries, freed on every exit path by release()
+    static constexpr int MAXN = 16;
+    void *p[MAXN];
+    int n = 0;
+    hipStream_t st;
+    int rc = PHL_OK;
+    explicit Temps(hipStream_t s) : st(s) {}
+    template <typename T>
+    T *get(size_t count)
+    {
+        if (rc != PHL_OK || n >= MAXN) return nullptr;
+        void *q = nullptr;
+        hipError_t e = hipMallocAsync(&q, max(count, (size_t)1) * sizeof(T), st);
+        if (e != hipSuccess) {
+            rc = phl_hip_fail(e, "hipMallocAsync", __FILE__, __LINE__);
+            return nullptr;
+        }
+        p[n++] = q;
+        return (T *)q;
+    }
+    int release()
+    {
+        for (int i = n - 1; i >= 0; i--) {
+            hipError_t e = hipFreeAsync(p[i], st);
+            if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, "hipFreeAsync", __FILE__, __LINE__);
+        }
+        n = 0;
+        return rc;
+    }
+};
+
+int run_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B, int cy, int cx,
+             int H, int W, int h, int w, int re, const int *row_of_low, const int *col_of_low, const int *low_of_row,
+             const int *low_of_col, const float *eps, float scale, int subtract_is_y, hipStream_t st)
+{
+    const bool tiled = max_lds(re) <= kMaxLds && halo_stride(re) <= 64 * NCO;
+    const bool full = h == H && w == W;                 // strictly increasing maps onto the same size: the identity
+    const bool need_x = grad_x != nullptr, need_xe = need_x || grad_eps != nullptr, need_apply = need_x || grad_y != nullptr;
+    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, nimg = (int64_t)B * cy;
+    const dim3 tiles((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH));
+    const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
+    const size_t lds_stats = tiled ? tile_lds(re, 1, false) : stream_lds(false);
+    const size_t lds_coef = tiled ? tile_lds(re, 2, false) : stream_lds(false);
+    const size_t lds_apply = tiled ? tile_lds(re, 1, true) : stream_lds(true);
+    auto stats = tiled ? k_guide_stats<false> : k_guide_stats<true>;
+    auto coefk = tiled ? k_grad_coef<false> : k_grad_coef<true>;
+    auto apply = tiled ? k_grad_apply<false> : k_grad_apply<true>;
+    auto gxk = tiled ? k_grad_x<false> : k_grad_x<true>;
+    if (int rc = phl_allow_lds(stats, lds_stats)) return rc;
+    if (int rc = phl_allow_lds(coefk, lds_coef)) return rc;
+    if (int rc = phl_allow_lds(apply, lds_apply)) return rc;
+    if (int rc = phl_allow_lds(gxk, lds_apply)) return rc;
+
+    // labels per chunk: the per-label planes of a chunk stay within kChunkBytes (and gridDim.y / z)
+    const int64_t per = hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * NPART * cx : 0));
+    const int64_t chunk = max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per));
+    const size_t nstat = (size_t)B * cx * hw;
+    Temps tmp(st);
+    double *mx = tmp.get<double>(nstat);
+    float *inv = tmp.get<float>(nstat);
+    float *xsb = full ? nullptr : tmp.get<float>(nstat);
+    float *ysb = full ? nullptr : tmp.get<float>((size_t)chunk * hw);
+    float *P = tmp.get<float>((size_t)chunk * (cx + 1) * hw), *Q = tmp.get<float>((size_t)chunk * (cx + 1) * hw);
+    float *A = need_x ? tmp.get<float>((size_t)chunk * cx * hw) : nullptr, *mA = need_x ? tmp.get<float>((size_t)chunk * cx * hw) : nullptr;
+    double *part = need_xe ? tmp.get<double>((size_t)chunk * NPART * cx * hw) : nullptr;
+    double *acc = need_xe ? tmp.get<double>((size_t)NPART * nstat) : nullptr;
+    float *F = need_x ? tmp.get<float>(2 * nstat) : nullptr;
+    double *D = need_x ? tmp.get<double>((size_t)B * cx * HWf) : nullptr;
+    double *epart = grad_eps ? tmp.get<double>((size_t)cx * NEB) : nullptr;
+    int rc = tmp.rc;
+    auto launched = [&](const char *what) {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, what, __FILE__, __LINE__);
+    };
+    const float *xs = full ? x : xsb;
+    if (rc == PHL_OK) {
+        stats<<<dim3(tiles.x, tiles.y, (unsigned)B), dim3(NT), lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
+        if (!full)
+            k_grad_gather<<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
+        launched("k_guide_stats / k_grad_gather");
+    }
+    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
+        const unsigned nz = (unsigned)min(chunk, nimg - n0);
+        const unsigned nb = (unsigned)((n0 + nz - 1) / cy - n0 / cy + 1);          // images the chunk touches
+        const float *ys = full ? y + n0 * HWf : ysb;
+        if (!full) k_grad_gather<<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
+        k_grad_down<<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, P, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h, w, re, scale);
+        coefk<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_coef, st>>>(ys, xs, P, mx, inv, Q, A, part, (int)n0, cy, cx, h, w, re);
+        if (need_apply)
+            apply<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low,
+                                                                          col_of_low, (int)n0, cy, cx, H, W, h, w, re, subtract_is_y);
+        if (need_xe)
+            k_grad_reduce<<<dim3(nblo, (unsigned)cx, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, cx, B, need_x ? NPART : 2, hw);
+        if (need_x)
+            k_grad_direct<<<dim3(nbfull, (unsigned)cx, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy, cx,
+                                                                              H, W, h, w);
+        launched("the backward's chunk kernels");
+    }
+    if (need_x && rc == PHL_OK) {
+        k_grad_finish<<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(acc, mx, F, B, cx, hw);
+        gxk<<<dim3(tiles.x, tiles.y, (unsigned)B), dim3(NT), lds_apply, st>>>(F, acc + (size_t)PART_YU * nstat, xs, D, grad_x, row_of_low,
+                                                                             col_of_low, cx, H, W, h, w, re, scale);
+        launched("k_grad_finish / k_grad_x");
+    }
+    if (grad_eps && rc == PHL_OK) {
+        k_grad_eps1<<<dim3(NEB, (unsigned)cx), dim3(NE), 0, st>>>(acc, epart, B, cx, h, w, re);
+        k_grad_eps2<<<dim3(1), dim3(64), 0, st>>>(epart, grad_eps, cx);
+        launched("k_grad_eps");
+    }
+    tmp.rc = rc;
+    return tmp.release();
+}
+
 }  // namespace
 
 extern "C" {
@@ -493,6 +924,52 @@ int phl_guided_filter(const float *y, const float *x, const float *src, float *o
     const int re = min(r, max(h, w));            // a window beyond the image on both axes sums the same pixels
     return run(y, x, src, out, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps, scale,
                       (hipStream_t)stream);
+}
+
+
+int phl_guided_filter_grad_max_r(void) { return phl_guided_filter_max_r(); }      // the same two LDS layouts as the forward
+
+int phl_guided_filter_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B, int cy,
+                           int cx, int H, int W, int h, int w, int r, const int *row_of_low, const int *col_of_low,
+                           const int *low_of_row, const int *low_of_col, const float *eps, float scale, int subtract_is_y,
+                           phl_stream stream)
+{
+    if (B < 0 || cy < 0 || cx < 1 || H < 0 || W < 0 || h < 0 || w < 0 || r < 0 || h > H || w > W || !isfinite(scale)) {
+        phl_set_error("phl_guided_filter_grad: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", B, cy, cx, H, W,
+                      h, w, r, (double)scale);
+        return PHL_ERR_INVALID;
+    }
+    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
+    if (h == 0 || w == 0) {
+        phl_set_error("phl_guided_filter_grad: empty solving resolution %d x %d for a %d x %d image", h, w, H, W);
+        return PHL_ERR_INVALID;
+    }
+    if (!y || !x || !g || !eps || !row_of_low || !col_of_low || !low_of_row || !low_of_col) {
+        phl_set_error("phl_guided_filter_grad: null y / x / g / eps / index map");
+        return PHL_ERR_INVALID;
+    }
+    const void *ins[4] = {y, x, g, eps}, *outs[3] = {grad_y, grad_x, grad_eps};
+    for (int o = 0; o < 3; o++)
+        for (int i = 0; i < 4; i++)
+            if (outs[o] && (outs[o] == ins[i] || (i < o && outs[o] == outs[i]))) {
+                phl_set_error("phl_guided_filter_grad: a gradient aliases an input or another gradient");
+                return PHL_ERR_INVALID;
+            }
+    const int64_t HWf = (int64_t)H * W, lim = INT64_MAX / 64;
+    const int64_t nimg = (int64_t)B * cy;
+    if (HWf > INT32_MAX || nimg > INT32_MAX || HWf > lim / nimg || HWf > lim / ((int64_t)B * cx) || (h + TH - 1) / TH > 65535 ||
+        B > 65535 || max(H, W) > (1 << 30)) {
+        phl_set_error("phl_guided_filter_grad: %d x %d x (%d | %d) x %d x %d elements are too many", B, cy, cx, cy, H, W);
+        return PHL_ERR_TOO_LARGE;
+    }
+    if (cx > PHL_GUIDED_MAX_CX) {
+        phl_set_error("phl_guided_filter_grad: %d guide channels, at most %d", cx, PHL_GUIDED_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (!grad_y && !grad_x && !grad_eps) return PHL_OK;
+    const int re = min(r, max(h, w));
+    return run_grad(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps,
+                    scale, subtract_is_y, (hipStream_t)stream);
 }
 
 }  // extern "C"

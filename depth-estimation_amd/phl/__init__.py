@@ -114,6 +114,8 @@ def load_library():
             lib.phl_box_blur_fused_max_r.argtypes = [i32, i32, i32]
         if hasattr(lib, "phl_guided_filter"):          # (an older build loaded through PHL_LIB lacks the guided filter)
             lib.phl_guided_filter.argtypes = [vp, vp, vp, vp] + [i32] * 8 + [vp, vp, vp, vp, vp, C.c_float, vp]
+        if hasattr(lib, "phl_guided_filter_grad"):     # (an older build loaded through PHL_LIB lacks its backward)
+            lib.phl_guided_filter_grad.argtypes = [vp] * 6 + [i32] * 8 + [vp, vp, vp, vp, vp, C.c_float, i32, vp]
         lib.phl_stream_copy.argtypes = [vp, vp, i64, vp]
         lib.phl_copy2d.argtypes = [vp, i64, i64, vp, i64, i64, i64, i32, vp]
         lib.phl_cost_volume.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
@@ -996,7 +998,7 @@ def box_blur_grad(v, g, r, dim, sigma, need_x=True, need_sigma=True):
 
 
 # ---------------------------------------------------------------------------------------------
-# box-window guided filter (crf/guided.py; include/phl.h, phl_guided.hip)
+# box-window guided filter and its backward (crf/guided.py; include/phl.h, phl_guided.hip)
 _nearest_maps = OrderedDict()
 
 
@@ -1047,15 +1049,7 @@ def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=No
     elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == y.shape
               and out.device == y.device):
         raise TypeError("guided_filter: out must be a contiguous fp32 tensor of y's shape and device")
-    if torch.is_tensor(eps):
-        e = eps.detach().to(device=y.device, dtype=torch.float32).reshape(-1)
-        if e.numel() == 1 and cx != 1:
-            e = e.expand(cx)
-        if e.numel() != cx:
-            raise ValueError(f"guided_filter: eps has {e.numel()} values for {cx} guide channels")
-        e = e.contiguous()
-    else:
-        e = torch.full((cx,), float(eps), dtype=torch.float32, device=y.device)
+    e = _guided_eps(eps, cx, y.device, "guided_filter")
     if out.numel() == 0:
         return out
     if H // s == 0 or W // s == 0:
@@ -1064,6 +1058,77 @@ def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=No
     _launch(y.device, "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), B, cy, cx, H, W, H // s, W // s, r // s,
             *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)))
     return out
+
+
+def _guided_eps(eps, cx, device, name):
+    """eps of the guided filter as the kernels read it: [cx] fp32 on the device, detached."""
+    if not torch.is_tensor(eps):
+        return torch.full((cx,), float(eps), dtype=torch.float32, device=device)
+    e = eps.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    if e.numel() == 1 and cx != 1:
+        e = e.expand(cx)
+    if e.numel() != cx:
+        raise ValueError(f"{name}: eps has {e.numel()} values for {cx} guide channels")
+    return e.contiguous()
+
+
+def guided_filter_grad(y, x, g, r, eps, *, subsample=1, scale=1.0, subtract_is_y=False, need_y=True, need_x=False, need_eps=False):
+    """Backward of ``guided_filter(y, x, r, eps, subsample=, scale=, subtract=y if subtract_is_y else None)`` for the upstream
+    gradient ``g`` [B, cy, H, W] (phl_guided_filter_grad): ``(grad_y, grad_x, grad_eps)``, None for those not asked for;
+    grad_eps has cx values.  Nothing of the forward is needed: the kernels recompute it from y, x and eps.  The same tensor
+    rules as guided_filter (fp32 CUDA, any strides, any radius; PhlError status 7 for more than 16 guide channels); the
+    same bits on every run."""
+    for t in (y, x, g):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise TypeError(f"guided_filter_grad: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+    if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:] or x.device != y.device:
+        raise ValueError(f"guided_filter_grad: y [B, cy, H, W] and x [B, cx, H, W] on one device, got {tuple(y.shape)} and {tuple(x.shape)}")
+    if g.shape != y.shape or g.device != y.device:
+        raise ValueError("guided_filter_grad: g must have y's shape and device")
+    s, r = int(subsample), int(r)
+    if s < 1 or r < 0:
+        raise ValueError(f"guided_filter_grad: needs subsample >= 1 and r >= 0, got {subsample} and {r}")
+    B, cy, H, W = (int(v) for v in y.shape)
+    cx = int(x.shape[1])
+    e = _guided_eps(eps, cx, y.device, "guided_filter_grad")
+    new = torch.zeros if y.numel() == 0 else torch.empty
+    gy = new((B, cy, H, W), dtype=torch.float32, device=y.device) if need_y else None
+    gx = new((B, cx, H, W), dtype=torch.float32, device=y.device) if need_x else None
+    ge = new((cx,), dtype=torch.float32, device=y.device) if need_eps else None
+    if y.numel() == 0 or not (need_y or need_x or need_eps):
+        return gy, gx, ge
+    if H // s == 0 or W // s == 0:
+        raise ValueError(f"guided_filter_grad: a {H} x {W} image has no pixels at subsample {s}")
+    maps = _nearest_index_maps(H, W, s, y.device)
+    yc, xc, gc = y.contiguous(), x.contiguous(), g.contiguous()         # (named: a copy must outlive the launch)
+    _launch(y.device, "phl_guided_filter_grad", _ptr(yc), _ptr(xc), _ptr(gc), _ptr(gy), _ptr(gx),
+            _ptr(ge), B, cy, cx, H, W, H // s, W // s, r // s, *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)),
+            1 if subtract_is_y else 0)
+    return gy, gx, ge
+
+
+class GuidedFilterFn(torch.autograd.Function):
+    """``guided_filter(y, x, r, eps) * scale - (y if subtract_is_y else 0)`` with its backward on the library's kernels
+    (guided_filter_grad): only y, x and eps are saved, one backward call computes the gradients that are asked for.
+    ``eps`` is a tensor of cx values (or one); its gradient has its shape.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, y, x, eps, r, subsample, scale, subtract_is_y):
+        ctx.save_for_backward(y, x, eps)
+        ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
+        return guided_filter(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        y, x, eps = ctx.saved_tensors
+        r, s, scale, sub = ctx.args
+        need = ctx.needs_input_grad
+        gy, gx, ge = guided_filter_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0], need_x=need[1],
+                                        need_eps=need[2])
+        if ge is not None:
+            ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
+        return gy, gx, ge, None, None, None, None
 
 
 def stream_copy(dst, src):

@@ -387,6 +387,22 @@ int phl_guided_filter(const float *y_dev, const float *x_dev, const float *src_d
                       const int *low_of_col_dev, const float *eps_dev, float scale, phl_stream stream);
 int phl_guided_filter_max_r(void);   /* largest window radius (at the solving resolution) of the LDS-tiled form */
 
+/* Backward of phl_guided_filter with src = NULL (subtract_is_y = 0) or src = y (subtract_is_y != 0): g [B][cy][H][W] is the
+ * gradient of out; grad_y [B][cy][H][W], grad_x [B][cx][H][W] and grad_eps [cx] are written (never accumulated into), each
+ * may be NULL, all three NULL is PHL_OK with nothing launched.  Nothing of the forward is saved: the statistics and the
+ * coefficients are recomputed from y, x and eps.  row_of_low / col_of_low must be strictly increasing (torch's nearest
+ * maps are), so that the samples of two low-resolution pixels never coincide.  Window sums, label sums and every product
+ * that feeds them are fp64; labels are summed in index order and grad_eps by a fixed two-stage reduction, without
+ * atomics: the same bits on every run.  Every gradient is rounded to fp32 once.  Temporaries are stream-ordered
+ * allocations, among them one fp64 plane [B][cx][H][W] when grad_x is asked for.
+ * Status as phl_guided_filter (checked before any HIP call; g must not be NULL; a gradient must not alias an input or
+ * another gradient).  Any r: above phl_guided_filter_grad_max_r() the streamed form of the window sums runs. */
+int phl_guided_filter_grad(const float *y_dev, const float *x_dev, const float *g_dev, float *grad_y_dev, float *grad_x_dev,
+                           float *grad_eps_dev, int B, int cy, int cx, int H, int W, int h, int w, int r,
+                           const int *row_of_low_dev, const int *col_of_low_dev, const int *low_of_row_dev,
+                           const int *low_of_col_dev, const float *eps_dev, float scale, int subtract_is_y, phl_stream stream);
+int phl_guided_filter_grad_max_r(void);   /* largest radius of the backward's LDS-tiled form */
+
 /* Plain float4 streaming copy dst <- src (n_floats % 4 == 0, 16-byte aligned): measures the
  * HBM read+write ceiling of the box that the roofline fractions are compared with. */
 int phl_stream_copy(const float *src_dev, float *dst_dev, int64_t n_floats, phl_stream stream);
