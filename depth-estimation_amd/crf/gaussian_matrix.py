@@ -80,7 +80,7 @@ def _fused_grad(src, ref, g, need_src):
             gs, gr = phl.lattice_for(ref.detach()).filter_grad(src, g, ref, need_src=need_src)
             gs, gr = (gs.to(src.device) if gs is not None else None), gr.to(ref.device)
     except phl.PhlError as e:
-        if e.status != 7:          # PHL_ERR_UNSUPPORTED: shape outside the fused path
+        if e.status != phl.ERR_UNSUPPORTED:          # shape outside the fused path
             raise
         return None
     if pad and gs is not None:

@@ -201,7 +201,7 @@ class GuidedFilter(nn.Module):
                 return phl.GuidedFilterFn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract)
         except phl.PhlError as e:
-            if e.status != 7:
+            if e.status != phl.ERR_UNSUPPORTED:
                 raise
         return None
 

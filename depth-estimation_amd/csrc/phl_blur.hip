@@ -339,19 +339,17 @@ int phl_box_blur(const float *src, float *dst, int64_t outer, int64_t h, int64_t
     }
     // above the fused limit: one pass per launch through two temporaries (stream-ordered allocations)
     const Geom gm = geom(outer, h, inner, re, 1);
-    const size_t bytes = (size_t)outer * h * inner * sizeof(float);
-    float *tmp[2] = {nullptr, nullptr};
-    const int ntmp = passes >= 3 ? 2 : passes - 1;
-    for (int i = 0; i < ntmp; i++) PHL_HIP(hipMallocAsync((void **)&tmp[i], bytes, st));
+    const size_t count = (size_t)outer * h * inner;
+    phl_temps tmp(st);
+    float *t[2] = {passes >= 2 ? tmp.get<float>(count) : nullptr, passes >= 3 ? tmp.get<float>(count) : nullptr};
     const float *in = src;
-    int rc = PHL_OK;
+    int &rc = tmp.rc;
     for (int p = 0; p < passes && rc == PHL_OK; p++) {
-        float *o = p == passes - 1 ? dst : tmp[p % 2];
+        float *o = p == passes - 1 ? dst : t[p % 2];
         rc = rows ? launch_fwd<true>(1, in, o, outer, h, inner, re, gm, st) : launch_fwd<false>(1, in, o, outer, h, inner, re, gm, st);
         in = o;
     }
-    for (int i = 0; i < ntmp; i++) PHL_HIP(hipFreeAsync(tmp[i], st));
-    return rc;
+    return tmp.release();
 }
 
 int phl_box_blur_grad(const float *v, const float *g, int64_t outer, int64_t h, int64_t inner, int r, double sigma,
@@ -381,17 +379,17 @@ int phl_box_blur_grad(const float *v, const float *g, int64_t outer, int64_t h, 
     }
     const Geom gm = geom(outer, h, inner, re, 3);
     const int64_t nparts = gm.groups * gm.chunks;
-    double *partial = nullptr;
-    PHL_HIP(hipMallocAsync((void **)&partial, (size_t)nparts * sizeof(double), st));
-    int rc = rows ? launch_one<true, 3, true>(v, g, grad_x, partial, outer, h, inner, re, 1.0 / sigma, gm, st)
+    phl_temps tmp(st);
+    double *partial = tmp.get<double>((size_t)nparts);
+    int &rc = tmp.rc;
+    if (rc == PHL_OK)
+        rc = rows ? launch_one<true, 3, true>(v, g, grad_x, partial, outer, h, inner, re, 1.0 / sigma, gm, st)
                   : launch_one<false, 3, true>(v, g, grad_x, partial, outer, h, inner, re, 1.0 / sigma, gm, st);
     if (rc == PHL_OK) {
         k_box_grad_sum<<<dim3(1), dim3(256), 0, st>>>(partial, nparts, 1.0 / sigma, grad_sigma);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = phl_hip_fail(e, "k_box_grad_sum", __FILE__, __LINE__);
+        phl_launched(rc, "k_box_grad_sum");
     }
-    PHL_HIP(hipFreeAsync(partial, st));
-    return rc;
+    return tmp.release();
 }
 
 }  // extern "C"

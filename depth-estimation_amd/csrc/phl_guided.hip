@@ -21,7 +21,8 @@
 //                   the full-resolution pixels that map into the tile: fp64 sum over the channels, * scale - src, one
 //                   rounding into out (with more than four planes the partial sum passes through out between groups)
 // Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
-// routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.
+// routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.  The
+// kernels of both directions reach the two forms through one front end (plane_sums, square_sums, product_sums).
 // The coefficient planes are a stream-ordered temporary; labels are processed in chunks whose planes stay within
 // kChunkBytes, so that k_guide_apply finds them in the Infinity Cache.
 #include <math.h>
@@ -54,6 +55,11 @@ inline size_t max_lds(int r) { return max(tile_lds(r, 2, false), tile_lds(r, 1, 
 inline size_t stream_lds(bool apply) { return (size_t)SR * HSP * sizeof(double) + (apply ? (size_t)GRP * TH * TW * sizeof(float) : 0); }
 enum { KIND_STATS = 0, KIND_COEF = 1, KIND_APPLY = 2 };
 
+// samples in the window of pixel i along an axis of length n
+__device__ __forceinline__ int win_count(int i, int r, int n) { return min(i + r, n - 1) - max(i - r, 0) + 1; }
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
 struct Tile {
     double *hs;     // [TH + 2r][HSP] horizontal window sums
     float *in;      // [TH + 2r][halo_stride] the tile and its halo
@@ -68,6 +74,13 @@ struct Tile {
     {
         const int I = rmap ? min(max(rmap[i], 0), ph - 1) : i, J = cmap ? min(max(cmap[j], 0), pw - 1) : j;
         return plane[(int64_t)I * pw + J];
+    }
+    // this thread's pixels are (i0() + k, j()), k < RPT; count(k) is N of pixel k (an axis outside the image counts 1)
+    __device__ __forceinline__ int i0() const { return ti + (threadIdx.x >> 6) * RPT; }
+    __device__ __forceinline__ int j() const { return tj + (threadIdx.x & 63); }
+    __device__ __forceinline__ double count(int k) const
+    {
+        return (double)(i0() + k < h ? win_count(i0() + k, r, h) : 1) * (double)(j() < w ? win_count(j(), r, w) : 1);
     }
 };
 
@@ -189,11 +202,6 @@ __device__ __forceinline__ void tile_sums_stream(const Tile &t, double (&res)[RP
     }
 }
 
-// samples in the window of pixel i along an axis of length n
-__device__ __forceinline__ int win_count(int i, int r, int n) { return min(i + r, n - 1) - max(i - r, 0) + 1; }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // The workgroup's tile over dynamic LDS (ST: the streamed form, which keeps no halo tile).  Source planes are ph x pw;
 // low-resolution row i / column j is their row rmap[i] / column cmap[j] (null maps: the identity).  Ends with a barrier
 // (rowoff is read by every wave).
@@ -230,6 +238,60 @@ __device__ __forceinline__ Tile make_tile(int r, int h, int w, const int *__rest
     return t;
 }
 
+// ---- the window-sum front end --------------------------------------------------------------------------------------
+// What the kernels below call, in the form they are built for (ST: streamed, through the tile's maps; else tiled, staged
+// through LDS).  Window sums of a plane, which the tiled form leaves in the halo tile `in` ...
+template <bool ST>
+__device__ __forceinline__ void plane_sums(const Tile &t, float *__restrict__ in, const float *__restrict__ pl, double (&s)[RPT])
+{
+    if constexpr (ST) {
+        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(pl, i, jj); });
+    } else {
+        tile_fill(t, in, pl);
+        tile_sums(t, s, [&](int e) { return (double)in[e]; });
+    }
+}
+// ... of the square of the plane pl that a plane_sums call has left in t.in ...
+template <bool ST>
+__device__ __forceinline__ void square_sums(const Tile &t, const float *__restrict__ pl, double (&s)[RPT])
+{
+    if constexpr (ST) {
+        tile_sums_stream(t, s, [&](int i, int jj) { const double v = t.ld(pl, i, jj); return v * v; });
+    } else {
+        tile_sums(t, s, [&](int e) { const double v = t.in[e]; return v * v; });
+    }
+}
+// ... and of its product with a second plane, which goes into t.in2 (exact in fp64: 24 + 24 bits)
+template <bool ST>
+__device__ __forceinline__ void product_sums(const Tile &t, const float *__restrict__ pl, const float *__restrict__ pl2,
+                                             double (&s)[RPT])
+{
+    if constexpr (ST) {
+        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(pl, i, jj) * (double)t.ld(pl2, i, jj); });
+    } else {
+        tile_fill(t, t.in2, pl2);
+        tile_sums(t, s, [&](int e) { return (double)t.in[e] * (double)t.in2[e]; });
+    }
+}
+// rn[k] = 1 / N of the thread's pixels
+__device__ __forceinline__ void recip_counts(const Tile &t, double (&rn)[RPT])
+{
+#pragma unroll
+    for (int k = 0; k < RPT; k++) rn[k] = 1.0 / t.count(k);
+}
+// f(k, offset in an h x w plane) for those of the thread's pixels that lie in the image.  (No unroll pragma: it would
+// unroll the loop here, before the kernel's loop over channels sees it, and the eight offsets then stay live across the
+// window sums -- up to 46 more VGPRs.  The constant trip count is unrolled in the kernel all the same.)
+template <typename F>
+__device__ __forceinline__ void for_pixels(const Tile &t, F f)
+{
+    const int i0 = t.i0(), j = t.j();
+    for (int k = 0; k < RPT; k++) {
+        const int i = i0 + k;
+        if (i < t.h && j < t.w) f(k, (int64_t)i * t.w + j);
+    }
+}
+
 // ---- guide statistics ----------------------------------------------------------------------------------------------
 template <bool ST>
 __global__ __launch_bounds__(NT) void k_guide_stats(const float *__restrict__ x, const int *__restrict__ rmap,
@@ -238,32 +300,21 @@ __global__ __launch_bounds__(NT) void k_guide_stats(const float *__restrict__ x,
                                                    int w, int r)
 {
     Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_STATS);
-    const int b = blockIdx.z, lane = threadIdx.x & 63, i0 = t.ti + (threadIdx.x >> 6) * RPT, j = t.tj + lane;
+    const int b = blockIdx.z;
     const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
-    const int cj = j < w ? win_count(j, r, w) : 1;
     for (int c = 0; c < cx; c++) {
         const float *xp = x + ((int64_t)b * cx + c) * HWf;
         double s1[RPT], s2[RPT];
-        if constexpr (ST) {
-            tile_sums_stream(t, s1, [&](int i, int jj) { return (double)t.ld(xp, i, jj); });
-            tile_sums_stream(t, s2, [&](int i, int jj) { const double v = t.ld(xp, i, jj); return v * v; });
-        } else {
-            tile_fill(t, t.in, xp);
-            tile_sums(t, s1, [&](int e) { return (double)t.in[e]; });
-            tile_sums(t, s2, [&](int e) { const double v = t.in[e]; return v * v; });
-        }
+        plane_sums<ST>(t, t.in, xp, s1);
+        square_sums<ST>(t, xp, s2);
         const double e = (double)eps[c];
-#pragma unroll
-        for (int k = 0; k < RPT; k++) {
-            const int i = i0 + k;
-            if (i < h && j < w) {
-                const double n = (double)win_count(i, r, h) * (double)cj;
-                const double m = s1[k] / n, var = s2[k] / n - m * m;
-                const int64_t o = ((int64_t)b * cx + c) * hw + (int64_t)i * w + j;
-                mx[o] = m;
-                inv[o] = (float)(1.0 / (var + e));
-            }
-        }
+        for_pixels(t, [&](int k, int64_t q) {
+            const double n = t.count(k);
+            const double m = s1[k] / n, var = s2[k] / n - m * m;
+            const int64_t o = ((int64_t)b * cx + c) * hw + q;
+            mx[o] = m;
+            inv[o] = (float)(1.0 / (var + e));
+        });
     }
 }
 
@@ -276,48 +327,26 @@ __global__ __launch_bounds__(NT) void k_guide_coef(const float *__restrict__ y, 
 {
     Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_COEF);
     const int n = n0 + blockIdx.z, b = n / cy;                     // n = image * cy + label
-    const int lane = threadIdx.x & 63, i0 = t.ti + (threadIdx.x >> 6) * RPT, j = t.tj + lane;
     const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
     const float *yp = y + (int64_t)n * HWf;
     float *cp = coef + (int64_t)blockIdx.z * (cx + 1) * hw;
-    const int cj = j < w ? win_count(j, r, w) : 1;
 
     double my[RPT], bacc[RPT], rn[RPT], s[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; k++) rn[k] = 1.0 / ((double)(i0 + k < h ? win_count(i0 + k, r, h) : 1) * (double)cj);
-    if constexpr (ST) {
-        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(yp, i, jj); });
-    } else {
-        tile_fill(t, t.in, yp);
-        tile_sums(t, s, [&](int e) { return (double)t.in[e]; });
-    }
+    recip_counts(t, rn);
+    plane_sums<ST>(t, t.in, yp, s);                                 // (tiled form: y stays in LDS for the products below)
 #pragma unroll
     for (int k = 0; k < RPT; k++) bacc[k] = my[k] = s[k] * rn[k];
     for (int c = 0; c < cx; c++) {
-        const float *xp = x + ((int64_t)b * cx + c) * HWf;
-        if constexpr (ST) {
-            tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(yp, i, jj) * (double)t.ld(xp, i, jj); });
-        } else {
-            tile_fill(t, t.in2, xp);
-            tile_sums(t, s, [&](int e) { return (double)t.in[e] * (double)t.in2[e]; });      // exact: 24 + 24 bits
-        }
-#pragma unroll
-        for (int k = 0; k < RPT; k++) {
-            const int i = i0 + k;
-            if (i < h && j < w) {
-                const int64_t o = (int64_t)i * w + j, g = ((int64_t)b * cx + c) * hw + o;
-                const double m = mx[g];
-                const float a = (float)((s[k] * rn[k] - my[k] * m) * (double)inv[g]);
-                cp[(int64_t)c * hw + o] = a;
-                bacc[k] -= (double)a * m;
-            }
-        }
+        product_sums<ST>(t, yp, x + ((int64_t)b * cx + c) * HWf, s);
+        for_pixels(t, [&](int k, int64_t o) {
+            const int64_t g = ((int64_t)b * cx + c) * hw + o;
+            const double m = mx[g];
+            const float a = (float)((s[k] * rn[k] - my[k] * m) * (double)inv[g]);
+            cp[(int64_t)c * hw + o] = a;
+            bacc[k] -= (double)a * m;
+        });
     }
-#pragma unroll
-    for (int k = 0; k < RPT; k++) {
-        const int i = i0 + k;
-        if (i < h && j < w) cp[(int64_t)cx * hw + (int64_t)i * w + j] = (float)bacc[k];
-    }
+    for_pixels(t, [&](int k, int64_t o) { cp[(int64_t)cx * hw + o] = (float)bacc[k]; });
 }
 
 // ---- apply ---------------------------------------------------------------------------------------------------------
@@ -341,13 +370,11 @@ __global__ __launch_bounds__(NT) void k_guide_apply(const float *__restrict__ co
     Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_APPLY);
     float *M = t.in2;                                               // [GRP][TH][TW] window means (both forms)
     const int n = n0 + blockIdx.z, b = n / cy;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i0 = t.ti + wave * RPT, j = t.tj + lane;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
     const float *cp = coef + (int64_t)blockIdx.z * (cx + 1) * hw;
-    const int cj = j < w ? win_count(j, r, w) : 1;
     double rn[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; k++) rn[k] = 1.0 / ((double)(i0 + k < h ? win_count(i0 + k, r, h) : 1) * (double)cj);
+    recip_counts(t, rn);
     // the full-resolution rows and columns whose low-resolution pixel lies in this tile
     const int I0 = lower_bound(rlow, H, t.ti), I1 = lower_bound(rlow, H, t.ti + TH);
     const int J0 = lower_bound(clow, W, t.tj), J1 = lower_bound(clow, W, t.tj + TW);
@@ -359,14 +386,8 @@ __global__ __launch_bounds__(NT) void k_guide_apply(const float *__restrict__ co
     for (int q0 = 0; q0 < np; q0 += GRP) {
         const int nq = min(GRP, np - q0);
         for (int q = 0; q < nq; q++) {
-            const float *pl = cp + (int64_t)(q0 + q) * hw;
             double s[RPT];
-            if constexpr (ST) {
-                tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(pl, i, jj); });
-            } else {
-                tile_fill(t, t.in, pl);
-                tile_sums(t, s, [&](int e) { return (double)t.in[e]; });
-            }
+            plane_sums<ST>(t, t.in, cp + (int64_t)(q0 + q) * hw, s);
 #pragma unroll
             for (int k = 0; k < RPT; k++) M[(q * TH + wave * RPT + k) * TW + lane] = (float)(s[k] * rn[k]);
         }
@@ -393,57 +414,56 @@ __global__ __launch_bounds__(NT) void k_guide_apply(const float *__restrict__ co
     }
 }
 
-// the three kernels in the tiled form while its LDS fits the radius, else in the streamed form
+// ---- host: what the forward and the backward derive from (re, h, w) -------------------------------------------------
+inline bool fits_tiled(int r) { return max_lds(r) <= kMaxLds && halo_stride(r) <= 64 * NCO; }
+
+// The tiled form while its LDS fits the radius, else the streamed form; the tile grid; the dynamic LDS of the three
+// layouts (one halo tile, two, one + the window means); the labels of a chunk.
+struct Plan {
+    bool tiled;
+    dim3 tiles;
+    size_t lds_stats, lds_coef, lds_apply;
+    Plan(int re, int h, int w)
+        : tiled(fits_tiled(re)), tiles((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH)),
+          lds_stats(tiled ? tile_lds(re, 1, false) : stream_lds(false)), lds_coef(tiled ? tile_lds(re, 2, false) : stream_lds(false)),
+          lds_apply(tiled ? tile_lds(re, 1, true) : stream_lds(true))
+    {
+    }
+    dim3 grid(unsigned nz) const { return dim3(tiles.x, tiles.y, nz); }
+    // labels per chunk: the per-label planes of a chunk (`per` bytes a label) stay within kChunkBytes (and gridDim.y / z)
+    static int64_t chunk(int64_t nimg, int64_t per) { return max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per)); }
+};
+
 int run(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h, int w, int re,
         const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col, const float *eps, float scale,
         hipStream_t st)
 {
-    const bool tiled = max_lds(re) <= kMaxLds && halo_stride(re) <= 64 * NCO;
+    const Plan p(re, h, w);
     const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
-    const dim3 tiles((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH));
-    const size_t lds_stats = tiled ? tile_lds(re, 1, false) : stream_lds(false);
-    const size_t lds_coef = tiled ? tile_lds(re, 2, false) : stream_lds(false);
-    const size_t lds_apply = tiled ? tile_lds(re, 1, true) : stream_lds(true);
-    auto stats = tiled ? k_guide_stats<false> : k_guide_stats<true>;
-    auto coefk = tiled ? k_guide_coef<false> : k_guide_coef<true>;
-    auto apply = tiled ? k_guide_apply<false> : k_guide_apply<true>;
-    if (int rc = phl_allow_lds(stats, lds_stats)) return rc;
-    if (int rc = phl_allow_lds(coefk, lds_coef)) return rc;
-    if (int rc = phl_allow_lds(apply, lds_apply)) return rc;
+    auto stats = p.tiled ? k_guide_stats<false> : k_guide_stats<true>;
+    auto coefk = p.tiled ? k_guide_coef<false> : k_guide_coef<true>;
+    auto apply = p.tiled ? k_guide_apply<false> : k_guide_apply<true>;
+    if (int rc = phl_allow_lds(stats, p.lds_stats)) return rc;
+    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
+    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
 
-    // labels per chunk: the coefficient planes of a chunk stay within kChunkBytes (and gridDim.z)
-    const int64_t per = (int64_t)(cx + 1) * hw * (int64_t)sizeof(float);
-    const int64_t chunk = max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per));
+    const int64_t chunk = Plan::chunk(nimg, (int64_t)(cx + 1) * hw * (int64_t)sizeof(float));
     const size_t nstat = (size_t)B * cx * hw;
-    void *tmp[3] = {nullptr, nullptr, nullptr};          // mx, inv, coef: every one that was allocated is freed below
-    const size_t bytes[3] = {nstat * sizeof(double), nstat * sizeof(float), (size_t)chunk * per};
-    int rc = PHL_OK;
-    for (int i = 0; i < 3 && rc == PHL_OK; i++) {
-        hipError_t e = hipMallocAsync(&tmp[i], bytes[i], st);
-        if (e != hipSuccess) tmp[i] = nullptr, rc = phl_hip_fail(e, "hipMallocAsync", __FILE__, __LINE__);
-    }
-    double *mx = (double *)tmp[0];
-    float *inv = (float *)tmp[1], *coef = (float *)tmp[2];
+    phl_temps tmp(st);
+    double *mx = tmp.get<double>(nstat);
+    float *inv = tmp.get<float>(nstat), *coef = tmp.get<float>((size_t)chunk * (cx + 1) * hw);
+    int &rc = tmp.rc;
     if (rc == PHL_OK) {
-        stats<<<dim3(tiles.x, tiles.y, (unsigned)B), dim3(NT), lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = phl_hip_fail(e, "k_guide_stats", __FILE__, __LINE__);
+        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
+        phl_launched(rc, "k_guide_stats");
     }
     for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
         const unsigned nz = (unsigned)min(chunk, nimg - n0);
-        coefk<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_coef, st>>>(y, x, row_of_low, col_of_low, mx, inv, coef, (int)n0, cy, cx, H, W, h,
-                                                                     w, re);
-        apply<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_apply, st>>>(coef, x, src, out, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h,
-                                                                      w, re, scale);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = phl_hip_fail(e, "k_guide_coef / k_guide_apply", __FILE__, __LINE__);
+        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, row_of_low, col_of_low, mx, inv, coef, (int)n0, cy, cx, H, W, h, w, re);
+        apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(coef, x, src, out, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h, w, re, scale);
+        phl_launched(rc, "k_guide_coef / k_guide_apply");
     }
-    for (int i = 2; i >= 0; i--) {
-        if (!tmp[i]) continue;
-        hipError_t e = hipFreeAsync(tmp[i], st);
-        if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, "hipFreeAsync", __FILE__, __LINE__);
-    }
-    return rc;
+    return tmp.release();
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
@@ -512,18 +532,6 @@ __global__ __launch_bounds__(NE) void k_grad_down(const float *__restrict__ g, c
     }
 }
 
-// window sums of a low-resolution plane (identity maps) in either form
-template <bool ST>
-__device__ __forceinline__ void plane_sums(const Tile &t, float *__restrict__ in, const float *__restrict__ pl, double (&s)[RPT])
-{
-    if constexpr (ST) {
-        tile_sums_stream(t, s, [&](int i, int jj) { return (double)pl[(int64_t)i * t.w + jj]; });
-    } else {
-        tile_fill(t, in, pl);
-        tile_sums(t, s, [&](int e) { return (double)in[e]; });
-    }
-}
-
 template <bool ST>
 __global__ __launch_bounds__(NT) void k_grad_coef(const float *__restrict__ ys, const float *__restrict__ xs,
                                                  const float *__restrict__ P, const double *__restrict__ mx,
@@ -532,16 +540,13 @@ __global__ __launch_bounds__(NT) void k_grad_coef(const float *__restrict__ ys, 
 {
     Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_COEF);
     const int z = blockIdx.z, b = (n0 + z) / cy;
-    const int lane = threadIdx.x & 63, i0 = t.ti + (threadIdx.x >> 6) * RPT, j = t.tj + lane;
     const int64_t hw = (int64_t)h * w;
     const float *yp = ys + (int64_t)z * hw, *pp = P + (int64_t)z * (cx + 1) * hw;
     float *qp = Q + (int64_t)z * (cx + 1) * hw, *ap = A ? A + (int64_t)z * cx * hw : nullptr;
     double *tp = part ? part + (int64_t)z * NPART * cx * hw : nullptr;
-    const int cj = j < w ? win_count(j, r, w) : 1;
 
     double my[RPT], gb[RPT], gmy[RPT], rn[RPT], a[RPT], s[RPT];
-#pragma unroll
-    for (int k = 0; k < RPT; k++) rn[k] = 1.0 / ((double)(i0 + k < h ? win_count(i0 + k, r, h) : 1) * (double)cj);
+    recip_counts(t, rn);
     plane_sums<ST>(t, t.in, yp, s);                                 // (tiled form: ys stays in LDS for the products below)
 #pragma unroll
     for (int k = 0; k < RPT; k++) my[k] = s[k] * rn[k];
@@ -549,39 +554,25 @@ __global__ __launch_bounds__(NT) void k_grad_coef(const float *__restrict__ ys, 
 #pragma unroll
     for (int k = 0; k < RPT; k++) gmy[k] = gb[k];
     for (int c = 0; c < cx; c++) {
-        const float *xp = xs + ((int64_t)b * cx + c) * hw;
-        if constexpr (ST) {
-            tile_sums_stream(t, s, [&](int i, int jj) { const int64_t o = (int64_t)i * w + jj; return (double)yp[o] * (double)xp[o]; });
-        } else {
-            tile_fill(t, t.in2, xp);
-            tile_sums(t, s, [&](int e) { return (double)t.in[e] * (double)t.in2[e]; });
-        }
+        product_sums<ST>(t, yp, xs + ((int64_t)b * cx + c) * hw, s);
 #pragma unroll
         for (int k = 0; k < RPT; k++) a[k] = s[k] * rn[k];            // mean(y x_c) for now
         plane_sums<ST>(t, t.in2, pp + (int64_t)c * hw, s);
-#pragma unroll
-        for (int k = 0; k < RPT; k++) {
-            const int i = i0 + k;
-            if (i < h && j < w) {
-                const int64_t o = (int64_t)i * w + j, gi = ((int64_t)b * cx + c) * hw + o;
-                const double m = mx[gi], iv = (double)inv[gi];
-                const double alc = (a[k] - my[k] * m) * iv;
-                const double gap = s[k] - gb[k] * m, gcov = gap * iv;
-                gmy[k] -= gcov * m;
-                qp[(int64_t)c * hw + o] = (float)(gcov * rn[k]);
-                if (ap) ap[(int64_t)c * hw + o] = (float)alc;
-                if (tp) {
-                    tp[((int64_t)PART_VAR * cx + c) * hw + o] = -(iv * (gap * alc)) * rn[k];
-                    tp[((int64_t)PART_MX * cx + c) * hw + o] = -(gb[k] * alc + gcov * my[k]) * rn[k];
-                }
+        for_pixels(t, [&](int k, int64_t o) {
+            const int64_t gi = ((int64_t)b * cx + c) * hw + o;
+            const double m = mx[gi], iv = (double)inv[gi];
+            const double alc = (a[k] - my[k] * m) * iv;
+            const double gap = s[k] - gb[k] * m, gcov = gap * iv;
+            gmy[k] -= gcov * m;
+            qp[(int64_t)c * hw + o] = (float)(gcov * rn[k]);
+            if (ap) ap[(int64_t)c * hw + o] = (float)alc;
+            if (tp) {
+                tp[((int64_t)PART_VAR * cx + c) * hw + o] = -(iv * (gap * alc)) * rn[k];
+                tp[((int64_t)PART_MX * cx + c) * hw + o] = -(gb[k] * alc + gcov * my[k]) * rn[k];
             }
-        }
+        });
     }
-#pragma unroll
-    for (int k = 0; k < RPT; k++) {
-        const int i = i0 + k;
-        if (i < h && j < w) qp[(int64_t)cx * hw + (int64_t)i * w + j] = (float)(gmy[k] * rn[k]);
-    }
+    for_pixels(t, [&](int k, int64_t o) { qp[(int64_t)cx * hw + o] = (float)(gmy[k] * rn[k]); });
 }
 
 // f(o, value) for every full-resolution pixel of the tile's share: G[li][lj] of the tile's LDS plane at the pixel that is
@@ -617,33 +608,21 @@ __global__ __launch_bounds__(NT) void k_grad_apply(const float *__restrict__ Q, 
     Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_APPLY);
     double *G = reinterpret_cast<double *>(t.in2);                  // [TH][TW] gys (both forms; 8-byte aligned)
     const int z = blockIdx.z, n = n0 + z, b = n / cy;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i0 = t.ti + wave * RPT, j = t.tj + lane;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W;
     const float *qp = Q + (int64_t)z * (cx + 1) * hw, *yp = ys + (int64_t)z * hw;
-    const int cj = j < w ? win_count(j, r, w) : 1;
     double gys[RPT], s[RPT];
     plane_sums<ST>(t, t.in, qp + (int64_t)cx * hw, gys);
     for (int c = 0; c < cx; c++) {
         const float *xp = xs + ((int64_t)b * cx + c) * hw;
         plane_sums<ST>(t, t.in, qp + (int64_t)c * hw, s);
-#pragma unroll
-        for (int k = 0; k < RPT; k++) {
-            const int i = i0 + k;
-            if (i < h && j < w) {
-                const int64_t o = (int64_t)i * w + j;
-                gys[k] += (double)xp[o] * s[k];
-                if (part) part[((int64_t)z * NPART * cx + (int64_t)PART_YU * cx + c) * hw + o] = (double)yp[o] * s[k];
-            }
-        }
+        for_pixels(t, [&](int k, int64_t o) {
+            gys[k] += (double)xp[o] * s[k];
+            if (part) part[((int64_t)z * NPART * cx + (int64_t)PART_YU * cx + c) * hw + o] = (double)yp[o] * s[k];
+        });
         if (mA) {
             plane_sums<ST>(t, t.in, A + ((int64_t)z * cx + c) * hw, s);
-#pragma unroll
-            for (int k = 0; k < RPT; k++) {
-                const int i = i0 + k;
-                if (i < h && j < w)
-                    mA[((int64_t)z * cx + c) * hw + (int64_t)i * w + j] =
-                        (float)(s[k] / ((double)win_count(i, r, h) * (double)cj));
-            }
+            for_pixels(t, [&](int k, int64_t o) { mA[((int64_t)z * cx + c) * hw + o] = (float)(s[k] / t.count(k)); });
         }
     }
     if (!grad_y) return;
@@ -764,64 +743,28 @@ __global__ void k_grad_eps2(const double *__restrict__ partial, float *__restric
     grad_eps[c] = (float)s;
 }
 
-struct Temps {                       // stream-ordered temporaries, freed on every exit path by release()
-    static constexpr int MAXN = 16;
-    void *p[MAXN];
-    int n = 0;
-    hipStream_t st;
-    int rc = PHL_OK;
-    explicit Temps(hipStream_t s) : st(s) {}
-    template <typename T>
-    T *get(size_t count)
-    {
-        if (rc != PHL_OK || n >= MAXN) return nullptr;
-        void *q = nullptr;
-        hipError_t e = hipMallocAsync(&q, max(count, (size_t)1) * sizeof(T), st);
-        if (e != hipSuccess) {
-            rc = phl_hip_fail(e, "hipMallocAsync", __FILE__, __LINE__);
-            return nullptr;
-        }
-        p[n++] = q;
-        return (T *)q;
-    }
-    int release()
-    {
-        for (int i = n - 1; i >= 0; i--) {
-            hipError_t e = hipFreeAsync(p[i], st);
-            if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, "hipFreeAsync", __FILE__, __LINE__);
-        }
-        n = 0;
-        return rc;
-    }
-};
-
 int run_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B, int cy, int cx,
              int H, int W, int h, int w, int re, const int *row_of_low, const int *col_of_low, const int *low_of_row,
              const int *low_of_col, const float *eps, float scale, int subtract_is_y, hipStream_t st)
 {
-    const bool tiled = max_lds(re) <= kMaxLds && halo_stride(re) <= 64 * NCO;
+    const Plan p(re, h, w);
     const bool full = h == H && w == W;                 // strictly increasing maps onto the same size: the identity
     const bool need_x = grad_x != nullptr, need_xe = need_x || grad_eps != nullptr, need_apply = need_x || grad_y != nullptr;
     const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, nimg = (int64_t)B * cy;
-    const dim3 tiles((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH));
     const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
-    const size_t lds_stats = tiled ? tile_lds(re, 1, false) : stream_lds(false);
-    const size_t lds_coef = tiled ? tile_lds(re, 2, false) : stream_lds(false);
-    const size_t lds_apply = tiled ? tile_lds(re, 1, true) : stream_lds(true);
-    auto stats = tiled ? k_guide_stats<false> : k_guide_stats<true>;
-    auto coefk = tiled ? k_grad_coef<false> : k_grad_coef<true>;
-    auto apply = tiled ? k_grad_apply<false> : k_grad_apply<true>;
-    auto gxk = tiled ? k_grad_x<false> : k_grad_x<true>;
-    if (int rc = phl_allow_lds(stats, lds_stats)) return rc;
-    if (int rc = phl_allow_lds(coefk, lds_coef)) return rc;
-    if (int rc = phl_allow_lds(apply, lds_apply)) return rc;
-    if (int rc = phl_allow_lds(gxk, lds_apply)) return rc;
+    auto stats = p.tiled ? k_guide_stats<false> : k_guide_stats<true>;
+    auto coefk = p.tiled ? k_grad_coef<false> : k_grad_coef<true>;
+    auto apply = p.tiled ? k_grad_apply<false> : k_grad_apply<true>;
+    auto gxk = p.tiled ? k_grad_x<false> : k_grad_x<true>;
+    if (int rc = phl_allow_lds(stats, p.lds_stats)) return rc;
+    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
+    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
+    if (int rc = phl_allow_lds(gxk, p.lds_apply)) return rc;
 
-    // labels per chunk: the per-label planes of a chunk stay within kChunkBytes (and gridDim.y / z)
     const int64_t per = hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * NPART * cx : 0));
-    const int64_t chunk = max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per));
+    const int64_t chunk = Plan::chunk(nimg, per);
     const size_t nstat = (size_t)B * cx * hw;
-    Temps tmp(st);
+    phl_temps tmp(st);
     double *mx = tmp.get<double>(nstat);
     float *inv = tmp.get<float>(nstat);
     float *xsb = full ? nullptr : tmp.get<float>(nstat);
@@ -833,17 +776,13 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
     float *F = need_x ? tmp.get<float>(2 * nstat) : nullptr;
     double *D = need_x ? tmp.get<double>((size_t)B * cx * HWf) : nullptr;
     double *epart = grad_eps ? tmp.get<double>((size_t)cx * NEB) : nullptr;
-    int rc = tmp.rc;
-    auto launched = [&](const char *what) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, what, __FILE__, __LINE__);
-    };
+    int &rc = tmp.rc;
     const float *xs = full ? x : xsb;
     if (rc == PHL_OK) {
-        stats<<<dim3(tiles.x, tiles.y, (unsigned)B), dim3(NT), lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
+        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
         if (!full)
             k_grad_gather<<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
-        launched("k_guide_stats / k_grad_gather");
+        phl_launched(rc, "k_guide_stats / k_grad_gather");
     }
     for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
         const unsigned nz = (unsigned)min(chunk, nimg - n0);
@@ -851,30 +790,63 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
         const float *ys = full ? y + n0 * HWf : ysb;
         if (!full) k_grad_gather<<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
         k_grad_down<<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, P, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h, w, re, scale);
-        coefk<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_coef, st>>>(ys, xs, P, mx, inv, Q, A, part, (int)n0, cy, cx, h, w, re);
+        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(ys, xs, P, mx, inv, Q, A, part, (int)n0, cy, cx, h, w, re);
         if (need_apply)
-            apply<<<dim3(tiles.x, tiles.y, nz), dim3(NT), lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low,
-                                                                          col_of_low, (int)n0, cy, cx, H, W, h, w, re, subtract_is_y);
+            apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low, col_of_low,
+                                                            (int)n0, cy, cx, H, W, h, w, re, subtract_is_y);
         if (need_xe)
             k_grad_reduce<<<dim3(nblo, (unsigned)cx, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, cx, B, need_x ? NPART : 2, hw);
         if (need_x)
             k_grad_direct<<<dim3(nbfull, (unsigned)cx, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy, cx,
                                                                               H, W, h, w);
-        launched("the backward's chunk kernels");
+        phl_launched(rc, "the backward's chunk kernels");
     }
     if (need_x && rc == PHL_OK) {
         k_grad_finish<<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(acc, mx, F, B, cx, hw);
-        gxk<<<dim3(tiles.x, tiles.y, (unsigned)B), dim3(NT), lds_apply, st>>>(F, acc + (size_t)PART_YU * nstat, xs, D, grad_x, row_of_low,
-                                                                             col_of_low, cx, H, W, h, w, re, scale);
-        launched("k_grad_finish / k_grad_x");
+        gxk<<<p.grid((unsigned)B), dim3(NT), p.lds_apply, st>>>(F, acc + (size_t)PART_YU * nstat, xs, D, grad_x, row_of_low, col_of_low, cx,
+                                                               H, W, h, w, re, scale);
+        phl_launched(rc, "k_grad_finish / k_grad_x");
     }
     if (grad_eps && rc == PHL_OK) {
         k_grad_eps1<<<dim3(NEB, (unsigned)cx), dim3(NE), 0, st>>>(acc, epart, B, cx, h, w, re);
         k_grad_eps2<<<dim3(1), dim3(64), 0, st>>>(epart, grad_eps, cx);
-        launched("k_grad_eps");
+        phl_launched(rc, "k_grad_eps");
     }
-    tmp.rc = rc;
     return tmp.release();
+}
+
+// The arguments the forward and the backward share (`third`: out or g); `who` names the entry point in the message.
+// PHL_OK also for zero elements, which the caller then tests for.
+int check_guided_args(const char *who, const void *y, const void *x, const void *third, const char *third_name, int B, int cy, int cx,
+                      int H, int W, int h, int w, int r, const int *row_of_low, const int *col_of_low, const int *low_of_row,
+                      const int *low_of_col, const float *eps, float scale)
+{
+    if (B < 0 || cy < 0 || cx < 1 || H < 0 || W < 0 || h < 0 || w < 0 || r < 0 || h > H || w > W || !isfinite(scale)) {
+        phl_set_error("%s: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", who, B, cy, cx, H, W, h, w, r,
+                      (double)scale);
+        return PHL_ERR_INVALID;
+    }
+    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
+    if (h == 0 || w == 0) {
+        phl_set_error("%s: empty solving resolution %d x %d for a %d x %d image", who, h, w, H, W);
+        return PHL_ERR_INVALID;
+    }
+    if (!y || !x || !third || !eps || !row_of_low || !col_of_low || !low_of_row || !low_of_col) {
+        phl_set_error("%s: null y / x / %s / eps / index map", who, third_name);
+        return PHL_ERR_INVALID;
+    }
+    const int64_t HWf = (int64_t)H * W, lim = INT64_MAX / 64;      // byte counts of the fp64 temporaries stay in int64
+    const int64_t nimg = (int64_t)B * cy;
+    if (HWf > INT32_MAX || nimg > INT32_MAX || HWf > lim / nimg || HWf > lim / ((int64_t)B * cx) || (h + TH - 1) / TH > 65535 ||
+        B > 65535 || max(H, W) > (1 << 30)) {
+        phl_set_error("%s: %d x %d x (%d | %d) x %d x %d elements are too many", who, B, cy, cx, cy, H, W);
+        return PHL_ERR_TOO_LARGE;
+    }
+    if (cx > PHL_GUIDED_MAX_CX) {
+        phl_set_error("%s: %d guide channels, at most %d", who, cx, PHL_GUIDED_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    return PHL_OK;
 }
 
 }  // namespace
@@ -884,7 +856,7 @@ extern "C" {
 int phl_guided_filter_max_r(void)
 {
     int r = 0;
-    while (max_lds(r + 1) <= kMaxLds && halo_stride(r + 1) <= 64 * NCO) r++;
+    while (fits_tiled(r + 1)) r++;
     return r;
 }
 
@@ -892,40 +864,17 @@ int phl_guided_filter(const float *y, const float *x, const float *src, float *o
                       int r, const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col,
                       const float *eps, float scale, phl_stream stream)
 {
-    if (B < 0 || cy < 0 || cx < 1 || H < 0 || W < 0 || h < 0 || w < 0 || r < 0 || h > H || w > W || !isfinite(scale)) {
-        phl_set_error("phl_guided_filter: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", B, cy, cx, H, W, h, w,
-                      r, (double)scale);
-        return PHL_ERR_INVALID;
-    }
+    if (int rc = check_guided_args("phl_guided_filter", y, x, out, "out", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low, low_of_row,
+                                   low_of_col, eps, scale))
+        return rc;
     if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
-    if (h == 0 || w == 0) {
-        phl_set_error("phl_guided_filter: empty solving resolution %d x %d for a %d x %d image", h, w, H, W);
-        return PHL_ERR_INVALID;
-    }
-    if (!y || !x || !out || !eps || !row_of_low || !col_of_low || !low_of_row || !low_of_col) {
-        phl_set_error("phl_guided_filter: null y / x / out / eps / index map");
-        return PHL_ERR_INVALID;
-    }
     if (out == y || out == x || out == src) {
         phl_set_error("phl_guided_filter: out aliases an input");
         return PHL_ERR_INVALID;
     }
-    const int64_t HWf = (int64_t)H * W, lim = INT64_MAX / 16;
-    const int64_t nimg = (int64_t)B * cy;
-    if (HWf > INT32_MAX || nimg > INT32_MAX || HWf > lim / nimg || HWf > lim / ((int64_t)B * cx) || (h + TH - 1) / TH > 65535 ||
-        B > 65535 || max(H, W) > (1 << 30)) {
-        phl_set_error("phl_guided_filter: %d x %d x (%d | %d) x %d x %d elements are too many", B, cy, cx, cy, H, W);
-        return PHL_ERR_TOO_LARGE;
-    }
-    if (cx > PHL_GUIDED_MAX_CX) {
-        phl_set_error("phl_guided_filter: %d guide channels, at most %d", cx, PHL_GUIDED_MAX_CX);
-        return PHL_ERR_UNSUPPORTED;
-    }
     const int re = min(r, max(h, w));            // a window beyond the image on both axes sums the same pixels
-    return run(y, x, src, out, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps, scale,
-                      (hipStream_t)stream);
+    return run(y, x, src, out, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps, scale, (hipStream_t)stream);
 }
-
 
 int phl_guided_filter_grad_max_r(void) { return phl_guided_filter_max_r(); }      // the same two LDS layouts as the forward
 
@@ -934,20 +883,10 @@ int phl_guided_filter_grad(const float *y, const float *x, const float *g, float
                            const int *low_of_row, const int *low_of_col, const float *eps, float scale, int subtract_is_y,
                            phl_stream stream)
 {
-    if (B < 0 || cy < 0 || cx < 1 || H < 0 || W < 0 || h < 0 || w < 0 || r < 0 || h > H || w > W || !isfinite(scale)) {
-        phl_set_error("phl_guided_filter_grad: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", B, cy, cx, H, W,
-                      h, w, r, (double)scale);
-        return PHL_ERR_INVALID;
-    }
-    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
-    if (h == 0 || w == 0) {
-        phl_set_error("phl_guided_filter_grad: empty solving resolution %d x %d for a %d x %d image", h, w, H, W);
-        return PHL_ERR_INVALID;
-    }
-    if (!y || !x || !g || !eps || !row_of_low || !col_of_low || !low_of_row || !low_of_col) {
-        phl_set_error("phl_guided_filter_grad: null y / x / g / eps / index map");
-        return PHL_ERR_INVALID;
-    }
+    if (int rc = check_guided_args("phl_guided_filter_grad", y, x, g, "g", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low, low_of_row,
+                                   low_of_col, eps, scale))
+        return rc;
+    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
     const void *ins[4] = {y, x, g, eps}, *outs[3] = {grad_y, grad_x, grad_eps};
     for (int o = 0; o < 3; o++)
         for (int i = 0; i < 4; i++)
@@ -955,18 +894,6 @@ int phl_guided_filter_grad(const float *y, const float *x, const float *g, float
                 phl_set_error("phl_guided_filter_grad: a gradient aliases an input or another gradient");
                 return PHL_ERR_INVALID;
             }
-    const int64_t HWf = (int64_t)H * W, lim = INT64_MAX / 64;
-    const int64_t nimg = (int64_t)B * cy;
-    if (HWf > INT32_MAX || nimg > INT32_MAX || HWf > lim / nimg || HWf > lim / ((int64_t)B * cx) || (h + TH - 1) / TH > 65535 ||
-        B > 65535 || max(H, W) > (1 << 30)) {
-        phl_set_error("phl_guided_filter_grad: %d x %d x (%d | %d) x %d x %d elements are too many", B, cy, cx, cy, H, W);
-        return PHL_ERR_TOO_LARGE;
-    }
-    if (cx > PHL_GUIDED_MAX_CX) {
-        phl_set_error("phl_guided_filter_grad: %d guide channels, at most %d", cx, PHL_GUIDED_MAX_CX);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (!grad_y && !grad_x && !grad_eps) return PHL_OK;
     const int re = min(r, max(h, w));
     return run_grad(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps,
                     scale, subtract_is_y, (hipStream_t)stream);

@@ -204,6 +204,55 @@ int phl_hip_fail(hipError_t e, const char *what, const char *file, int line);
         hipError_t e__ = (call);                                                   \
         if (e__ != hipSuccess) return phl_hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
+// after a group of launches: rc takes the launch error unless it already holds an earlier one (the first error wins)
+inline void phl_launched(int &rc, const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, what, __FILE__, __LINE__);
+}
+
+// The stream-ordered temporaries of one call.  get() allocates on the stream; release() frees every allocation, latest
+// first, and returns the call's status; the destructor does the same on any other exit path.  The first error wins:
+// after one, get() allocates nothing and returns null, so the caller checks rc once, before its first launch, and
+// writes what its launches return into rc.
+struct phl_temps {
+    static constexpr int MAXN = 16;
+    void *p[MAXN];
+    int n = 0;
+    hipStream_t st;
+    int rc = PHL_OK;
+    explicit phl_temps(hipStream_t s) : st(s) {}
+    phl_temps(const phl_temps &) = delete;
+    phl_temps &operator=(const phl_temps &) = delete;
+    ~phl_temps() { release(); }
+    template <typename T>
+    T *get(size_t count)
+    {
+        if (rc != PHL_OK) return nullptr;
+        if (n >= MAXN) {
+            phl_set_error("phl_temps: more than %d temporaries in one call", MAXN);
+            rc = PHL_ERR_INVALID;
+            return nullptr;
+        }
+        void *q = nullptr;
+        hipError_t e = hipMallocAsync(&q, (count ? count : (size_t)1) * sizeof(T), st);
+        if (e != hipSuccess) {
+            rc = phl_hip_fail(e, "hipMallocAsync", __FILE__, __LINE__);
+            return nullptr;
+        }
+        p[n++] = q;
+        return (T *)q;
+    }
+    int release()
+    {
+        for (int i = n - 1; i >= 0; i--) {
+            hipError_t e = hipFreeAsync(p[i], st);
+            if (e != hipSuccess && rc == PHL_OK) rc = phl_hip_fail(e, "hipFreeAsync", __FILE__, __LINE__);
+        }
+        n = 0;
+        return rc;
+    }
+};
 
 // Raise kernel K's dynamic-LDS limit on the current device to at least `bytes` (phl_api.hip).  A no-op at or below the
 // default 64 KiB; at most one attribute call per (device, kernel, larger size), never per launch: the call is not a stream

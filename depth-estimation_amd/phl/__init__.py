@@ -27,6 +27,7 @@ LIB_PATH = os.environ.get("PHL_LIB") or os.path.join(os.path.dirname(_HERE), "li
 SUBTRACT_INPUT = 1
 EXACT = 4
 NO_TILES = 8
+ERR_UNSUPPORTED = 7          # PHL_ERR_UNSUPPORTED: the kernels do not take this shape, the caller keeps its own path
 BUILD_REFERENCE_TABLE = 1
 
 _f32p = C.c_void_p
@@ -985,7 +986,7 @@ def box_blur_grad(v, g, r, dim, sigma, need_x=True, need_sigma=True):
                 _ptr(gs))
         return gx, gs
     except PhlError as e:
-        if e.status != 7:          # PHL_ERR_UNSUPPORTED: r above the fused kernel's limit
+        if e.status != ERR_UNSUPPORTED:          # r above the fused kernel's limit
             raise
     shape = (1,) * dim + (h,) + (1,) * (v.dim() - dim - 1)
     f = (torch.arange(h, device=v.device, dtype=torch.float64) / float(sigma)).reshape(shape)
@@ -1030,34 +1031,43 @@ def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=No
     (FastGuidedFilter).  ``eps``: a number or a tensor of cx values (softplus(omega) stays on the device).  fp32 CUDA
     tensors of any strides (copied contiguous); any radius (above phl_guided_filter_max_r at the solving resolution the
     kernels read the image from memory instead of LDS tiles); PhlError status 7 for more than 16 guide channels."""
-    for t in (y, x) + (() if subtract is None else (subtract,)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise TypeError(f"guided_filter: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
-    if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:] or x.device != y.device:
-        raise ValueError(f"guided_filter: y [B, cy, H, W] and x [B, cx, H, W] on one device, got {tuple(y.shape)} and {tuple(x.shape)}")
-    if subtract is not None and (subtract.shape != y.shape or subtract.device != y.device):
-        raise ValueError("guided_filter: subtract must have y's shape and device")
-    s, r = int(subsample), int(r)
-    if s < 1 or r < 0:
-        raise ValueError(f"guided_filter: needs subsample >= 1 and r >= 0, got {subsample} and {r}")
-    B, cy, H, W = (int(v) for v in y.shape)
-    cx = int(x.shape[1])
-    yc, xc = y.contiguous(), x.contiguous()
-    sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
+    _, e, dims, maps = _guided_launch_args("guided_filter", y, x, subtract, "subtract", r, eps, subsample)
     if out is None:
-        out = torch.empty((B, cy, H, W), dtype=torch.float32, device=y.device)
+        out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
     elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == y.shape
               and out.device == y.device):
         raise TypeError("guided_filter: out must be a contiguous fp32 tensor of y's shape and device")
-    e = _guided_eps(eps, cx, y.device, "guided_filter")
-    if out.numel() == 0:
+    if dims is None:
         return out
-    if H // s == 0 or W // s == 0:
-        raise ValueError(f"guided_filter: a {H} x {W} image has no pixels at subsample {s}")
-    maps = _nearest_index_maps(H, W, s, y.device)
-    _launch(y.device, "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), B, cy, cx, H, W, H // s, W // s, r // s,
-            *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)))
+    yc, xc = y.contiguous(), x.contiguous()
+    sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
+    _launch(y.device, "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims, *(_ptr(m) for m in maps), _ptr(e),
+            C.c_float(float(scale)))
     return out
+
+
+def _guided_launch_args(name, y, x, third, third_name, r, eps, subsample, launch=True):
+    """What guided_filter and guided_filter_grad (``name``) share: the checks of y, x and ``third`` (subtract or g: y's
+    shape, may be None), of subsample and r; then (cx, eps as the kernels read it, the launch's (B, cy, cx, H, W, h, w,
+    r // s), its four index maps).  The last two are None when y has no elements or the caller launches nothing."""
+    for t in (y, x) + (() if third is None else (third,)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise TypeError(f"{name}: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+    if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:] or x.device != y.device:
+        raise ValueError(f"{name}: y [B, cy, H, W] and x [B, cx, H, W] on one device, got {tuple(y.shape)} and {tuple(x.shape)}")
+    if third is not None and (third.shape != y.shape or third.device != y.device):
+        raise ValueError(f"{name}: {third_name} must have y's shape and device")
+    s, r = int(subsample), int(r)
+    if s < 1 or r < 0:
+        raise ValueError(f"{name}: needs subsample >= 1 and r >= 0, got {subsample} and {r}")
+    B, cy, H, W = (int(v) for v in y.shape)
+    cx = int(x.shape[1])
+    e = _guided_eps(eps, cx, y.device, name)
+    if y.numel() == 0 or not launch:
+        return cx, e, None, None
+    if H // s == 0 or W // s == 0:
+        raise ValueError(f"{name}: a {H} x {W} image has no pixels at subsample {s}")
+    return cx, e, (B, cy, cx, H, W, H // s, W // s, r // s), _nearest_index_maps(H, W, s, y.device)
 
 
 def _guided_eps(eps, cx, device, name):
@@ -1078,32 +1088,16 @@ def guided_filter_grad(y, x, g, r, eps, *, subsample=1, scale=1.0, subtract_is_y
     grad_eps has cx values.  Nothing of the forward is needed: the kernels recompute it from y, x and eps.  The same tensor
     rules as guided_filter (fp32 CUDA, any strides, any radius; PhlError status 7 for more than 16 guide channels); the
     same bits on every run."""
-    for t in (y, x, g):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise TypeError(f"guided_filter_grad: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
-    if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:] or x.device != y.device:
-        raise ValueError(f"guided_filter_grad: y [B, cy, H, W] and x [B, cx, H, W] on one device, got {tuple(y.shape)} and {tuple(x.shape)}")
-    if g.shape != y.shape or g.device != y.device:
-        raise ValueError("guided_filter_grad: g must have y's shape and device")
-    s, r = int(subsample), int(r)
-    if s < 1 or r < 0:
-        raise ValueError(f"guided_filter_grad: needs subsample >= 1 and r >= 0, got {subsample} and {r}")
-    B, cy, H, W = (int(v) for v in y.shape)
-    cx = int(x.shape[1])
-    e = _guided_eps(eps, cx, y.device, "guided_filter_grad")
+    cx, e, dims, maps = _guided_launch_args("guided_filter_grad", y, x, g, "g", r, eps, subsample, need_y or need_x or need_eps)
     new = torch.zeros if y.numel() == 0 else torch.empty
-    gy = new((B, cy, H, W), dtype=torch.float32, device=y.device) if need_y else None
-    gx = new((B, cx, H, W), dtype=torch.float32, device=y.device) if need_x else None
+    gy = new(y.shape, dtype=torch.float32, device=y.device) if need_y else None
+    gx = new(x.shape, dtype=torch.float32, device=y.device) if need_x else None
     ge = new((cx,), dtype=torch.float32, device=y.device) if need_eps else None
-    if y.numel() == 0 or not (need_y or need_x or need_eps):
+    if dims is None:
         return gy, gx, ge
-    if H // s == 0 or W // s == 0:
-        raise ValueError(f"guided_filter_grad: a {H} x {W} image has no pixels at subsample {s}")
-    maps = _nearest_index_maps(H, W, s, y.device)
     yc, xc, gc = y.contiguous(), x.contiguous(), g.contiguous()         # (named: a copy must outlive the launch)
-    _launch(y.device, "phl_guided_filter_grad", _ptr(yc), _ptr(xc), _ptr(gc), _ptr(gy), _ptr(gx),
-            _ptr(ge), B, cy, cx, H, W, H // s, W // s, r // s, *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)),
-            1 if subtract_is_y else 0)
+    _launch(y.device, "phl_guided_filter_grad", _ptr(yc), _ptr(xc), _ptr(gc), _ptr(gy), _ptr(gx), _ptr(ge), *dims,
+            *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)), 1 if subtract_is_y else 0)
     return gy, gx, ge
 
 

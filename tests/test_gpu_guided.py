@@ -5,61 +5,14 @@ device), e_hip = max|hip - g| and e_torch = max|fp32 torch form - g| over ALL el
 e_hip <= e_torch with no margin -- fp64 window sums must beat fp32 prefix sums.  The two multi-iteration fixtures
 (CRFasRNN, mean_field_infer) are held to e_hip <= 2 e_torch: the fp32 compatibility and softmax steps are common to both
 paths.  Both numbers are printed."""
-import contextlib
-
-import numpy as np
 import pytest
 import torch
 
-from _guided_util import CASES, END_TO_END, build_module, load_case
+from _guided_util import CASES, DEV, END_TO_END, build_module, load_case, spy, torch_form
+from _guided_util import report as _report
+from _guided_util import sweep_case as _sweep_case
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-
-
-@contextlib.contextmanager
-def torch_form():
-    """The classes with the HIP dispatch switched off (what they were before it existed)."""
-    from crf import guided
-
-    real = guided.GuidedFilter._fused
-    guided.GuidedFilter._fused = lambda self, *a, **k: None
-    try:
-        yield
-    finally:
-        guided.GuidedFilter._fused = real
-
-
-@contextlib.contextmanager
-def spy():
-    """Counts of phl.guided_filter and crf.guided._box_sum calls."""
-    import phl
-    from crf import guided
-
-    calls = {"hip": 0, "box_sum": 0}
-    real_h, real_b = phl.guided_filter, guided._box_sum
-
-    def h(*a, **k):
-        calls["hip"] += 1
-        return real_h(*a, **k)
-
-    def b(*a, **k):
-        calls["box_sum"] += 1
-        return real_b(*a, **k)
-
-    phl.guided_filter, guided._box_sum = h, b
-    try:
-        yield calls
-    finally:
-        phl.guided_filter, guided._box_sum = real_h, real_b
-
-
-def _report(name, hip, t32, want, factor=1):
-    e_hip = float((hip.double() - want).abs().max())
-    e_torch = float((t32.double() - want).abs().max())
-    print(f"{name}: e_hip = {e_hip:.3e}  e_torch = {e_torch:.3e}  |out| <= {float(want.abs().max()):.4g}")
-    assert torch.isfinite(hip).all()
-    assert e_hip <= factor * e_torch, (name, e_hip, e_torch)
 
 
 @pytest.mark.parametrize("name", [c for c in CASES if c not in END_TO_END])
@@ -110,42 +63,6 @@ def test_golden_mean_field_guided_adjacency():
     with torch.no_grad(), torch_form():
         t32 = mean_field_infer(E0, W, Mu, int(z["niters"]))
     _report("meanfield_guided", hip, t32, torch.from_numpy(z["out"]).to(DEV), factor=2)
-
-
-def _sweep_case(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=False, use_out=False):
-    import phl
-    from crf import guided
-
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    if noncontiguous:
-        y = torch.rand((B, H, W, cy), device=DEV, generator=g).permute(0, 3, 1, 2)
-        x = torch.rand((B, cx, H, 2 * W), device=DEV, generator=g)[..., ::2]
-    else:
-        y = torch.rand((B, cy, H, W), device=DEV, generator=g)
-        x = torch.rand((B, cx, H, W), device=DEV, generator=g)
-    if kind == "gf":
-        m = guided.GuidedFilter(cx, r, eps)
-    elif kind == "fast":
-        m = guided.FastGuidedFilter(cx, r, eps, subsample_ratio=s)
-    else:
-        m = guided.BatchedGuidedAdjacency(cx, r, eps, subsample_ratio=s)
-    m = m.to(DEV)
-    name = f"{kind} B{B} cy{cy} cx{cx} {H}x{W} r{r} s{s} eps{eps:g}"
-    with torch.no_grad():
-        if use_out:
-            out = torch.full((B, cy, H, W), float("nan"), device=DEV)
-            k = 0.5 * (2 * r + 1) ** 2 if kind == "bga" else 1.0
-            hip = phl.guided_filter(y, x, r, m.eps, subsample=s, scale=k, subtract=y if kind == "bga" else None, out=out)
-            assert hip is out
-        else:
-            with spy() as calls:
-                hip = m(y, x)
-            assert calls == {"hip": 1, "box_sum": 0}, name
-        with torch_form():
-            t32 = m(y, x)
-            want = m.double()(y.double(), x.double())
-        m.float()
-    _report(name, hip, t32, want)
 
 
 @pytest.mark.parametrize("s", [1, 2, 3])

@@ -6,45 +6,20 @@ float64 gradient (the reference's fixture, or the torch form in float64 on the d
 e_torch = max|fp32 torch autograd - g64| over ALL elements, on the same device, and e_hip <= e_torch with no margin.
 The end-to-end CRFasRNN case is held to e_hip <= 2 e_torch: the fp32 compatibility and softmax steps are common to both
 paths.  Both numbers are printed."""
-import contextlib
+import functools
 
 import pytest
 import torch
 
+import _guided_util as util
 from _guided_grad_util import GRAD_CASES, load_grad_case, torch_form_grads
+from _guided_util import DEV
+from _guided_util import grads as _grads
+from _guided_util import sweep_case_grad as _sweep_case
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-
-
-@contextlib.contextmanager
-def spy():
-    """Counts of phl.guided_filter, phl.guided_filter_grad and crf.guided._box_sum calls."""
-    import phl
-    from crf import guided
-
-    calls = {"hip": 0, "hip_grad": 0, "box_sum": 0}
-    real_h, real_g, real_b = phl.guided_filter, phl.guided_filter_grad, guided._box_sum
-
-    def counted(key, fn):
-        def f(*a, **k):
-            calls[key] += 1
-            return fn(*a, **k)
-        return f
-
-    phl.guided_filter, phl.guided_filter_grad, guided._box_sum = counted("hip", real_h), counted("hip_grad", real_g), counted("box_sum", real_b)
-    try:
-        yield calls
-    finally:
-        phl.guided_filter, phl.guided_filter_grad, guided._box_sum = real_h, real_g, real_b
-
-
-def _report(name, hip, t32, want, factor=1):
-    e_hip = float((hip.double() - want).abs().max())
-    e_torch = float((t32.double() - want).abs().max())
-    print(f"{name}: e_hip = {e_hip:.3e}  e_torch = {e_torch:.3e}  |grad| <= {float(want.abs().max()):.4g}")
-    assert torch.isfinite(hip).all()
-    assert e_hip <= factor * e_torch, (name, e_hip, e_torch)
+spy = functools.partial(util.spy, grad=True)
+_report = functools.partial(util.report, what="grad")
 
 
 @pytest.mark.parametrize("name", GRAD_CASES)
@@ -58,47 +33,6 @@ def test_goldens(name):
     t32 = torch_form_grads(guided, z, torch.float32, DEV)
     for k, a, b in zip(("y", "x", "omega"), hip, t32):
         _report(f"{name} grad_{k}", a, b, torch.from_numpy(z["grad_" + k]).to(DEV))
-
-
-def _module(kind, cx, r, s, eps, **kw):
-    from crf import guided
-
-    if kind == "gf":
-        return guided.GuidedFilter(cx, r, eps, **kw)
-    if kind == "fast":
-        return guided.FastGuidedFilter(cx, r, eps, subsample_ratio=s, **kw)
-    return guided.BatchedGuidedAdjacency(cx, r, eps, subsample_ratio=s, **kw)
-
-
-def _grads(m, y, x, g, dtype):
-    yy, xx = y.detach().to(dtype).requires_grad_(True), x.detach().to(dtype).requires_grad_(True)
-    m.omega.grad = None
-    (m(yy, xx) * g.to(dtype)).sum().backward()
-    return yy.grad, xx.grad, m.omega.grad.clone()
-
-
-def _sweep_case(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=False):
-    gen = torch.Generator(device=DEV).manual_seed(seed)
-    if noncontiguous:
-        y = torch.rand((B, H, W, cy), device=DEV, generator=gen).permute(0, 3, 1, 2)
-        x = torch.rand((B, cx, H, 2 * W), device=DEV, generator=gen)[..., ::2]
-        g = (torch.rand((B, cy, W, H), device=DEV, generator=gen) * 2 - 1).transpose(2, 3)
-    else:
-        y = torch.rand((B, cy, H, W), device=DEV, generator=gen)
-        x = torch.rand((B, cx, H, W), device=DEV, generator=gen)
-        g = torch.rand((B, cy, H, W), device=DEV, generator=gen) * 2 - 1
-    name = f"{kind} B{B} cy{cy} cx{cx} {H}x{W} r{r} s{s} eps{eps:g}"
-    m = _module(kind, cx, r, s, eps, fused_grad=True).to(DEV)
-    with spy() as calls:
-        hip = _grads(m, y, x, g, torch.float32)
-    assert calls == {"hip": 1, "hip_grad": 1, "box_sum": 0}, name
-    m.fused_grad = False
-    with spy() as calls:
-        t32 = _grads(m, y, x, g, torch.float32)
-    assert calls["hip"] == 0 and calls["hip_grad"] == 0 and calls["box_sum"] > 0
-    want = _grads(m.double(), y, x, g, torch.float64)
-    for k, a, b, c in zip(("y", "x", "omega"), hip, t32, want):
-        _report(f"{name} grad_{k}", a, b, c)
 
 
 @pytest.mark.parametrize("s", [1, 2, 3])
