@@ -6,6 +6,8 @@
 whose product is one splat -> blur -> slice on the MI355X lattice built ONCE for the fixed
 reference features (the reference rebuilds it on every iteration).
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -278,6 +280,38 @@ def _mean_field_nchw(E0, message, niters):
     return E
 
 
+# PHL_NCHW_STEP=0 keeps CRFasRNN's non-lattice W on the plain loop above (read once; the two loops side by side)
+_NCHW_STEP = os.environ.get("PHL_NCHW_STEP", "1") not in ("", "0")
+
+
+def _mean_field_nchw_step_fused(E0, refs, W, M, niters):
+    """The same iteration for any other W (the default guided filter), without autograd, in the reference's order
+    E = E0 + W(Mu(Q)) (crf_module.py:97-99): everything between two W calls -- the add, the negation, the softmax over
+    the label channels and the compatibility product -- is ONE channel-major kernel (phl.nchw_softmax_compat), so Q and E
+    never exist in memory and nothing is transposed.  W is called once per iteration as the module it is, on whatever
+    engine it picks.  M: _compat_matrix of the Mu module.  Gives the logits -E of the last iteration."""
+    import phl
+
+    uniform = (phl._mu_uniform(M) or False) if M.shape[0] <= phl.NCHW_UNIFORM_MAX_L else False   # one read per forward
+    Y = phl.nchw_softmax_compat(E0, None, M, uniform=uniform)
+    for it in range(niters):
+        G = W(Y, refs)
+        if it == niters - 1:
+            return phl.nchw_softmax_compat(E0, G, logits=True)
+        Y = phl.nchw_softmax_compat(E0, G, M, uniform=uniform, out=Y)
+
+
+def _nchw_step_matrix(mu, E0, labels):
+    """_compat_matrix of ``mu`` if phl.nchw_softmax_compat takes it at this label count, else None."""
+    import phl
+
+    L = E0.shape[1]
+    M = _compat_matrix(mu, L, labels, E0.device) if L <= phl.NCHW_UNIFORM_MAX_L else None
+    if M is not None and L > phl.NCHW_PRODUCT_MAX_L and not phl._mu_uniform(M):
+        return None
+    return M
+
+
 _nchw_streams = {}
 
 
@@ -364,9 +398,13 @@ class CRFasRNN(nn.Module):
     """Batched NCHW mean field (crf_module.py:81-104); returns logits -E of the LAST iteration.
 
     ``lattice=True`` selects the permutohedral W (BatchedAdjacency, the MI355X path); the default
-    stays the reference's guided-filter W.  ``fused_grad=True`` keeps W on the library's kernels under autograd: the
-    lattice W through _mean_field_nchw_grad, the guided W through phl.GuidedFilterFn inside the plain NCHW loop (Mu and
-    the softmax stay torch ops there)."""
+    stays the reference's guided-filter W.  With that W, a forward on fp32 CUDA tensors that autograd does not record
+    (no gradient asked of the logits, the guide, Mu's or W's parameters) and a Mu that is a matrix (``charb``, a
+    bias-free 1x1 conv: at most 256 labels, 1024 for the Potts family) runs _mean_field_nchw_step_fused: per iteration W
+    and one channel-major kernel for everything else (phl.nchw_softmax_compat); PHL_NCHW_STEP=0 in the environment
+    keeps the plain loop.  Anything else -- training, CPU tensors, float64, another Mu -- is the plain NCHW loop.
+    ``fused_grad=True`` keeps W on the library's kernels under autograd: the lattice W through _mean_field_nchw_grad, the
+    guided W through phl.GuidedFilterFn inside the plain NCHW loop (Mu and the softmax stay torch ops there)."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
                  fused_grad=False):
@@ -395,6 +433,13 @@ class CRFasRNN(nn.Module):
                 M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device, detach=False)
                 if M is not None:
                     return _mean_field_nchw_grad(E0, refs, M, self.niters)                    # already -E
+        elif (_NCHW_STEP and not isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda
+              and E0.dtype == torch.float32 and E0.dim() == 4):
+            params = list(self.Mu.parameters()) + list(self.W.parameters())
+            grad = torch.is_grad_enabled() and (E0.requires_grad or refs.requires_grad or any(p.requires_grad for p in params))
+            M = None if grad else _nchw_step_matrix(self.Mu, E0, labels)
+            if M is not None:
+                return _mean_field_nchw_step_fused(E0.contiguous(), refs, self.W, M, self.niters)   # already -E
         return -_mean_field_nchw(E0, lambda Q: self.W(self.Mu(Q, *extra), refs), self.niters)
 
 

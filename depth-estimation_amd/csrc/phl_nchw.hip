@@ -1,0 +1,319 @@
+// phl_nchw.hip -- the non-W half of one mean-field iteration for channel-major (NCHW) data, fused.
+//
+// Reference (crf/crf_module.py:66-79, 97-103): per iteration  Y = Mu(Q);  E = E0 + W(Y);  Q = softmax(-E, dim=1)  on
+// [B, L, H, W] tensors, Mu a 1x1 convolution over the label channels.  Around W that is a library convolution, an add,
+// a negation and a 2-3 pass softmax over a strided dimension: about seven sweeps over an L-plane tensor.  Here the
+// piece between two W calls is ONE kernel -- softmax first, then the product (the dual of k_compat_softmax, which is
+// product first, then softmax, on pixel-major rows):
+//
+//     Y[b, c, p] = sum_a M[a, c] * softmax_a( -(E0[b, a, p] + G[b, a, p]) )            (G optional)
+//
+// E0 and G are read once, Y is written once, Q and E never exist in memory.
+//
+//   k_nchw_tile     L <= 256: a workgroup owns TP = 64 consecutive pixels of one image and all L labels of them.  The
+//                   [L][TP] block of -(E0 + G) is staged in LDS (64 KiB at 256 labels: two workgroups per CU), the column
+//                   softmax runs there (four threads per pixel, max-subtracted, expf, one 1.0f / s per pixel), then
+//                     PRODUCT, L > 32   Y^T = M^T Q^T on v_mfma_f32_32x32x2_f32 (exact f32: a k-ordered fma chain).  M^T
+//                                       is operand A, read from global memory / L2 as it is (lane l: M[a = k + l/32]
+//                                       [c = 32 ct + l%32], 128 contiguous bytes per k); the softmaxed tile is operand B,
+//                                       read from LDS (lane l: Q[a = k + l/32][pixel 32 h + l%32]: one ds_read_b32, the two
+//                                       lane halves on rows of their own, no bank conflict at a row stride of TP).  Wave w
+//                                       owns pixel half w & 1 and the label tiles (w >> 1) + 2 i: at most four 32x32
+//                                       accumulators, 64 registers.
+//                     PRODUCT, L <= 32  the same fma chain on the VALU: one label tile would leave half the waves without
+//                                       work and pad 32 labels; at L = 18 the step needs ~1.5 fma per byte moved.
+//                     UNIFORM           Y = alpha * colsum(Q) + beta * Q (M = alpha J + beta I, the Potts family), the
+//                                       column sum computed, no product.
+//                     SOFTMAX           Y = Q.
+//                   The result goes back into the LDS block and is stored the way the input was loaded: along the pixel
+//                   axis, 256 contiguous bytes per label plane and wave quarter -- float4 accesses when n % 4 == 0 and all
+//                   pointers are 16-byte aligned (then every plane base and every tile base is), dwords otherwise.  The
+//                   last tile of an image may be shorter than TP: its missing pixels are computed on zeros and not stored.
+//   k_nchw_stream   L > 256 (UNIFORM up to 1024, SOFTMAX any): a thread per pixel walks its column in memory, three
+//                   reading passes (max, sum, quotient) and for UNIFORM a fourth over its own output.
+//   k_nchw_logits   out = -(E0 + G): what CRFasRNN returns after the last iteration.
+// No atomics, every sum in a fixed order: a repeated call gives the same bits.
+#include <math.h>
+
+#include "phl_internal.h"
+
+namespace {
+
+constexpr int TP = 64;                 // pixels of a tile
+constexpr int NT = 256;                // threads of a workgroup: 4 per pixel in the softmax, 4 waves in the product
+constexpr int VALU_MAX_L = 32;         // the product runs on the VALU up to here, on the matrix cores above
+constexpr int TILE_MAX_L = 256;        // k_nchw_tile's range
+enum { T_MFMA = 0, T_VALU = 1, T_UNIFORM = 2, T_SOFTMAX = 3 };
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+inline size_t tile_lds_bytes(int L) { return ((size_t)((L + 1) & ~1) * TP + 3 * 4 * TP) * sizeof(float); }
+
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(NT) void k_nchw_tile(const float *__restrict__ E0, const float *__restrict__ G,
+                                                  const float *__restrict__ M, float alpha, float beta,
+                                                  float *__restrict__ out, int L, int64_t n, int tiles)
+{
+    // S [La][TP]: the tile, La = L rounded up to the MFMA's k step; then three [4][TP] arrays of per-pixel partials
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int La = (L + 1) & ~1;
+    float *S = lds, *red_m = lds + La * TP, *red_s = red_m + 4 * TP, *red_c = red_s + 4 * TP;
+    const int t = threadIdx.x;
+    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+    const int64_t p0 = (int64_t)tile * TP, base = (int64_t)b * L * n + p0;
+    const int np = (int)(n - p0 < TP ? n - p0 : TP);            // pixels of this tile
+    const float *e0 = E0 + base, *g = G ? G + base : nullptr;
+    float *o = out + base;
+
+    // ---- 1. S = -(E0 + G), coalesced along the pixel axis
+    if (VEC) {
+        const int q = (t & 15) * 4, r = t >> 4;                  // n % 4 == 0: a float4 lies inside the image or outside
+#pragma unroll 4
+        for (int a = r; a < L; a += 16) {
+            float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (q < np) {
+                x = *reinterpret_cast<const float4 *>(e0 + a * n + q);
+                if (g) {
+                    const float4 y = *reinterpret_cast<const float4 *>(g + a * n + q);
+                    x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+                }
+                x = make_float4(-x.x, -x.y, -x.z, -x.w);
+            }
+            *reinterpret_cast<float4 *>(S + a * TP + q) = x;
+        }
+    } else {
+        const int q = t & 63, r = t >> 6;
+#pragma unroll 4
+        for (int a = r; a < L; a += 4) {
+            float x = 0.f;
+            if (q < np) {
+                x = e0[a * n + q];
+                if (g) x += g[a * n + q];
+                x = -x;
+            }
+            S[a * TP + q] = x;
+        }
+    }
+    if (MODE == T_MFMA && La != L && t < TP) S[L * TP + t] = 0.f;       // the k step's second row at an odd L
+    __syncthreads();
+
+    // ---- 2. column softmax: pixel p, labels part, part + 4, ... per thread; partials combined in a fixed order
+    const int p = t & 63, part = __builtin_amdgcn_readfirstlane(t >> 6);
+    float m = -INFINITY;
+    for (int a = part; a < L; a += 4) m = fmaxf(m, S[a * TP + p]);
+    red_m[part * TP + p] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red_m[p], red_m[TP + p]), fmaxf(red_m[2 * TP + p], red_m[3 * TP + p]));
+    float s = 0.f;
+    for (int a = part; a < L; a += 4) {
+        const float e = expf(S[a * TP + p] - m);
+        S[a * TP + p] = e;
+        s += e;
+    }
+    red_s[part * TP + p] = s;
+    __syncthreads();
+    s = (red_s[p] + red_s[TP + p]) + (red_s[2 * TP + p] + red_s[3 * TP + p]);
+    const float inv = 1.0f / s;
+    float cs = 0.f;
+    for (int a = part; a < L; a += 4) {
+        const float qv = S[a * TP + p] * inv;
+        S[a * TP + p] = qv;
+        cs += qv;
+    }
+    if (MODE == T_UNIFORM) {         // Y = alpha colsum(Q) + beta Q: every thread rewrites the labels it owns
+        red_c[part * TP + p] = cs;
+        __syncthreads();
+        cs = alpha * ((red_c[p] + red_c[TP + p]) + (red_c[2 * TP + p] + red_c[3 * TP + p]));
+        for (int a = part; a < L; a += 4) S[a * TP + p] = cs + beta * S[a * TP + p];
+    }
+    __syncthreads();                 // S = Q (UNIFORM: Y already)
+
+    // ---- 3. Y[c][p] = sum_a M[a][c] Q[a][p], an fma chain in a order, back into S
+    if (MODE == T_VALU) {
+        float y[VALU_MAX_L / 4];
+#pragma unroll
+        for (int i = 0; i < VALU_MAX_L / 4; i++) {
+            const int c = part + 4 * i;                          // wave-uniform: M comes through scalar loads
+            y[i] = 0.f;
+            if (c < L)
+                for (int a = 0; a < L; a++) y[i] = __builtin_fmaf(M[a * L + c], S[a * TP + p], y[i]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < VALU_MAX_L / 4; i++)
+            if (part + 4 * i < L) S[(part + 4 * i) * TP + p] = y[i];
+        __syncthreads();
+    }
+    if (MODE == T_MFMA) {
+        const int j = t & 31, kh = (t >> 5) & 1;                 // 32x32x2: A[i = j][k = kh], B[k = kh][column j]
+        const int ph = part & 1, ct0 = part >> 1, nct = (L + 31) >> 5;
+        f32x16 acc[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][r] = 0.f;
+#pragma unroll 4
+        for (int k = 0; k < La; k += 2) {
+            const int a = k + kh;
+            const float bv = S[a * TP + 32 * ph + j];
+            const int ar = a < L ? a : L - 1;                    // loads stay inside M; what lies beyond L counts as 0
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int ct = ct0 + 2 * i;
+                if (ct < nct) {
+                    const int c = 32 * ct + j;
+                    float av = M[ar * L + (c < L ? c : L - 1)];
+                    av = (a < L && c < L) ? av : 0.f;
+                    acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i], 0, 0, 0);
+                }
+            }
+        }
+        __syncthreads();             // every wave has read its Q
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int ct = ct0 + 2 * i;
+            if (ct < nct) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {                   // C/D: column = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+                    const int c = 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                    if (c < L) S[c * TP + 32 * ph + j] = acc[i][r];
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- 4. store, as loaded
+    if (VEC) {
+        const int q = (t & 15) * 4, r = t >> 4;
+        if (q < np)
+#pragma unroll 4
+            for (int a = r; a < L; a += 16) *reinterpret_cast<float4 *>(o + a * n + q) = *reinterpret_cast<const float4 *>(S + a * TP + q);
+    } else {
+        const int q = t & 63, r = t >> 6;
+        if (q < np)
+#pragma unroll 4
+            for (int a = r; a < L; a += 4) o[a * n + q] = S[a * TP + q];
+    }
+}
+
+// Columns longer than an LDS tile: a thread per pixel, the column read from memory in every pass (consecutive threads on
+// consecutive pixels of a label plane).  The arithmetic is k_nchw_tile's with one partial instead of four.
+template <bool UNIFORM>
+__global__ __launch_bounds__(NT) void k_nchw_stream(const float *__restrict__ E0, const float *__restrict__ G, float alpha,
+                                                    float beta, float *__restrict__ out, int L, int64_t n, int tiles)
+{
+    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
+    const int64_t p = (int64_t)tile * NT + threadIdx.x;
+    if (p >= n) return;
+    const int64_t base = (int64_t)b * L * n + p;
+    const float *e0 = E0 + base, *g = G ? G + base : nullptr;
+    float *o = out + base;
+    float m = -INFINITY;
+    for (int a = 0; a < L; a++) m = fmaxf(m, -(e0[a * n] + (g ? g[a * n] : 0.f)));
+    float s = 0.f;
+    for (int a = 0; a < L; a++) s += expf(-(e0[a * n] + (g ? g[a * n] : 0.f)) - m);
+    const float inv = 1.0f / s;
+    float cs = 0.f;
+    for (int a = 0; a < L; a++) {
+        const float qv = expf(-(e0[a * n] + (g ? g[a * n] : 0.f)) - m) * inv;
+        o[a * n] = qv;
+        cs += qv;
+    }
+    if (UNIFORM) {
+        cs *= alpha;
+        for (int a = 0; a < L; a++) o[a * n] = cs + beta * o[a * n];       // the thread's own stores
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(NT) void k_nchw_logits(const float *__restrict__ E0, const float *__restrict__ G,
+                                                    float *__restrict__ out, int64_t count)       // count: float4s if VEC
+{
+    const int64_t stride = (int64_t)gridDim.x * NT;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < count; i += stride) {
+        if (VEC) {
+            const float4 e = reinterpret_cast<const float4 *>(E0)[i], y = reinterpret_cast<const float4 *>(G)[i];
+            reinterpret_cast<float4 *>(out)[i] = make_float4(-(e.x + y.x), -(e.y + y.y), -(e.z + y.z), -(e.w + y.w));
+        } else {
+            out[i] = -(E0[i] + G[i]);
+        }
+    }
+}
+
+template <int MODE>
+int launch_tile(const float *E0, const float *G, const float *M, float alpha, float beta, float *out, int B, int L, int64_t n,
+                hipStream_t st)
+{
+    const int tiles = (int)((n + TP - 1) / TP);
+    const size_t lds = tile_lds_bytes(L);
+    const dim3 grid((unsigned)((int64_t)B * tiles));
+    if (n % 4 == 0 && phl_al16(E0) && phl_al16(G) && phl_al16(out)) {
+        if (const int rc = phl_allow_lds(&k_nchw_tile<MODE, true>, lds)) return rc;
+        k_nchw_tile<MODE, true><<<grid, dim3(NT), lds, st>>>(E0, G, M, alpha, beta, out, L, n, tiles);
+    } else {
+        if (const int rc = phl_allow_lds(&k_nchw_tile<MODE, false>, lds)) return rc;
+        k_nchw_tile<MODE, false><<<grid, dim3(NT), lds, st>>>(E0, G, M, alpha, beta, out, L, n, tiles);
+    }
+    PHL_HIP(hipGetLastError());
+    return PHL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int phl_nchw_softmax_compat(const float *E0, const float *G, const float *mu, float alpha, float beta, float *out, int B, int L,
+                            int64_t n, int mode, phl_stream stream)
+{
+    const bool known = mode == PHL_NCHW_PRODUCT || mode == PHL_NCHW_UNIFORM || mode == PHL_NCHW_SOFTMAX || mode == PHL_NCHW_LOGITS;
+    if (B < 0 || n < 0 || L < 1 || !known || (mode == PHL_NCHW_UNIFORM && !(isfinite(alpha) && isfinite(beta)))) {
+        phl_set_error("phl_nchw_softmax_compat: bad arguments (B=%d L=%d n=%lld mode=%d alpha=%g beta=%g)", B, L, (long long)n, mode,
+                      (double)alpha, (double)beta);
+        return PHL_ERR_INVALID;
+    }
+    if (B == 0 || n == 0) return PHL_OK;
+    if (!E0 || !out || (mode == PHL_NCHW_PRODUCT && !mu) || (mode == PHL_NCHW_LOGITS && !G)) {
+        phl_set_error("phl_nchw_softmax_compat: null E0 / out%s", mode == PHL_NCHW_PRODUCT ? " / mu" : mode == PHL_NCHW_LOGITS ? " / G" : "");
+        return PHL_ERR_INVALID;
+    }
+    if (out == E0 || out == G) {
+        phl_set_error("phl_nchw_softmax_compat: out aliases an input");
+        return PHL_ERR_INVALID;
+    }
+    const int64_t planes = (int64_t)B * L, lim = INT64_MAX / 4;          // B, L <= 2^31 - 1: their product stays in int64
+    const int64_t px = L > TILE_MAX_L ? NT : TP;                          // pixels of a workgroup (the logits' grid is capped)
+    if (n > lim / planes || (mode != PHL_NCHW_LOGITS && (n + px - 1) / px > INT32_MAX / (int64_t)B)) {
+        phl_set_error("phl_nchw_softmax_compat: %d x %d x %lld elements are too many", B, L, (long long)n);
+        return PHL_ERR_TOO_LARGE;
+    }
+    if ((mode == PHL_NCHW_PRODUCT && L > TILE_MAX_L) || (mode == PHL_NCHW_UNIFORM && L > 1024)) {
+        phl_set_error("phl_nchw_softmax_compat: %d labels, at most %d in this mode", L, mode == PHL_NCHW_PRODUCT ? TILE_MAX_L : 1024);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == PHL_NCHW_LOGITS) {
+        const int64_t total = planes * n;
+        const bool vec = total % 4 == 0 && phl_al16(E0) && phl_al16(G) && phl_al16(out);
+        const int64_t count = vec ? total / 4 : total, want = (count + NT - 1) / NT;
+        const dim3 grid((unsigned)(want < 65536 ? want : 65536));
+        if (vec) k_nchw_logits<true><<<grid, dim3(NT), 0, st>>>(E0, G, out, count);
+        else k_nchw_logits<false><<<grid, dim3(NT), 0, st>>>(E0, G, out, count);
+        PHL_HIP(hipGetLastError());
+        return PHL_OK;
+    }
+    if (L > TILE_MAX_L) {
+        const int tiles = (int)((n + NT - 1) / NT);
+        const dim3 grid((unsigned)((int64_t)B * tiles));
+        if (mode == PHL_NCHW_UNIFORM) k_nchw_stream<true><<<grid, dim3(NT), 0, st>>>(E0, G, alpha, beta, out, L, n, tiles);
+        else k_nchw_stream<false><<<grid, dim3(NT), 0, st>>>(E0, G, alpha, beta, out, L, n, tiles);
+        PHL_HIP(hipGetLastError());
+        return PHL_OK;
+    }
+    if (mode == PHL_NCHW_UNIFORM) return launch_tile<T_UNIFORM>(E0, G, nullptr, alpha, beta, out, B, L, n, st);
+    if (mode == PHL_NCHW_SOFTMAX) return launch_tile<T_SOFTMAX>(E0, G, nullptr, 0.f, 0.f, out, B, L, n, st);
+    if (L <= VALU_MAX_L) return launch_tile<T_VALU>(E0, G, mu, 0.f, 0.f, out, B, L, n, st);
+    return launch_tile<T_MFMA>(E0, G, mu, 0.f, 0.f, out, B, L, n, st);
+}
+
+}  // extern "C"

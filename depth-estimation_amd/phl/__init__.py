@@ -102,6 +102,8 @@ def load_library():
             lib.phl_compat_planes_bytes.restype = C.c_size_t
             lib.phl_compat_prepare.argtypes = [vp, i32, vp, vp]
             lib.phl_compat_softmax_split.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, u32, vp]
+        if hasattr(lib, "phl_nchw_softmax_compat"):    # (an older build loaded through PHL_LIB lacks the NCHW step)
+            lib.phl_nchw_softmax_compat.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, i32, i32, i64, i32, vp]
         if hasattr(lib, "phl_compat_grad_x"):          # (an older build loaded through PHL_LIB lacks the backward)
             lib.phl_softmax_neg_grad.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, vp]
             lib.phl_uniform_compat_grad.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, vp, i64, vp, i64, i64, i32, vp]
@@ -620,6 +622,12 @@ class _MuForms:
             return planes
         return self._form(("planes", str(device)), device, make)
 
+    def dense(self, device):
+        """Mu itself as a dense fp32 [L, L] device tensor (phl_nchw_softmax_compat reads it untransposed)."""
+        if self.Mu.dtype == torch.float32 and self.Mu.device == device and self.Mu.is_contiguous():
+            return self.Mu
+        return self._form(("dense", str(device)), device, lambda: self.Mu.to(device, torch.float32).contiguous())
+
     def padded(self, Lp, device):
         """(Mu with zero rows / columns up to Lp, the Potts-family structure of the ORIGINAL matrix or False): the padded
         matrix no longer shows it (crf_module._pad_labels)."""
@@ -707,6 +715,55 @@ def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None
         if logits:
             return out.copy_(-(E0 + G))
         return softmax_neg_add(E0, G, out=out)
+    return out
+
+
+NCHW_PRODUCT, NCHW_UNIFORM, NCHW_SOFTMAX, NCHW_LOGITS = 0, 1, 2, 3       # enum phl_nchw_mode
+NCHW_PRODUCT_MAX_L, NCHW_UNIFORM_MAX_L = 256, 1024
+
+
+def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=None):
+    """The non-W half of a CRFasRNN iteration on channel-major tensors, one kernel (phl_nchw_softmax_compat):
+    ``out[:, c] = sum_a Mu[a, c] * softmax(-(E0 + G), dim=1)[:, a]`` for fp32 CUDA E0, G [B, L, H, W] (or [B, L, n]; G
+    optional) and Mu [L, L] in the _compat_matrix convention; Q and E never exist in memory.  Inputs that are not
+    contiguous are made so.
+    Mu=None: ``out = softmax(-(E0 + G), dim=1)`` (the caller runs a compatibility module of its own on it).
+    uniform: (alpha, beta) = Mu is alpha * ones + beta * eye, the streaming form without a product (Mu may then be None);
+    None = look at Mu, once per Mu (_mu_forms: one device -> host read, not one per call); False = it is not.
+    logits=True: ``out = -(E0 + G)``, CRFasRNN's return value; G is required, Mu is not read.
+    out: a contiguous fp32 tensor of E0's shape, returned.  Raises PhlError with the library's status: 1 for out aliasing
+    E0 or G, 7 for more than 256 labels with a general Mu or more than 1024 with a uniform one."""
+    for t in (E0,) + (() if G is None else (G,)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise TypeError(f"nchw_softmax_compat: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on "
+                            f"{getattr(t, 'device', '?')}")
+    if E0.dim() not in (3, 4) or (G is not None and (G.shape != E0.shape or G.device != E0.device)):
+        raise ValueError("nchw_softmax_compat: E0 [B, L, H, W] or [B, L, n] and G of the same shape and device")
+    B, L = int(E0.shape[0]), int(E0.shape[1])
+    n = int(E0[0, 0].numel()) if B and L else 0
+    dev = E0.device
+    if out is None:
+        out = torch.empty(E0.shape, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == E0.shape
+              and out.device == dev):
+        raise TypeError("nchw_softmax_compat: out must be a contiguous fp32 tensor of E0's shape and device")
+    if logits:
+        if G is None:
+            raise ValueError("nchw_softmax_compat: logits=True needs G")
+        mode, M, ab = NCHW_LOGITS, None, (0.0, 0.0)
+    else:
+        if Mu is not None and (not torch.is_tensor(Mu) or tuple(Mu.shape) != (L, L)):
+            raise ValueError(f"nchw_softmax_compat: Mu must be an [L, L] = [{L}, {L}] tensor")
+        if uniform is None and Mu is not None and L <= NCHW_UNIFORM_MAX_L:
+            uniform = _mu_forms(Mu).uniform()
+        if uniform:
+            mode, M, ab = NCHW_UNIFORM, None, (float(uniform[0]), float(uniform[1]))
+        elif Mu is None:
+            mode, M, ab = NCHW_SOFTMAX, None, (0.0, 0.0)
+        else:
+            mode, M, ab = NCHW_PRODUCT, _mu_forms(Mu).dense(dev), (0.0, 0.0)
+    e, g = E0.contiguous(), None if G is None else G.contiguous()        # (named: a copy must outlive the launch)
+    _launch(dev, "phl_nchw_softmax_compat", _ptr(e), _ptr(g), _ptr(M), C.c_float(ab[0]), C.c_float(ab[1]), _ptr(out), B, L, n, mode)
     return out
 
 

@@ -292,6 +292,30 @@ int phl_compat_softmax_split(const float *E0_dev, int64_t e0_row_stride, const f
 int phl_uniform_compat_softmax(const float *E0_dev, int64_t e0_row_stride, const float *X_dev, int64_t x_row_stride,
                                float alpha, float beta, float *out_dev, int64_t out_row_stride, int64_t n, int L,
                                unsigned flags, phl_stream stream);
+/* ---- the same half of the iteration for channel-major (NCHW) data: CRFasRNN with a W that is not the lattice ----
+ * CRFasRNN evaluates W(Mu(Q)) on [B, L, H, W] tensors (crf/crf_module.py:66-79, 97-103), so what lies between two W
+ * calls is the dual of phl_compat_softmax -- softmax first, then the product -- in one kernel:
+ *   PHL_NCHW_PRODUCT   out[b,c,p] = sum_a mu[a*L + c] * softmax_a(-(E0[b,a,p] + G[b,a,p]))
+ *                      mu is the dense [L][L] matrix itself (row stride L, NOT transposed; a scale such as charb's exp(s)
+ *                      already inside).  1 <= L <= 256.  The softmax is max-subtracted (expf, one 1.0f / s per pixel) over
+ *                      an LDS-staged [L][64 pixels] block; the product is an f32 fma chain in a order, on the f32-input
+ *                      matrix cores above 32 labels and on the vector unit up to 32.
+ *   PHL_NCHW_UNIFORM   mu = alpha*J + beta*I (the Potts family; `potts` is alpha = 1, beta = -1, crf_module.py:55-64):
+ *                      out = alpha * colsum(Q) + beta * Q, the column sum computed; one streaming pass, no product.
+ *                      L <= 1024.  mu is ignored.
+ *   PHL_NCHW_SOFTMAX   out = Q: for a compatibility module that is not a matrix (the caller runs it on Q).  Any L >= 1.
+ *   PHL_NCHW_LOGITS    out = -(E0 + G): what CRFasRNN returns after the last iteration (:103).  G is required.  Any L >= 1.
+ * E0, G, out: contiguous fp32 [B][L][n] on the device, n = H*W; G may be NULL except for the logits (the first step of
+ * the loop is Q = softmax(-E0)).  Any n: float4 accesses along the pixel axis when n % 4 == 0 and E0 / G / out are
+ * 16-byte aligned, dwords otherwise.  alpha / beta are read in uniform mode only.  No atomics: the same bits on every
+ * run.  Status, checked before any HIP call: PHL_ERR_INVALID for negative sizes, L < 1, an unknown mode or non-finite
+ * alpha / beta in uniform mode; then zero elements (B == 0 or n == 0) are PHL_OK with nothing launched; then
+ * PHL_ERR_INVALID for NULL E0 / out, NULL mu in product mode, NULL G in logits mode or out aliasing E0 or G;
+ * PHL_ERR_TOO_LARGE when B*L*n*4 bytes leave int64 or the workgroups (64 pixels each; 256 above 256 labels) leave
+ * 2^31 - 1; PHL_ERR_UNSUPPORTED for L outside the mode's range (the caller keeps its torch ops). */
+enum phl_nchw_mode { PHL_NCHW_PRODUCT = 0, PHL_NCHW_UNIFORM = 1, PHL_NCHW_SOFTMAX = 2, PHL_NCHW_LOGITS = 3 };
+int phl_nchw_softmax_compat(const float *E0_dev, const float *G_dev, const float *mu_dev, float alpha, float beta,
+                            float *out_dev, int B, int L, int64_t n, int mode, phl_stream stream);
 /* ---- backward of the compatibility + softmax step (CRF training) ---------------------------------------------
  * Forward: Q = softmax(-E), E = E0 + X Mu.  With the upstream gradient gQ: dE = Q (s - gQ), s[p] = sum_c gQ[p,c] Q[p,c];
  * gE0 = dE, gX = dE Mu^T, gMu = X^T dE.  All entry points: fp32 rows with unit channel stride, row strides % 4 == 0,
