@@ -284,12 +284,14 @@ def _mean_field_nchw(E0, message, niters):
 _NCHW_STEP = os.environ.get("PHL_NCHW_STEP", "1") not in ("", "0")
 
 
-def _mean_field_nchw_step_fused(E0, refs, W, M, niters):
+def _mean_field_nchw_step_fused(E0, refs, W, M, niters, expect=False, values=None):
     """The same iteration for any other W (the default guided filter), without autograd, in the reference's order
     E = E0 + W(Mu(Q)) (crf_module.py:97-99): everything between two W calls -- the add, the negation, the softmax over
     the label channels and the compatibility product -- is ONE channel-major kernel (phl.nchw_softmax_compat), so Q and E
     never exist in memory and nothing is transposed.  W is called once per iteration as the module it is, on whatever
-    engine it picks.  M: _compat_matrix of the Mu module.  Gives the logits -E of the last iteration."""
+    engine it picks.  M: _compat_matrix of the Mu module.  Gives the logits -E of the last iteration -- or, with
+    ``expect``, their expected label [B, 1, H, W] under ``values`` (None: 0 .. L-1) straight from E0 and G
+    (phl.nchw_expected_value), the logits never written."""
     import phl
 
     uniform = (phl._mu_uniform(M) or False) if M.shape[0] <= phl.NCHW_UNIFORM_MAX_L else False   # one read per forward
@@ -297,6 +299,8 @@ def _mean_field_nchw_step_fused(E0, refs, W, M, niters):
     for it in range(niters):
         G = W(Y, refs)
         if it == niters - 1:
+            if expect:
+                return phl.nchw_expected_value(E0, G, values, negate=True)
             return phl.nchw_softmax_compat(E0, G, logits=True)
         Y = phl.nchw_softmax_compat(E0, G, M, uniform=uniform, out=Y)
 
@@ -310,6 +314,21 @@ def _nchw_step_matrix(mu, E0, labels):
     if M is not None and L > phl.NCHW_PRODUCT_MAX_L and not phl._mu_uniform(M):
         return None
     return M
+
+
+def _expect_routable(logits, labels):
+    """What phl.nchw_expected_value computes in place of ``(softmax(logits, 1) * labels).sum(1, keepdim=True)``: fp32 CUDA
+    [B, L, H, W] logits, L >= 1, and labels that are None or a fp32 tensor on the logits' device with one value per label
+    channel ([1, L, 1, 1] or [L, 1, 1]) that asks for no gradient.  PHL_NCHW_STEP=0 switches it off with the step."""
+    if not (_NCHW_STEP and torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 4
+            and logits.shape[1] >= 1):
+        return False
+    if labels is None:
+        return True
+    L = logits.shape[1]
+    return (torch.is_tensor(labels) and labels.dtype == torch.float32 and labels.device == logits.device
+            and labels.dim() in (3, 4) and tuple(labels.shape[-3:]) == (L, 1, 1) and labels.numel() == L
+            and not labels.requires_grad)
 
 
 _nchw_streams = {}
@@ -403,6 +422,8 @@ class CRFasRNN(nn.Module):
     bias-free 1x1 conv: at most 256 labels, 1024 for the Potts family) runs _mean_field_nchw_step_fused: per iteration W
     and one channel-major kernel for everything else (phl.nchw_softmax_compat); PHL_NCHW_STEP=0 in the environment
     keeps the plain loop.  Anything else -- training, CPU tensors, float64, another Mu -- is the plain NCHW loop.
+    ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with: on
+    that route the loop's last call is phl.nchw_expected_value on E0 and G, and the logits are never written.
     ``fused_grad=True`` keeps W on the library's kernels under autograd: the lattice W through _mean_field_nchw_grad, the
     guided W through phl.GuidedFilterFn inside the plain NCHW loop (Mu and the softmax stay torch ops there)."""
 
@@ -420,6 +441,25 @@ class CRFasRNN(nn.Module):
 
     def forward(self, refs, logits, confidence=None, labels=None):
         """refs [B, C, H, W], logits [B, L, H, W]."""
+        return self._run(refs, logits, confidence, labels)[0]
+
+    def expected_depth(self, refs, logits, confidence=None, labels=None, values=None):
+        """``logits2average_depth(self(refs, logits, confidence, labels), values)`` [B, 1, H, W]: the expected value under
+        the softmax of the returned logits.  values: None = 0 .. L-1, a tensor with one value per label ([L] or
+        [1, L, 1, 1]), or anything ``probs * values`` broadcasts.  A tensor of fewer than four dimensions with exactly L
+        elements always means one value per label -- also a [W] tensor when W == L, which ``probs * values`` alone would
+        spread along the width; hand such values over as [1, 1, 1, W].  Where forward takes _mean_field_nchw_step_fused,
+        the loop itself ends with the expected value; everything else goes through forward."""
+        from crf.mb_stereo_crf import logits2average_depth
+
+        if torch.is_tensor(values) and values.dim() != 4 and values.numel() == logits.shape[1]:
+            values = values.reshape(1, -1, 1, 1)
+        out, done = self._run(refs, logits, confidence, labels, expect=_expect_routable(logits, values), values=values)
+        return out if done else logits2average_depth(out, values)
+
+    def _run(self, refs, logits, confidence, labels, expect=False, values=None):
+        """(forward's logits, False) -- or, with ``expect`` on the _mean_field_nchw_step_fused route, (their expected label
+        under ``values``, True)."""
         E0 = -logits if confidence is None else -logits * confidence
         extra = () if labels is None else (labels,)
         if isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda and E0.dtype == torch.float32:
@@ -428,19 +468,20 @@ class CRFasRNN(nn.Module):
             if not grad:
                 M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device)
                 if M is not None:
-                    return _mean_field_nchw_fused(E0.contiguous(), refs, M, self.niters)      # already -E
+                    return _mean_field_nchw_fused(E0.contiguous(), refs, M, self.niters), False   # already -E
             elif self.fused_grad and refs.is_cuda and refs.dtype == torch.float32 and _label_pad(E0.shape[1]) <= 512:
                 M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device, detach=False)
                 if M is not None:
-                    return _mean_field_nchw_grad(E0, refs, M, self.niters)                    # already -E
+                    return _mean_field_nchw_grad(E0, refs, M, self.niters), False                 # already -E
         elif (_NCHW_STEP and not isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda
               and E0.dtype == torch.float32 and E0.dim() == 4):
             params = list(self.Mu.parameters()) + list(self.W.parameters())
             grad = torch.is_grad_enabled() and (E0.requires_grad or refs.requires_grad or any(p.requires_grad for p in params))
             M = None if grad else _nchw_step_matrix(self.Mu, E0, labels)
             if M is not None:
-                return _mean_field_nchw_step_fused(E0.contiguous(), refs, self.W, M, self.niters)   # already -E
-        return -_mean_field_nchw(E0, lambda Q: self.W(self.Mu(Q, *extra), refs), self.niters)
+                out = _mean_field_nchw_step_fused(E0.contiguous(), refs, self.W, M, self.niters, expect, values)
+                return out, bool(expect)                                                  # already -E
+        return -_mean_field_nchw(E0, lambda Q: self.W(self.Mu(Q, *extra), refs), self.niters), False
 
 
 class ijGuide(nn.Module):

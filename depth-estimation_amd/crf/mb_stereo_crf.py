@@ -8,11 +8,22 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from crf import crf_module
 from crf.crf_module import CRFasRNN, charb
 
 
 def logits2average_depth(logits, labels=None):
-    """Expected label under softmax(logits): [bs, L, h, w] -> [bs, 1, h, w] (:62-66)."""
+    """Expected label under softmax(logits): [bs, L, h, w] -> [bs, 1, h, w] (:62-66).
+
+    fp32 CUDA logits with one label value per channel (crf_module._expect_routable) are one kernel that reads the logits
+    once (phl.nchw_expected_value; phl.NchwExpectedValue when the logits ask for a gradient).  Everything else -- CPU,
+    float64, labels per pixel or asking for a gradient, PHL_NCHW_STEP=0 -- is the torch lines below."""
+    if crf_module._expect_routable(logits, labels):
+        import phl
+
+        if torch.is_grad_enabled() and logits.requires_grad:
+            return phl.nchw_expected_value_fn(logits, None, labels, False)
+        return phl.nchw_expected_value(logits, labels=labels, negate=False)
     probs = F.softmax(logits, dim=1)
     if labels is None:
         labels = torch.arange(probs.shape[1], dtype=torch.float32, device=probs.device)[None, :, None, None]
@@ -46,7 +57,7 @@ class CRFdepthRefiner(nn.Module):
 
     def forward(self, inputs):
         logits, imgrgb, features = inputs
-        return logits2average_depth(self.CRF(self._guide(imgrgb, features), logits))
+        return self.CRF.expected_depth(self._guide(imgrgb, features), logits)
 
 
 class CRFwUncertainty(CRFdepthRefiner):
@@ -59,8 +70,7 @@ class CRFwUncertainty(CRFdepthRefiner):
     def forward(self, inputs):
         logits, imgrgb, features = inputs
         confidence = torch.exp(-self.uncertainty_net(imgrgb))
-        out = self.CRF(self._guide(imgrgb, features), logits, confidence)
-        return logits2average_depth(out), confidence
+        return self.CRF.expected_depth(self._guide(imgrgb, features), logits, confidence), confidence
 
 
 class CRFdepthUpsampler(nn.Module):
@@ -75,5 +85,4 @@ class CRFdepthUpsampler(nn.Module):
         labels = torch.linspace(0, float(up.max()), 18, device=up.device)
         logits = -10 * self.CRF.Mu.get_energies_from_scalar(up, labels[None, :, None, None])
         confidence = (up > 1e-2).float()
-        out = self.CRF(img_highres, logits, confidence=confidence, labels=labels)
-        return logits2average_depth(out, labels[None, :, None, None])
+        return self.CRF.expected_depth(img_highres, logits, confidence=confidence, labels=labels, values=labels)

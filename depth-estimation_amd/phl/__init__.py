@@ -104,6 +104,9 @@ def load_library():
             lib.phl_compat_softmax_split.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, u32, vp]
         if hasattr(lib, "phl_nchw_softmax_compat"):    # (an older build loaded through PHL_LIB lacks the NCHW step)
             lib.phl_nchw_softmax_compat.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, i32, i32, i64, i32, vp]
+        if hasattr(lib, "phl_nchw_expected_value"):    # (an older build loaded through PHL_LIB lacks the expected label)
+            lib.phl_nchw_expected_value.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, vp]
+            lib.phl_nchw_expected_value_grad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]
         if hasattr(lib, "phl_compat_grad_x"):          # (an older build loaded through PHL_LIB lacks the backward)
             lib.phl_softmax_neg_grad.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, vp]
             lib.phl_uniform_compat_grad.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, vp, i64, vp, i64, i64, i32, vp]
@@ -765,6 +768,85 @@ def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=
     e, g = E0.contiguous(), None if G is None else G.contiguous()        # (named: a copy must outlive the launch)
     _launch(dev, "phl_nchw_softmax_compat", _ptr(e), _ptr(g), _ptr(M), C.c_float(ab[0]), C.c_float(ab[1]), _ptr(out), B, L, n, mode)
     return out
+
+
+NCHW_EXPECT_PIXELS = 1024            # PHL_NCHW_EXPECT_PIXELS: pixels of a workgroup of the expected-label kernels
+
+
+def _expect_operands(name, X, G, labels):
+    """(X, G contiguous, labels as fp32 [L] on X's device or None, B, L, n) of the expected-label entry points."""
+    for t in (X,) + (() if G is None else (G,)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise TypeError(f"{name}: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+    if X.dim() not in (3, 4) or (G is not None and (G.shape != X.shape or G.device != X.device)):
+        raise ValueError(f"{name}: X [B, L, H, W] or [B, L, n] and G of the same shape and device")
+    B, L = int(X.shape[0]), int(X.shape[1])
+    n = int(X[0, 0].numel()) if B and L else 0
+    if labels is not None:
+        labels = torch.as_tensor(labels)
+        if labels.numel() != L:
+            raise ValueError(f"{name}: labels must hold one value per label channel ({L}), got shape {tuple(labels.shape)}")
+        labels = labels.detach().reshape(L).to(X.device, torch.float32).contiguous()
+    return X.contiguous(), None if G is None else G.contiguous(), labels, B, L, n
+
+
+def nchw_expected_value(X, G=None, labels=None, *, negate=False, out=None):
+    """The expected label of channel-major columns, one kernel (phl_nchw_expected_value):
+    ``(softmax(sign * (X + G), dim=1) * labels[None, :, None, None]).sum(1, keepdim=True)``, sign = -1 with ``negate``
+    (the mean-field loop's E0 and G) and +1 without (plain logits), for fp32 CUDA X, G [B, L, H, W] -> [B, 1, H, W] (or
+    [B, L, n] -> [B, 1, n]; G optional).  X and G are read once; neither the probabilities nor the logits are written.
+    Any L >= 1.  Inputs that are not contiguous are made so.
+    labels: None = 0, 1, .., L-1; else [L] or anything with L elements ([1, L, 1, 1]), converted to fp32 on X's device;
+    anything else (labels per pixel) is a ValueError.  out: a contiguous fp32 tensor of the result's shape, returned."""
+    x, g, lab, B, L, n = _expect_operands("nchw_expected_value", X, G, labels)
+    shape = (B, 1) + tuple(X.shape[2:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=X.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
+              and tuple(out.shape) == shape and out.device == X.device):
+        raise TypeError(f"nchw_expected_value: out must be a contiguous fp32 tensor of shape {shape} on X's device")
+    _launch(X.device, "phl_nchw_expected_value", _ptr(x), _ptr(g), _ptr(lab), _ptr(out), B, L, n, 1 if negate else 0)
+    return out
+
+
+def nchw_expected_value_grad(X, G, labels, gout, *, negate=False):
+    """gZ = sign * gout * q * (labels - d) with q = softmax(sign * (X + G), dim=1) and d = nchw_expected_value(X, G,
+    labels): the gradient of X and of G alike, of X's shape (phl_nchw_expected_value_grad).  gout: the upstream gradient,
+    fp32 CUDA with one element per pixel ([B, 1, H, W]).  Only X, G and the labels are read: the column's statistics are
+    recomputed.  Same bits on every call."""
+    x, g, lab, B, L, n = _expect_operands("nchw_expected_value_grad", X, G, labels)
+    if not (torch.is_tensor(gout) and gout.is_cuda and gout.dtype == torch.float32 and gout.device == X.device):
+        raise TypeError("nchw_expected_value_grad: gout must be a fp32 CUDA tensor on X's device")
+    if gout.numel() != B * n:
+        raise ValueError(f"nchw_expected_value_grad: gout must hold one value per pixel ({B} x {n}), got {tuple(gout.shape)}")
+    go = gout.contiguous()
+    gZ = torch.empty(X.shape, dtype=torch.float32, device=X.device)
+    _launch(X.device, "phl_nchw_expected_value_grad", _ptr(x), _ptr(g), _ptr(lab), _ptr(go), _ptr(gZ), B, L, n, 1 if negate else 0)
+    return gZ
+
+
+class NchwExpectedValue(torch.autograd.Function):
+    """``nchw_expected_value(X, G, labels, negate=negate)`` with its backward on phl_nchw_expected_value_grad.  Saves X, G
+    and the labels, nothing the forward computed.  X and G get the same gradient (one tensor, computed when either asks);
+    the labels get none."""
+
+    @staticmethod
+    def forward(ctx, X, G=None, labels=None, negate=False):
+        ctx.negate = bool(negate)
+        labels = None if labels is None else torch.as_tensor(labels)
+        ctx.save_for_backward(X, G, labels)
+        return nchw_expected_value(X, G, labels, negate=negate)
+
+    @staticmethod
+    def backward(ctx, g):
+        X, G, labels = ctx.saved_tensors
+        gZ = nchw_expected_value_grad(X, G, labels, g, negate=ctx.negate) if any(ctx.needs_input_grad[:2]) else None
+        return (gZ if ctx.needs_input_grad[0] else None), (gZ if ctx.needs_input_grad[1] else None), None, None
+
+
+def nchw_expected_value_fn(X, G=None, labels=None, negate=False):
+    """Differentiable ``nchw_expected_value``: NchwExpectedValue.apply(X, G, labels, negate)."""
+    return NchwExpectedValue.apply(X, G, labels, negate)
 
 
 # ---------------------------------------------------------------------------------------------

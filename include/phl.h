@@ -316,6 +316,30 @@ int phl_uniform_compat_softmax(const float *E0_dev, int64_t e0_row_stride, const
 enum phl_nchw_mode { PHL_NCHW_PRODUCT = 0, PHL_NCHW_UNIFORM = 1, PHL_NCHW_SOFTMAX = 2, PHL_NCHW_LOGITS = 3 };
 int phl_nchw_softmax_compat(const float *E0_dev, const float *G_dev, const float *mu_dev, float alpha, float beta,
                             float *out_dev, int B, int L, int64_t n, int mode, phl_stream stream);
+/* ---- the expected label of a channel-major column: the end of the CRFasRNN heads (crf/mb_stereo_crf.py) -----------
+ * Every head finishes with logits2average_depth(CRF(...)): a softmax over the label channels, a broadcast product with
+ * the labels and a sum.  Here that is one kernel, and with negate != 0 it takes the loop's E0 and G as they are, so the
+ * logits of the last iteration are never written:
+ *   out[b, p] = sum_a labels[a] * softmax_a( sign * (X[b,a,p] + G[b,a,p]) ),   sign = negate ? -1 : +1
+ * X, G: contiguous fp32 [B][L][n] on the device (G may be NULL), labels fp32 [L] on the device or NULL for 0, 1, ..,
+ * L-1, out [B][n].  Any L >= 1, any n, any B.  A thread owns four pixels and walks the label planes once, eight planes
+ * in flight, with a running maximum, sum and label-weighted sum per pixel (rescaled once per eight planes when the
+ * maximum rises; the arithmetic between the fp32 loads and stores is float64); it ends with one division per pixel.
+ * float4 accesses along the pixel axis when n % 4 == 0 and X / G / out are 16-byte aligned, dwords otherwise.  No LDS,
+ * no atomics, a fixed label order: the same bits on every run.
+ * phl_nchw_expected_value_grad: with z = sign * (X + G), q = softmax(z), d = sum_a labels[a] q_a and the upstream
+ * gradient gout [B][n]:   gZ[b,a,p] = sign * gout[b,p] * q_a * (labels[a] - d)   -- the gradient of X and of G alike,
+ * [B][L][n].  Nothing but the forward's inputs is needed: the kernel recomputes the column's maximum, sum and d (the
+ * forward's code) and then reads X and G a second time to write gZ.  There is no gradient for the labels.
+ * Status, checked before any HIP call: PHL_ERR_INVALID for negative sizes or L < 1; then zero elements (B == 0 or
+ * n == 0) are PHL_OK with nothing launched; then PHL_ERR_INVALID for NULL X / out (gout / gZ) or an output that is one
+ * of the inputs; PHL_ERR_TOO_LARGE when B*L*n*4 bytes leave int64 or the workgroups (PHL_NCHW_EXPECT_PIXELS pixels
+ * each) leave 2^31 - 1.  Every label count is taken: there is no PHL_ERR_UNSUPPORTED. */
+#define PHL_NCHW_EXPECT_PIXELS 1024
+int phl_nchw_expected_value(const float *X_dev, const float *G_dev, const float *labels_dev, float *out_dev, int B, int L,
+                            int64_t n, int negate, phl_stream stream);
+int phl_nchw_expected_value_grad(const float *X_dev, const float *G_dev, const float *labels_dev, const float *gout_dev,
+                                 float *gZ_dev, int B, int L, int64_t n, int negate, phl_stream stream);
 /* ---- backward of the compatibility + softmax step (CRF training) ---------------------------------------------
  * Forward: Q = softmax(-E), E = E0 + X Mu.  With the upstream gradient gQ: dE = Q (s - gQ), s[p] = sum_c gQ[p,c] Q[p,c];
  * gE0 = dE, gX = dE Mu^T, gMu = X^T dE.  All entry points: fp32 rows with unit channel stride, row strides % 4 == 0,
