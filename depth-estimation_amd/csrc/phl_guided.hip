@@ -41,6 +41,7 @@ constexpr int SR = 64;               // rows per strip of the streamed form
 constexpr int GRP = 4;              // coefficient planes per pass of k_guide_apply
 constexpr size_t kMaxLds = 160 << 10;
 constexpr size_t kChunkBytes = (size_t)96 << 20;
+constexpr int kGradParts = 3;        // fp64 planes per (label, channel) that the backward sums over labels (NPART below)
 
 __host__ __device__ inline int halo_rows(int r) { return TH + 2 * r; }
 __host__ __device__ inline int halo_stride(int r) { return (TW + 2 * r) | 1; }   // odd: lanes across rows, distinct banks
@@ -432,6 +433,13 @@ struct Plan {
     dim3 grid(unsigned nz) const { return dim3(tiles.x, tiles.y, nz); }
     // labels per chunk: the per-label planes of a chunk (`per` bytes a label) stay within kChunkBytes (and gridDim.y / z)
     static int64_t chunk(int64_t nimg, int64_t per) { return max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per)); }
+    // `per` of the forward (the cx + 1 coefficient planes) and of the backward (ys unless full resolution, P and Q, A and
+    // mA for grad_x, the NPART fp64 terms for grad_x / grad_eps): run(), run_grad() and the query below all come here
+    static int64_t per_forward(int cx, int64_t hw) { return (int64_t)(cx + 1) * hw * (int64_t)sizeof(float); }
+    static int64_t per_backward(int cx, int64_t hw, bool full, bool need_x, bool need_xe)
+    {
+        return hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * kGradParts * cx : 0));
+    }
 };
 
 int run(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h, int w, int re,
@@ -447,7 +455,7 @@ int run(const float *y, const float *x, const float *src, float *out, int B, int
     if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
     if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
 
-    const int64_t chunk = Plan::chunk(nimg, (int64_t)(cx + 1) * hw * (int64_t)sizeof(float));
+    const int64_t chunk = Plan::chunk(nimg, Plan::per_forward(cx, hw));
     const size_t nstat = (size_t)B * cx * hw;
     phl_temps tmp(st);
     double *mx = tmp.get<double>(nstat);
@@ -495,7 +503,7 @@ int run(const float *y, const float *x, const float *src, float *out, int B, int
 // No atomics anywhere; every gradient is rounded to fp32 once.
 constexpr int NE = 256;             // threads of the pointwise kernels
 constexpr int NEB = 128;            // first-stage workgroups per channel of the grad_eps reduction
-enum { PART_VAR = 0, PART_MX = 1, PART_YU = 2, NPART = 3 };
+enum { PART_VAR = 0, PART_MX = 1, PART_YU = 2, NPART = kGradParts };
 
 __global__ __launch_bounds__(NE) void k_grad_gather(const float *__restrict__ src, float *__restrict__ dst,
                                                    const int *__restrict__ rmap, const int *__restrict__ cmap, int H, int W, int h,
@@ -761,8 +769,7 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
     if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
     if (int rc = phl_allow_lds(gxk, p.lds_apply)) return rc;
 
-    const int64_t per = hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * NPART * cx : 0));
-    const int64_t chunk = Plan::chunk(nimg, per);
+    const int64_t chunk = Plan::chunk(nimg, Plan::per_backward(cx, hw, full, need_x, need_xe));
     const size_t nstat = (size_t)B * cx * hw;
     phl_temps tmp(st);
     double *mx = tmp.get<double>(nstat);
@@ -858,6 +865,14 @@ int phl_guided_filter_max_r(void)
     int r = 0;
     while (fits_tiled(r + 1)) r++;
     return r;
+}
+
+int phl_guided_filter_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs)
+{
+    if (B < 1 || cy < 1 || cx < 1 || h < 1 || w < 1 || needs < -1 || needs > 7) return 0;
+    const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
+    const bool need_x = (needs & 2) != 0, need_xe = (needs & 6) != 0;
+    return (int)Plan::chunk(nimg, needs < 0 ? Plan::per_forward(cx, hw) : Plan::per_backward(cx, hw, full != 0, need_x, need_xe));
 }
 
 int phl_guided_filter(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h, int w,

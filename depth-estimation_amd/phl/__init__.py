@@ -122,6 +122,8 @@ def load_library():
             lib.phl_guided_filter.argtypes = [vp, vp, vp, vp] + [i32] * 8 + [vp, vp, vp, vp, vp, C.c_float, vp]
         if hasattr(lib, "phl_guided_filter_grad"):     # (an older build loaded through PHL_LIB lacks its backward)
             lib.phl_guided_filter_grad.argtypes = [vp] * 6 + [i32] * 8 + [vp, vp, vp, vp, vp, C.c_float, i32, vp]
+        if hasattr(lib, "phl_guided_filter_labels_per_chunk"):     # (an older build loaded through PHL_LIB lacks the query)
+            lib.phl_guided_filter_labels_per_chunk.argtypes = [i32] * 7
         lib.phl_stream_copy.argtypes = [vp, vp, i64, vp]
         lib.phl_copy2d.argtypes = [vp, i64, i64, vp, i64, i64, i64, i32, vp]
         lib.phl_cost_volume.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
@@ -1183,6 +1185,17 @@ def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=No
     _launch(y.device, "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims, *(_ptr(m) for m in maps), _ptr(e),
             C.c_float(float(scale)))
     return out
+
+
+def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False, need_x=False, need_eps=False, grad=None):
+    """Labels (of the B * cy planes of y) that one chunk of a guided_filter call holds at the solving resolution h x w,
+    or, with any ``need_*`` flag or ``grad=True``, of the guided_filter_grad call that is asked for those gradients
+    (``full``: subsample == 1).  Host arithmetic of the library (phl_guided_filter_labels_per_chunk), no device needed."""
+    needs = (1 if need_y else 0) | (2 if need_x else 0) | (4 if need_eps else 0)
+    if grad is None:
+        grad = needs != 0
+    return int(load_library().phl_guided_filter_labels_per_chunk(int(B), int(cy), int(cx), int(h), int(w), 1 if full else 0,
+                                                                 needs if grad else -1))
 
 
 def _guided_launch_args(name, y, x, third, third_name, r, eps, subsample, launch=True):

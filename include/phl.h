@@ -434,6 +434,12 @@ int phl_guided_filter(const float *y_dev, const float *x_dev, const float *src_d
                       int W, int h, int w, int r, const int *row_of_low_dev, const int *col_of_low_dev, const int *low_of_row_dev,
                       const int *low_of_col_dev, const float *eps_dev, float scale, phl_stream stream);
 int phl_guided_filter_max_r(void);   /* largest window radius (at the solving resolution) of the LDS-tiled form */
+/* Labels (planes of y) per chunk of a call: the labels B * cy are processed in chunks whose per-label temporaries stay
+ * within a fixed budget.  h x w is the solving resolution; needs = -1 asks for phl_guided_filter, otherwise for
+ * phl_guided_filter_grad with the bit mask 1 = grad_y, 2 = grad_x, 4 = grad_eps, and full != 0 for h x w = H x W (the
+ * forward ignores it).  Host arithmetic only, no HIP call; the same function sizes the chunks of the two entry points.
+ * 0 for sizes below 1 or another needs. */
+int phl_guided_filter_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs);
 
 /* Backward of phl_guided_filter with src = NULL (subtract_is_y = 0) or src = y (subtract_is_y != 0): g [B][cy][H][W] is the
  * gradient of out; grad_y [B][cy][H][W], grad_x [B][cx][H][W] and grad_eps [cx] are written (never accumulated into), each

@@ -82,12 +82,21 @@ def spy(grad=False):
             setattr(mod, name, real[key])
 
 
-def report(name, hip, t32, want, factor=1, what="out"):
+def report(name, hip, t32, want, factor=1, what="out", min_torch_u=None):
+    """The accuracy rule e_hip <= factor * e_torch.  ``min_torch_u``: a precondition on the input, checked first -- the
+    fp32 torch form must err by at least that many u = 2^-24 * max|want|, or the rule judges nothing (a shape at which
+    fp32 prefix sums are exact leaves the kernel no room for its own roundings).  Returns (e_hip, e_torch, max|want|)."""
     e_hip = float((hip.double() - want).abs().max())
     e_torch = float((t32.double() - want).abs().max())
-    print(f"{name}: e_hip = {e_hip:.3e}  e_torch = {e_torch:.3e}  |{what}| <= {float(want.abs().max()):.4g}")
+    mag = float(want.abs().max())
+    print(f"{name}: e_hip = {e_hip:.3e}  e_torch = {e_torch:.3e}  |{what}| <= {mag:.4g}")
     assert torch.isfinite(hip).all()
+    if min_torch_u is not None:
+        u = 2.0 ** -24 * mag
+        print(f"{name}: e_hip = {e_hip / u:.2f} u  e_torch = {e_torch / u:.1f} u  (precondition: e_torch >= {min_torch_u} u)")
+        assert e_torch >= min_torch_u * u, ("precondition", name, e_torch / u)
     assert e_hip <= factor * e_torch, (name, e_hip, e_torch)
+    return e_hip, e_torch, mag
 
 
 def module(kind, cx, r, s, eps, **kw):
@@ -121,8 +130,9 @@ def _sweep_inputs(B, cy, cx, H, W, seed, noncontiguous, with_g):
     return y, x, g
 
 
-def sweep_case(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=False, use_out=False):
-    """The forward on the kernels against the fp32 and the float64 torch form."""
+def sweep_case(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=False, use_out=False, min_torch_u=None):
+    """The forward on the kernels against the fp32 and the float64 torch form (``min_torch_u``: report's precondition).
+    Returns the module, its inputs and the kernels' output."""
     import phl
 
     y, x, _ = _sweep_inputs(B, cy, cx, H, W, seed, noncontiguous, False)
@@ -142,11 +152,13 @@ def sweep_case(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=False, us
             t32 = m(y, x)
             want = m.double()(y.double(), x.double())
         m.float()
-    report(name, hip, t32, want)
+    report(name, hip, t32, want, min_torch_u=min_torch_u)
+    return {"name": name, "m": m, "y": y, "x": x, "hip": hip}
 
 
-def sweep_case_grad(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=False):
-    """The gradients of y, x and omega on the kernels against fp32 and float64 torch autograd."""
+def sweep_case_grad(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=False, min_torch_u=None):
+    """The gradients of y, x and omega on the kernels against fp32 and float64 torch autograd (``min_torch_u``: report's
+    precondition).  Returns the module (fp32, ``fused_grad`` off), its inputs and the kernels' gradients."""
     y, x, g = _sweep_inputs(B, cy, cx, H, W, seed, noncontiguous, True)
     name = f"{kind} B{B} cy{cy} cx{cx} {H}x{W} r{r} s{s} eps{eps:g}"
     m = module(kind, cx, r, s, eps, fused_grad=True).to(DEV)
@@ -159,4 +171,5 @@ def sweep_case_grad(kind, B, cy, cx, H, W, r, s, eps, seed=0, noncontiguous=Fals
     assert calls["hip"] == 0 and calls["hip_grad"] == 0 and calls["box_sum"] > 0
     want = grads(m.double(), y, x, g, torch.float64)
     for k, a, b, c in zip(("y", "x", "omega"), hip, t32, want):
-        report(f"{name} grad_{k}", a, b, c, what="grad")
+        report(f"{name} grad_{k}", a, b, c, what="grad", min_torch_u=min_torch_u)
+    return {"name": name, "m": m.float(), "y": y, "x": x, "g": g, "hip": hip}

@@ -18,11 +18,15 @@ pytestmark = pytest.mark.gpu
 
 LS = [1, 5, 16, 18, 33, 64, 231, 256]         # VALU product up to 32 labels, matrix cores above; odd and full tiles
 SIZES = [(7, 9), (13, 17), (16, 24)]         # n = 63 (one short tile, planes off the 16-byte grid), 221, 384 (aligned)
+# the float4 path (n % 4 == 0, 16-byte aligned bases) with a short last tile: n = 100 (a full tile + 36 pixels), 12 (one
+# short tile), 4 (one float4), 260 (four pixels past the streaming kernel's 256-pixel workgroup as well)
+VEC_SIZES = [(5, 20), (2, 6), (1, 4), (4, 65)]
 B = 2
+TP = 64                                      # pixels of a tile of k_nchw_tile
 PRODUCT, UNIFORM, SOFTMAX, LOGITS = 0, 1, 2, 3
 
 
-def _inputs(L, H, W, seed):
+def _inputs(L, H, W, seed, B=B):
     g = torch.Generator(device=DEV).manual_seed(seed)
     E0 = torch.rand((B, L, H, W), device=DEV, generator=g) * 30 - 5
     G = torch.randn((B, L, H, W), device=DEV, generator=g) * 5
@@ -144,6 +148,91 @@ def test_uniform_mode(L):
                 prod = phl.nchw_softmax_compat(E0, G, Mp, uniform=False)
             assert seen == [("phl_nchw_softmax_compat", PRODUCT)]
             _check_product(f"potts as a product L{L} {H}x{W}", prod, E0, G, Mp)
+
+
+def _on_float4_path(*tensors):
+    return all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0 and t[0, 0].numel() % 4 == 0) for t in tensors)
+
+
+@pytest.mark.parametrize("batch", [1, 2, 3])
+@pytest.mark.parametrize("L", [5, 18, 32, 33, 64, 231, 256])
+def test_product_parity_short_float4_tiles(L, batch):
+    import phl
+
+    for H, W in VEC_SIZES:
+        E0, G, Mu = _inputs(L, H, W, seed=L + W + batch, B=batch)
+        assert _on_float4_path(E0, G) and (H * W) % TP != 0
+        for g in (G, None):
+            with _launch_spy() as seen:
+                hip = phl.nchw_softmax_compat(E0, g, Mu)
+            assert seen == [("phl_nchw_softmax_compat", PRODUCT)] and _on_float4_path(hip)
+            _check_product(f"product L{L} B{batch} {H}x{W} G={'yes' if g is not None else 'none'}", hip, E0, g, Mu)
+
+
+@pytest.mark.parametrize("L", [5, 64, 300])                      # 300: the streaming kernel, a thread per pixel
+def test_uniform_and_softmax_short_float4_tiles(L):
+    import phl
+
+    for H, W in VEC_SIZES:
+        E0, G, _ = _inputs(L, H, W, seed=3 * L + W)
+        assert _on_float4_path(E0, G)
+        M64 = 0.3 * torch.ones((L, L), dtype=torch.float64, device=DEV) - 1.7 * torch.eye(L, dtype=torch.float64, device=DEV)
+        for g in (G, None):
+            name = f"L{L} {H}x{W} G={'yes' if g is not None else 'none'}"
+            with _launch_spy() as seen:
+                hip = phl.nchw_softmax_compat(E0, g, uniform=(0.3, -1.7))
+            assert seen == [("phl_nchw_softmax_compat", UNIFORM)]
+            _check_product("uniform (0.3, -1.7) " + name, hip, E0, g, M64.float(), M64)
+            with _launch_spy() as seen:
+                q = phl.nchw_softmax_compat(E0, g)
+            assert seen == [("phl_nchw_softmax_compat", SOFTMAX)]
+            want = F.softmax(-_energy(E0.double(), None if g is None else g.double()), 1)
+            err, colsum = float((q.double() - want).abs().max()), float((q.sum(1) - 1).abs().max())
+            print(f"softmax {name}: err = {err:.3e}  |colsum - 1| = {colsum:.3e}")
+            assert torch.isfinite(q).all() and err <= 2e-6 and colsum <= 1e-5
+
+
+def _shifted(t):
+    """A contiguous copy of t whose base lies 4 bytes past the 16-byte grid."""
+    buf = torch.zeros((t.numel() + 5,), device=DEV)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+@pytest.mark.parametrize("L", [18, 64])                          # VALU, matrix cores
+def test_dword_fallback_for_a_base_off_the_16_byte_grid(L):
+    """n % 4 == 0 with one of E0, G, out off the 16-byte grid takes the dword loads and stores; nothing else differs
+    between the two forms, so the bits are those of the aligned call."""
+    import phl
+
+    H, W = VEC_SIZES[0]
+    E0, G, Mu = _inputs(L, H, W, seed=L + 40)
+    want = phl.nchw_softmax_compat(E0, G, Mu)
+    assert _on_float4_path(E0, G, want)
+    assert torch.equal(phl.nchw_softmax_compat(_shifted(E0), G, Mu), want)
+    assert torch.equal(phl.nchw_softmax_compat(E0, _shifted(G), Mu), want)
+    out = _shifted(torch.full(E0.shape, float("nan"), device=DEV))
+    assert phl.nchw_softmax_compat(E0, G, Mu, out=out) is out and torch.equal(out, want)
+    _check_product(f"product L{L} {H}x{W}, out off the 16-byte grid", out, E0, G, Mu)
+
+
+@pytest.mark.parametrize("L", [18, 64])
+@pytest.mark.parametrize("H,W", VEC_SIZES[:2])
+def test_nothing_written_behind_out(H, W, L):
+    """``out`` as a view at the front of a larger buffer: a short last tile leaves the 4096 floats behind it alone."""
+    import phl
+
+    E0, G, Mu = _inputs(L, H, W, seed=L + 50)
+    want = phl.nchw_softmax_compat(E0, G, Mu)
+    sentinel, pad = -12345.5, 4096
+    buf = torch.full((E0.numel() + pad,), sentinel, device=DEV)
+    out = buf[:E0.numel()].view(E0.shape)
+    assert _on_float4_path(E0, G, out)
+    assert phl.nchw_softmax_compat(E0, G, Mu, out=out) is out
+    assert torch.equal(out, want)
+    assert torch.equal(buf[E0.numel():], torch.full((pad,), sentinel, device=DEV))
 
 
 def test_label_ranges():

@@ -102,6 +102,35 @@ def test_tiled_form_takes_the_default_radius():
     assert phl.load_library().phl_guided_filter_max_r() >= 20
 
 
+def test_labels_per_chunk_query():
+    """phl_guided_filter_labels_per_chunk against the formula of phl_guided.hip worked by hand: min(B * cy, 96 MiB / per),
+    per = 4 (cx + 1) hw bytes a label in the forward, hw (4 unless full + 8 (cx + 1) + 8 cx for grad_x + 24 cx for grad_x
+    or grad_eps) in the backward.  The GPU tests of the chunk loop ask this query, not a copy of the constant."""
+    import phl
+
+    q = phl.guided_filter_labels_per_chunk
+    budget = 96 << 20
+    assert budget == 100663296
+    assert q(1, 8, 1, 555, 695) == 8 == min(8, budget // 3085800)                     # the suite's large image: one chunk
+    assert q(1, 100, 1, 555, 695) == 32 and q(4, 25, 1, 555, 695) == 32
+    assert q(1, 8, 1, 555, 695, need_y=True, need_x=True, need_eps=True) == 5 == budget // (52 * 385725)
+    assert q(2, 50, 16, 128, 128) == 90 == budget // (17 * 4 * 16384)
+    assert q(2, 50, 16, 128, 128, full=True) == 90                                     # the forward ignores full
+    assert q(2, 50, 16, 128, 128, full=True, need_y=True, need_x=True, need_eps=True) == 9 == budget // (648 * 16384)
+    assert q(2, 50, 3, 128, 128, need_y=True, need_x=True, need_eps=True) == 46 == budget // (132 * 16384)
+    # the need flags change the bytes of a label: grad_y alone keeps P and Q only, grad_eps adds the fp64 terms
+    assert q(2, 50, 16, 128, 128, full=True, need_y=True) == 45 == budget // (136 * 16384)
+    assert q(2, 50, 16, 128, 128, full=True, need_eps=True) == 11 == budget // (520 * 16384)
+    assert q(2, 50, 16, 128, 128, full=True, need_y=True, need_eps=True) == 11
+    assert q(2, 50, 16, 128, 128, full=True, need_x=True) == 9
+    assert q(2, 50, 16, 128, 128, full=True, grad=True) == 45                          # a backward that is asked for nothing
+    # never fewer than one label, never more than a grid dimension; nothing for sizes below 1 or another mask
+    assert q(1, 3, 16, 8192, 8192) == 1 and q(1, 70000, 1, 1, 1) == 65535
+    lib = phl.load_library()
+    assert lib.phl_guided_filter_labels_per_chunk(0, 5, 1, 8, 8, 0, -1) == 0
+    assert lib.phl_guided_filter_labels_per_chunk(1, 5, 1, 8, 8, 0, 8) == 0 == lib.phl_guided_filter_labels_per_chunk(1, 5, 1, 8, 8, 0, -2)
+
+
 def test_guided_adjacency_keeps_fp32_for_an_fp32_guide():
     """GuidedAdjacency.__matmul__ casts U to its guide's dtype.  The constructor makes the guide fp32, so a float64 U is
     still filtered in fp32, as it was when the cast was a fixed .float(): same bits as the product of U.float()."""
