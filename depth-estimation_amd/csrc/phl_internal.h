@@ -287,10 +287,35 @@ std::mutex *phl_csr_mutex(phl_lattice *lat);
 int phl_add_vertices_device(phl_lattice *lat, const int16_t *keys_host, int64_t count, int32_t *vid_host, hipStream_t st);
 int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, void **scratch_out);
 
-// ---- implemented in phl_tiles.hip ----
+// ---- side streams for launches that are independent of their neighbours in a call (phl_api.hip) ----
+// A forked chain: work enqueued on stream() starts behind everything enqueued on `st` before fork(st), runs beside what
+// `st` gets afterwards, and join(st) makes `st` wait for it (event fork / join: legal inside a stream capture too, no
+// host synchronisation).  The guard is the only way to hold a slot of the pool: on any exit without a successful join
+// -- an early error return of the host function -- its destructor drains the side stream before the function's
+// temporaries are released and gives the slot back.
+struct phl_fork_slot;
+class phl_fork_guard {
+    phl_fork_slot *f = nullptr;
+
+public:
+    phl_fork_guard() = default;
+    phl_fork_guard(const phl_fork_guard &) = delete;
+    phl_fork_guard &operator=(const phl_fork_guard &) = delete;
+    ~phl_fork_guard();
+    bool fork(hipStream_t st);          // false: no slot to be had (the caller stays on `st`)
+    explicit operator bool() const { return f != nullptr; }
+    hipStream_t stream() const;         // the side stream; only while a slot is held
+    hipError_t join(hipStream_t st);    // success: the slot is given back; no slot held: nothing to do
+};
+
+// ---- the chunk build, implemented in phl_tiles_build.hip (once per lattice) ----
 int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, hipStream_t st);   // + renumbering, tables
 int phl_tiles_link_vertices(phl_lattice *lat, hipStream_t st);
 int phl_tiles_free(phl_lattice *lat);
+// a vertex fed by more chunks than this is listed in lat->vlong by the build and summed by k_splat_reduce_long
+constexpr int LONG_LIST = 24;
+
+// ---- the chunk kernels' planning and launchers, implemented in phl_tiles.hip (every filter call) ----
 int phl_tiles_lprs(const phl_lattice *lat, int vd, int for_slice);  // -1: LDS-staged path unavailable
 // wide splat (phl_filter_grad): block 0 = splat(src), block 1+k = splat(src (x) fref[:, k]); rows of nsets * vd floats
 struct phl_splat_wide {
@@ -307,7 +332,7 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
 int phl_launch_slice_grad(const phl_lattice *lat, const float *vertw, int L, const float *y, int64_t y_rs, const float *ref,
                           int64_t ref_rs, int64_t ref_cs, float *grad_ref, int accumulate, float *wx_out, int64_t wx_rs,
                           hipStream_t st);
-int phl_tiles_chunks_touching(phl_lattice *lat, const int64_t *rows_dev, int64_t k, int32_t *mask_host, hipStream_t st);
+int phl_tiles_chunks_touching(phl_lattice *lat, const int64_t *rows_dev, int64_t k, int32_t *mask_host, hipStream_t st);   // (phl_tiles_build.hip)
 int phl_launch_slice_tiled(const phl_lattice *lat, const float *vert, int vd, float *out, int64_t out_rs, const float *sub,
                            int64_t sub_rs, unsigned flags, hipStream_t st);
 

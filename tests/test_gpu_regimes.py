@@ -195,12 +195,10 @@ def test_randomised_mixtures_of_chunk_kinds(phl):
         assert scaled_err(lat.filter(s, no_tiles=True).cpu().numpy(), want) <= 1e-5
 
 
-def test_both_chunk_kernels_build_the_same_filter():
-    """k_chunk_masks (bit masks + popcounts, chunks with <= 256 local vertices) and k_chunk_group (radix passes, any
-    chunk; PHL_CHUNK_MASKS=0 sends every chunk through it) differ only in the order of a chunk's local vertex list --
-    what is summed, and in which order, does not depend on it: the filter's output must be the same bit for bit, in
-    the default arithmetic as well.  Fresh processes: the switch is read once."""
-    import hashlib
+def _mixed_image_child(body, **env):
+    """Runs `body` in a fresh process (the library's switches are read once) that holds the lattice L of
+    _mixed_image(256, 768, 30.0), a source `src` of 64 channels and sha(tensor); returns the fields of the RESULT line
+    the body prints."""
     import subprocess
 
     code = (
@@ -213,17 +211,44 @@ def test_both_chunk_kernels_build_the_same_filter():
         "ref = torch.from_numpy(np.ascontiguousarray(feat.reshape(-1, 5))).cuda()\n"
         "rng = np.random.default_rng(4)\n"
         "src = torch.from_numpy(rng.standard_normal((ref.shape[0], 64)).astype(np.float32)).cuda()\n"
+        "sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()\n"
         "L = phl.Lattice(ref)\n"
-        "st = L.tile_stats(64)\n"
-        "out = L.filter(src).cpu().numpy()\n"
-        "print('RESULT', st['max_local_vertices'], st['slots'], hashlib.sha256(out.tobytes()).hexdigest())\n")
+        "st = L.tile_stats(64)\n") + body
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = []
-    for masks in ("1", "0"):
-        env = dict(os.environ, PHL_CHUNK_MASKS=masks)
-        r = subprocess.run([sys.executable, "-c", code, root], env=env, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        line = [l for l in r.stdout.splitlines() if l.startswith("RESULT")][0].split()
-        res.append(line[1:])
+    r = subprocess.run([sys.executable, "-c", code, root], env=dict(os.environ, **env), capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return [l for l in r.stdout.splitlines() if l.startswith("RESULT")][0].split()[1:]
+
+
+def test_both_chunk_kernels_build_the_same_filter():
+    """k_chunk_masks (bit masks + popcounts, chunks with <= 256 local vertices) and k_chunk_group (radix passes, any
+    chunk; PHL_CHUNK_MASKS=0 sends every chunk through it) differ only in the order of a chunk's local vertex list --
+    what is summed, and in which order, does not depend on it: the filter's output must be the same bit for bit, in
+    the default arithmetic as well.  Fresh processes: the switch is read once."""
+    body = "print('RESULT', st['max_local_vertices'], st['slots'], sha(L.filter(src)))\n"
+    res = [_mixed_image_child(body, PHL_CHUNK_MASKS=masks) for masks in ("1", "0")]
     assert int(res[0][0]) > 384, "the image should hold chunks of all three kinds (<= 256, <= 384, more)"
     assert res[0] == res[1], res
+
+
+def test_side_stream_of_the_chunk_classes_changes_no_bit_and_is_given_back():
+    """The splat runs its small chunk classes on a pooled side stream beside the main grid (PHL_SIDE_CLASSES=0: one
+    launch behind the other on the caller's stream).  Same kernels, same launches, no atomics: the filter's output
+    must be the same bit for bit.  A call holds a slot of the pool only while it enqueues: 20 calls in a row on the
+    current stream -- more than the pool has slots (16) -- and one on a second stream all give that output."""
+    body = (
+        "out = L.filter(src)\n"
+        "runs = [L.filter(src) for _ in range(20)]\n"
+        "s2 = torch.cuda.Stream()\n"
+        "s2.wait_stream(torch.cuda.current_stream())\n"
+        "with torch.cuda.stream(s2):\n"
+        "    runs.append(L.filter(src))\n"
+        "s2.synchronize()\n"
+        "torch.cuda.synchronize()\n"
+        "same = sum(int(torch.equal(r.view(torch.int32), out.view(torch.int32))) for r in runs)\n"     # equal bits = equal digest
+        "print('RESULT', st['max_local_vertices'], sha(out), sha(runs[-1]), same)\n")
+    side, plain = [_mixed_image_child(body, PHL_SIDE_CLASSES=v) for v in ("1", "0")]
+    assert int(side[0]) > 384, "more than one chunk class is needed for the side stream to be taken"
+    assert side[1] == plain[1], (side, plain)
+    assert side[2] == side[1] and int(side[3]) == 21, side
