@@ -150,14 +150,15 @@ int launch_r(int R, const float *img1, const float *img2, int h, int w, int C, i
 extern "C" int phl_cost_volume(const float *img1, const float *img2, int h, int w, int channels, int max_disp, int window,
                                int criterion, float *out, int64_t out_rs, phl_stream stream)
 {
-    if (h < 1 || w < 1 || max_disp < 0 || !img1 || !img2 || (max_disp > 0 && !out) || out_rs < max_disp) {
-        phl_set_error("phl_cost_volume: bad arguments");
-        return PHL_ERR_INVALID;
-    }
+    // the supported set first: an image without channels has no data, and its NULL pointer is not the caller's mistake
     if (channels < 1 || channels > CMAX || window < 1 || window % 2 == 0 || window > 17 || criterion < 0 || criterion > 2) {
         phl_set_error("phl_cost_volume: supports 1..%d channels, odd windows up to 17, criterion 0 (AD) / 1 (SD) / 2 (nprod); got c=%d ws=%d crit=%d",
                       CMAX, channels, window, criterion);
         return PHL_ERR_UNSUPPORTED;
+    }
+    if (h < 1 || w < 1 || max_disp < 0 || !img1 || !img2 || (max_disp > 0 && !out) || out_rs < max_disp) {
+        phl_set_error("phl_cost_volume: bad arguments");
+        return PHL_ERR_INVALID;
     }
     if (max_disp == 0) return PHL_OK;
     const int R = window / 2;

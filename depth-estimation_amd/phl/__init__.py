@@ -1059,8 +1059,10 @@ def cost_volume(img1, img2, max_disp=None, window_size=9, criterion="AD", out=No
     img1/img2: [h, w, c] float tensors or numpy arrays; max_disp defaults to w // 6 (:40)."""
     _require_gpu()
     dev = img1.device if (torch.is_tensor(img1) and img1.is_cuda) else torch.device("cuda", torch.cuda.current_device())
-    a = torch.as_tensor(img1).to(device=dev, dtype=torch.float32).contiguous()
-    b = torch.as_tensor(img2).to(device=dev, dtype=torch.float32).contiguous()
+    # (numpy views with a negative stride -- a mirrored image, reversed channels -- are not tensors: copied first)
+    a, b = (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v for v in (img1, img2))
+    a = torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
+    b = torch.as_tensor(b).to(device=dev, dtype=torch.float32).contiguous()
     if a.dim() == 2:
         a, b = a[..., None], b[..., None]
     if a.shape != b.shape or a.dim() != 3:
