@@ -47,6 +47,35 @@ def disparity_energy_device(img1, img2, window_size=9, criterion=AD, max_disp=No
     return phl.cost_volume(img1, img2, max_disp=max_disp, window_size=window_size, criterion=criterion)
 
 
+def disparity_logits_device(img1, img2, window_size=1, criterion=AD, max_disp=None):
+    """The unary logits of the CRF heads, ``-disparity_badness`` as fp32 [1, L, H, W], computed on the GPU
+    (csrc/phl_costvol_nchw.hip) and left there: what ``planar_sweep_algorithm()(left, right)`` followed by the data
+    set's ``.permute(2, 0, 1)[None]`` gives (crf/dataloader.py:54-57, :83).  The default window is the reference's, 1."""
+    import phl
+
+    return phl.cost_volume_nchw(img1, img2, max_disp=max_disp, window_size=window_size, criterion=criterion, negate=True)
+
+
+def disparity_estimate_device(img1, img2, window_size=9, criterion=AD, max_disp=None):
+    """``disparity_estimate`` on the GPU: the winner-takes-all disparity as an int32 [H, W] CUDA tensor, without the
+    cost volume ever being written."""
+    import phl
+
+    return phl.disparity_wta(img1, img2, max_disp=max_disp, window_size=window_size, criterion=criterion)[0]
+
+
+def planar_sweep_algorithm(ws=1, criterion=AD, device=False):
+    """The unary algorithm of the reference's data set (crf/dataloader.py:54-57): a closure (left, right) ->
+    ``-1 * disparity_badness(left, right, ws, criterion)``, [h, w, L] numpy.  ``device=True``: the same logits from the
+    GPU, [1, L, H, W] (``disparity_logits_device``)."""
+    if device:
+        return lambda img_left, img_right: disparity_logits_device(img_left, img_right, ws, criterion)
+
+    def get_disp(img_left, img_right):
+        return -1 * disparity_badness(img_left, img_right, ws, criterion=criterion)
+    return get_disp
+
+
 # ---- small numpy / scipy helpers of the same module (crf/depth.py:10-22, :102-147), used by the notebooks
 # around the spectral-clustering experiments; nothing here touches the GPU path ---------------------------
 def normalized(img, window_shape=None):

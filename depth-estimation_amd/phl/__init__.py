@@ -127,6 +127,9 @@ def load_library():
         lib.phl_stream_copy.argtypes = [vp, vp, i64, vp]
         lib.phl_copy2d.argtypes = [vp, i64, i64, vp, i64, i64, i64, i32, vp]
         lib.phl_cost_volume.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
+        if hasattr(lib, "phl_cost_volume_nchw"):       # (an older build loaded through PHL_LIB lacks the channel-major sweep)
+            lib.phl_cost_volume_nchw.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, u32, vp, i64, i64, i64, vp]
+            lib.phl_disparity_wta.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, i64, i64, vp]
         lib.phl_get_keys.argtypes = [vp, vp]
         lib.phl_get_vertex_order.argtypes = [vp, vp]
         lib.phl_get_replay.argtypes = [vp, vp, vp]
@@ -1074,6 +1077,83 @@ def cost_volume(img1, img2, max_disp=None, window_size=9, criterion="AD", out=No
     assert res.shape == (h * w, L) and res.stride(1) == 1 and res.dtype == torch.float32
     _launch(dev, "phl_cost_volume", _ptr(a), _ptr(b), h, w, c, L, int(window_size), crit, _ptr(res), res.stride(0) if L else 0)
     return res
+
+
+COSTVOL_NEGATE = 1                   # PHL_COSTVOL_NEGATE
+COSTVOL_NCHW_TILE = (64, 8, 8)       # (PHL_COSTVOL_NCHW_TX, _TY, _DC): pixels in x, pixels in y, disparities of a workgroup
+
+
+def _sweep_views(name, img1, img2, channels_first):
+    """Both images of a sweep as [B, H, W, C] views of what the caller passed (no GPU needed): [H, W] / [H, W, C] arrays
+    or tensors are one pair, [B, C, H, W] tensors with ``channels_first``."""
+    def view(v):
+        t = torch.as_tensor(np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v)
+        if channels_first:
+            return t.permute(0, 2, 3, 1) if t.dim() == 4 else None
+        t = t[..., None] if t.dim() == 2 else t
+        return t[None] if t.dim() == 3 else None
+
+    a, b = view(img1), view(img2)
+    if a is None or b is None or a.shape != b.shape:
+        form = "[B, C, H, W]" if channels_first else "[H, W, C] or [H, W]"
+        raise ValueError(f"{name}: images must both be {form}, got {tuple(np.shape(img1))} and {tuple(np.shape(img2))}")
+    return a, b
+
+
+def _sweep_operands(a, b, dev):
+    """fp32 tensors on ``dev`` with one set of strides: an fp32 CUDA tensor stays where it is, whatever its strides; the
+    second image is copied into the first one's layout only if the two differ."""
+    a, b = a.to(device=dev, dtype=torch.float32), b.to(device=dev, dtype=torch.float32)
+    if any(n > 1 and sa != sb for n, sa, sb in zip(a.shape, a.stride(), b.stride())):
+        b = torch.empty_strided(a.shape, a.stride(), dtype=torch.float32, device=dev).copy_(b)
+    return a, b, tuple(int(v) for v in a.shape), tuple(int(s) for s in a.stride())
+
+
+def _sweep_device(img1):
+    _require_gpu()
+    return img1.device if (torch.is_tensor(img1) and img1.is_cuda) else torch.device("cuda", torch.cuda.current_device())
+
+
+def cost_volume_nchw(img1, img2, max_disp=None, window_size=9, criterion="AD", negate=False, out=None, channels_first=False):
+    """The cost volume of ``cost_volume`` in the channel-major layout of CRFasRNN and the heads: fp32 [B, L, H, W], written
+    once (csrc/phl_costvol_nchw.hip).  ``negate=True`` gives the reference's unary logits, ``-1 * disparity_badness``
+    permuted to [L, H, W] (crf/dataloader.py:54-57,83).  Images: [H, W, C] / [H, W] numpy or torch (B = 1), or
+    [B, C, H, W] torch tensors with ``channels_first=True``; fp32 CUDA tensors are read through their strides without a
+    copy.  ``out``: any fp32 CUDA view [B, L, H, W] with unit x stride.  max_disp defaults to w // 6 (crf/depth.py:40)."""
+    a, b = _sweep_views("cost_volume_nchw", img1, img2, channels_first)
+    B, h, w, c = (int(v) for v in a.shape)
+    L = w // 6 if max_disp is None else int(max_disp)
+    crit = CRITERIA[getattr(criterion, "__name__", criterion)]
+    if out is not None and (tuple(out.shape) != (B, L, h, w) or out.dtype != torch.float32 or (w > 1 and out.stride(3) != 1)):
+        raise ValueError(f"cost_volume_nchw: out must be fp32 [{B}, {L}, {h}, {w}] with unit x stride, got {out.dtype} "
+                         f"{tuple(out.shape)} with strides {tuple(out.stride())}")
+    dev = _sweep_device(img1)
+    if out is not None and out.device != dev:
+        raise ValueError(f"cost_volume_nchw: out is on {out.device}, the images on {dev}")
+    a, b, _, (ibs, iys, ixs, ics) = _sweep_operands(a, b, dev)
+    res = torch.empty((B, L, h, w), dtype=torch.float32, device=dev) if out is None else out
+    _launch(dev, "phl_cost_volume_nchw", _ptr(a), _ptr(b), B, h, w, c, ibs, iys, ixs, ics, L, int(window_size), crit,
+            COSTVOL_NEGATE if negate else 0, _ptr(res), res.stride(0), res.stride(1), res.stride(2))
+    return res
+
+
+def disparity_wta(img1, img2, max_disp=None, window_size=9, criterion="AD", return_cost=False, channels_first=False):
+    """Winner-takes-all disparity of the same sweep, the reference's ``disparity_estimate`` (crf/depth.py:31-34): int32
+    [B, H, W], the smallest disparity of minimal cost as ``np.argmin`` gives it, and with ``return_cost`` the fp32 minimum
+    beside it -- the argmin / min of ``cost_volume_nchw`` bit for bit, without the volume (4 bytes per pixel, not 4 L)."""
+    a, b = _sweep_views("disparity_wta", img1, img2, channels_first)
+    B, h, w, c = (int(v) for v in a.shape)
+    L = w // 6 if max_disp is None else int(max_disp)
+    if L == 0:
+        raise ValueError("disparity_wta: max_disp = 0, an argmin over nothing")
+    crit = CRITERIA[getattr(criterion, "__name__", criterion)]
+    dev = _sweep_device(img1)
+    a, b, _, (ibs, iys, ixs, ics) = _sweep_operands(a, b, dev)
+    disp = torch.empty((B, h, w), dtype=torch.int32, device=dev)
+    cost = torch.empty((B, h, w), dtype=torch.float32, device=dev) if return_cost else None
+    _launch(dev, "phl_disparity_wta", _ptr(a), _ptr(b), B, h, w, c, ibs, iys, ixs, ics, L, int(window_size), crit,
+            _ptr(disp), _ptr(cost), disp.stride(0), disp.stride(1))
+    return (disp, cost) if return_cost else disp
 
 
 # ---------------------------------------------------------------------------------------------

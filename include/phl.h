@@ -383,6 +383,41 @@ int phl_expected_value(const float *Q_dev, int64_t q_row_stride, const float *la
 int phl_cost_volume(const float *img1_dev, const float *img2_dev, int h, int w, int channels, int max_disp,
                     int window, int criterion, float *out_dev, int64_t out_row_stride, phl_stream stream);
 
+/* ---- the same sweep for the channel-major consumers, and its winner-takes-all disparity (phl_costvol_nchw.hip) ----
+ * crf/dataloader.py:54-57,83: the unary logits of CRFdepthRefiner / CRFwUncertainty are -1 * disparity_badness(left,
+ * right, ws, criterion), permuted to [L, H, W]; crf/depth.py:31-34: disparity_estimate is the argmin of
+ * disparity_badness (crf/depth.py:36-53, the mathematics of phl_cost_volume above) over the disparities.
+ *   phl_cost_volume_nchw  out[b*out_bs + k*out_ls + y*out_ys + x] = cost(b, y, x, k), or -cost with
+ *                         PHL_COSTVOL_NEGATE (the reference's logits; a cost of exactly 0 becomes -0.0, as -1 * 0.0).
+ *   phl_disparity_wta     disp[b*o_bs + y*o_ys + x] = the smallest k that attains min_k cost(b, y, x, k), as np.argmin;
+ *                         cost_dev, when not NULL, gets that minimum (positive cost) at the same strides.  Nothing of
+ *                         size h*w*max_disp is allocated or written.  Its window sums are formed by the same device
+ *                         code, tile geometry and order as phl_cost_volume_nchw's: the result is the argmin of that
+ *                         call's output bit for bit.  Inputs are taken as finite.
+ * Both images are read in place through one set of ELEMENT strides (batch, row, column, channel): interleaved
+ * [H][W][C] is (0, W*C, C, 1) with batch 1, planar [B][C][H][W] is (C*H*W, W, 1, H*W).  1..4 channels, odd window
+ * <= 17, criterion 0 = AD, 1 = SD, 2 = nprod.  The x stride of every output is 1; rows may start off the 16-byte grid
+ * (they are then written with 4-byte stores).  A workgroup makes PHL_COSTVOL_NCHW_TY x _TX pixels for _DC disparities.
+ * Deterministic: no atomics, the same bytes on every call.
+ * Status, checked in this order and before any HIP call: PHL_ERR_UNSUPPORTED for channels, window or criterion outside
+ * that set or unknown flag bits; PHL_ERR_INVALID for negative sizes, and for max_disp == 0 in phl_disparity_wta (an
+ * argmin over nothing); then batch == 0, h*w == 0 or (volume) max_disp == 0 are PHL_OK with nothing launched, whatever
+ * the pointers; PHL_ERR_INVALID for a NULL image or output, for out_ys < w, out_ls smaller than what h rows span or
+ * out_bs smaller than what one item spans (rows would overlap), and for an output that overlaps an image (or cost_dev
+ * overlapping disp_dev); PHL_ERR_TOO_LARGE when byte offsets leave int64 or the workgroups leave 2^31 - 1. */
+#define PHL_COSTVOL_NEGATE 1u
+#define PHL_COSTVOL_NCHW_TX 64
+#define PHL_COSTVOL_NCHW_TY 8
+#define PHL_COSTVOL_NCHW_DC 8
+int phl_cost_volume_nchw(const float *img1_dev, const float *img2_dev, int batch, int h, int w, int channels,
+                         int64_t img_bs, int64_t img_ys, int64_t img_xs, int64_t img_cs,
+                         int max_disp, int window, int criterion, unsigned flags,
+                         float *out_dev, int64_t out_bs, int64_t out_ls, int64_t out_ys, phl_stream stream);
+int phl_disparity_wta(const float *img1_dev, const float *img2_dev, int batch, int h, int w, int channels,
+                      int64_t img_bs, int64_t img_ys, int64_t img_xs, int64_t img_cs,
+                      int max_disp, int window, int criterion,
+                      int32_t *disp_dev, float *cost_dev /* may be NULL */, int64_t o_bs, int64_t o_ys, phl_stream stream);
+
 /* ---- separable Gaussian of the guided filter (crf/guided.py: box_filter, gaussian_blur) -------------------------
  * Dense contiguous fp32 viewed as [outer][h][inner]; every (outer, inner) line is filtered along h by `passes` box
  * passes  B_r(x)[i] = sum(x[max(0, i-r+1) .. min(h-1, i+r)]) / (min(i, r) + min(h-1-i, r) + 1).

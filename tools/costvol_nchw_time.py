@@ -1,0 +1,128 @@
+"""Time the channel-major cost volume and the fused winner-takes-all disparity (csrc/phl_costvol_nchw.hip) against the
+routes they replace, built from the public calls that existed before them, in one process:
+
+    (a) phl.cost_volume + negate + permute(...).contiguous() to [1, L, H, W]     the old way to CRFasRNN's logits
+    (b) phl.cost_volume_nchw(negate=True)
+    (c) phl.cost_volume(...).argmin(1)                                          the old winner-takes-all
+    (d) phl.disparity_wta
+    (e) peak allocated memory of (c) and (d)
+
+Window 9, AD, three channels, L = w // 6.  Every buffer of the timed calls is allocated beforehand ((a) negates and
+permutes into buffers of its own: its best case); each repetition is timed with its own pair of device events, the
+routes alternate inside a repetition, and the median is reported.  The results of old and new routes are compared at the
+sizes timed.  The bars are (b) <= (a) and (d) <= (c), measured in the same run.
+
+    python tools/costvol_nchw_time.py [--reps 15] [--sizes 384x288 1390x1110 2048x1536]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "depth-estimation_amd"))
+import numpy as np
+import torch
+
+import phl
+
+WS, CRIT = 9, "AD"
+
+
+def timed(fn, inner):
+    """Milliseconds per call over a window of ``inner`` calls between two device events."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(inner):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / inner
+
+
+def peak_of(fn):
+    """Peak allocated bytes above what is allocated now, of a call that allocates everything it needs itself."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    del out
+    return peak
+
+
+def measure(w, h, reps, warmup):
+    rng = np.random.default_rng(0)
+    a = torch.from_numpy(rng.random((h, w, 3), dtype=np.float32)).cuda()
+    b = torch.from_numpy(rng.random((h, w, 3), dtype=np.float32)).cuda()
+    L = w // 6
+    kw = dict(max_disp=L, window_size=WS, criterion=CRIT)
+    E = torch.empty((h * w, L), device="cuda")
+    neg = torch.empty_like(E)
+    old_logits = torch.empty((1, L, h, w), device="cuda")
+    new_logits = torch.empty((1, L, h, w), device="cuda")
+    results = {}
+
+    def route_a():
+        phl.cost_volume(a, b, out=E, **kw)
+        torch.neg(E, out=neg)
+        old_logits[0].copy_(neg.view(h, w, L).permute(2, 0, 1))
+
+    def route_b():
+        phl.cost_volume_nchw(a, b, negate=True, out=new_logits, **kw)
+
+    def route_c():
+        phl.cost_volume(a, b, out=E, **kw)
+        results["c"] = E.argmin(1)
+
+    def route_d():
+        results["d"] = phl.disparity_wta(a, b, **kw)
+
+    routes = {"a": route_a, "b": route_b, "c": route_c, "d": route_d}
+    for _ in range(warmup):
+        for fn in routes.values():
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in routes}
+    inner = 50 if h * w * L < 5e7 else 1             # a window of tens of microseconds measures the events
+    for _ in range(reps):
+        for k, fn in routes.items():
+            times[k].append(timed(fn, inner))
+    ms = {k: statistics.median(v) for k, v in times.items()}
+    spread = {k: (min(v), max(v)) for k, v in times.items()}
+    # the same results? (real-valued input: the two kernels restart their running sums at different columns and rows)
+    scale = float(old_logits.abs().max())
+    logits_diff = float((old_logits - new_logits).abs().max()) / scale
+    wta_old, wta_new = results["c"].view(h, w), results["d"][0]
+    wta_differ = int((wta_old != wta_new).sum())
+    del E, neg, old_logits, new_logits, wta_old, wta_new
+    results.clear()
+    peak_c = peak_of(lambda: phl.cost_volume(a, b, **kw).argmin(1))
+    peak_d = peak_of(lambda: phl.disparity_wta(a, b, **kw))
+    return dict(size=f"{w}x{h}x{L}", volume_gb=round(h * w * L * 4 / 1e9, 3), ms={k: round(v, 4) for k, v in ms.items()},
+                min_max_ms={k: (round(lo, 4), round(hi, 4)) for k, (lo, hi) in spread.items()},
+                b_over_a=round(ms["b"] / ms["a"], 3), d_over_c=round(ms["d"] / ms["c"], 3), peak_c_mb=round(peak_c / 2 ** 20, 2),
+                peak_d_mb=round(peak_d / 2 ** 20, 2), logits_max_diff_of_max=logits_diff, wta_pixels_differ=wta_differ,
+                pixels=h * w)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--sizes", nargs="*", default=["384x288", "1390x1110", "2048x1536"])
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "this tool measures on the GPU; there is nothing to report without one"
+    rows = []
+    for s in args.sizes:
+        w, h = (int(v) for v in s.split("x"))
+        r = measure(w, h, args.reps, args.warmup)
+        rows.append(r)
+        m = r["ms"]
+        print(f"{r['size']} ({r['volume_gb']} GB volume): (a) old logits {m['a']:.3f} ms, (b) cost_volume_nchw {m['b']:.3f} ms "
+              f"[b/a {r['b_over_a']}]; (c) old WTA {m['c']:.3f} ms, (d) disparity_wta {m['d']:.3f} ms [d/c {r['d_over_c']}]; "
+              f"peak memory (c) {r['peak_c_mb']} MiB, (d) {r['peak_d_mb']} MiB; logits differ by {r['logits_max_diff_of_max']:.1e} "
+              f"of the maximum, WTA differs at {r['wta_pixels_differ']} of {r['pixels']} pixels", flush=True)
+    print(json.dumps({"costvol_nchw_time": rows, "bars_met": all(r["b_over_a"] <= 1 and r["d_over_c"] <= 1 for r in rows)}))
