@@ -952,13 +952,13 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
     const int64_t n = lat->n;
     const int d = lat->d;
     if (n == 0) return PHL_OK;
-    if (!src || !g || !ref) { phl_set_error("phl_filter_grad: NULL src / g / ref"); return PHL_ERR_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     device_guard guard(lat->device);
-    if (L == 0) {
+    if (L == 0) {       // (before the NULL tests: an [n, 0] tensor has no storage, and nothing of src / g / ref is read)
         PHL_HIP(hipMemsetAsync(grad_ref, 0, sizeof(float) * (size_t)n * d, st));
         return PHL_OK;
     }
+    if (!src || !g || !ref) { phl_set_error("phl_filter_grad: NULL src / g / ref"); return PHL_ERR_INVALID; }
     const int64_t vdw = (int64_t)L * (d + 1);
     if (d > 7 || L % 4 != 0 || !use_tiled_splat(lat, L, 0, src, g, src_rs) || g_rs % 4 || vdw > (1 << 20) ||
         (grad_src && ((reinterpret_cast<uintptr_t>(grad_src) & 15) || grad_src_rs % 4))) {

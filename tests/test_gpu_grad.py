@@ -41,11 +41,25 @@ def test_fused_gradient_equals_the_wide_filter(kind, n, d, L):
     g = torch.from_numpy(rng.standard_normal((n, L)).astype(np.float32)).cuda()
     lat = phl.Lattice(ref)
     want_src, want_ref = _composition(lat, src, ref, g)
+    st = lat.tile_stats(L)
     try:
         got_src, got_ref = lat.filter_grad(src, g, ref)
     except phl.PhlError as e:
         assert e.status == 7 and kind == "random", e        # only the no-sharing case may be declined
+        # ... and only as tile_stats predicts it: chunks that share too little for the staged splat (S_multi > 2n)
+        assert st["staged_splat"] == 0 and st["multi_chunk_slots"] > 2 * n, st
+        # the formulation the caller then falls back to is still checked, against float64 on the CPU
+        from _filter_grad_util import grad64, scaled
+        from oracle import phl_oracle as po
+
+        Wg64, T64 = grad64(po.Oracle(f), src.cpu().numpy(), f, g.cpu().numpy())
+        assert scaled(want_src.cpu().numpy(), Wg64) <= 1e-5 and scaled(want_ref.cpu().numpy(), T64) <= 2e-4
         return
+    assert st["staged_splat"] == 1, st                      # taken: then tile_stats must have said so
+    if kind == "random":                                    # the one case meant for the slice's unstaged form
+        from _filter_grad_util import slice_grad_mode
+
+        assert slice_grad_mode(st["pixels_per_chunk"], d, st["max_local_vertices"], st["max_local_vertices"]) == 0, st
     assert float((got_src - want_src).abs().max()) <= 1e-5 * float(want_src.abs().max())
     scale = float(want_ref.abs().max())
     assert float((got_ref - want_ref).abs().max()) <= 2e-4 * scale, (float((got_ref - want_ref).abs().max()), scale)
