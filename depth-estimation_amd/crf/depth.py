@@ -39,7 +39,8 @@ def disparity_estimate(img1, img2, window_size=9, criterion=AD):
 
 
 def disparity_energy_device(img1, img2, window_size=9, criterion=AD, max_disp=None):
-    """``disparity_badness`` computed on the GPU (csrc/phl_costvol.hip) and left there as the
+    """``disparity_badness`` computed on the GPU (csrc/phl_costvol.hip on
+    csrc/phl_costvol_common.h) and left there as the
     E_0 [h*w, L] fp32 tensor ``mean_field_infer`` consumes (DenseCrf.ipynb cell 7 does
     ``torch.from_numpy(disp_energy.reshape(-1, L)).float().to(device)`` after the CPU sweep)."""
     import phl
@@ -49,7 +50,7 @@ def disparity_energy_device(img1, img2, window_size=9, criterion=AD, max_disp=No
 
 def disparity_logits_device(img1, img2, window_size=1, criterion=AD, max_disp=None):
     """The unary logits of the CRF heads, ``-disparity_badness`` as fp32 [1, L, H, W], computed on the GPU
-    (csrc/phl_costvol_nchw.hip) and left there: what ``planar_sweep_algorithm()(left, right)`` followed by the data
+    (csrc/phl_costvol_nchw.hip on csrc/phl_costvol_common.h) and left there: what ``planar_sweep_algorithm()(left, right)`` followed by the data
     set's ``.permute(2, 0, 1)[None]`` gives (crf/dataloader.py:54-57, :83).  The default window is the reference's, 1."""
     import phl
 

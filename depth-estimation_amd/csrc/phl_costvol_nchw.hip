@@ -2,10 +2,9 @@
 // (CRFasRNN's default W, phl_nchw_softmax_compat, phl_nchw_expected_value: logits [B][L][H][W]), and the
 // winner-takes-all disparity of the same sweep without the volume.
 //
-// Reference: crf/depth.py:31-53 (disparity_estimate = argmin over the last axis of disparity_badness) and
+// Reference: crf/depth.py:31-34 (disparity_estimate = argmin over the last axis of disparity_badness) and
 // crf/dataloader.py:54-57,83 (planar_sweep_algorithm: logits = -1 * disparity_badness, permuted to [L, H, W]).
-// The mathematics is phl_costvol.hip's (its header, lines 1-16): shifted criterion summed over the channels, img2 zero
-// left of the image, ws x ws box sum with scipy's 'reflect' border on the COST array.
+// The mathematics and the staging are phl_costvol_common.h's.
 //
 // One workgroup (512 threads) makes a TY x TX = 8 x 64 pixel tile for DC = 8 consecutive disparities:
 //   0. the image rows it needs go to LDS as zero-padded float4 pixels, read through the caller's element strides;
@@ -13,19 +12,16 @@
 //   2. horizontal window sums: a thread owns one (row, k) and 8 adjacent columns, a running sum in registers that is
 //      restarted every 8 columns -> hs[row][k][x] (over the dead image stage);
 //   3. vertical window sums: a thread owns one (k, 4 adjacent columns), a running float4 sum down the tile's 8 rows.
-// Every running sum adds the entering element before it subtracts the leaving one.  Step 3 hands each float4 to the
-// caller's sink: k_cost_volume_nchw stores it (16 lanes x 16 bytes = 256 contiguous bytes of one (k, y) row, four such
-// rows per wave instruction), k_disparity_wta folds it into a per-thread running (min, argmin) and walks all
-// disparity blocks of its tile; both run the same device function, so the second is the argmin of the first bit for bit.
-#include <math.h>
-#include <stdint.h>
-
-#include "phl_internal.h"
+// Step 3 hands each float4 to the caller's sink: k_cost_volume_nchw stores it (16 lanes x 16 bytes = 256 contiguous
+// bytes of one (k, y) row, four such rows per wave instruction), k_disparity_wta folds it into a per-thread running
+// (min, argmin) and walks all disparity blocks of its tile; both run the same device function, so the second is the
+// argmin of the first bit for bit.
+#include "phl_costvol_common.h"
 
 namespace {
 
 constexpr int TX = PHL_COSTVOL_NCHW_TX, TY = PHL_COSTVOL_NCHW_TY, DC = PHL_COSTVOL_NCHW_DC;
-constexpr int CMAX = 4, NT = 512, SEG = 8;      // SEG: columns per horizontal running sum
+constexpr int NT = 512, SEG = 8;                // SEG: columns per horizontal running sum
 constexpr int HS = TX + 4;                      // row stride of hs in floats: 16-byte rows, 4 banks apart
 static_assert(TX % SEG == 0 && SEG % 4 == 0 && TX % 4 == 0 && (TX / 4) * DC <= NT && TX * TY <= NT, "thread maps");
 
@@ -43,39 +39,6 @@ struct geo {
     static_assert(lds_bytes <= 160 * 1024, "LDS of one workgroup");
     static_assert(lds_bytes >= 2 * sizeof(float) * DC * TY * TX, "the WTA's final exchange lies over the tile's LDS");
 };
-
-struct images {
-    const float *img1, *img2;
-    int64_t bs, ys, xs, cs;     // element strides: batch, row, column, channel (the same for both images)
-    int h, w, C;
-};
-
-__device__ __forceinline__ int reflect(int i, int n)
-{
-    // scipy 'reflect': -1 -> 0, -2 -> 1, n -> n-1, n+1 -> n-2 (period 2n)
-    if (i >= 0 && i < n) return i;
-    if (i < 0 && i >= -n) return -i - 1;
-    if (i >= n && i < 2 * n) return 2 * n - 1 - i;
-    const int p = 2 * n;
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - 1 - i;
-}
-
-__device__ __forceinline__ float4 ld_pixel(const float *p, int64_t cs, int C)
-{
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);   // channels padded with zeros: every criterion gives 0 on (0, 0)
-    v.x = p[0];
-    if (C > 1) v.y = p[cs];
-    if (C > 2) v.z = p[2 * cs];
-    if (C > 3) v.w = p[3 * cs];
-    return v;
-}
-
-template <int CRIT> __device__ __forceinline__ float crit(float a, float b);
-template <> __device__ __forceinline__ float crit<0>(float a, float b) { return fabsf(a - b); }
-template <> __device__ __forceinline__ float crit<1>(float a, float b) { return (a - b) * (a - b); }
-template <> __device__ __forceinline__ float crit<2>(float a, float b) { return -1.0f * a * b; }
 
 __device__ __forceinline__ float4 add_sub(float4 s, float4 in, float4 out)
 {
@@ -95,24 +58,7 @@ __device__ __forceinline__ void tile_window_sums(float *lds, const images &im, i
     float *hs = lds;                                              // [ROWS][DC][HS] horizontal sums, over the two above
     float *craw = lds + G::a_bytes / sizeof(float);               // [ROWS][DC][CS] raw costs
     int *xr = reinterpret_cast<int *>(craw + ROWS * DC * CS);     // [COLS] reflected column as index into a row of i2s
-    const int h = im.h, w = im.w, C = im.C;
-    const float *img1 = im.img1 + b * im.bs, *img2 = im.img2 + b * im.bs;
-    // the tile's reflected columns fall on a contiguous range of actual columns, at most COLS wide
-    int cmin = w;
-    for (int xx = 0; xx < COLS; xx++) cmin = min(cmin, reflect(x0 - R + xx, w));      // uniform over the workgroup
-    const int base2 = cmin - (d0 + DC - 1);                       // leftmost img2 column any (column, disparity) pair reads
-    for (int xx = threadIdx.x; xx < COLS; xx += NT) xr[xx] = reflect(x0 - R + xx, w) - d0 - base2;
-    for (int e = threadIdx.x; e < ROWS * COLS; e += NT) {
-        const int rr = e / COLS, xx = e - rr * COLS;
-        const int y = reflect(y0 - R + rr, h), x = reflect(x0 - R + xx, w);
-        i1s[e] = ld_pixel(img1 + y * im.ys + x * im.xs, im.cs, C);
-    }
-    for (int e = threadIdx.x; e < ROWS * W2; e += NT) {
-        const int rr = e / W2, cc = e - rr * W2;
-        const int y = reflect(y0 - R + rr, h), x = base2 + cc;
-        i2s[e] = (x >= 0 && x < w) ? ld_pixel(img2 + y * im.ys + x * im.xs, im.cs, C) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    __syncthreads();
+    stage_images<R, TX, TY, DC, NT>(im, b, x0, y0, d0, i1s, i2s, xr);
     // 1: raw costs, lanes along the staged columns
     for (int e = threadIdx.x; e < ROWS * COLS; e += NT) {
         const int rr = e / COLS, xx = e - rr * COLS;
@@ -120,10 +66,7 @@ __device__ __forceinline__ void tile_window_sums(float *lds, const images &im, i
         const float4 *brow = i2s + rr * W2 + xr[xx];
         float *c = craw + rr * DC * CS + xx;
 #pragma unroll
-        for (int k = 0; k < DC; k++) {
-            const float4 v = brow[-k];
-            c[k * CS] = ((crit<CRIT>(a.x, v.x) + crit<CRIT>(a.y, v.y)) + crit<CRIT>(a.z, v.z)) + crit<CRIT>(a.w, v.w);
-        }
+        for (int k = 0; k < DC; k++) c[k * CS] = raw_cost<CRIT>(a, brow[-k]);
     }
     __syncthreads();
     // 2: horizontal running sums of SEG columns each (the image stage is dead: hs lies over it)
@@ -288,22 +231,6 @@ int launch(const request &q, hipStream_t st)
     return PHL_OK;
 }
 
-template <int CRIT>
-int launch_r(int R, const request &q, hipStream_t st)
-{
-    switch (R) {
-        case 0: return launch<0, CRIT>(q, st);
-        case 1: return launch<1, CRIT>(q, st);
-        case 2: return launch<2, CRIT>(q, st);
-        case 3: return launch<3, CRIT>(q, st);
-        case 4: return launch<4, CRIT>(q, st);
-        case 5: return launch<5, CRIT>(q, st);
-        case 6: return launch<6, CRIT>(q, st);
-        case 7: return launch<7, CRIT>(q, st);
-        default: return launch<8, CRIT>(q, st);
-    }
-}
-
 typedef __int128 wide;
 const wide I64_MAX = (wide)INT64_MAX;
 constexpr int INDEX_MAX = (1 << 30) - 128;      // h, w, max_disp: reflect() doubles a length, a tile reaches TX + 16 past it
@@ -329,10 +256,9 @@ bool overlaps(const void *p, wide bytes, const void *img, wide lo, wide hi)
 int check(const char *name, request &q, int window, int criterion, bool wta)
 {
     const images &im = q.im;
-    if (im.C < 1 || im.C > CMAX || window < 1 || window % 2 == 0 || window > 17 || criterion < 0 || criterion > 2 ||
-        (q.flags & ~PHL_COSTVOL_NEGATE)) {
-        phl_set_error("%s: supports 1..%d channels, odd windows up to 17, criterion 0 (AD) / 1 (SD) / 2 (nprod), flags within "
-                      "PHL_COSTVOL_NEGATE; got c=%d ws=%d crit=%d flags=%#x", name, CMAX, im.C, window, criterion, q.flags);
+    if (const int rc = check_supported(name, im.C, window, criterion)) return rc;
+    if (q.flags & ~PHL_COSTVOL_NEGATE) {
+        phl_set_error("%s: supports flags within PHL_COSTVOL_NEGATE; got flags=%#x", name, q.flags);
         return PHL_ERR_UNSUPPORTED;
     }
     q.grid = 0;
@@ -382,13 +308,12 @@ int check(const char *name, request &q, int window, int criterion, bool wta)
     return PHL_OK;
 }
 
-int dispatch(request &q, int window, int criterion, hipStream_t st)
+// checks, then launches what they left to launch
+int run(const char *name, request &q, int window, int criterion, bool wta, phl_stream stream)
 {
-    switch (criterion) {
-        case 0: return launch_r<0>(window / 2, q, st);
-        case 1: return launch_r<1>(window / 2, q, st);
-        default: return launch_r<2>(window / 2, q, st);
-    }
+    if (const int rc = check(name, q, window, criterion, wta)) return rc;
+    if (!q.grid) return PHL_OK;
+    return dispatch(window, criterion, [&](auto r, auto c) { return launch<decltype(r)::value, decltype(c)::value>(q, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -399,8 +324,7 @@ extern "C" int phl_cost_volume_nchw(const float *img1, const float *img2, int ba
 {
     request q = {{img1, img2, img_bs, img_ys, img_xs, img_cs, h, w, channels}, batch, max_disp, flags, out, out_bs, out_ls, out_ys,
                  nullptr, nullptr, 0, 0, 0, 0};
-    if (const int rc = check("phl_cost_volume_nchw", q, window, criterion, false)) return rc;
-    return q.grid ? dispatch(q, window, criterion, (hipStream_t)stream) : PHL_OK;
+    return run("phl_cost_volume_nchw", q, window, criterion, false, stream);
 }
 
 extern "C" int phl_disparity_wta(const float *img1, const float *img2, int batch, int h, int w, int channels, int64_t img_bs,
@@ -409,6 +333,5 @@ extern "C" int phl_disparity_wta(const float *img1, const float *img2, int batch
 {
     request q = {{img1, img2, img_bs, img_ys, img_xs, img_cs, h, w, channels}, batch, max_disp, 0u, nullptr, o_bs, 0, o_ys,
                  disp, cost, 0, 0, 0, 0};
-    if (const int rc = check("phl_disparity_wta", q, window, criterion, true)) return rc;
-    return q.grid ? dispatch(q, window, criterion, (hipStream_t)stream) : PHL_OK;
+    return run("phl_disparity_wta", q, window, criterion, true, stream);
 }

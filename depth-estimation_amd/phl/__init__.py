@@ -1060,19 +1060,11 @@ def cost_volume(img1, img2, max_disp=None, window_size=9, criterion="AD", out=No
     criterion)`` (crf/depth.py:36-53), returned as E_0 [h*w, max_disp] fp32 pixel-major (what
     ``mean_field_infer`` takes after the notebook's reshape, DenseCrf.ipynb cell 7).
     img1/img2: [h, w, c] float tensors or numpy arrays; max_disp defaults to w // 6 (:40)."""
-    _require_gpu()
-    dev = img1.device if (torch.is_tensor(img1) and img1.is_cuda) else torch.device("cuda", torch.cuda.current_device())
-    # (numpy views with a negative stride -- a mirrored image, reversed channels -- are not tensors: copied first)
-    a, b = (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v for v in (img1, img2))
-    a = torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()
-    b = torch.as_tensor(b).to(device=dev, dtype=torch.float32).contiguous()
-    if a.dim() == 2:
-        a, b = a[..., None], b[..., None]
-    if a.shape != b.shape or a.dim() != 3:
-        raise ValueError(f"cost_volume: images must both be [h, w, c], got {tuple(a.shape)} and {tuple(b.shape)}")
-    h, w, c = (int(v) for v in a.shape)
-    L = w // 6 if max_disp is None else int(max_disp)
-    crit = CRITERIA[getattr(criterion, "__name__", criterion)]
+    a, b = _sweep_views("cost_volume", img1, img2, False)
+    _, h, w, c = (int(v) for v in a.shape)
+    L, crit = _sweep_request(w, max_disp, criterion)
+    dev = _sweep_device(img1)
+    a, b = (v.to(device=dev, dtype=torch.float32).contiguous() for v in (a, b))      # the kernel's ABI is dense [h, w, c]
     res = torch.empty((h * w, L), dtype=torch.float32, device=dev) if out is None else out
     assert res.shape == (h * w, L) and res.stride(1) == 1 and res.dtype == torch.float32
     _launch(dev, "phl_cost_volume", _ptr(a), _ptr(b), h, w, c, L, int(window_size), crit, _ptr(res), res.stride(0) if L else 0)
@@ -1114,6 +1106,12 @@ def _sweep_device(img1):
     return img1.device if (torch.is_tensor(img1) and img1.is_cuda) else torch.device("cuda", torch.cuda.current_device())
 
 
+def _sweep_request(w, max_disp, criterion):
+    """(max_disp, criterion code): max_disp defaults to w // 6 (crf/depth.py:40), a criterion is one of CRITERIA's names
+    or the reference's function of that name."""
+    return (w // 6 if max_disp is None else int(max_disp)), CRITERIA[getattr(criterion, "__name__", criterion)]
+
+
 def cost_volume_nchw(img1, img2, max_disp=None, window_size=9, criterion="AD", negate=False, out=None, channels_first=False):
     """The cost volume of ``cost_volume`` in the channel-major layout of CRFasRNN and the heads: fp32 [B, L, H, W], written
     once (csrc/phl_costvol_nchw.hip).  ``negate=True`` gives the reference's unary logits, ``-1 * disparity_badness``
@@ -1122,8 +1120,7 @@ def cost_volume_nchw(img1, img2, max_disp=None, window_size=9, criterion="AD", n
     copy.  ``out``: any fp32 CUDA view [B, L, H, W] with unit x stride.  max_disp defaults to w // 6 (crf/depth.py:40)."""
     a, b = _sweep_views("cost_volume_nchw", img1, img2, channels_first)
     B, h, w, c = (int(v) for v in a.shape)
-    L = w // 6 if max_disp is None else int(max_disp)
-    crit = CRITERIA[getattr(criterion, "__name__", criterion)]
+    L, crit = _sweep_request(w, max_disp, criterion)
     if out is not None and (tuple(out.shape) != (B, L, h, w) or out.dtype != torch.float32 or (w > 1 and out.stride(3) != 1)):
         raise ValueError(f"cost_volume_nchw: out must be fp32 [{B}, {L}, {h}, {w}] with unit x stride, got {out.dtype} "
                          f"{tuple(out.shape)} with strides {tuple(out.stride())}")
@@ -1143,10 +1140,9 @@ def disparity_wta(img1, img2, max_disp=None, window_size=9, criterion="AD", retu
     beside it -- the argmin / min of ``cost_volume_nchw`` bit for bit, without the volume (4 bytes per pixel, not 4 L)."""
     a, b = _sweep_views("disparity_wta", img1, img2, channels_first)
     B, h, w, c = (int(v) for v in a.shape)
-    L = w // 6 if max_disp is None else int(max_disp)
+    L, crit = _sweep_request(w, max_disp, criterion)
     if L == 0:
         raise ValueError("disparity_wta: max_disp = 0, an argmin over nothing")
-    crit = CRITERIA[getattr(criterion, "__name__", criterion)]
     dev = _sweep_device(img1)
     a, b, _, (ibs, iys, ixs, ics) = _sweep_operands(a, b, dev)
     disp = torch.empty((B, h, w), dtype=torch.int32, device=dev)

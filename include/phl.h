@@ -383,7 +383,8 @@ int phl_expected_value(const float *Q_dev, int64_t q_row_stride, const float *la
 int phl_cost_volume(const float *img1_dev, const float *img2_dev, int h, int w, int channels, int max_disp,
                     int window, int criterion, float *out_dev, int64_t out_row_stride, phl_stream stream);
 
-/* ---- the same sweep for the channel-major consumers, and its winner-takes-all disparity (phl_costvol_nchw.hip) ----
+/* ---- the same sweep for the channel-major consumers, and its winner-takes-all disparity (phl_costvol_nchw.hip;
+ * what it shares with phl_costvol.hip: phl_costvol_common.h) ----
  * crf/dataloader.py:54-57,83: the unary logits of CRFdepthRefiner / CRFwUncertainty are -1 * disparity_badness(left,
  * right, ws, criterion), permuted to [L, H, W]; crf/depth.py:31-34: disparity_estimate is the argmin of
  * disparity_badness (crf/depth.py:36-53, the mathematics of phl_cost_volume above) over the disparities.

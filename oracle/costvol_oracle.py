@@ -1,5 +1,6 @@
 """CPU restatement of the reference's unary cost volume -- TEST INFRASTRUCTURE ONLY (imported by
-tests/, tests/golden/generate.py and nothing else; the product path is csrc/phl_costvol.hip).
+tests/, tests/golden/generate.py and nothing else; the product path is
+csrc/phl_costvol_common.h with csrc/phl_costvol.hip and csrc/phl_costvol_nchw.hip).
 
 Follows crf/depth.py:36-53 (``disparity_badness``) and its criteria :24-29, float64 like the
 reference.  Pinned bit for bit against the reference's own function by tests/golden/generate.py

@@ -1,7 +1,7 @@
-"""What needs no GPU of the channel-major cost volume and the winner-takes-all disparity (include/phl.h:
-phl_cost_volume_nchw, phl_disparity_wta): the argument checks of both entry points with the status each returns and the
-order they run in -- every case returns before the first HIP call, the fake addresses are never dereferenced --, what the
-binding refuses, the numpy side of the reference's names, and the precondition of the exact GPU tests."""
+"""What needs no GPU of the stereo sweep's three entry points (include/phl.h: phl_cost_volume, phl_cost_volume_nchw,
+phl_disparity_wta): the argument checks of each with the status it returns and the order they run in -- every case
+returns before the first HIP call, the fake addresses are never dereferenced --, what the binding refuses, the numpy
+side of the reference's names, and the precondition of the exact GPU tests."""
 import numpy as np
 import pytest
 import torch
@@ -31,6 +31,29 @@ def wta(i1=I1, i2=I2, B=2, h=4, w=8, C=3, st=None, L=5, ws=9, crit=0, disp=O, co
     return (i1, i2, B, h, w, C, *st, L, ws, crit, disp, cost, obs, oys)
 
 
+def pix(i1=I1, i2=I2, h=4, w=8, C=3, L=5, ws=9, crit=0, out=O, ors=None):
+    """Arguments of phl_cost_volume (pixel-major [h*w][L]); the unnamed row stride is the dense one."""
+    return (i1, i2, h, w, C, L, ws, crit, out, L if ors is None else ors)
+
+
+PIXEL_MAJOR = [
+    # the supported set, before everything else: also with bad sizes, NULL pointers, a short row stride
+    (pix(C=0), UNSUPPORTED), (pix(C=5), UNSUPPORTED), (pix(ws=0), UNSUPPORTED), (pix(ws=4), UNSUPPORTED),
+    (pix(ws=19), UNSUPPORTED), (pix(ws=-3), UNSUPPORTED), (pix(crit=3), UNSUPPORTED), (pix(crit=-1), UNSUPPORTED),
+    (pix(C=5, h=0), UNSUPPORTED), (pix(ws=2, i1=None, out=None), UNSUPPORTED), (pix(crit=7, L=-1), UNSUPPORTED),
+    (pix(C=0, i1=None, i2=None), UNSUPPORTED), (pix(ws=19, ors=4), UNSUPPORTED), (pix(crit=3, L=0, w=0), UNSUPPORTED),
+    # an image without pixels is PHL_ERR_INVALID here (not PHL_OK as in the channel-major entry points), also with max_disp = 0
+    (pix(h=0), INVALID), (pix(w=0), INVALID), (pix(h=-4), INVALID), (pix(w=-8), INVALID),
+    (pix(h=0, L=0), INVALID), (pix(w=0, L=0, out=None), INVALID),
+    (pix(L=-1), INVALID), (pix(L=-1, ors=-1), INVALID),
+    # max_disp = 0: PHL_OK with or without an output, after the image pointers and the row stride
+    (pix(L=0), OK), (pix(L=0, out=None), OK), (pix(L=0, out=None, ors=7), OK),
+    (pix(L=0, i1=None), INVALID), (pix(L=0, i2=None, out=None), INVALID), (pix(L=0, ors=-1), INVALID),
+    # NULL with elements present
+    (pix(i1=None), INVALID), (pix(i2=None), INVALID), (pix(out=None), INVALID),
+    # rows that would overlap
+    (pix(ors=4), INVALID), (pix(ors=0), INVALID), (pix(L=1, ors=0), INVALID),
+]
 VOLUME = [
     # the supported set, before everything else: also with negative sizes, NULL pointers, zero sizes, bad strides
     (vol(C=0), UNSUPPORTED), (vol(C=5), UNSUPPORTED), (vol(ws=0), UNSUPPORTED), (vol(ws=4), UNSUPPORTED),
@@ -88,6 +111,11 @@ def _check(name, args, status):
     if status != OK:
         text = lib.phl_last_error().decode()
         assert text.startswith(name + ":"), text
+
+
+@pytest.mark.parametrize("args,status", PIXEL_MAJOR, ids=[f"{i}-{c[1]}" for i, c in enumerate(PIXEL_MAJOR)])
+def test_cost_volume_argument_checks(args, status):
+    _check("phl_cost_volume", args, status)
 
 
 @pytest.mark.parametrize("args,status", VOLUME, ids=[f"{i}-{c[1]}" for i, c in enumerate(VOLUME)])

@@ -1,5 +1,6 @@
-"""Time the channel-major cost volume and the fused winner-takes-all disparity (csrc/phl_costvol_nchw.hip) against the
-routes they replace, built from the public calls that existed before them, in one process:
+"""Time the channel-major cost volume and the fused winner-takes-all disparity (csrc/phl_costvol_nchw.hip, its staging
+and dispatch in csrc/phl_costvol_common.h) against the routes they replace, built from the public calls that existed
+before them, in one process:
 
     (a) phl.cost_volume + negate + permute(...).contiguous() to [1, L, H, W]     the old way to CRFasRNN's logits
     (b) phl.cost_volume_nchw(negate=True)
