@@ -439,28 +439,34 @@ class CRFasRNN(nn.Module):
                                                                              fused_grad=fused_grad and not gaussian)
         self.fused_grad = fused_grad
 
-    def forward(self, refs, logits, confidence=None, labels=None):
-        """refs [B, C, H, W], logits [B, L, H, W]."""
-        return self._run(refs, logits, confidence, labels)[0]
+    def forward(self, refs, logits, confidence=None, labels=None, energies=None):
+        """refs [B, C, H, W], logits [B, L, H, W].  energies: the unaries E0 [B, L, H, W] themselves in place of
+        ``-logits * confidence`` (logits and confidence must then be None), for a caller that has them already."""
+        return self._run(refs, logits, confidence, labels, energies=energies)[0]
 
-    def expected_depth(self, refs, logits, confidence=None, labels=None, values=None):
+    def expected_depth(self, refs, logits, confidence=None, labels=None, values=None, energies=None):
         """``logits2average_depth(self(refs, logits, confidence, labels), values)`` [B, 1, H, W]: the expected value under
         the softmax of the returned logits.  values: None = 0 .. L-1, a tensor with one value per label ([L] or
         [1, L, 1, 1]), or anything ``probs * values`` broadcasts.  A tensor of fewer than four dimensions with exactly L
         elements always means one value per label -- also a [W] tensor when W == L, which ``probs * values`` alone would
         spread along the width; hand such values over as [1, 1, 1, W].  Where forward takes _mean_field_nchw_step_fused,
-        the loop itself ends with the expected value; everything else goes through forward."""
+        the loop itself ends with the expected value; everything else goes through forward.  energies: as in forward
+        (``expected_depth(refs, None, energies=E0, ...)``)."""
         from crf.mb_stereo_crf import logits2average_depth
 
-        if torch.is_tensor(values) and values.dim() != 4 and values.numel() == logits.shape[1]:
+        unary = logits if energies is None else energies
+        if torch.is_tensor(values) and values.dim() != 4 and values.numel() == unary.shape[1]:
             values = values.reshape(1, -1, 1, 1)
-        out, done = self._run(refs, logits, confidence, labels, expect=_expect_routable(logits, values), values=values)
+        out, done = self._run(refs, logits, confidence, labels, expect=_expect_routable(unary, values), values=values,
+                              energies=energies)
         return out if done else logits2average_depth(out, values)
 
-    def _run(self, refs, logits, confidence, labels, expect=False, values=None):
+    def _run(self, refs, logits, confidence, labels, expect=False, values=None, energies=None):
         """(forward's logits, False) -- or, with ``expect`` on the _mean_field_nchw_step_fused route, (their expected label
-        under ``values``, True)."""
-        E0 = -logits if confidence is None else -logits * confidence
+        under ``values``, True).  energies: E0 itself, on every route."""
+        if energies is not None and (logits is not None or confidence is not None):
+            raise ValueError("CRFasRNN: energies are E0 itself; logits and confidence must be None with them")
+        E0 = energies if energies is not None else -logits if confidence is None else -logits * confidence
         extra = () if labels is None else (labels,)
         if isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda and E0.dtype == torch.float32:
             grad = torch.is_grad_enabled() and (E0.requires_grad or refs.requires_grad

@@ -4,6 +4,8 @@ CRFwUncertainty, :138-163 CRFdepthUpsampler).  API surface only: the reference i
 with the guided-filter W (out of the lattice scope); ``lattice=True`` switches W to the
 permutohedral BatchedAdjacency.  The trainer classes (:14-60, :105-136) and ``__main__`` need the
 un-vendored ``oil`` package and Middlebury data and are not mirrored."""
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -73,6 +75,21 @@ class CRFwUncertainty(CRFdepthRefiner):
         return self.CRF.expected_depth(self._guide(imgrgb, features), logits, confidence), confidence
 
 
+# PHL_SCALAR_UNARIES=0 keeps the upsampler's prologue on its torch lines (read once).  A switch of its own: the prologue
+# is the same whether the loop behind it runs fused or plain (crf_module._NCHW_STEP).
+_SCALAR_UNARIES = os.environ.get("PHL_SCALAR_UNARIES", "1") not in ("", "0")
+
+
+def _scalar_unaries_routable(disp, mu):
+    """What phl.nchw_scalar_unaries computes in place of CRFdepthUpsampler's prologue: a non-empty fp32 CUDA [B, 1, h, w]
+    disparity that asks for no gradient (the kernel has none for it), and a ``charb`` Mu whose gamma and s are fp32 on the
+    disparity's device."""
+    if not (_SCALAR_UNARIES and torch.is_tensor(disp) and disp.is_cuda and disp.dtype == torch.float32 and disp.dim() == 4
+            and disp.shape[1] == 1 and disp.numel() > 0 and not disp.requires_grad and isinstance(mu, charb)):
+        return False
+    return all(p.dtype == torch.float32 and p.device == disp.device and p.numel() == 1 for p in (mu.gamma, mu.s))
+
+
 class CRFdepthUpsampler(nn.Module):
     def __init__(self, d_in=64, d_guide=3, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False):
         super().__init__()
@@ -80,7 +97,18 @@ class CRFdepthUpsampler(nn.Module):
                             fused_grad=fused_grad)
 
     def forward(self, inputs):
+        """fp32 CUDA inputs (_scalar_unaries_routable) get E0 and the labels from phl.nchw_scalar_unaries -- two launches,
+        no read-back -- and hand E0 to the CRF as it is; under autograd phl.NchwScalarUnaries gives gamma and s their
+        gradients.  Everything else is the torch lines below."""
         disp_lowres, img_highres, _ = inputs
+        if _scalar_unaries_routable(disp_lowres, self.CRF.Mu):
+            import phl
+
+            mu = self.CRF.Mu
+            fn = phl.nchw_scalar_unaries_fn if torch.is_grad_enabled() and (mu.gamma.requires_grad or mu.s.requires_grad) \
+                else phl.nchw_scalar_unaries
+            E0, labels = fn(disp_lowres, img_highres.shape[2:], 18, mu.gamma, mu.s)
+            return self.CRF.expected_depth(img_highres, None, energies=E0, labels=labels, values=labels)
         up = F.interpolate(disp_lowres, size=img_highres.shape[2:], mode="bilinear", align_corners=False)
         labels = torch.linspace(0, float(up.max()), 18, device=up.device)
         logits = -10 * self.CRF.Mu.get_energies_from_scalar(up, labels[None, :, None, None])

@@ -107,6 +107,9 @@ def load_library():
         if hasattr(lib, "phl_nchw_expected_value"):    # (an older build loaded through PHL_LIB lacks the expected label)
             lib.phl_nchw_expected_value.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, vp]
             lib.phl_nchw_expected_value_grad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]
+        if hasattr(lib, "phl_nchw_scalar_unaries"):    # (an older build loaded through PHL_LIB lacks the scalar unaries)
+            lib.phl_nchw_scalar_unaries.argtypes = [vp] * 5 + [i32] * 6 + [C.c_double, C.c_double, vp]
+            lib.phl_nchw_scalar_unaries_grad.argtypes = [vp] * 6 + [i32] * 6 + [C.c_double, C.c_double, vp]
         if hasattr(lib, "phl_compat_grad_x"):          # (an older build loaded through PHL_LIB lacks the backward)
             lib.phl_softmax_neg_grad.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, vp]
             lib.phl_uniform_compat_grad.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, vp, i64, vp, i64, i64, i32, vp]
@@ -852,6 +855,93 @@ class NchwExpectedValue(torch.autograd.Function):
 def nchw_expected_value_fn(X, G=None, labels=None, negate=False):
     """Differentiable ``nchw_expected_value``: NchwExpectedValue.apply(X, G, labels, negate)."""
     return NchwExpectedValue.apply(X, G, labels, negate)
+
+
+# ---------------------------------------------------------------------------------------------
+# the upsampler head's unaries from a scalar disparity (crf/mb_stereo_crf.py; include/phl.h, phl_nchw_scalar.hip)
+NCHW_SCALAR_PIXELS = 1024            # PHL_NCHW_SCALAR_PIXELS: pixels of a workgroup of the scalar-unary kernels
+
+
+def _scalar_operands(name, disp, size, L, gamma, s):
+    """(disp contiguous, gamma, s, B, h, w, H, W, L) of the scalar-unary entry points: disp fp32 CUDA [B, 1, h, w] with at
+    least one element, gamma and s fp32 tensors of one element on its device (read there, never on the host)."""
+    for t in (disp, gamma, s):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
+            raise TypeError(f"{name}: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+    if disp.dim() != 4 or disp.shape[1] != 1 or disp.numel() == 0:
+        raise ValueError(f"{name}: disp must be a non-empty [B, 1, h, w], got {tuple(disp.shape)}")
+    if gamma.numel() != 1 or s.numel() != 1 or gamma.device != disp.device or s.device != disp.device:
+        raise ValueError(f"{name}: gamma and s must hold one value each on disp's device")
+    H, W = (int(v) for v in size)
+    L = int(L)
+    if L < 2 or H < 1 or W < 1:
+        raise ValueError(f"{name}: needs L >= 2 and an output size >= 1 x 1, got L={L}, size={(H, W)}")
+    B, _, h, w = (int(v) for v in disp.shape)
+    return disp.detach().contiguous(), gamma.detach(), s.detach(), B, h, w, H, W, L
+
+
+def nchw_scalar_unaries(disp, size, L, gamma, s, *, scale=10.0, threshold=1e-2):
+    """(E0 [B, L, H, W], labels [L]) of the upsampler head in two launches, nothing read back on the host
+    (phl_nchw_scalar_unaries): with ``up = F.interpolate(disp, size, mode="bilinear", align_corners=False)`` (evaluated in
+    float64 per output pixel, never written), ``lmax = up.max()`` and ``labels = linspace(0, lmax, L)``,
+
+        E0 = scale * exp(s) * (sqrt(g^2 + (labels[a] - up)^2) - g) * (up > threshold),      g = gamma * lmax
+
+    -- CRFasRNN's ``-logits * confidence`` for the head's ``logits = -10 * charb.get_energies_from_scalar(up, labels)`` and
+    ``confidence = (up > 1e-2).float()``.  disp: fp32 CUDA [B, 1, h, w]; size: (H, W), any ratio; gamma, s: fp32 CUDA tensors
+    of one element (charb's parameters), read on the device.  Float64 between the loads and the one fp32 store."""
+    d, gm, sv, B, h, w, H, W, L = _scalar_operands("nchw_scalar_unaries", disp, size, L, gamma, s)
+    E0 = torch.empty((B, L, H, W), dtype=torch.float32, device=disp.device)
+    labels = torch.empty((L,), dtype=torch.float32, device=disp.device)
+    _launch(disp.device, "phl_nchw_scalar_unaries", _ptr(d), _ptr(gm), _ptr(sv), _ptr(E0), _ptr(labels), B, h, w, H, W, L,
+            float(scale), float(threshold))
+    return E0, labels
+
+
+def nchw_scalar_unaries_grad(disp, size, labels, gamma, s, gE0, *, scale=10.0, threshold=1e-2):
+    """(grad_gamma, grad_s), 0-dim fp32, of ``nchw_scalar_unaries`` for the upstream gradient gE0 [B, L, H, W]
+    (phl_nchw_scalar_unaries_grad).  labels: the forward's.  gE0 is read once and everything else recomputed from the
+    forward's inputs; float64 sums in a fixed order, the same bits on every call.  There is no gradient for disp."""
+    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.float32 and labels.dim() == 1):
+        raise TypeError("nchw_scalar_unaries_grad: labels must be the fp32 CUDA [L] tensor the forward returned")
+    d, gm, sv, B, h, w, H, W, L = _scalar_operands("nchw_scalar_unaries_grad", disp, size, labels.numel(), gamma, s)
+    if not (torch.is_tensor(gE0) and gE0.is_cuda and gE0.dtype == torch.float32 and gE0.device == disp.device
+            and labels.device == disp.device):
+        raise TypeError("nchw_scalar_unaries_grad: gE0 and labels must be fp32 CUDA tensors on disp's device")
+    if tuple(gE0.shape) != (B, L, H, W):
+        raise ValueError(f"nchw_scalar_unaries_grad: gE0 must be {(B, L, H, W)}, got {tuple(gE0.shape)}")
+    grad = torch.empty((2,), dtype=torch.float32, device=disp.device)
+    _launch(disp.device, "phl_nchw_scalar_unaries_grad", _ptr(d), _ptr(labels.detach().contiguous()), _ptr(gm), _ptr(sv),
+            _ptr(gE0.detach().contiguous()), _ptr(grad), B, h, w, H, W, L, float(scale), float(threshold))
+    return grad[0], grad[1]
+
+
+class NchwScalarUnaries(torch.autograd.Function):
+    """``nchw_scalar_unaries`` with its backward on phl_nchw_scalar_unaries_grad: gradients for gamma and s, none for
+    disp; the labels are marked non-differentiable (the reference's ``float(up.max())`` cuts their graph).  Saves disp,
+    the labels, gamma and s -- nothing of E0's size."""
+
+    @staticmethod
+    def forward(ctx, disp, size, L, gamma, s, scale=10.0, threshold=1e-2):
+        E0, labels = nchw_scalar_unaries(disp, size, L, gamma, s, scale=scale, threshold=threshold)
+        ctx.size, ctx.scale, ctx.threshold = tuple(size), scale, threshold
+        ctx.save_for_backward(disp, labels, gamma, s)
+        ctx.mark_non_differentiable(labels)
+        return E0, labels
+
+    @staticmethod
+    def backward(ctx, gE0, _glabels):
+        disp, labels, gamma, s = ctx.saved_tensors
+        gg = gs = None
+        if any(ctx.needs_input_grad[3:5]):
+            gg, gs = nchw_scalar_unaries_grad(disp, ctx.size, labels, gamma, s, gE0, scale=ctx.scale, threshold=ctx.threshold)
+            gg, gs = gg.reshape(gamma.shape), gs.reshape(s.shape)
+        return (None, None, None, gg if ctx.needs_input_grad[3] else None, gs if ctx.needs_input_grad[4] else None, None, None)
+
+
+def nchw_scalar_unaries_fn(disp, size, L, gamma, s, scale=10.0, threshold=1e-2):
+    """Differentiable ``nchw_scalar_unaries``: NchwScalarUnaries.apply(disp, size, L, gamma, s, scale, threshold)."""
+    return NchwScalarUnaries.apply(disp, size, L, gamma, s, scale, threshold)
 
 
 # ---------------------------------------------------------------------------------------------

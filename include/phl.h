@@ -340,6 +340,35 @@ int phl_nchw_expected_value(const float *X_dev, const float *G_dev, const float 
                             int64_t n, int negate, phl_stream stream);
 int phl_nchw_expected_value_grad(const float *X_dev, const float *G_dev, const float *labels_dev, const float *gout_dev,
                                  float *gZ_dev, int B, int L, int64_t n, int negate, phl_stream stream);
+/* ---- the unary energies of the upsampler head from a scalar disparity (crf/mb_stereo_crf.py, CRFdepthUpsampler) ------
+ * For disp [B][1][h][w] and an output size (H, W): up[b,y,x] = torch's bilinear interpolation with align_corners=False,
+ * no antialias, any ratio (src = max(0, (dst + 0.5) * in/out - 0.5), i0 = floor(src), i1 = min(i0 + 1, in - 1), lambda =
+ * src - i0), evaluated in float64 from the fp32 samples; lmax = the fp32 value nearest to max(up) over the batch;
+ * labels[i] = the fp32 value nearest to lmax * i / (L - 1) (labels[0] = 0, labels[L-1] = lmax exactly);
+ *   E0[b,a,y,x] = scale * exp(s) * (sqrt(g^2 + d^2) - g),  g = gamma * lmax,  d = labels[a] - up[b,y,x]
+ * where (float)up > (float)threshold, and +0.0 elsewhere -- the reference's -(-10 get_energies_from_scalar(up, labels)) *
+ * (up > 1e-2) with scale = 10, threshold = 1e-2.  Float64 between the fp32 loads and the one fp32 store.
+ * phl_nchw_scalar_unaries: two launches on the stream, nothing read back.  The first evaluates up per output pixel (no
+ * [B][H][W] plane is written), reduces the maximum and writes labels[L]; the second writes E0 [B][L][H*W], a thread owning
+ * four pixels and walking the L planes: float4 stores when H*W % 4 == 0 and E0 is 16-byte aligned, dwords otherwise.
+ * gamma, s: one fp32 value each IN DEVICE MEMORY (charb's parameters).  Its scratch (the maxima of the at most 256 workgroups of the first launch) is a
+ * stream-ordered allocation.
+ * phl_nchw_scalar_unaries_grad: from disp, labels (the forward's), gamma, s and the upstream gE0 [B][L][H*W]
+ *   grad[0] = grad_gamma = sum gE0 * c * scale * exp(s) * lmax * (g / r - 1),  r = sqrt(g^2 + d^2)  (r == 0: the term is 0)
+ *   grad[1] = grad_s     = sum gE0 * E0
+ * with c the mask above and lmax = labels[L-1].  gE0 is read once, everything else recomputed; products and sums are
+ * float64, one partial pair per workgroup added in index order by a second kernel: no atomics, the same bits on every
+ * call.  disp, labels and lmax get no gradient (the reference's float(up.max()) cuts that graph).
+ * Status, checked before any HIP call: PHL_ERR_INVALID for L < 2, any of h, w, H, W < 1 or B < 0; then B == 0 is PHL_OK
+ * with nothing launched; then PHL_ERR_INVALID for a NULL pointer or an output that is one of the inputs;
+ * PHL_ERR_TOO_LARGE when B*L*H*W*4 or B*h*w*4 bytes leave int64 or the workgroups (PHL_NCHW_SCALAR_PIXELS pixels each)
+ * leave 2^31 - 1. */
+#define PHL_NCHW_SCALAR_PIXELS 1024
+int phl_nchw_scalar_unaries(const float *disp_dev, const float *gamma_dev, const float *s_dev, float *E0_dev, float *labels_dev,
+                            int B, int h, int w, int H, int W, int L, double scale, double threshold, phl_stream stream);
+int phl_nchw_scalar_unaries_grad(const float *disp_dev, const float *labels_dev, const float *gamma_dev, const float *s_dev,
+                                 const float *gE0_dev, float *grad_dev, int B, int h, int w, int H, int W, int L, double scale,
+                                 double threshold, phl_stream stream);
 /* ---- backward of the compatibility + softmax step (CRF training) ---------------------------------------------
  * Forward: Q = softmax(-E), E = E0 + X Mu.  With the upstream gradient gQ: dE = Q (s - gQ), s[p] = sum_c gQ[p,c] Q[p,c];
  * gE0 = dE, gX = dE Mu^T, gMu = X^T dE.  All entry points: fp32 rows with unit channel stride, row strides % 4 == 0,
