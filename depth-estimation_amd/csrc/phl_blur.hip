@@ -23,23 +23,17 @@
 // coordinates: f = i / sigma = fl + i0 / sigma and every f-term of the gradient is shift invariant, so the cancellation
 // between f B(g) and B(g f) is bounded by the chunk, not by the line length), writes grad_x = B(g) when asked, and sums
 //   D f - B(g) v,   D = v fl B(g) - v B(g fl) + g fl B(v) - g B(v fl)      (= -grad_f of the reference)
-// per workgroup in fp64 into one partial; k_box_grad_sum adds the partials in a fixed order: grad_sigma = sum / sigma.
+// per workgroup in fp64 into one partial; k_sum_partials<1> (phl_reduce.h) adds the partials in a fixed order:
+// grad_sigma = sum / sigma.
 #include <math.h>
 
-#include "phl_internal.h"
+#include "phl_reduce.h"
 
 namespace {
 
 constexpr int SB = 16;              // steps per staged block (inner == 1 form)
 constexpr int TP = SB + 1;          // padded tile row: lane l reads word l * 17 + s, 32 distinct banks per lane group
 constexpr int CB = 8;               // steps of loads issued ahead (inner >= 2 form)
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 template <bool ROWS, int K, bool GRAD>
 __global__ __launch_bounds__(64) void k_box_cascade(const float *__restrict__ x, const float *__restrict__ gin,
@@ -218,23 +212,6 @@ __global__ __launch_bounds__(64) void k_box_cascade(const float *__restrict__ x,
     }
 }
 
-// grad_sigma = inv_sigma * sum(partial[0 .. n)): strided per-thread sums in index order, then a fixed tree -- the same
-// bits on every run
-__global__ __launch_bounds__(256) void k_box_grad_sum(const double *__restrict__ partial, int64_t n, double inv_sigma,
-                                                      float *__restrict__ grad_sigma)
-{
-    __shared__ double red[256];
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 256) s += partial[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *grad_sigma = (float)(red[0] * inv_sigma);
-}
-
 // ---- geometry ----------------------------------------------------------------------------------------------------
 struct Geom {
     bool rows;
@@ -386,8 +363,8 @@ int phl_box_blur_grad(const float *v, const float *g, int64_t outer, int64_t h, 
         rc = rows ? launch_one<true, 3, true>(v, g, grad_x, partial, outer, h, inner, re, 1.0 / sigma, gm, st)
                   : launch_one<false, 3, true>(v, g, grad_x, partial, outer, h, inner, re, 1.0 / sigma, gm, st);
     if (rc == PHL_OK) {
-        k_box_grad_sum<<<dim3(1), dim3(256), 0, st>>>(partial, nparts, 1.0 / sigma, grad_sigma);
-        phl_launched(rc, "k_box_grad_sum");
+        k_sum_partials<1><<<dim3(1), dim3(256), 0, st>>>(partial, nparts, 1.0 / sigma, grad_sigma);
+        phl_launched(rc, "k_sum_partials");
     }
     return tmp.release();
 }

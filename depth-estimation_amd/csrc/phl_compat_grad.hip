@@ -18,7 +18,7 @@
 // any n.  Every access is a 16-byte piece of a row (L % 4 == 0: a piece is wholly inside the row or wholly outside).
 #include <math.h>
 
-#include "phl_internal.h"
+#include "phl_reduce.h"
 
 namespace {
 
@@ -28,12 +28,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // beta dE from the same registers (one read of Q and gQ, two writes).  The row sums and dE itself are formed in fp64 and
 // rounded once (the pass is bound by its bytes: the fp64 arithmetic is free), so dE carries half an ulp, not the
 // rounding of an f32 dot product -- the products behind it start from the most accurate operand there is.
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 template <int NV, bool LOGITS, bool UNIFORM>
 __global__ __launch_bounds__(256) void k_softmax_neg_grad(const float *__restrict__ Q, int64_t q_rs,
                                                           const float *__restrict__ gQ, int64_t g_rs, float alpha, float beta,

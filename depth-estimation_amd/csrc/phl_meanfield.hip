@@ -12,21 +12,9 @@
 
 #include "phl_internal.h"
 #include "phl_compat_common.h"
+#include "phl_reduce.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // NV = float4 per lane held in registers: rows up to NV*256 channels in one pass
 template <int NV>

@@ -32,15 +32,15 @@
 //   k_nchw_stream   L > 256 (UNIFORM up to 1024, SOFTMAX any): a thread per pixel walks its column in memory, three
 //                   reading passes (max, sum, quotient) and for UNIFORM a fourth over its own output.
 //   k_nchw_logits   out = -(E0 + G): what CRFasRNN returns after the last iteration.
-// No atomics, every sum in a fixed order: a repeated call gives the same bits.
+// No atomics, every sum in a fixed order: a repeated call gives the same bits.  The host side (tile counts, the float4
+// predicate, the VEC dispatch, the argument checks) is phl_nchw_common.h's, shared with the other channel-major files.
 #include <math.h>
 
-#include "phl_internal.h"
+#include "phl_nchw_common.h"
 
 namespace {
 
-constexpr int TP = 64;                 // pixels of a tile
-constexpr int NT = 256;                // threads of a workgroup: 4 per pixel in the softmax, 4 waves in the product
+constexpr int TP = 64;                 // pixels of a tile; its NT = 256 threads: 4 per pixel in the softmax, 4 waves in the product
 constexpr int VALU_MAX_L = 32;         // the product runs on the VALU up to here, on the matrix cores above
 constexpr int TILE_MAX_L = 256;        // k_nchw_tile's range
 enum { T_MFMA = 0, T_VALU = 1, T_UNIFORM = 2, T_SOFTMAX = 3 };
@@ -245,18 +245,15 @@ template <int MODE>
 int launch_tile(const float *E0, const float *G, const float *M, float alpha, float beta, float *out, int B, int L, int64_t n,
                 hipStream_t st)
 {
-    const int tiles = (int)((n + TP - 1) / TP);
+    const int tiles = nchw_tiles(n, TP);
     const size_t lds = tile_lds_bytes(L);
-    const dim3 grid((unsigned)((int64_t)B * tiles));
-    if (n % 4 == 0 && phl_al16(E0) && phl_al16(G) && phl_al16(out)) {
-        if (const int rc = phl_allow_lds(&k_nchw_tile<MODE, true>, lds)) return rc;
-        k_nchw_tile<MODE, true><<<grid, dim3(NT), lds, st>>>(E0, G, M, alpha, beta, out, L, n, tiles);
-    } else {
-        if (const int rc = phl_allow_lds(&k_nchw_tile<MODE, false>, lds)) return rc;
-        k_nchw_tile<MODE, false><<<grid, dim3(NT), lds, st>>>(E0, G, M, alpha, beta, out, L, n, tiles);
-    }
-    PHL_HIP(hipGetLastError());
-    return PHL_OK;
+    return nchw_dispatch(nchw_vec(n, {E0, G, out}), false, [&](auto vec, auto) -> int {
+        constexpr bool VEC = decltype(vec)::value;
+        if (const int rc = phl_allow_lds(&k_nchw_tile<MODE, VEC>, lds)) return rc;
+        k_nchw_tile<MODE, VEC><<<nchw_grid(B, tiles), dim3(NT), lds, st>>>(E0, G, M, alpha, beta, out, L, n, tiles);
+        PHL_HIP(hipGetLastError());
+        return PHL_OK;
+    });
 }
 
 }  // namespace
@@ -266,35 +263,24 @@ extern "C" {
 int phl_nchw_softmax_compat(const float *E0, const float *G, const float *mu, float alpha, float beta, float *out, int B, int L,
                             int64_t n, int mode, phl_stream stream)
 {
+    const char *who = "phl_nchw_softmax_compat";
     const bool known = mode == PHL_NCHW_PRODUCT || mode == PHL_NCHW_UNIFORM || mode == PHL_NCHW_SOFTMAX || mode == PHL_NCHW_LOGITS;
-    if (B < 0 || n < 0 || L < 1 || !known || (mode == PHL_NCHW_UNIFORM && !(isfinite(alpha) && isfinite(beta)))) {
-        phl_set_error("phl_nchw_softmax_compat: bad arguments (B=%d L=%d n=%lld mode=%d alpha=%g beta=%g)", B, L, (long long)n, mode,
-                      (double)alpha, (double)beta);
-        return PHL_ERR_INVALID;
-    }
-    if (B == 0 || n == 0) return PHL_OK;
-    if (!E0 || !out || (mode == PHL_NCHW_PRODUCT && !mu) || (mode == PHL_NCHW_LOGITS && !G)) {
-        phl_set_error("phl_nchw_softmax_compat: null E0 / out%s", mode == PHL_NCHW_PRODUCT ? " / mu" : mode == PHL_NCHW_LOGITS ? " / G" : "");
-        return PHL_ERR_INVALID;
-    }
-    if (out == E0 || out == G) {
-        phl_set_error("phl_nchw_softmax_compat: out aliases an input");
-        return PHL_ERR_INVALID;
-    }
-    const int64_t planes = (int64_t)B * L, lim = INT64_MAX / 4;          // B, L <= 2^31 - 1: their product stays in int64
-    const int64_t px = L > TILE_MAX_L ? NT : TP;                          // pixels of a workgroup (the logits' grid is capped)
-    if (n > lim / planes || (mode != PHL_NCHW_LOGITS && (n + px - 1) / px > INT32_MAX / (int64_t)B)) {
-        phl_set_error("phl_nchw_softmax_compat: %d x %d x %lld elements are too many", B, L, (long long)n);
-        return PHL_ERR_TOO_LARGE;
-    }
+    const bool bad = B < 0 || n < 0 || L < 1 || !known || (mode == PHL_NCHW_UNIFORM && !(isfinite(alpha) && isfinite(beta)));
+    const int px = mode == PHL_NCHW_LOGITS ? 0 : L > TILE_MAX_L ? NT : TP;      // pixels of a workgroup (the logits' grid is capped)
+    int rc;
+    if (nchw_check(who, nchw_text("B=%d L=%d n=%lld mode=%d alpha=%g beta=%g", B, L, (long long)n, mode, (double)alpha, (double)beta).s,
+                   bad, B == 0 || n == 0, {E0, out, mode == PHL_NCHW_PRODUCT ? mu : out, mode == PHL_NCHW_LOGITS ? G : out},
+                   mode == PHL_NCHW_PRODUCT ? "E0 / out / mu" : mode == PHL_NCHW_LOGITS ? "E0 / out / G" : "E0 / out", {E0, G}, out,
+                   "out", B, L, n, px, rc))
+        return rc;
     if ((mode == PHL_NCHW_PRODUCT && L > TILE_MAX_L) || (mode == PHL_NCHW_UNIFORM && L > 1024)) {
-        phl_set_error("phl_nchw_softmax_compat: %d labels, at most %d in this mode", L, mode == PHL_NCHW_PRODUCT ? TILE_MAX_L : 1024);
+        phl_set_error("%s: %d labels, at most %d in this mode", who, L, mode == PHL_NCHW_PRODUCT ? TILE_MAX_L : 1024);
         return PHL_ERR_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)stream;
     if (mode == PHL_NCHW_LOGITS) {
-        const int64_t total = planes * n;
-        const bool vec = total % 4 == 0 && phl_al16(E0) && phl_al16(G) && phl_al16(out);
+        const int64_t total = (int64_t)B * L * n;
+        const bool vec = nchw_vec(total, {E0, G, out});
         const int64_t count = vec ? total / 4 : total, want = (count + NT - 1) / NT;
         const dim3 grid((unsigned)(want < 65536 ? want : 65536));
         if (vec) k_nchw_logits<true><<<grid, dim3(NT), 0, st>>>(E0, G, out, count);
@@ -303,10 +289,9 @@ int phl_nchw_softmax_compat(const float *E0, const float *G, const float *mu, fl
         return PHL_OK;
     }
     if (L > TILE_MAX_L) {
-        const int tiles = (int)((n + NT - 1) / NT);
-        const dim3 grid((unsigned)((int64_t)B * tiles));
-        if (mode == PHL_NCHW_UNIFORM) k_nchw_stream<true><<<grid, dim3(NT), 0, st>>>(E0, G, alpha, beta, out, L, n, tiles);
-        else k_nchw_stream<false><<<grid, dim3(NT), 0, st>>>(E0, G, alpha, beta, out, L, n, tiles);
+        const int tiles = nchw_tiles(n, NT);
+        if (mode == PHL_NCHW_UNIFORM) k_nchw_stream<true><<<nchw_grid(B, tiles), dim3(NT), 0, st>>>(E0, G, alpha, beta, out, L, n, tiles);
+        else k_nchw_stream<false><<<nchw_grid(B, tiles), dim3(NT), 0, st>>>(E0, G, alpha, beta, out, L, n, tiles);
         PHL_HIP(hipGetLastError());
         return PHL_OK;
     }

@@ -9,14 +9,12 @@
 // is ONE kernel that reads X and G once and writes the plane; with sign = -1 it takes the mean-field loop's E0 and G as
 // they are, so the logits of the last iteration never exist in memory either (phl_nchw.hip, k_nchw_logits).
 //
-//   k_nchw_expect        a thread owns PX = 4 pixels of one image and walks their label planes once, BLK = 8 planes in
-//                        flight.  Per pixel it keeps the running maximum m, the sum s of exp(z - m) and the label-weighted
-//                        sum t (online softmax): the maximum of the eight new values is taken first, s and t are rescaled
-//                        by exp(m - m') where it rose -- one exp per element plus at most one per block.  m starts from
-//                        the first block's maximum (no exp(-inf - -inf)).  It ends with t / s.
-//                        float4 accesses when n % 4 == 0 and every pointer is 16-byte aligned (a thread's pixels are
-//                        4 t .. 4 t + 3 of the tile, and a float4 lies inside the image or outside); dwords otherwise (the
-//                        pixels are t, t + 256, t + 512, t + 768: a wave still reads 256 contiguous bytes per plane).
+//   k_nchw_expect        a thread walks the label planes of its four pixels once (the layout of phl_nchw_common.h),
+//                        BLK = 8 planes in flight.  Per pixel it keeps the running maximum m, the sum s of exp(z - m)
+//                        and the label-weighted sum t (online softmax): the maximum of the eight new values is taken
+//                        first, s and t are rescaled by exp(m - m') where it rose -- one exp per element plus at most
+//                        one per block.  m starts from the first block's maximum (no exp(-inf - -inf)).  It ends with
+//                        t / s.
 //   k_nchw_expect_grad   gZ[b, a, p] = sign * g[b, p] * q_a * (labels[a] - d), the gradient of X and of G alike.  Pass 1
 //                        is the forward's code (m, s, d); pass 2 reads X and G again and writes gZ = exp(z - m) * (w *
 //                        (labels[a] - d)), w = sign * g / s.  Nothing but the forward's inputs is needed.
@@ -35,15 +33,11 @@
 // order: a repeated call gives the same bits.
 #include <math.h>
 
-#include "phl_internal.h"
+#include "phl_nchw_common.h"
 
 namespace {
 
-constexpr int NT = 256;                // threads of a workgroup
-constexpr int PX = 4;                  // pixels of a thread
 constexpr int BLK = 8;                 // label planes in flight
-constexpr int WGP = NT * PX;           // pixels of a workgroup
-static_assert(WGP == PHL_NCHW_EXPECT_PIXELS, "include/phl.h documents the workgroup's pixel count");
 
 // x[i][j], g[i][j] of planes a0 .. a0 + BLK - 1 and lab[i] their labels; planes beyond L are left alone.  xp / gp: the
 // thread's first pixel in plane 0.  FULL: all BLK planes exist.
@@ -56,18 +50,16 @@ __device__ __forceinline__ void load_block(const float *xp, const float *gp, con
         const int a = a0 + i;                                    // wave-uniform
         if (FULL || a < L) {
             const float *xa = xp + (int64_t)a * n, *ga = HASG ? gp + (int64_t)a * n : nullptr;
-            if (VEC) {
-                const float4 v = *reinterpret_cast<const float4 *>(xa);
-                x[i][0] = v.x; x[i][1] = v.y; x[i][2] = v.z; x[i][3] = v.w;
-                if (HASG) {
-                    const float4 y = *reinterpret_cast<const float4 *>(ga);
-                    g[i][0] = y.x; g[i][1] = y.y; g[i][2] = y.z; g[i][3] = y.w;
-                }
+            // dwords of x and g: load_px's by hand, the two loads of a pixel under ONE guard (as two load_px calls, each
+            // guarded load in a branch of its own, these kernels took 1.33 times as long)
+            if (VEC || !HASG) {
+                load_px<VEC>(xa, ok, x[i]);
+                if (HASG) load_px<VEC>(ga, ok, g[i]);
             } else {
 #pragma unroll
                 for (int j = 0; j < PX; j++) {
                     x[i][j] = ok[j] ? xa[j * NT] : 0.f;
-                    if (HASG) g[i][j] = ok[j] ? ga[j * NT] : 0.f;
+                    g[i][j] = ok[j] ? ga[j * NT] : 0.f;
                 }
             }
             lab[i] = labels ? labels[a] : (float)a;
@@ -143,18 +135,6 @@ __device__ __forceinline__ void column_stats(const float *xp, const float *gp, c
     for (int j = 0; j < PX; j++) d[j] = (L == 1 && s[j] > 0.0) ? only : t[j] / s[j];
 }
 
-// The thread's place: q = its first pixel, ok[j] = pixel j lies inside the image; false: the thread has no pixel.
-template <bool VEC>
-__device__ __forceinline__ bool thread_pixels(int64_t n, int tiles, int &b, int64_t &q, bool (&ok)[PX])
-{
-    b = blockIdx.x / tiles;
-    const int tile = blockIdx.x - b * tiles;
-    q = (int64_t)tile * WGP + (VEC ? PX * (int)threadIdx.x : (int)threadIdx.x);
-#pragma unroll
-    for (int j = 0; j < PX; j++) ok[j] = VEC ? q < n : q + j * NT < n;      // VEC: n % 4 == 0
-    return ok[0];
-}
-
 template <bool VEC, bool HASG>
 __global__ __launch_bounds__(NT) void k_nchw_expect(const float *__restrict__ X, const float *__restrict__ G,
                                                     const float *__restrict__ labels, float *__restrict__ out, int L, int64_t n,
@@ -163,19 +143,14 @@ __global__ __launch_bounds__(NT) void k_nchw_expect(const float *__restrict__ X,
     int b;
     int64_t q;
     bool ok[PX];
-    if (!thread_pixels<VEC>(n, tiles, b, q, ok)) return;
+    if (!thread_pixels<VEC>(n, tiles, blockIdx.x, b, q, ok)) return;
     const int64_t base = (int64_t)b * L * n + q;
-    float m[PX];
+    float m[PX], r[PX];
     double s[PX], d[PX];
     column_stats<VEC, HASG>(X + base, HASG ? G + base : nullptr, labels, L, n, negate != 0, ok, m, s, d);
-    float *o = out + (int64_t)b * n + q;
-    if (VEC) {
-        *reinterpret_cast<float4 *>(o) = make_float4((float)d[0], (float)d[1], (float)d[2], (float)d[3]);
-    } else {
 #pragma unroll
-        for (int j = 0; j < PX; j++)
-            if (ok[j]) o[j * NT] = (float)d[j];
-    }
+    for (int j = 0; j < PX; j++) r[j] = (float)d[j];
+    store_px<VEC>(out + (int64_t)b * n + q, ok, r);
 }
 
 template <bool VEC, bool HASG, bool FULL>
@@ -192,14 +167,7 @@ __device__ __forceinline__ void grad_block(const float *xp, const float *gp, con
 #pragma unroll
             for (int j = 0; j < PX; j++)
                 r[j] = (float)(exp_rel(zval<HASG>(x[i][j], g[i][j], neg), m[j]) * (w[j] * ((double)lab[i] - d[j])));
-            float *o = zp + (int64_t)(a0 + i) * n;
-            if (VEC) {
-                *reinterpret_cast<float4 *>(o) = make_float4(r[0], r[1], r[2], r[3]);
-            } else {
-#pragma unroll
-                for (int j = 0; j < PX; j++)
-                    if (ok[j]) o[j * NT] = r[j];
-            }
+            store_px<VEC>(zp + (int64_t)(a0 + i) * n, ok, r);
         }
     }
 }
@@ -212,56 +180,19 @@ __global__ __launch_bounds__(NT) void k_nchw_expect_grad(const float *__restrict
     int b;
     int64_t q;
     bool ok[PX];
-    if (!thread_pixels<VEC>(n, tiles, b, q, ok)) return;
+    if (!thread_pixels<VEC>(n, tiles, blockIdx.x, b, q, ok)) return;
     const int64_t base = (int64_t)b * L * n + q;
     const float *xp = X + base, *gp = HASG ? G + base : nullptr;
     const bool neg = negate != 0;
     float m[PX], g[PX];
     double s[PX], d[PX], w[PX];
     column_stats<VEC, HASG>(xp, gp, labels, L, n, neg, ok, m, s, d);
-    const float *go = gout + (int64_t)b * n + q;
-    if (VEC) {
-        const float4 v = *reinterpret_cast<const float4 *>(go);
-        g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < PX; j++) g[j] = ok[j] ? go[j * NT] : 0.f;
-    }
+    load_px<VEC>(gout + (int64_t)b * n + q, ok, g);
 #pragma unroll
     for (int j = 0; j < PX; j++) w[j] = (double)(neg ? -g[j] : g[j]) / s[j];
     int a0 = 0;
     for (; a0 + BLK <= L; a0 += BLK) grad_block<VEC, HASG, true>(xp, gp, labels, gZ + base, a0, L, n, neg, ok, m, w, d);
     if (a0 < L) grad_block<VEC, HASG, false>(xp, gp, labels, gZ + base, a0, L, n, neg, ok, m, w, d);
-}
-
-// the argument checks both entry points share, in the order include/phl.h states; 1 = nothing to launch
-int check_args(const char *who, const float *X, const float *G, const float *labels, const float *gout, bool grad,
-               const float *result, int B, int L, int64_t n, int &status)
-{
-    status = PHL_OK;
-    if (B < 0 || n < 0 || L < 1) {
-        phl_set_error("%s: bad arguments (B=%d L=%d n=%lld)", who, B, L, (long long)n);
-        status = PHL_ERR_INVALID;
-        return 1;
-    }
-    if (B == 0 || n == 0) return 1;
-    if (!X || !result || (grad && !gout)) {
-        phl_set_error("%s: null %s", who, grad ? "X / gout / gZ" : "X / out");
-        status = PHL_ERR_INVALID;
-        return 1;
-    }
-    if (result == X || result == G || result == labels || (grad && result == gout)) {
-        phl_set_error("%s: %s aliases an input", who, grad ? "gZ" : "out");
-        status = PHL_ERR_INVALID;
-        return 1;
-    }
-    const int64_t planes = (int64_t)B * L, lim = INT64_MAX / 4;          // B, L <= 2^31 - 1: their product stays in int64
-    if (n > lim / planes || (n + WGP - 1) / WGP > INT32_MAX / (int64_t)B) {
-        phl_set_error("%s: %d x %d x %lld elements are too many", who, B, L, (long long)n);
-        status = PHL_ERR_TOO_LARGE;
-        return 1;
-    }
-    return 0;
 }
 
 }  // namespace
@@ -271,34 +202,34 @@ extern "C" {
 int phl_nchw_expected_value(const float *X, const float *G, const float *labels, float *out, int B, int L, int64_t n, int negate,
                             phl_stream stream)
 {
+    const char *who = "phl_nchw_expected_value";
     int rc;
-    if (check_args("phl_nchw_expected_value", X, G, labels, nullptr, false, out, B, L, n, rc)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles = (int)((n + WGP - 1) / WGP);
-    const dim3 grid((unsigned)((int64_t)B * tiles));
-    const bool vec = n % 4 == 0 && phl_al16(X) && phl_al16(G) && phl_al16(out);
-    if (vec && G) k_nchw_expect<true, true><<<grid, dim3(NT), 0, st>>>(X, G, labels, out, L, n, tiles, negate);
-    else if (vec) k_nchw_expect<true, false><<<grid, dim3(NT), 0, st>>>(X, G, labels, out, L, n, tiles, negate);
-    else if (G) k_nchw_expect<false, true><<<grid, dim3(NT), 0, st>>>(X, G, labels, out, L, n, tiles, negate);
-    else k_nchw_expect<false, false><<<grid, dim3(NT), 0, st>>>(X, G, labels, out, L, n, tiles, negate);
-    phl_launched(rc, "phl_nchw_expected_value");
+    if (nchw_check(who, nchw_text("B=%d L=%d n=%lld", B, L, (long long)n).s, B < 0 || n < 0 || L < 1, B == 0 || n == 0, {X, out},
+                   "X / out", {X, G, labels}, out, "out", B, L, n, WGP, rc))
+        return rc;
+    const int tiles = nchw_tiles(n);
+    nchw_dispatch(nchw_vec(n, {X, G, out}), G != nullptr, [&](auto vec, auto has_g) {
+        k_nchw_expect<decltype(vec)::value, decltype(has_g)::value>
+            <<<nchw_grid(B, tiles), dim3(NT), 0, (hipStream_t)stream>>>(X, G, labels, out, L, n, tiles, negate);
+    });
+    phl_launched(rc, who);
     return rc;
 }
 
 int phl_nchw_expected_value_grad(const float *X, const float *G, const float *labels, const float *gout, float *gZ, int B, int L,
                                  int64_t n, int negate, phl_stream stream)
 {
+    const char *who = "phl_nchw_expected_value_grad";
     int rc;
-    if (check_args("phl_nchw_expected_value_grad", X, G, labels, gout, true, gZ, B, L, n, rc)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles = (int)((n + WGP - 1) / WGP);
-    const dim3 grid((unsigned)((int64_t)B * tiles));
-    const bool vec = n % 4 == 0 && phl_al16(X) && phl_al16(G) && phl_al16(gout) && phl_al16(gZ);
-    if (vec && G) k_nchw_expect_grad<true, true><<<grid, dim3(NT), 0, st>>>(X, G, labels, gout, gZ, L, n, tiles, negate);
-    else if (vec) k_nchw_expect_grad<true, false><<<grid, dim3(NT), 0, st>>>(X, G, labels, gout, gZ, L, n, tiles, negate);
-    else if (G) k_nchw_expect_grad<false, true><<<grid, dim3(NT), 0, st>>>(X, G, labels, gout, gZ, L, n, tiles, negate);
-    else k_nchw_expect_grad<false, false><<<grid, dim3(NT), 0, st>>>(X, G, labels, gout, gZ, L, n, tiles, negate);
-    phl_launched(rc, "phl_nchw_expected_value_grad");
+    if (nchw_check(who, nchw_text("B=%d L=%d n=%lld", B, L, (long long)n).s, B < 0 || n < 0 || L < 1, B == 0 || n == 0,
+                   {X, gout, gZ}, "X / gout / gZ", {X, G, labels, gout}, gZ, "gZ", B, L, n, WGP, rc))
+        return rc;
+    const int tiles = nchw_tiles(n);
+    nchw_dispatch(nchw_vec(n, {X, G, gout, gZ}), G != nullptr, [&](auto vec, auto has_g) {
+        k_nchw_expect_grad<decltype(vec)::value, decltype(has_g)::value>
+            <<<nchw_grid(B, tiles), dim3(NT), 0, (hipStream_t)stream>>>(X, G, labels, gout, gZ, L, n, tiles, negate);
+    });
+    phl_launched(rc, who);
     return rc;
 }
 

@@ -13,14 +13,14 @@
 //                          the workgroup that arrives last, which reduces the workgroups' maxima and writes labels[L]
 //                          (labels[L - 1] = lmax).  The maximum does not depend on the order, so this is the same bits
 //                          whichever workgroup comes last.
-//   k_scalar_unaries       launch 2, the layout of phl_nchw_expect.hip: a thread owns PX = 4 pixels, evaluates up and the
-//                          mask once and walks the L planes; float4 stores when n % 4 == 0 and E0 is 16-byte aligned,
-//                          dwords otherwise.  Its only global traffic worth the name is one write of the volume.
+//   k_scalar_unaries       launch 2, the layout of phl_nchw_common.h: a thread evaluates up and the mask at its four
+//                          pixels once and walks the L planes.  Its only global traffic worth the name is one write of
+//                          the volume.
 //   k_scalar_grad          reads gE0 once in the same layout, recomputes up, the mask and r = sqrt(g^2 + delta^2), and sums
 //                            grad_s     = sum gE0 * E0
 //                            grad_gamma = sum gE0 * c * scale * exp(s) * lmax * (g / r - 1)        (a term with r == 0: 0)
-//                          per workgroup into one float64 pair; k_scalar_grad_sum adds the pairs in index order (the
-//                          scheme of k_box_grad / k_box_grad_sum, phl_blur.hip): no atomics, the same bits on every call.
+//                          per workgroup into one float64 pair; k_sum_partials<2> (phl_reduce.h) adds the pairs in index
+//                          order: no atomics, the same bits on every call.
 //
 // gamma and s are read from device memory (the 0-dim parameters of charb): nothing is read back on the host.
 //
@@ -30,14 +30,10 @@
 // scale * exp(s).  The float64 cancellation that remains is 1e-16 of g.
 #include <math.h>
 
-#include "phl_internal.h"
+#include "phl_nchw_common.h"
+#include "phl_reduce.h"
 
 namespace {
-
-constexpr int NT = 256;                // threads of a workgroup
-constexpr int PX = 4;                  // pixels of a thread
-constexpr int WGP = NT * PX;           // pixels of a workgroup
-static_assert(WGP == PHL_NCHW_SCALAR_PIXELS, "include/phl.h documents the workgroup's pixel count");
 
 // the bilinear sampling of one image: sizes and the ratios in / out
 struct Resize {
@@ -66,23 +62,17 @@ __device__ __forceinline__ double up_at(const float *__restrict__ img, const Res
     return (1.0 - ly) * ((1.0 - lx) * a + lx * b) + ly * ((1.0 - lx) * c + lx * d);
 }
 
-// The thread's place in tile blk of the B * tiles (phl_nchw_expect.hip, thread_pixels): b = its image, q = its first
-// pixel, ok[j] = pixel j lies inside the image, up[j] its sample; false: the thread has no pixel.  VEC: pixels q .. q + 3
-// (n % 4 == 0), else q + j NT.
+// thread_pixels of tile blk, and up[j] = the sample at pixel j (0 outside the image); false: the thread has no pixel
 template <bool VEC>
 __device__ __forceinline__ bool thread_samples(const float *__restrict__ disp, const Resize &z, int64_t n, int tiles, unsigned blk,
                                                int &b, int64_t &q, bool (&ok)[PX], double (&up)[PX])
 {
-    b = blk / tiles;
-    const int tile = blk - b * tiles;
-    q = (int64_t)tile * WGP + (VEC ? PX * (int)threadIdx.x : (int)threadIdx.x);
-    if (q >= n) return false;
+    if (!thread_pixels<VEC>(n, tiles, blk, b, q, ok)) return false;
     const float *img = disp + (int64_t)b * z.h * z.w;
     int y = n <= INT32_MAX ? (int)((unsigned)q / (unsigned)z.W) : (int)(q / z.W);      // (wave-uniform choice)
     unsigned x = (unsigned)(q - (int64_t)y * z.W);               // x + NT < 2^32
 #pragma unroll
     for (int j = 0; j < PX; j++) {
-        ok[j] = VEC ? true : q + j * NT < n;
         up[j] = ok[j] ? up_at(img, z, y, (int)x) : 0.0;
         x += VEC ? 1u : (unsigned)NT;
         if (x >= (unsigned)z.W) {
@@ -91,29 +81,6 @@ __device__ __forceinline__ bool thread_samples(const float *__restrict__ disp, c
         }
     }
     return true;
-}
-
-__device__ __forceinline__ float wave_max_f(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// max over the workgroup, in every thread; red is free again behind the caller's next barrier
-__device__ __forceinline__ float block_max_f(float v, float *red)
-{
-    v = wave_max_f(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
 // Launch 1, at most MAX_GRID workgroups that stride over the `total` tiles.  part[gridDim.x]: the workgroups' maxima,
@@ -197,13 +164,7 @@ __global__ __launch_bounds__(NT) void k_scalar_unaries(const float *__restrict__
             const double d = lab - up[j];
             e[j] = c[j] ? (float)(p.k * (sqrt(g2 + d * d) - p.g)) : 0.f;
         }
-        if (VEC) {
-            *reinterpret_cast<float4 *>(o) = make_float4(e[0], e[1], e[2], e[3]);
-        } else {
-#pragma unroll
-            for (int j = 0; j < PX; j++)
-                if (ok[j]) o[j * NT] = e[j];
-        }
+        store_px<VEC>(o, ok, e);
     }
 }
 
@@ -229,13 +190,7 @@ __global__ __launch_bounds__(NT) void k_scalar_grad(const float *__restrict__ di
         for (int a = 0; a < L; a++, gp += n) {
             const double lab = labels[a];
             float ge[PX];
-            if (VEC) {
-                const float4 v = *reinterpret_cast<const float4 *>(gp);
-                ge[0] = v.x; ge[1] = v.y; ge[2] = v.z; ge[3] = v.w;
-            } else {
-#pragma unroll
-                for (int j = 0; j < PX; j++) ge[j] = ok[j] ? gp[j * NT] : 0.f;
-            }
+            load_px<VEC>(gp, ok, ge);
 #pragma unroll
             for (int j = 0; j < PX; j++) {
                 const double d = lab - up[j], r = sqrt(g2 + d * d);
@@ -260,57 +215,23 @@ __global__ __launch_bounds__(NT) void k_scalar_grad(const float *__restrict__ di
     }
 }
 
-// grad[0] = grad_gamma, grad[1] = grad_s: strided per-thread sums of the nparts pairs in index order, then a fixed tree
-__global__ __launch_bounds__(256) void k_scalar_grad_sum(const double *__restrict__ partial, int64_t nparts, float *__restrict__ grad)
+// The argument checks both entry points share, in the order include/phl.h states (the forward's second output, labels,
+// is checked against its inputs by the forward itself); true: nothing to launch
+bool check_args(const char *who, const float *disp, const float *labels, const float *gamma, const float *s, const float *gE0,
+                bool grad, const float *result, int B, int h, int w, int H, int W, int L, int &status)
 {
-    __shared__ double red[2][256];
-    double sg = 0.0, ss = 0.0;
-    for (int64_t i = threadIdx.x; i < nparts; i += 256) {
-        sg += partial[2 * i];
-        ss += partial[2 * i + 1];
-    }
-    red[0][threadIdx.x] = sg;
-    red[1][threadIdx.x] = ss;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 2) grad[threadIdx.x] = (float)red[threadIdx.x][0];
-}
-
-// the argument checks both entry points share, in the order include/phl.h states; 1 = nothing to launch
-int check_args(const char *who, const float *disp, const float *labels, const float *gamma, const float *s, const float *gE0,
-               bool grad, const float *result, int B, int h, int w, int H, int W, int L, int &status)
-{
-    status = PHL_OK;
-    if (L < 2 || h < 1 || w < 1 || H < 1 || W < 1 || B < 0) {
-        phl_set_error("%s: bad arguments (B=%d h=%d w=%d H=%d W=%d L=%d)", who, B, h, w, H, W, L);
-        status = PHL_ERR_INVALID;
-        return 1;
-    }
-    if (B == 0) return 1;
-    if (!disp || !labels || !gamma || !s || !result || (grad && !gE0)) {
-        phl_set_error("%s: null %s", who, grad ? "disp / labels / gamma / s / gE0 / grad" : "disp / gamma / s / E0 / labels");
-        status = PHL_ERR_INVALID;
-        return 1;
-    }
-    // (the forward's second output, labels, is checked against its inputs by the caller of this function)
-    if (result == disp || result == gamma || result == s || result == labels || (grad && result == gE0)) {
-        phl_set_error("%s: %s aliases an input", who, grad ? "grad" : "E0");
-        status = PHL_ERR_INVALID;
-        return 1;
-    }
-    const int64_t n = (int64_t)H * W, planes = (int64_t)B * L, lim = INT64_MAX / 4;   // H, W, B, L <= 2^31 - 1: no overflow
-    if (n > lim / planes || (int64_t)h * w > lim / B || (n + WGP - 1) / WGP > INT32_MAX / (int64_t)B) {
-        phl_set_error("%s: %d x %d x %d x %d elements (from %d x %d) are too many", who, B, L, H, W, h, w);
+    const nchw_text sizes("B=%d L=%d H=%d W=%d from h=%d w=%d", B, L, H, W, h, w);
+    if (nchw_check(who, sizes.s, L < 2 || h < 1 || w < 1 || H < 1 || W < 1 || B < 0, B == 0,
+                   {disp, labels, gamma, s, result, grad ? gE0 : result},
+                   grad ? "disp / labels / gamma / s / gE0 / grad" : "disp / gamma / s / E0 / labels", {disp, gamma, s, labels, gE0},
+                   result, grad ? "grad" : "E0", B, L, (int64_t)H * W, WGP, status))
+        return true;
+    if (nchw_too_large(B, 1, (int64_t)h * w, 0)) {              // the disparity alone (h, w <= 2^31 - 1: no overflow)
+        phl_set_error("%s: too many elements (%s)", who, sizes.s);
         status = PHL_ERR_TOO_LARGE;
-        return 1;
+        return true;
     }
-    return 0;
+    return false;
 }
 
 inline Resize resize(int h, int w, int H, int W)
@@ -334,8 +255,8 @@ int phl_nchw_scalar_unaries(const float *disp, const float *gamma, const float *
     }
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)H * W;
-    const int tiles = (int)((n + WGP - 1) / WGP);
-    const unsigned blocks = (unsigned)((int64_t)B * tiles);
+    const int tiles = nchw_tiles(n);
+    const unsigned blocks = nchw_grid(B, tiles).x;
     const Resize z = resize(h, w, H, W);
     // scratch: 16 bytes that hold the arrival counter (the block the memset zeroes), then one maximum per workgroup
     const unsigned grid1 = blocks < MAX_GRID ? blocks : MAX_GRID;
@@ -344,10 +265,10 @@ int phl_nchw_scalar_unaries(const float *disp, const float *gamma, const float *
     if (tmp.rc != PHL_OK) return tmp.release();
     PHL_HIP(hipMemsetAsync(words, 0, 16, st));
     k_scalar_max<<<dim3(grid1), dim3(NT), 0, st>>>(disp, z, n, tiles, blocks, L, reinterpret_cast<float *>(words + 4), words, labels);
-    if (n % 4 == 0 && phl_al16(E0))
-        k_scalar_unaries<true><<<dim3(blocks), dim3(NT), 0, st>>>(disp, labels, gamma, s, E0, z, n, tiles, L, scale, (float)threshold);
-    else
-        k_scalar_unaries<false><<<dim3(blocks), dim3(NT), 0, st>>>(disp, labels, gamma, s, E0, z, n, tiles, L, scale, (float)threshold);
+    nchw_dispatch(nchw_vec(n, {E0}), false, [&](auto vec, auto) {
+        k_scalar_unaries<decltype(vec)::value>
+            <<<dim3(blocks), dim3(NT), 0, st>>>(disp, labels, gamma, s, E0, z, n, tiles, L, scale, (float)threshold);
+    });
     phl_launched(tmp.rc, who);
     return tmp.release();
 }
@@ -361,17 +282,17 @@ int phl_nchw_scalar_unaries_grad(const float *disp, const float *labels, const f
     if (check_args(who, disp, labels, gamma, s, gE0, true, grad, B, h, w, H, W, L, rc)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = (int64_t)H * W;
-    const int tiles = (int)((n + WGP - 1) / WGP);
-    const unsigned blocks = (unsigned)((int64_t)B * tiles);
+    const int tiles = nchw_tiles(n);
+    const unsigned blocks = nchw_grid(B, tiles).x;
     const Resize z = resize(h, w, H, W);
     phl_temps tmp(st);
     double *partial = tmp.get<double>(2 * (size_t)blocks);
     if (tmp.rc != PHL_OK) return tmp.release();
-    if (n % 4 == 0 && phl_al16(gE0))
-        k_scalar_grad<true><<<dim3(blocks), dim3(NT), 0, st>>>(disp, labels, gamma, s, gE0, partial, z, n, tiles, L, scale, (float)threshold);
-    else
-        k_scalar_grad<false><<<dim3(blocks), dim3(NT), 0, st>>>(disp, labels, gamma, s, gE0, partial, z, n, tiles, L, scale, (float)threshold);
-    k_scalar_grad_sum<<<dim3(1), dim3(256), 0, st>>>(partial, (int64_t)blocks, grad);
+    nchw_dispatch(nchw_vec(n, {gE0}), false, [&](auto vec, auto) {
+        k_scalar_grad<decltype(vec)::value>
+            <<<dim3(blocks), dim3(NT), 0, st>>>(disp, labels, gamma, s, gE0, partial, z, n, tiles, L, scale, (float)threshold);
+    });
+    k_sum_partials<2><<<dim3(1), dim3(256), 0, st>>>(partial, (int64_t)blocks, 1.0, grad);      // grad[0] = grad_gamma, grad[1] = grad_s
     phl_launched(tmp.rc, who);
     return tmp.release();
 }

@@ -733,6 +733,33 @@ NCHW_PRODUCT, NCHW_UNIFORM, NCHW_SOFTMAX, NCHW_LOGITS = 0, 1, 2, 3       # enum 
 NCHW_PRODUCT_MAX_L, NCHW_UNIFORM_MAX_L = 256, 1024
 
 
+def _fp32_cuda(name, *tensors, device=None):
+    """TypeError unless every one of ``tensors`` is an fp32 CUDA tensor (on ``device``, where one is given)."""
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and device in (None, t.device)):
+            raise TypeError(f"{name}: takes fp32 CUDA tensors{f' on {device}' if device else ''}, got "
+                            f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+
+
+def _nchw_operands(name, X, G, xname):
+    """(B, L, n) of the fp32 CUDA volume X [B, L, H, W] or [B, L, n] and an optional G of the same shape and device."""
+    _fp32_cuda(name, *((X,) if G is None else (X, G)))
+    if X.dim() not in (3, 4) or (G is not None and (G.shape != X.shape or G.device != X.device)):
+        raise ValueError(f"{name}: {xname} [B, L, H, W] or [B, L, n] and G of the same shape and device")
+    B, L = int(X.shape[0]), int(X.shape[1])
+    return B, L, int(X[0, 0].numel()) if B and L else 0
+
+
+def _out_or_empty(name, out, shape, device, what):
+    """``out`` if it is a contiguous fp32 tensor of ``shape`` on ``device`` (TypeError if it is another), a new one for None."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
+            and tuple(out.shape) == tuple(shape) and out.device == device):
+        raise TypeError(f"{name}: out must be a contiguous fp32 tensor of {what}")
+    return out
+
+
 def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=None):
     """The non-W half of a CRFasRNN iteration on channel-major tensors, one kernel (phl_nchw_softmax_compat):
     ``out[:, c] = sum_a Mu[a, c] * softmax(-(E0 + G), dim=1)[:, a]`` for fp32 CUDA E0, G [B, L, H, W] (or [B, L, n]; G
@@ -744,20 +771,9 @@ def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=
     logits=True: ``out = -(E0 + G)``, CRFasRNN's return value; G is required, Mu is not read.
     out: a contiguous fp32 tensor of E0's shape, returned.  Raises PhlError with the library's status: 1 for out aliasing
     E0 or G, 7 for more than 256 labels with a general Mu or more than 1024 with a uniform one."""
-    for t in (E0,) + (() if G is None else (G,)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise TypeError(f"nchw_softmax_compat: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on "
-                            f"{getattr(t, 'device', '?')}")
-    if E0.dim() not in (3, 4) or (G is not None and (G.shape != E0.shape or G.device != E0.device)):
-        raise ValueError("nchw_softmax_compat: E0 [B, L, H, W] or [B, L, n] and G of the same shape and device")
-    B, L = int(E0.shape[0]), int(E0.shape[1])
-    n = int(E0[0, 0].numel()) if B and L else 0
+    B, L, n = _nchw_operands("nchw_softmax_compat", E0, G, "E0")
     dev = E0.device
-    if out is None:
-        out = torch.empty(E0.shape, dtype=torch.float32, device=dev)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == E0.shape
-              and out.device == dev):
-        raise TypeError("nchw_softmax_compat: out must be a contiguous fp32 tensor of E0's shape and device")
+    out = _out_or_empty("nchw_softmax_compat", out, E0.shape, dev, "E0's shape and device")
     if logits:
         if G is None:
             raise ValueError("nchw_softmax_compat: logits=True needs G")
@@ -783,13 +799,7 @@ NCHW_EXPECT_PIXELS = 1024            # PHL_NCHW_EXPECT_PIXELS: pixels of a workg
 
 def _expect_operands(name, X, G, labels):
     """(X, G contiguous, labels as fp32 [L] on X's device or None, B, L, n) of the expected-label entry points."""
-    for t in (X,) + (() if G is None else (G,)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise TypeError(f"{name}: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
-    if X.dim() not in (3, 4) or (G is not None and (G.shape != X.shape or G.device != X.device)):
-        raise ValueError(f"{name}: X [B, L, H, W] or [B, L, n] and G of the same shape and device")
-    B, L = int(X.shape[0]), int(X.shape[1])
-    n = int(X[0, 0].numel()) if B and L else 0
+    B, L, n = _nchw_operands(name, X, G, "X")
     if labels is not None:
         labels = torch.as_tensor(labels)
         if labels.numel() != L:
@@ -808,11 +818,7 @@ def nchw_expected_value(X, G=None, labels=None, *, negate=False, out=None):
     anything else (labels per pixel) is a ValueError.  out: a contiguous fp32 tensor of the result's shape, returned."""
     x, g, lab, B, L, n = _expect_operands("nchw_expected_value", X, G, labels)
     shape = (B, 1) + tuple(X.shape[2:])
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=X.device)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32
-              and tuple(out.shape) == shape and out.device == X.device):
-        raise TypeError(f"nchw_expected_value: out must be a contiguous fp32 tensor of shape {shape} on X's device")
+    out = _out_or_empty("nchw_expected_value", out, shape, X.device, f"shape {shape} on X's device")
     _launch(X.device, "phl_nchw_expected_value", _ptr(x), _ptr(g), _ptr(lab), _ptr(out), B, L, n, 1 if negate else 0)
     return out
 
@@ -823,8 +829,7 @@ def nchw_expected_value_grad(X, G, labels, gout, *, negate=False):
     fp32 CUDA with one element per pixel ([B, 1, H, W]).  Only X, G and the labels are read: the column's statistics are
     recomputed.  Same bits on every call."""
     x, g, lab, B, L, n = _expect_operands("nchw_expected_value_grad", X, G, labels)
-    if not (torch.is_tensor(gout) and gout.is_cuda and gout.dtype == torch.float32 and gout.device == X.device):
-        raise TypeError("nchw_expected_value_grad: gout must be a fp32 CUDA tensor on X's device")
+    _fp32_cuda("nchw_expected_value_grad", gout, device=X.device)
     if gout.numel() != B * n:
         raise ValueError(f"nchw_expected_value_grad: gout must hold one value per pixel ({B} x {n}), got {tuple(gout.shape)}")
     go = gout.contiguous()
@@ -865,9 +870,7 @@ NCHW_SCALAR_PIXELS = 1024            # PHL_NCHW_SCALAR_PIXELS: pixels of a workg
 def _scalar_operands(name, disp, size, L, gamma, s):
     """(disp contiguous, gamma, s, B, h, w, H, W, L) of the scalar-unary entry points: disp fp32 CUDA [B, 1, h, w] with at
     least one element, gamma and s fp32 tensors of one element on its device (read there, never on the host)."""
-    for t in (disp, gamma, s):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise TypeError(f"{name}: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+    _fp32_cuda(name, disp, gamma, s)
     if disp.dim() != 4 or disp.shape[1] != 1 or disp.numel() == 0:
         raise ValueError(f"{name}: disp must be a non-empty [B, 1, h, w], got {tuple(disp.shape)}")
     if gamma.numel() != 1 or s.numel() != 1 or gamma.device != disp.device or s.device != disp.device:
@@ -902,12 +905,11 @@ def nchw_scalar_unaries_grad(disp, size, labels, gamma, s, gE0, *, scale=10.0, t
     """(grad_gamma, grad_s), 0-dim fp32, of ``nchw_scalar_unaries`` for the upstream gradient gE0 [B, L, H, W]
     (phl_nchw_scalar_unaries_grad).  labels: the forward's.  gE0 is read once and everything else recomputed from the
     forward's inputs; float64 sums in a fixed order, the same bits on every call.  There is no gradient for disp."""
-    if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.float32 and labels.dim() == 1):
-        raise TypeError("nchw_scalar_unaries_grad: labels must be the fp32 CUDA [L] tensor the forward returned")
+    _fp32_cuda("nchw_scalar_unaries_grad", labels)
+    if labels.dim() != 1:
+        raise TypeError("nchw_scalar_unaries_grad: labels must be the [L] tensor the forward returned")
     d, gm, sv, B, h, w, H, W, L = _scalar_operands("nchw_scalar_unaries_grad", disp, size, labels.numel(), gamma, s)
-    if not (torch.is_tensor(gE0) and gE0.is_cuda and gE0.dtype == torch.float32 and gE0.device == disp.device
-            and labels.device == disp.device):
-        raise TypeError("nchw_scalar_unaries_grad: gE0 and labels must be fp32 CUDA tensors on disp's device")
+    _fp32_cuda("nchw_scalar_unaries_grad", gE0, labels, device=disp.device)
     if tuple(gE0.shape) != (B, L, H, W):
         raise ValueError(f"nchw_scalar_unaries_grad: gE0 must be {(B, L, H, W)}, got {tuple(gE0.shape)}")
     grad = torch.empty((2,), dtype=torch.float32, device=disp.device)
