@@ -495,6 +495,98 @@ int phl_lattice_blank(phl_lattice **out, int device, int d, int64_t n)
     return PHL_OK;
 }
 
+// ---- the plan of a filter call ----------------------------------------------------------------------------------------
+// Every call that runs the splat or the slice makes one decision: the width the kernels run at, which side is staged,
+// chunk kernels or gather kernels for each of the two stages, and what that asks of the workspace.  plan_call is the
+// only place that makes it -- phl_reserve_ex sizes the workspace from the same plan the next phl_filter will compute,
+// which is what "the next filter call allocates nothing" (HIP-graph capture) rests on.
+namespace {
+// fp32 rows as a call sees them; the default is "none": on the 16-byte grid, pixel-major
+struct phl_operand {
+    const void *base = nullptr;
+    int64_t rs = 0, cs = 1;
+};
+bool rows16(const phl_operand &o) { return phl_rows16(o.base, o.rs); }
+
+struct phl_call_plan {
+    int vdw;                    // the width the kernels run at: vd, or vd rounded up to a multiple of 4 (both sides staged)
+    bool stage_src, stage_dst;  // copied into / out of [n][vdw] rows of the workspace
+    bool chunk_splat, chunk_slice;      // the chunk kernels (phl_tiles.hip); else the gather kernels (phl_filter.hip)
+    int64_t buf_elems, partial_elems, stage_elems;      // floats asked of the workspace (phl_ws_acquire)
+};
+
+// src: what the splat reads (and the slice subtracts under PHL_FILTER_SUBTRACT_INPUT); dst: what the slice writes.
+// in_place: the stage-level calls hand in vertex rows of their own (phl_filter_grad: its second splat source) -- then
+// every operand is used where it lies, nothing is staged or widened, and the workspace holds the partial rows only.
+phl_call_plan plan_call(const phl_lattice *lat, int vd, unsigned flags, phl_operand src, phl_operand dst,
+                        const phl_operand *in_place = nullptr)
+{
+    phl_call_plan p = {};
+    p.vdw = vd;
+    const bool no_chunk_splat = (flags & (PHL_FILTER_EXACT | PHL_FILTER_NO_TILES)) != 0;
+    if (!in_place) {
+        // pixel-major rows are consumed in place; anything else (e.g. the [n,L] view of an NCHW
+        // tensor, gaussian_matrix.py:348) is staged through one coalesced transpose
+        p.stage_src = (src.cs != 1) && vd > 1;
+        p.stage_dst = (dst.cs != 1) && vd > 1;
+        // Rows the chunk kernels cannot take -- a channel count that is not a multiple of 4 (the reference's max_disp = w // 6:
+        // 231 at 1390 columns), a row stride or base address off the 16-byte grid (a column slice of a wider tensor) -- used to
+        // fall back to the gather kernels (2.4x slower at 1390x1110x231).  From 128 channels on they are staged instead: one
+        // copy into / out of a buffer with 16-byte rows, the kernels run at the width rounded up to a multiple of 4.  (Below
+        // that the two extra passes over the volume cost more than the gather kernels lose: tools/odd_narrow.py, 1390x1110 --
+        // 9 channels 0.46 vs 0.27 ms, 50: 0.87 vs 0.83, 110: 1.29 vs 1.20, 130: 1.48 vs 1.59, 231: 2.59 vs 3.14.)
+        if (vd >= 128 && !no_chunk_splat) {
+            if (vd % 4) {
+                p.vdw = (vd + 3) & ~3;
+                p.stage_src = p.stage_dst = true;
+            } else {
+                p.stage_src = p.stage_src || !rows16(src);
+                p.stage_dst = p.stage_dst || !rows16(dst);
+            }
+        }
+        p.buf_elems = lat->M * (int64_t)p.vdw;
+        if (p.stage_src || p.stage_dst) p.stage_elems = lat->n * (int64_t)p.vdw;
+    }
+    if (p.stage_src) src = {nullptr, p.vdw, 1};
+    if (p.stage_dst) dst = {nullptr, p.vdw, 1};
+    const bool vert16 = !in_place || rows16(*in_place);     // (the workspace's own vertex rows are on the grid)
+    // Partial rows cost 2 * S_multi row transfers (written, re-read); staging saves d of the d+1 reads the gather
+    // splat makes of every pixel row.  Break-even is far out (S_multi = d/2 * n); beyond 2n the chunks share so
+    // little that the gather form is taken (the iid stress case sits at ~0.9n and is still 1.3x faster staged).
+    p.chunk_splat = !no_chunk_splat && phl_tiles_lprs(lat, p.vdw, 0) >= 0 && rows16(src) && vert16 && lat->S_multi <= 2 * lat->n;
+    const bool sub16 = !(flags & PHL_FILTER_SUBTRACT_INPUT) || rows16(src);
+    p.chunk_slice = !(flags & PHL_FILTER_NO_TILES) && phl_tiles_lprs(lat, p.vdw, 1) >= 0 && vert16 && rows16(dst) && sub16 &&
+                    lat->S <= 3 * lat->n;
+    if (p.chunk_splat) p.partial_elems = lat->S_multi * (int64_t)p.vdw;
+    return p;
+}
+// the operands phl_reserve_ex's flags describe, and phl_tile_stats' "any rows on the grid": aligned pixel-major rows, or
+// (strided) a view whose columns are not adjacent, which both sides of a filter call stage
+phl_operand described_rows(int vd, bool strided = false) { return {nullptr, (vd + 3) & ~3, strided ? 2 : 1}; }
+
+// A workspace for the duration of a host call: acquired on request, given back by the destructor on every exit (a
+// workspace that is never released stays marked in_enqueue for good).  idle: it was sized and carries no work.
+struct ws_lease {
+    phl_lattice *lat;
+    hipStream_t st;
+    phl_workspace *w = nullptr;
+    bool idle = false;
+    ws_lease(phl_lattice *l, hipStream_t s) : lat(l), st(s) {}
+    ws_lease(const ws_lease &) = delete;
+    ws_lease &operator=(const ws_lease &) = delete;
+    ~ws_lease()
+    {
+        if (w) phl_ws_release(lat, w, st, idle);
+    }
+    int acquire(int64_t buf_elems, int64_t partial_elems, int64_t stage_elems)
+    {
+        return phl_ws_acquire(lat, st, buf_elems, partial_elems, stage_elems, &w);
+    }
+    int acquire(const phl_call_plan &p) { return acquire(p.buf_elems, p.partial_elems, p.stage_elems); }
+    phl_workspace *operator->() const { return w; }
+};
+}  // namespace
+
 extern "C" {
 
 int phl_version(void) { return PHL_VERSION; }
@@ -673,73 +765,34 @@ int phl_set_blur_rows(phl_lattice *lat, const int64_t *ranges, int naxes)
     return PHL_OK;
 }
 
-namespace {
-bool use_tiled_splat(const phl_lattice *lat, int vd, unsigned flags, const void *a, const void *b, int64_t rs)
-{
-    if (flags & (PHL_FILTER_EXACT | PHL_FILTER_NO_TILES)) return false;
-    if (phl_tiles_lprs(lat, vd, 0) < 0) return false;
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15 || rs % 4) return false;
-    // Partial rows cost 2 * S_multi row transfers (written, re-read); staging saves d of the d+1 reads the gather
-    // splat makes of every pixel row.  Break-even is far out (S_multi = d/2 * n); beyond 2n the chunks share so
-    // little that the gather form is taken (the iid stress case sits at ~0.9n and is still 1.3x faster staged).
-    return lat->S_multi <= 2 * lat->n;
-}
-bool use_tiled_slice(const phl_lattice *lat, int vd, unsigned flags, const void *a, const void *b, const void *c, int64_t rs,
-                     int64_t rs2)
-{
-    if (flags & PHL_FILTER_NO_TILES) return false;
-    if (phl_tiles_lprs(lat, vd, 1) < 0) return false;
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15 || rs % 4 || rs2 % 4) return false;
-    return lat->S <= 3 * lat->n;
-}
-}  // namespace
-
 int phl_tile_stats(const phl_lattice *lat, int vd, int64_t out[7])
 {
     if (!lat || !out) { phl_set_error("phl_tile_stats: bad arguments"); return PHL_ERR_INVALID; }
     out[0] = lat->P; out[1] = lat->nchunks; out[2] = lat->nv_max; out[3] = lat->S; out[4] = lat->S_multi;
-    out[5] = use_tiled_splat(lat, vd, 0, nullptr, nullptr, 0);
-    out[6] = use_tiled_slice(lat, vd, 0, nullptr, nullptr, nullptr, 0, 0);
+    const phl_operand rows = described_rows(vd);
+    const phl_call_plan p = plan_call(lat, vd, 0, rows, rows, &rows);
+    out[5] = p.chunk_splat;
+    out[6] = p.chunk_slice;
     return PHL_OK;
 }
-
-namespace {
-// workspace sizes of a filter call over vd channels
-int64_t need_partial(const phl_lattice *lat, int vd, unsigned flags)
-{
-    if (flags & (PHL_FILTER_EXACT | PHL_FILTER_NO_TILES)) return 0;
-    if (phl_tiles_lprs(lat, vd, 0) < 0 || lat->S_multi > 2 * lat->n) return 0;
-    return lat->S_multi * (int64_t)vd;
-}
-}  // namespace
 
 int phl_reserve_ex(phl_lattice *lat, int vd, unsigned reserve_flags)
 {
     if (!lat || vd < 0) { phl_set_error("phl_reserve: bad arguments"); return PHL_ERR_INVALID; }
     device_guard g(lat->device);
-    const unsigned fflags = (reserve_flags & PHL_RESERVE_EXACT) ? PHL_FILTER_EXACT : 0;
-    // what phl_filter will do with this width: channel counts >= 128 that are not a multiple of 4 run staged at the width
-    // rounded up (both sides); rows off the 16-byte grid at a multiple of 4 cannot be known here -- PHL_RESERVE_STRIDED_IO
-    // sizes the staging buffers for those as for channel-major views
-    int vdw = vd;
-    bool staged = (reserve_flags & PHL_RESERVE_STRIDED_IO) != 0;
-    if (vd >= 128 && vd % 4 && !(fflags & PHL_FILTER_EXACT)) {
-        vdw = (vd + 3) & ~3;
-        staged = true;
-    }
-    const int64_t partial = need_partial(lat, vdw, fflags);
+    // the plan phl_filter will compute for this width and operands as the flags describe them.  (Rows off the 16-byte
+    // grid at a multiple of 4 channels cannot be known here: PHL_RESERVE_STRIDED_IO sizes the staging buffers for those
+    // as for channel-major views.)
+    const phl_operand io = described_rows(vd, (reserve_flags & PHL_RESERVE_STRIDED_IO) != 0);
+    const phl_call_plan p = plan_call(lat, vd, (reserve_flags & PHL_RESERVE_EXACT) ? PHL_FILTER_EXACT : 0, io, io);
     // the gather splat (exact mode, or shapes the chunk splat does not take) needs its pixel-sorted lists
-    const bool gather = partial == 0 && !use_tiled_splat(lat, vdw, fflags, nullptr, nullptr, 0);
-    if (gather) {
+    if (!p.chunk_splat) {
         const int rc = phl_ensure_csr(lat, nullptr);
         if (rc) return rc;
     }
-    phl_workspace *w = nullptr;
-    const int64_t stage = staged ? lat->n * (int64_t)vdw : 0;
-    int rc = phl_ws_acquire(lat, nullptr, lat->M * (int64_t)vdw, partial, stage, &w);
-    if (rc) return rc;
-    phl_ws_release(lat, w, nullptr, /*idle=*/true);      // sized, carries no work: the next call on any stream takes it
-    return PHL_OK;
+    ws_lease w(lat, nullptr);
+    w.idle = true;      // sized, carries no work: the next call on any stream takes it
+    return w.acquire(p);
 }
 
 int phl_reserve(phl_lattice *lat, int vd) { return phl_reserve_ex(lat, vd, 0); }
@@ -748,15 +801,12 @@ int phl_splat(phl_lattice *lat, const float *src, int vd, int64_t src_rs, float 
 {
     if (!lat || vd < 0 || (lat->n > 0 && vd > 0 && (!src || !vert))) { phl_set_error("phl_splat: bad arguments"); return PHL_ERR_INVALID; }
     device_guard g(lat->device);
-    if (use_tiled_splat(lat, vd, flags, src, vert, src_rs)) {
-        phl_workspace *w = nullptr;       // only the partial rows come from the workspace here
-        int rc = phl_ws_acquire(lat, (hipStream_t)st, 0, need_partial(lat, vd, flags), 0, &w);
-        if (rc) return rc;
-        rc = phl_launch_splat_tiled(lat, src, src_rs, vd, vert, w->partial, (hipStream_t)st);
-        phl_ws_release(lat, w, (hipStream_t)st, false);
-        return rc;
-    }
-    return phl_launch_splat(lat, src, src_rs, vd, vert, (hipStream_t)st);
+    const phl_operand rows = {vert, vd, 1};
+    const phl_call_plan p = plan_call(lat, vd, flags, {src, src_rs, 1}, {}, &rows);
+    if (!p.chunk_splat) return phl_launch_splat(lat, src, src_rs, vd, vert, (hipStream_t)st);
+    ws_lease w(lat, (hipStream_t)st);       // only the partial rows come from the workspace here
+    const int rc = w.acquire(p);
+    return rc ? rc : phl_launch_splat_tiled(lat, src, src_rs, vd, vert, w->partial, (hipStream_t)st);
 }
 
 int64_t phl_num_chunks(const phl_lattice *lat) { return lat ? lat->nchunks : -1; }
@@ -769,6 +819,29 @@ int phl_chunks_touching(phl_lattice *lat, const int64_t *rows_dev, int64_t k, in
     return phl_tiles_chunks_touching(lat, rows_dev, k, mask_host, (hipStream_t)st);
 }
 
+// what the two subset entry points share, behind their argument checks
+static int splat_subset(const char *who, phl_lattice *lat, const float *src, int vd, int64_t src_rs, float *vert, float *partial_dev,
+                        const int32_t *chunks_dev, int64_t nchunks_sel, const int32_t *rows_dev, int64_t nrows,
+                        const int32_t *pack_pos_dev, float *pack_dev, int64_t pack_rs, phl_stream st)
+{
+    device_guard g(lat->device);
+    const phl_operand rows = {vert, vd, 1};
+    if (!plan_call(lat, vd, 0, {src, src_rs, 1}, {}, &rows).chunk_splat || !phl_al16(partial_dev)) {
+        phl_set_error("%s: the chunk splat is not available for this shape (vd %% 4, alignment, sharing)", who);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    phl_splat_opts o;
+    o.subset = true;
+    o.chunk_list = chunks_dev;
+    o.nlist = (int)nchunks_sel;
+    o.vlist = rows_dev;
+    o.nvl = nrows;
+    o.pack_pos = pack_pos_dev;
+    o.pack = pack_dev;
+    o.pack_rs = pack_rs;
+    return phl_launch_splat_tiled(lat, src, src_rs, vd, vert, partial_dev, (hipStream_t)st, o);
+}
+
 int phl_splat_part(phl_lattice *lat, const float *src, int vd, int64_t src_rs, float *vert, float *partial_dev,
                    const int32_t *chunks_dev, int64_t nchunks_sel, const int32_t *rows_dev, int64_t nrows, phl_stream st)
 {
@@ -777,13 +850,8 @@ int phl_splat_part(phl_lattice *lat, const float *src, int vd, int64_t src_rs, f
         phl_set_error("phl_splat_part: bad arguments");
         return PHL_ERR_INVALID;
     }
-    device_guard g(lat->device);
-    if (!use_tiled_splat(lat, vd, 0, src, vert, src_rs) || (reinterpret_cast<uintptr_t>(partial_dev) & 15)) {
-        phl_set_error("phl_splat_part: the chunk splat is not available for this shape (vd %% 4, alignment, sharing)");
-        return PHL_ERR_UNSUPPORTED;
-    }
-    return phl_launch_splat_tiled(lat, src, src_rs, vd, vert, partial_dev, (hipStream_t)st, /*subset=*/true, chunks_dev,
-                                  (int)nchunks_sel, rows_dev, nrows);
+    return splat_subset("phl_splat_part", lat, src, vd, src_rs, vert, partial_dev, chunks_dev, nchunks_sel, rows_dev, nrows,
+                        /*no row packing*/ nullptr, nullptr, 0, st);
 }
 
 int phl_splat_part_pack(phl_lattice *lat, const float *src, int vd, int64_t src_rs, float *vert, float *partial_dev,
@@ -791,18 +859,12 @@ int phl_splat_part_pack(phl_lattice *lat, const float *src, int vd, int64_t src_
                         const int32_t *pack_pos_dev, float *pack_dev, int64_t pack_rs, phl_stream st)
 {
     if (!lat || vd < 0 || nchunks_sel < 0 || nrows < 0 || !vert || (nchunks_sel > 0 && (!chunks_dev || !src)) || (nrows > 0 && !rows_dev) ||
-        (lat->S_multi > 0 && !partial_dev) || (pack_pos_dev && (!pack_dev || pack_rs < vd || pack_rs % 4 ||
-                                                                   (reinterpret_cast<uintptr_t>(pack_dev) & 15)))) {
+        (lat->S_multi > 0 && !partial_dev) || (pack_pos_dev && (!pack_dev || pack_rs < vd || pack_rs % 4 || !phl_al16(pack_dev)))) {
         phl_set_error("phl_splat_part_pack: bad arguments");
         return PHL_ERR_INVALID;
     }
-    device_guard g(lat->device);
-    if (!use_tiled_splat(lat, vd, 0, src, vert, src_rs) || (reinterpret_cast<uintptr_t>(partial_dev) & 15)) {
-        phl_set_error("phl_splat_part_pack: the chunk splat is not available for this shape (vd %% 4, alignment, sharing)");
-        return PHL_ERR_UNSUPPORTED;
-    }
-    return phl_launch_splat_tiled(lat, src, src_rs, vd, vert, partial_dev, (hipStream_t)st, /*subset=*/true, chunks_dev,
-                                  (int)nchunks_sel, rows_dev, nrows, nullptr, pack_pos_dev, pack_dev, pack_rs);
+    return splat_subset("phl_splat_part_pack", lat, src, vd, src_rs, vert, partial_dev, chunks_dev, nchunks_sel, rows_dev, nrows,
+                        pack_pos_dev, pack_dev, pack_rs, st);
 }
 
 int phl_blur_axis(phl_lattice *lat, int axis, const float *vin, float *vout, int vd, phl_stream st)
@@ -861,47 +923,11 @@ int phl_slice(phl_lattice *lat, const float *vert, int vd, float *out, int64_t o
 {
     if (!lat || vd < 0) { phl_set_error("phl_slice: bad arguments"); return PHL_ERR_INVALID; }
     device_guard g(lat->device);
-    if (use_tiled_slice(lat, vd, flags, vert, out, sub, out_rs, sub ? sub_rs : 0))
+    // (`sub`, where given, is read whatever the flags say)
+    const phl_operand rows = {vert, vd, 1};
+    if (plan_call(lat, vd, flags | PHL_FILTER_SUBTRACT_INPUT, {sub, sub ? sub_rs : 0, 1}, {out, out_rs, 1}, &rows).chunk_slice)
         return phl_launch_slice_tiled(lat, vert, vd, out, out_rs, sub, sub_rs, flags, (hipStream_t)st);
     return phl_launch_slice(lat, vert, vd, out, out_rs, sub, sub_rs, flags, (hipStream_t)st);
-}
-
-// vdw: the width the kernels run at -- vd, or vd rounded up to a multiple of 4 when both sides are staged for that (the
-// extra channels hold whatever the staging buffer held: channels never mix, and they are not copied out)
-static int filter_on(phl_lattice *lat, phl_workspace *w, const float *src, int vd_user, int vdw, int64_t src_rs, int64_t src_cs, float *out,
-                     int64_t out_rs, int64_t out_cs, unsigned flags, bool stage_src, bool stage_dst, hipStream_t st)
-{
-    const int64_t n = lat->n;
-    const float *src_eff = src;
-    int64_t src_eff_rs = src_rs;
-    float *out_eff = out;
-    int64_t out_eff_rs = out_rs;
-    int rc = PHL_OK;
-    const int vd = vdw;
-    if (stage_src) {
-        rc = phl_launch_copy2d(src, src_rs, src_cs, w->stage_in, vdw, 1, n, vd_user, st);
-        if (rc) return rc;
-        src_eff = w->stage_in;
-        src_eff_rs = vdw;
-    }
-    if (stage_dst) {
-        out_eff = w->stage_out;
-        out_eff_rs = vdw;
-    }
-    if (use_tiled_splat(lat, vd, flags, src_eff, w->buf[0], src_eff_rs)) rc = phl_launch_splat_tiled(lat, src_eff, src_eff_rs, vd, w->buf[0], w->partial, st);
-    else rc = phl_launch_splat(lat, src_eff, src_eff_rs, vd, w->buf[0], st);
-    if (rc) return rc;
-    int cur = 0;
-    rc = blur_all(lat, w->buf, vd, st, &cur);
-    if (rc) return rc;
-    const float *sub = (flags & PHL_FILTER_SUBTRACT_INPUT) ? src_eff : nullptr;
-    if (use_tiled_slice(lat, vd, flags, w->buf[cur], out_eff, sub, out_eff_rs, sub ? src_eff_rs : 0))
-        rc = phl_launch_slice_tiled(lat, w->buf[cur], vd, out_eff, out_eff_rs, sub, src_eff_rs, flags, st);
-    else
-        rc = phl_launch_slice(lat, w->buf[cur], vd, out_eff, out_eff_rs, sub, src_eff_rs, flags, st);
-    if (rc) return rc;
-    if (stage_dst) rc = phl_launch_copy2d(w->stage_out, vdw, 1, out, out_rs, out_cs, n, vd_user, st);
-    return rc;
 }
 
 int phl_filter(phl_lattice *lat, const float *src, int vd, int64_t src_rs, int64_t src_cs, float *out, int64_t out_rs,
@@ -914,34 +940,29 @@ int phl_filter(phl_lattice *lat, const float *src, int vd, int64_t src_rs, int64
     if (src == out) { phl_set_error("phl_filter: out may not alias src"); return PHL_ERR_INVALID; }
     hipStream_t st = (hipStream_t)stream;
     device_guard g(lat->device);
-
-    // pixel-major rows are consumed in place; anything else (e.g. the [n,L] view of an NCHW
-    // tensor, gaussian_matrix.py:348) is staged through one coalesced transpose
-    bool stage_src = (src_cs != 1) && vd > 1;
-    bool stage_dst = (out_cs != 1) && vd > 1;
-    // Rows the chunk kernels cannot take -- a channel count that is not a multiple of 4 (the reference's max_disp = w // 6:
-    // 231 at 1390 columns), a row stride or base address off the 16-byte grid (a column slice of a wider tensor) -- used to
-    // fall back to the gather kernels (2.4x slower at 1390x1110x231).  From 128 channels on they are staged instead: one
-    // copy into / out of a buffer with 16-byte rows, the kernels run at the width rounded up to a multiple of 4.  (Below
-    // that the two extra passes over the volume cost more than the gather kernels lose: tools/odd_narrow.py, 1390x1110 --
-    // 9 channels 0.46 vs 0.27 ms, 50: 0.87 vs 0.83, 110: 1.29 vs 1.20, 130: 1.48 vs 1.59, 231: 2.59 vs 3.14.)
-    int vdw = vd;
-    if (vd >= 128 && !(flags & (PHL_FILTER_EXACT | PHL_FILTER_NO_TILES))) {
-        auto off_grid = [](const void *p, int64_t rs) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0 || rs % 4 != 0; };
-        if (vd % 4) {
-            vdw = (vd + 3) & ~3;
-            stage_src = stage_dst = true;
-        } else {
-            if (!stage_src && off_grid(src, src_rs)) stage_src = true;
-            if (!stage_dst && off_grid(out, out_rs)) stage_dst = true;
-        }
-    }
-    phl_workspace *w = nullptr;
-    int rc = phl_ws_acquire(lat, st, lat->M * (int64_t)vdw, need_partial(lat, vdw, flags),
-                            (stage_src || stage_dst) ? n * (int64_t)vdw : 0, &w);
+    const phl_call_plan p = plan_call(lat, vd, flags, {src, src_rs, src_cs}, {out, out_rs, out_cs});
+    ws_lease w(lat, st);
+    int rc = w.acquire(p);
     if (rc) return rc;
-    rc = filter_on(lat, w, src, vd, vdw, src_rs, src_cs, out, out_rs, out_cs, flags, stage_src, stage_dst, st);
-    phl_ws_release(lat, w, st, false);
+    // the kernels run at vdw channels on the operands or on their staged copies (at a rounded-up width the extra
+    // channels hold whatever the staging buffer held: channels never mix, and they are not copied out)
+    const int vdw = p.vdw;
+    const float *const src_eff = p.stage_src ? w->stage_in : src;
+    float *const out_eff = p.stage_dst ? w->stage_out : out;
+    const int64_t src_eff_rs = p.stage_src ? vdw : src_rs, out_eff_rs = p.stage_dst ? vdw : out_rs;
+    if (p.stage_src) rc = phl_launch_copy2d(src, src_rs, src_cs, w->stage_in, vdw, 1, n, vd, st);
+    if (rc) return rc;
+    if (p.chunk_splat) rc = phl_launch_splat_tiled(lat, src_eff, src_eff_rs, vdw, w->buf[0], w->partial, st);
+    else rc = phl_launch_splat(lat, src_eff, src_eff_rs, vdw, w->buf[0], st);
+    if (rc) return rc;
+    int cur = 0;
+    rc = blur_all(lat, w->buf, vdw, st, &cur);
+    if (rc) return rc;
+    const float *sub = (flags & PHL_FILTER_SUBTRACT_INPUT) ? src_eff : nullptr;
+    if (p.chunk_slice) rc = phl_launch_slice_tiled(lat, w->buf[cur], vdw, out_eff, out_eff_rs, sub, src_eff_rs, flags, st);
+    else rc = phl_launch_slice(lat, w->buf[cur], vdw, out_eff, out_eff_rs, sub, src_eff_rs, flags, st);
+    if (rc) return rc;
+    if (p.stage_dst) rc = phl_launch_copy2d(w->stage_out, vdw, 1, out, out_rs, out_cs, n, vd, st);
     return rc;
 }
 
@@ -960,8 +981,9 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
     }
     if (!src || !g || !ref) { phl_set_error("phl_filter_grad: NULL src / g / ref"); return PHL_ERR_INVALID; }
     const int64_t vdw = (int64_t)L * (d + 1);
-    if (d > 7 || L % 4 != 0 || !use_tiled_splat(lat, L, 0, src, g, src_rs) || g_rs % 4 || vdw > (1 << 20) ||
-        (grad_src && ((reinterpret_cast<uintptr_t>(grad_src) & 15) || grad_src_rs % 4))) {
+    const phl_operand g_rows = {g, g_rs, 1};
+    if (d > 7 || L % 4 != 0 || !plan_call(lat, L, 0, {src, src_rs, 1}, {}, &g_rows).chunk_splat || vdw > (1 << 20) ||
+        (grad_src && !phl_rows16(grad_src, grad_src_rs))) {
         phl_set_error("phl_filter_grad: shape not covered by the fused path (d <= 7, L %% 4 == 0, 16-byte aligned pixel-major rows, "
                       "chunk splat available); filter the 2L(1+d)-channel operand instead");
         return PHL_ERR_UNSUPPORTED;
@@ -987,8 +1009,8 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
         Lg = (int)(fit < L ? fit : L);
     }
     const int64_t vdg = (int64_t)Lg * (d + 1);
-    phl_workspace *w = nullptr;
-    int rc = phl_ws_acquire(lat, st, lat->M * vdg, lat->S_multi * vdg, 0, &w);
+    ws_lease w(lat, st);
+    int rc = w.acquire(lat->M * vdg, lat->S_multi * vdg, 0);
     if (rc) return rc;
     // Two passes of the same three stages, each over (1+d) L channels instead of the reference's 2 (1+d) L at once:
     //   pass 1  x = g,   y = src:  T  = -2 sum_l src (f Wg - W(g f))      (+ Wg itself = the gradient w.r.t. src)
@@ -998,8 +1020,10 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
     for (int c0 = 0; c0 < L && rc == PHL_OK; c0 += Lg) {
         const int Lc = L - c0 < Lg ? L - c0 : Lg;
         for (int pass = 0; pass < 2 && rc == PHL_OK; pass++) {
-            phl_splat_wide wide = {d + 1, ref, ref_rs, ref_cs};
-            rc = phl_launch_splat_tiled(lat, xs[pass] + c0, xrs[pass], Lc, w->buf[0], w->partial, st, false, nullptr, 0, nullptr, 0, &wide);
+            const phl_splat_wide wide = {d + 1, ref, ref_rs, ref_cs};
+            phl_splat_opts o;
+            o.wide = &wide;
+            rc = phl_launch_splat_tiled(lat, xs[pass] + c0, xrs[pass], Lc, w->buf[0], w->partial, st, o);
             if (rc) break;
             int cur = 0;
             rc = blur_all(lat, w->buf, Lc * (d + 1), st, &cur);
@@ -1008,7 +1032,6 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
                                        (pass == 0 && grad_src) ? grad_src + c0 : nullptr, grad_src_rs, st);
         }
     }
-    phl_ws_release(lat, w, st, false);
     return rc;
 }
 

@@ -425,8 +425,8 @@ __global__ __launch_bounds__(256) void k_scatter_add_rows(float *__restrict__ ve
     }
 }
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
+// lanes per row; PHL_LPRS lists every value it returns (the launchers' dispatch_int)
+#define PHL_LPRS 1, 4, 16, 32, 64
 inline int pick_lpr(int vd, int vec)
 {
     const int need = (vd + vec - 1) / vec;
@@ -447,16 +447,20 @@ inline unsigned grid_for(int64_t rows, int rows_per_wave)
     return (unsigned)blocks;
 }
 
-template <typename F>
-inline void dispatch_lpr(int lpr, F &&f)
+// Launch shape of the gather kernels that walk `rows` vertex rows: lanes per row, and the XCD-ordered grid of 4-wave
+// blocks in which a wave takes `groups` groups of 64 / lpr rows.
+struct row_launch {
+    int lpr;
+    unsigned grid;
+    int xcd_chunk;
+};
+inline row_launch launch_rows(int64_t rows, int vd, bool v4, int groups)
 {
-    switch (lpr) {
-        case 64: f(std::integral_constant<int, 64>{}); break;
-        case 32: f(std::integral_constant<int, 32>{}); break;
-        case 16: f(std::integral_constant<int, 16>{}); break;
-        case 4: f(std::integral_constant<int, 4>{}); break;
-        default: f(std::integral_constant<int, 1>{}); break;
-    }
+    row_launch r;
+    r.lpr = pick_lpr(vd, v4 ? 4 : 1);
+    const int rows_per_block = (64 / r.lpr) * groups * 4;
+    r.grid = phl_xcd_grid((rows + rows_per_block - 1) / rows_per_block, &r.xcd_chunk);
+    return r;
 }
 
 }  // namespace
@@ -467,21 +471,12 @@ int phl_launch_splat(phl_lattice *lat, const float *src, int64_t src_rs, int vd,
     if (M == 0 || vd == 0) return PHL_OK;
     const int rc_csr = phl_ensure_csr(lat, st);
     if (rc_csr) return rc_csr;
-    const bool v4 = (vd % 4 == 0) && (src_rs % 4 == 0) && aligned16(src) && aligned16(vert);
-    const int lpr = pick_lpr(vd, v4 ? 4 : 1);
-    const int rows_per_block = (64 / lpr) * 4;
-    int64_t blocks = ((int64_t)M + rows_per_block - 1) / rows_per_block;
-    static const bool xcd = !(getenv("PHL_XCD") && atoi(getenv("PHL_XCD")) == 0);
-    int xcd_chunk = 0;
-    if (xcd && blocks >= 64) {
-        blocks = (blocks + 7) / 8 * 8;
-        xcd_chunk = (int)(blocks / 8);
-    }
-    const unsigned grid = (unsigned)blocks;
-    dispatch_lpr(lpr, [&](auto L) {
+    const bool v4 = (vd % 4 == 0) && (src_rs % 4 == 0) && phl_al16(src) && phl_al16(vert);
+    const row_launch rl = launch_rows(M, vd, v4, 1);
+    dispatch_int<PHL_LPRS>(rl.lpr, [&](auto L) {
         constexpr int LPR = decltype(L)::value;
-        if (v4) k_splat<4, LPR><<<dim3(grid), dim3(256), 0, st>>>(src, src_rs, vd, lat->csr_ptr, lat->csr, M, vert, lat->vorder, xcd_chunk);
-        else k_splat<1, LPR><<<dim3(grid), dim3(256), 0, st>>>(src, src_rs, vd, lat->csr_ptr, lat->csr, M, vert, lat->vorder, xcd_chunk);
+        if (v4) k_splat<4, LPR><<<dim3(rl.grid), dim3(256), 0, st>>>(src, src_rs, vd, lat->csr_ptr, lat->csr, M, vert, lat->vorder, rl.xcd_chunk);
+        else k_splat<1, LPR><<<dim3(rl.grid), dim3(256), 0, st>>>(src, src_rs, vd, lat->csr_ptr, lat->csr, M, vert, lat->vorder, rl.xcd_chunk);
     });
     PHL_HIP(hipGetLastError());
     return PHL_OK;
@@ -512,21 +507,12 @@ int phl_launch_blur(const phl_lattice *lat, int axis, const float *vin, float *v
     const blur_rows_t rr = rows_of(lat, axis, restricted);
     if (rr.total == 0) return PHL_OK;
     const int2 *nbr = reinterpret_cast<const int2 *>(lat->nbr) + (int64_t)axis * M;
-    const bool v4 = (vd % 4 == 0) && aligned16(vin) && aligned16(vout);
-    const int lpr = pick_lpr(vd, v4 ? 4 : 1);
-    const int rows_per_block = (64 / lpr) * 4 * 4;
-    int64_t blocks = ((int64_t)rr.total + rows_per_block - 1) / rows_per_block;
-    static const bool xcd = !(getenv("PHL_XCD") && atoi(getenv("PHL_XCD")) == 0);
-    int xcd_chunk = 0;
-    if (xcd && blocks >= 64) {
-        blocks = (blocks + 7) / 8 * 8;
-        xcd_chunk = (int)(blocks / 8);
-    }
-    const unsigned grid = (unsigned)blocks;
-    dispatch_lpr(lpr, [&](auto L) {
+    const bool v4 = (vd % 4 == 0) && phl_al16(vin) && phl_al16(vout);
+    const row_launch rl = launch_rows(rr.total, vd, v4, 4);
+    dispatch_int<PHL_LPRS>(rl.lpr, [&](auto L) {
         constexpr int LPR = decltype(L)::value;
-        if (v4) k_blur<4, LPR><<<dim3(grid), dim3(256), 0, st>>>(vin, vout, nbr, M, vd, xcd_chunk, rr);
-        else k_blur<1, LPR><<<dim3(grid), dim3(256), 0, st>>>(vin, vout, nbr, M, vd, xcd_chunk, rr);
+        if (v4) k_blur<4, LPR><<<dim3(rl.grid), dim3(256), 0, st>>>(vin, vout, nbr, M, vd, rl.xcd_chunk, rr);
+        else k_blur<1, LPR><<<dim3(rl.grid), dim3(256), 0, st>>>(vin, vout, nbr, M, vd, rl.xcd_chunk, rr);
     });
     PHL_HIP(hipGetLastError());
     return PHL_OK;
@@ -535,13 +521,13 @@ int phl_launch_blur(const phl_lattice *lat, int axis, const float *vin, float *v
 int phl_launch_rows(bool scatter, float *vert, int vd, const int64_t *idx, int64_t k, float *buf, int64_t buf_rs, hipStream_t st)
 {
     if (k == 0 || vd == 0) return PHL_OK;
-    if (vd % 4 || buf_rs % 4 || !aligned16(vert) || !aligned16(buf)) {
+    if (vd % 4 || buf_rs % 4 || !phl_al16(vert) || !phl_al16(buf)) {
         phl_set_error("row gather/scatter: needs vd %% 4 == 0 and 16-byte aligned rows");
         return PHL_ERR_UNSUPPORTED;
     }
     const int lpr = pick_lpr(vd, 4);
     const unsigned grid = (unsigned)((k + (64 / lpr) * 4 - 1) / ((64 / lpr) * 4));
-    dispatch_lpr(lpr, [&](auto L) {
+    dispatch_int<PHL_LPRS>(lpr, [&](auto L) {
         constexpr int LPR = decltype(L)::value;
         if (scatter) k_scatter_add_rows<LPR><<<dim3(grid), dim3(256), 0, st>>>(vert, vd, idx, k, buf, buf_rs);
         else k_gather_rows<LPR><<<dim3(grid), dim3(256), 0, st>>>(vert, vd, idx, k, buf, buf_rs);
@@ -557,22 +543,13 @@ int phl_launch_blur2(const phl_lattice *lat, int pair, const float *vin, float *
     const blur_rows_t rr = rows_of(lat, 2 * pair + 1, restricted);      // out = blur_b(blur_a(in)): the rows axis b's output is read at
     if (rr.total == 0) return PHL_OK;
     const int4 *nb2 = reinterpret_cast<const int4 *>(lat->nbr2) + (int64_t)pair * M * 2;
-    const bool v4 = (vd % 4 == 0) && aligned16(vin) && aligned16(vout);
-    const int lpr = pick_lpr(vd, v4 ? 4 : 1);
+    const bool v4 = (vd % 4 == 0) && phl_al16(vin) && phl_al16(vout);
     constexpr int U2 = 1;   // row groups in flight per wave: 9 row loads each; 1 measured best (2: +3 %, 4: +15 %)
-    const int rows_per_block = (64 / lpr) * U2 * 4;
-    int64_t blocks = ((int64_t)rr.total + rows_per_block - 1) / rows_per_block;
-    static const bool xcd = !(getenv("PHL_XCD") && atoi(getenv("PHL_XCD")) == 0);
-    int xcd_chunk = 0;
-    if (xcd && blocks >= 64) {
-        blocks = (blocks + 7) / 8 * 8;
-        xcd_chunk = (int)(blocks / 8);
-    }
-    const unsigned grid = (unsigned)blocks;
-    dispatch_lpr(lpr, [&](auto L) {
+    const row_launch rl = launch_rows(rr.total, vd, v4, U2);
+    dispatch_int<PHL_LPRS>(rl.lpr, [&](auto L) {
         constexpr int LPR = decltype(L)::value;
-        if (v4) k_blur2<4, LPR, U2><<<dim3(grid), dim3(256), 0, st>>>(vin, vout, nb2, M, vd, xcd_chunk, rr);
-        else k_blur2<1, LPR, U2><<<dim3(grid), dim3(256), 0, st>>>(vin, vout, nb2, M, vd, xcd_chunk, rr);
+        if (v4) k_blur2<4, LPR, U2><<<dim3(rl.grid), dim3(256), 0, st>>>(vin, vout, nb2, M, vd, rl.xcd_chunk, rr);
+        else k_blur2<1, LPR, U2><<<dim3(rl.grid), dim3(256), 0, st>>>(vin, vout, nb2, M, vd, rl.xcd_chunk, rr);
     });
     PHL_HIP(hipGetLastError());
     return PHL_OK;
@@ -587,19 +564,19 @@ int phl_launch_slice(const phl_lattice *lat, const float *vert, int vd, float *o
     // the reference's constant, computed as it computes it: 1 + powf(2, -d)   (:480)
     const float cdiv = 1 + powf(2, -lat->d);
     const float rcdiv = 1.0f / cdiv;
-    const bool v4 = (vd % 4 == 0) && (out_rs % 4 == 0) && aligned16(vert) && aligned16(out) &&
-                    (!sub || ((sub_rs % 4 == 0) && aligned16(sub)));
+    const bool v4 = (vd % 4 == 0) && (out_rs % 4 == 0) && phl_al16(vert) && phl_al16(out) &&
+                    (!sub || ((sub_rs % 4 == 0) && phl_al16(sub)));
     const int lpr = pick_lpr(vd, v4 ? 4 : 1);
     const unsigned grid = grid_for(n, 64 / lpr);
     const bool exact = (flags & PHL_FILTER_EXACT) != 0;
-    dispatch_lpr(lpr, [&](auto L) {
+    dispatch_int<PHL_LPRS>(lpr, [&](auto L) {
         constexpr int LPR = decltype(L)::value;
-#define PHL_SLICE_ARGS vert, vd, lat->replay, dp1, n, out, out_rs, sub, sub_rs, cdiv, rcdiv
-        if (v4 && exact) k_slice<4, LPR, true><<<dim3(grid), dim3(256), 0, st>>>(PHL_SLICE_ARGS);
-        else if (v4) k_slice<4, LPR, false><<<dim3(grid), dim3(256), 0, st>>>(PHL_SLICE_ARGS);
-        else if (exact) k_slice<1, LPR, true><<<dim3(grid), dim3(256), 0, st>>>(PHL_SLICE_ARGS);
-        else k_slice<1, LPR, false><<<dim3(grid), dim3(256), 0, st>>>(PHL_SLICE_ARGS);
-#undef PHL_SLICE_ARGS
+        dispatch_bool(v4, [&](auto V4) {
+            dispatch_bool(exact, [&](auto X) {
+                k_slice<decltype(V4)::value ? 4 : 1, LPR, decltype(X)::value><<<dim3(grid), dim3(256), 0, st>>>(
+                    vert, vd, lat->replay, dp1, n, out, out_rs, sub, sub_rs, cdiv, rcdiv);
+            });
+        });
     });
     PHL_HIP(hipGetLastError());
     return PHL_OK;

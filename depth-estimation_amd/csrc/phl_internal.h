@@ -2,9 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "phl.h"
 
+#include <type_traits>
 #include <vector>
 
 #define PHL_WAVE 64
@@ -264,6 +266,34 @@ inline int phl_allow_lds(K kernel, size_t bytes)
     return phl_raise_lds_limit(reinterpret_cast<const void *>(kernel), bytes);
 }
 
+// Run-time value -> template argument: f(std::integral_constant<int, V>{}) for the V of the list that equals v;
+// false (f not called) if there is none.  f is a generic lambda that launches its kernel with decltype(arg)::value.
+template <int... Vs, typename F>
+inline bool dispatch_int(int v, F &&f)
+{
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// the same for a flag: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+inline void dispatch_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// Grid of a kernel that walks its blocks in XCD-aware order: from 64 blocks on, the count is rounded up to a multiple of
+// the eight XCDs and *xcd_chunk gets the blocks per XCD; below that (or with PHL_XCD=0) the grid is `blocks`, *xcd_chunk 0.
+inline unsigned phl_xcd_grid(int64_t blocks, int *xcd_chunk)
+{
+    static const bool xcd = !(getenv("PHL_XCD") && atoi(getenv("PHL_XCD")) == 0);
+    *xcd_chunk = 0;
+    if (xcd && blocks >= 64) {
+        blocks = (blocks + 7) / 8 * 8;
+        *xcd_chunk = (int)(blocks / 8);
+    }
+    return (unsigned)blocks;
+}
+
 // argument checks of the entry points: a 16-byte aligned address (null counts as aligned), and fp32 rows of 16-byte
 // pieces (aligned base, row stride a multiple of 4 floats)
 inline bool phl_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -323,11 +353,22 @@ struct phl_splat_wide {
     const float *fref;
     int64_t rs, cs;
 };
+// what a chunk splat does beyond the whole lattice at plain width; a call names what it sets
+struct phl_splat_opts {
+    // subset: run only the listed chunks, then complete only the listed vertex rows (either list may be empty)
+    bool subset = false;
+    const int *chunk_list = nullptr;
+    int nlist = 0;
+    const int *vlist = nullptr;
+    int64_t nvl = 0;
+    const phl_splat_wide *wide = nullptr;
+    // subset calls only: listed row i is also written to pack[pack_pos[i]] (pack_pos[i] < 0: not)
+    const int *pack_pos = nullptr;
+    float *pack = nullptr;
+    int64_t pack_rs = 0;
+};
 int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, int vd, float *vert, float *partial,
-                           hipStream_t st, bool subset = false, const int *chunk_list = nullptr, int nlist = 0,
-                           const int *vlist = nullptr, int64_t nvl = 0, const phl_splat_wide *wide = nullptr,
-                           const int *pack_pos = nullptr, float *pack = nullptr, int64_t pack_rs = 0);
-// (pack_pos / pack: subset calls only -- listed row i is also written to pack[pack_pos[i]] (pack_pos[i] < 0: not))
+                           hipStream_t st, const phl_splat_opts &o = {});
 // slice of a wide vertex buffer contracted to the feature gradient (phl_tiles.hip, k_slice_grad)
 int phl_launch_slice_grad(const phl_lattice *lat, const float *vertw, int L, const float *y, int64_t y_rs, const float *ref,
                           int64_t ref_rs, int64_t ref_cs, float *grad_ref, int accumulate, float *wx_out, int64_t wx_rs,

@@ -948,21 +948,6 @@ __global__ __launch_bounds__(TPB) void k_slice_grad(const float *__restrict__ ve
                                       wx_out, wx_rs, rcdiv);
 }
 
-// Run-time value -> template argument: f(std::integral_constant<int, V>{}) for the V of the list that equals v;
-// false (f not called) if there is none.  f is a generic lambda that launches its kernel with decltype(arg)::value.
-template <int... Vs, typename F>
-inline bool dispatch_int(int v, F &&f)
-{
-    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
-}
-// the same for a flag: f(std::true_type{}) or f(std::false_type{})
-template <typename F>
-inline void dispatch_bool(bool b, F &&f)
-{
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-
 // LDS per workgroup: default 80 KiB -> two workgroups per CU (160 KiB LDS per CU on gfx950)
 int lds_budget()
 {
@@ -1150,19 +1135,6 @@ inline int allow_lds(K kernel, size_t bytes, int threads = 512)
     return PHL_OK;
 }
 
-// grid size and per-XCD chunk count for the XCD-aware chunk order
-inline void chunk_grid(int nchunks, unsigned *grid, int *xcd_chunk)
-{
-    static const bool xcd = !(getenv("PHL_XCD") && atoi(getenv("PHL_XCD")) == 0);
-    if (xcd && nchunks >= 64) {
-        *grid = (unsigned)((nchunks + 7) / 8 * 8);
-        *xcd_chunk = (int)(*grid / 8);
-    } else {
-        *grid = (unsigned)nchunks;
-        *xcd_chunk = 0;
-    }
-}
-
 inline int pick_lpr_row(int vd)
 {
     const int need = (vd + 3) / 4;
@@ -1180,14 +1152,13 @@ int phl_tiles_lprs(const phl_lattice *lat, int vd, int for_slice)
 }
 
 int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, int vd, float *vert, float *partial,
-                           hipStream_t st, bool subset, const int *chunk_list, int nlist, const int *vlist, int64_t nvl,
-                           const phl_splat_wide *wide, const int *pack_pos, float *pack, int64_t pack_rs)
+                           hipStream_t st, const phl_splat_opts &o)
 {
-    if (pack_pos && (!subset || wide)) { phl_set_error("tiled splat: row packing needs a row list and a plain splat"); return PHL_ERR_INVALID; }
+    const phl_splat_wide *const wide = o.wide;
+    if (o.pack_pos && (!o.subset || wide)) { phl_set_error("tiled splat: row packing needs a row list and a plain splat"); return PHL_ERR_INVALID; }
     // wide: vertex / partial rows of wide->nsets * vd floats, block k+1 = splat of src (x) fref[:, k] (k_splat_tiled)
     const int64_t out_rs = (int64_t)vd * (wide ? wide->nsets : 1);
-    // subset: run only the listed chunks, then complete only the listed vertex rows (either list may be empty)
-    const int M = subset ? (int)nvl : (int)lat->M;
+    const int M = o.subset ? (int)o.nvl : (int)lat->M;
     if (lat->M == 0 || vd == 0) return PHL_OK;
     const tile_plan plan = plan_tiles(lat, vd);
     if (plan.n == 0) {
@@ -1195,7 +1166,7 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
         return PHL_ERR_UNSUPPORTED;
     }
     int rc = PHL_OK;
-    const int nrun = subset ? nlist : lat->nchunks;
+    const int nrun = o.subset ? o.nlist : lat->nchunks;
     static const char *tl_path = getenv("PHL_TIMELINE");     // debug: dump per-workgroup time stamps of the main launch
     struct dev_free {
         void operator()(void *p) const { (void)phl_dev_free(p); }
@@ -1206,7 +1177,7 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
     // any early return below drains that stream and gives the slot back (the guard's destructor)
     static const bool side_classes = !(getenv("PHL_SIDE_CLASSES") && atoi(getenv("PHL_SIDE_CLASSES")) == 0);
     phl_fork_guard fk;
-    if (plan.n > 1 && !subset && !tl_path && side_classes) fk.fork(st);
+    if (plan.n > 1 && !o.subset && !tl_path && side_classes) fk.fork(st);
     hipStream_t const st_main = st;
     int order[12];
     int no = 0;
@@ -1220,13 +1191,12 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
         st = (fk && !c.full_grid) ? fk.stream() : st_main;
         // the largest class (and every class of a caller's subset) walks the whole grid / list in chunk order and
         // filters by vertex count in the kernel; the others run exactly their range of chunk_by_nv
-        const bool filtered = subset || c.full_grid;
-        const int *list = subset ? chunk_list : (c.full_grid ? nullptr : lat->chunk_by_nv + c.begin);
+        const bool filtered = o.subset || c.full_grid;
+        const int *list = o.subset ? o.chunk_list : (c.full_grid ? nullptr : lat->chunk_by_nv + c.begin);
         const int cnt = filtered ? nrun : c.count;
         if (cnt == 0) continue;
-        unsigned cgrid;
         int xcd_chunk;
-        chunk_grid(cnt, &cgrid, &xcd_chunk);
+        const unsigned cgrid = phl_xcd_grid(cnt, &xcd_chunk);
         unsigned long long *tlc = nullptr;
         if (tl_path && c.full_grid && !tl) {
             tl_n = (size_t)cgrid * 8;
@@ -1284,18 +1254,18 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
     //  tens of thousands of empty workgroups on the row-band path otherwise)
     // (with a send buffer to fill, the long kernel walks the caller's rows even when ... see above: n_long == 0 means no
     //  listed row can be long, so nothing is lost by skipping it)
-    const int *llist = subset ? vlist : lat->vlong;
-    const int64_t nl = lat->n_long == 0 ? 0 : (subset ? nvl : lat->n_long);
+    const int *llist = o.subset ? o.vlist : lat->vlong;
+    const int64_t nl = lat->n_long == 0 ? 0 : (o.subset ? o.nvl : lat->n_long);
     const int long_list = llist ? LONG_LIST : 0x7FFFFFFF;
     auto reduce = [&](auto W) {
         constexpr int LPR = decltype(W)::value;
         k_splat_reduce<LPR><<<dim3((unsigned)blocks), dim3(256), 0, st>>>(partial, lat->vs_ptr, lat->vs, lat->slot_pidx, M,
-                                                                          (int)out_rs, vert, vlist, long_list, pack_pos, pack,
-                                                                          pack_rs);
+                                                                          (int)out_rs, vert, o.vlist, long_list, o.pack_pos, o.pack,
+                                                                          o.pack_rs);
         if (llist && nl > 0)
             k_splat_reduce_long<LPR><<<dim3((unsigned)nl), dim3(256), 0, st>>>(partial, lat->vs_ptr, lat->vs, lat->slot_pidx,
                                                                                (int)out_rs, vert, llist, long_list,
-                                                                               subset ? pack_pos : nullptr, pack, pack_rs);
+                                                                               o.subset ? o.pack_pos : nullptr, o.pack, o.pack_rs);
     };
     if (!dispatch_int<64, 16, 4>(lpr, reduce)) reduce(std::integral_constant<int, 1>{});
     PHL_HIP(hipGetLastError());
@@ -1311,9 +1281,8 @@ int phl_launch_slice_tiled(const phl_lattice *lat, const float *vert, int vd, fl
     const float rcdiv = 1.0f / cdiv;
     const bool exact = (flags & PHL_FILTER_EXACT) != 0;
     int rc = PHL_OK;
-    unsigned cgrid;
     int xcd_chunk;
-    chunk_grid(lat->nchunks, &cgrid, &xcd_chunk);
+    unsigned cgrid = phl_xcd_grid(lat->nchunks, &xcd_chunk);
     // heavy chunks = those that cannot take at least half the widest slab; worth a head start only if they are few
     int heavy_thr = 0x7FFFFFFF, heavy_n = 0;
     if (lat->nv_cum && lat->chunk_by_nv && cfg.lsh_max > 2) {
@@ -1352,9 +1321,8 @@ int phl_launch_slice_grad(const phl_lattice *lat, const float *vertw, int L, con
     int64_t lds = fixed + (int64_t)lat->nv_max * dp1 * 128;      // every chunk on 32-channel slabs, if the budget allows
     if (lds > lds_budget()) lds = lds_budget();
     const float rcdiv = 1.0f / (1 + powf(2, -lat->d));      // permutohedral.h:480
-    unsigned cgrid;
     int xcd_chunk;
-    chunk_grid(lat->nchunks, &cgrid, &xcd_chunk);
+    const unsigned cgrid = phl_xcd_grid(lat->nchunks, &xcd_chunk);
     int rc = PHL_OK;
     dispatch_int<2, 3, 4, 5, 6, 7, 8>(dp1, [&](auto N) {          // (dp1 outside 2..8 was rejected above)
         constexpr int NS = decltype(N)::value;

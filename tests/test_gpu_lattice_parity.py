@@ -655,15 +655,31 @@ def test_filter_is_graph_capturable(phl):
     assert torch.equal(out, want2) and not torch.equal(out, want1)
 
 
-@pytest.mark.parametrize("layout", ["pixel_major", "nchw_view", "exact"])
+LOW_SHARING_SCALE = 6       # multi_chunk_slots / n = 2.79 on the MI355X: of 3, 4, 6, 8, 12 the smallest that meets the assertion,
+                            # and the slice still takes the chunk kernel there (slots 2.88 n <= 3 n): gather splat, chunk slice
+
+
+@pytest.mark.parametrize("layout", ["pixel_major", "nchw_view", "exact", "gather_width", "low_sharing"])
 def test_reserve_then_capture_without_warm_up(phl, layout):
     """phl_reserve's contract (include/phl.h): after it the NEXT filter call allocates nothing -- so a capture
     may follow a single reserve() directly, with no un-captured warm-up call, in the pixel-major layout, through
-    the channel-major views BatchedAdjacency passes (gaussian_matrix.py:348-349) and for exact-mode calls."""
+    the channel-major views BatchedAdjacency passes (gaussian_matrix.py:348-349) and for exact-mode calls; and on
+    the two default-mode branches that take the gather kernels, whose pixel-sorted lists reserve() must have built:
+    a channel count below 128 that is no multiple of 4 (gather_width), and chunks that share too little for the
+    chunk splat (low_sharing: iid features)."""
     rng = np.random.default_rng(19)
     n, d, L = 30000, 5, 32
     ref = np.cumsum(rng.random((n, d), dtype=np.float32) * 0.02, axis=0).astype(np.float32)
+    if layout == "gather_width":
+        L = 6
+    if layout == "low_sharing":
+        ref = (rng.random((n, 5)) * LOW_SHARING_SCALE).astype(np.float32)
     Lat = phl.Lattice(torch.from_numpy(ref).cuda())
+    if layout == "gather_width":
+        assert Lat.tile_stats(6)["staged_splat"] == 0
+    if layout == "low_sharing":
+        st = Lat.tile_stats(L)
+        assert st["staged_splat"] == 0 and st["multi_chunk_slots"] > 2 * n, st
     exact = layout == "exact"
     Lat.reserve(L, strided_io=(layout == "nchw_view"), exact=exact)
     if layout == "nchw_view":
