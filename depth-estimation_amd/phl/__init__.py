@@ -30,7 +30,6 @@ NO_TILES = 8
 ERR_UNSUPPORTED = 7          # PHL_ERR_UNSUPPORTED: the kernels do not take this shape, the caller keeps its own path
 BUILD_REFERENCE_TABLE = 1
 
-_f32p = C.c_void_p
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -41,8 +40,93 @@ class PhlError(RuntimeError):
         self.status = status
 
 
+# The C ABI: one line per prototype of include/phl.h, in the header's order (name, return kind, argument kinds), kept
+# equal to the header by tests/test_abi_table_host.py.  Argument kinds: P pointer (arrays and phl_lattice ** included),
+# S phl_stream, i int, q int64_t, I unsigned, Q uint64_t, f float, d double; return kinds: i int, q int64_t, N size_t,
+# z const char *.
+_KINDS = {"P": C.c_void_p, "S": C.c_void_p, "i": C.c_int, "q": C.c_int64, "I": C.c_uint, "Q": C.c_uint64, "f": C.c_float,
+          "d": C.c_double, "N": C.c_size_t, "z": C.c_char_p}
+_ABI = (
+    ("phl_version", "i", ""),
+    ("phl_last_error", "z", ""),
+    ("phl_status_string", "z", "i"),
+    ("phl_device_count", "i", ""),
+    ("phl_build", "i", "PPqiqqiS"),
+    ("phl_build_ex", "i", "PPqiqqiSI"),
+    ("phl_destroy", "i", "P"),
+    ("phl_num_pixels", "q", "P"),
+    ("phl_num_vertices", "q", "P"),
+    ("phl_num_dims", "i", "P"),
+    ("phl_device", "i", "P"),
+    ("phl_device_bytes", "q", "P"),
+    ("phl_trim_scratch", "i", ""),
+    ("phl_add_vertices", "i", "PPqPS"),
+    ("phl_num_local_vertices", "q", "P"),
+    ("phl_vertices_of_pixels", "i", "PqqPS"),
+    ("phl_sub_lattice", "i", "PPqqPqqPqqS"),
+    ("phl_reserve", "i", "Pi"),
+    ("phl_reserve_ex", "i", "PiI"),
+    ("phl_filter", "i", "PPiqqPqqIS"),
+    ("phl_filter_once", "i", "PiqqPiqqqPqqIiS"),
+    ("phl_filter_grad", "i", "PPqPqiPqqPPqS"),
+    ("phl_splat", "i", "PPiqPIS"),
+    ("phl_blur_axis", "i", "PiPPiS"),
+    ("phl_blur", "i", "PPPiPS"),
+    ("phl_gather_rows", "i", "PiPqPqS"),
+    ("phl_scatter_add_rows", "i", "PiPqPqS"),
+    ("phl_num_chunks", "q", "P"),
+    ("phl_partial_rows", "q", "P"),
+    ("phl_chunks_touching", "i", "PPqPS"),
+    ("phl_splat_part", "i", "PPiqPPPqPqS"),
+    ("phl_splat_part_pack", "i", "PPiqPPPqPqPPqS"),
+    ("phl_set_blur_rows", "i", "PPi"),
+    ("phl_slice", "i", "PPiPqPqIS"),
+    ("phl_softmax_neg_add", "i", "PqPqPqqiS"),
+    ("phl_compat_softmax", "i", "PqPqPPqqiIS"),
+    ("phl_compat_planes_bytes", "N", "i"),
+    ("phl_compat_prepare", "i", "PiPS"),
+    ("phl_compat_softmax_split", "i", "PqPqPPPqqiIS"),
+    ("phl_uniform_compat_softmax", "i", "PqPqffPqqiIS"),
+    ("phl_nchw_softmax_compat", "i", "PPPffPiiqiS"),
+    ("phl_nchw_expected_value", "i", "PPPPiiqiS"),
+    ("phl_nchw_expected_value_grad", "i", "PPPPPiiqiS"),
+    ("phl_nchw_scalar_unaries", "i", "PPPPPiiiiiiddS"),
+    ("phl_nchw_scalar_unaries_grad", "i", "PPPPPPiiiiiiddS"),
+    ("phl_softmax_neg_grad", "i", "PqPqPqqiS"),
+    ("phl_uniform_compat_grad", "i", "PqPqffPqPqqiS"),
+    ("phl_compat_grad_x", "i", "PqPfPqqiS"),
+    ("phl_compat_mu_grad_workspace_bytes", "N", "qi"),
+    ("phl_compat_mu_grad", "i", "PqPqfqiPPiS"),
+    ("phl_expected_value", "i", "PqPPqiS"),
+    ("phl_cost_volume", "i", "PPiiiiiiPqS"),
+    ("phl_cost_volume_nchw", "i", "PPiiiiqqqqiiiIPqqqS"),
+    ("phl_disparity_wta", "i", "PPiiiiqqqqiiiPPqqS"),
+    ("phl_box_blur", "i", "PPqqqiiS"),
+    ("phl_box_blur_grad", "i", "PPqqqidPPS"),
+    ("phl_box_blur_fused_max_r", "i", "iii"),
+    ("phl_guided_filter", "i", "PPPPiiiiiiiiPPPPPfS"),
+    ("phl_guided_filter_max_r", "i", ""),
+    ("phl_guided_filter_labels_per_chunk", "i", "iiiiiii"),
+    ("phl_guided_filter_grad", "i", "PPPPPPiiiiiiiiPPPPPfiS"),
+    ("phl_guided_filter_grad_max_r", "i", ""),
+    ("phl_stream_copy", "i", "PPqS"),
+    ("phl_copy2d", "i", "PqqPqqqiS"),
+    ("phl_tile_stats", "i", "PiP"),
+    ("phl_get_vertex_order", "i", "PP"),
+    ("phl_get_pixel_order", "i", "PP"),
+    ("phl_get_keys", "i", "PP"),
+    ("phl_get_replay", "i", "PPP"),
+    ("phl_get_neighbors", "i", "PP"),
+    ("phl_get_splat_lists", "i", "PPPP"),
+    ("phl_debug_reference_table", "i", "PPqiqPqPPPiPP"),
+    ("phl_debug_probe_paths", "i", "PqiPiPiQPiiP"),
+    ("phl_debug_slow_copy", "i", "PPqiiS"),
+    ("phl_debug_side_streams", "i", ""),
+)
+
+
 def load_library():
-    """Load lib/libphl.so (built by ``python __graft_entry__.py`` / ``make -C csrc``)."""
+    """Load lib/libphl.so (built by ``python __graft_entry__.py`` / ``make -C csrc``) and declare its signatures."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -52,92 +136,10 @@ def load_library():
                 f"{LIB_PATH} not found: the HIP extension is not built (run `python __graft_entry__.py`). "
                 "There is no CPU fallback for the lattice filter.")
         lib = C.CDLL(LIB_PATH)
-        i64, i32, vp, u32 = C.c_int64, C.c_int, C.c_void_p, C.c_uint
-        lib.phl_version.restype = i32
-        lib.phl_last_error.restype = C.c_char_p
-        lib.phl_status_string.restype = C.c_char_p
-        lib.phl_status_string.argtypes = [i32]
-        lib.phl_device_count.restype = i32
-        lib.phl_build.argtypes = [C.POINTER(vp), vp, i64, i32, i64, i64, i32, vp]
-        lib.phl_build_ex.argtypes = [C.POINTER(vp), vp, i64, i32, i64, i64, i32, vp, u32]
-        lib.phl_debug_reference_table.argtypes = [vp, vp, i64, i32, i64, vp, i64, C.POINTER(i64), vp, vp, i32,
-                                                  C.POINTER(i32), C.POINTER(i32)]
-        if hasattr(lib, "phl_debug_probe_paths"):       # (test hook; an older build loaded through PHL_LIB lacks it)
-            lib.phl_debug_probe_paths.argtypes = [vp, i64, i32, vp, i32, vp, i32, C.c_uint64, vp, i32, i32, C.POINTER(i32)]
-        lib.phl_destroy.argtypes = [vp]
-        for name in ("phl_num_pixels", "phl_num_vertices", "phl_device_bytes"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [vp]
-        lib.phl_num_dims.argtypes = [vp]
-        lib.phl_device.argtypes = [vp]
-        lib.phl_filter_grad.argtypes = [vp, vp, i64, vp, i64, i32, vp, i64, i64, vp, vp, i64, vp]
-        lib.phl_reserve.argtypes = [vp, i32]
-        lib.phl_reserve_ex.argtypes = [vp, i32, u32]
-        lib.phl_add_vertices.argtypes = [vp, vp, i64, vp, vp]
-        lib.phl_num_local_vertices.restype = i64
-        lib.phl_num_local_vertices.argtypes = [vp]
-        lib.phl_filter.argtypes = [vp, vp, i32, i64, i64, vp, i64, i64, u32, vp]
-        lib.phl_filter_once.argtypes = [vp, i32, i64, i64, vp, i32, i64, i64, i64, vp, i64, i64, u32, i32, vp]
-        lib.phl_splat.argtypes = [vp, vp, i32, i64, vp, u32, vp]
-        lib.phl_tile_stats.argtypes = [vp, i32, vp]
-        for name in ("phl_num_chunks", "phl_partial_rows"):
-            getattr(lib, name).restype = i64
-            getattr(lib, name).argtypes = [vp]
-        lib.phl_chunks_touching.argtypes = [vp, vp, i64, vp, vp]
-        lib.phl_splat_part.argtypes = [vp, vp, i32, i64, vp, vp, vp, i64, vp, i64, vp]
-        if hasattr(lib, "phl_splat_part_pack"):         # (an older build loaded through PHL_LIB lacks these)
-            lib.phl_splat_part_pack.argtypes = [vp, vp, i32, i64, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp]
-            lib.phl_set_blur_rows.argtypes = [vp, vp, i32]
-        lib.phl_blur_axis.argtypes = [vp, i32, vp, vp, i32, vp]
-        lib.phl_blur.argtypes = [vp, vp, vp, i32, C.POINTER(i32), vp]
-        lib.phl_gather_rows.argtypes = [vp, i32, vp, i64, vp, i64, vp]
-        lib.phl_scatter_add_rows.argtypes = [vp, i32, vp, i64, vp, i64, vp]
-        lib.phl_slice.argtypes = [vp, vp, i32, vp, i64, vp, i64, u32, vp]
-        lib.phl_softmax_neg_add.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, vp]
-        lib.phl_expected_value.argtypes = [vp, i64, vp, vp, i64, i32, vp]
-        lib.phl_compat_softmax.argtypes = [vp, i64, vp, i64, vp, vp, i64, i64, i32, u32, vp]
-        lib.phl_uniform_compat_softmax.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, vp, i64, i64, i32, u32, vp]
-        if hasattr(lib, "phl_compat_softmax_split"):
-            lib.phl_compat_planes_bytes.argtypes = [i32]
-            lib.phl_compat_planes_bytes.restype = C.c_size_t
-            lib.phl_compat_prepare.argtypes = [vp, i32, vp, vp]
-            lib.phl_compat_softmax_split.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i64, i32, u32, vp]
-        if hasattr(lib, "phl_nchw_softmax_compat"):    # (an older build loaded through PHL_LIB lacks the NCHW step)
-            lib.phl_nchw_softmax_compat.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, i32, i32, i64, i32, vp]
-        if hasattr(lib, "phl_nchw_expected_value"):    # (an older build loaded through PHL_LIB lacks the expected label)
-            lib.phl_nchw_expected_value.argtypes = [vp, vp, vp, vp, i32, i32, i64, i32, vp]
-            lib.phl_nchw_expected_value_grad.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp]
-        if hasattr(lib, "phl_nchw_scalar_unaries"):    # (an older build loaded through PHL_LIB lacks the scalar unaries)
-            lib.phl_nchw_scalar_unaries.argtypes = [vp] * 5 + [i32] * 6 + [C.c_double, C.c_double, vp]
-            lib.phl_nchw_scalar_unaries_grad.argtypes = [vp] * 6 + [i32] * 6 + [C.c_double, C.c_double, vp]
-        if hasattr(lib, "phl_compat_grad_x"):          # (an older build loaded through PHL_LIB lacks the backward)
-            lib.phl_softmax_neg_grad.argtypes = [vp, i64, vp, i64, vp, i64, i64, i32, vp]
-            lib.phl_uniform_compat_grad.argtypes = [vp, i64, vp, i64, C.c_float, C.c_float, vp, i64, vp, i64, i64, i32, vp]
-            lib.phl_compat_grad_x.argtypes = [vp, i64, vp, C.c_float, vp, i64, i64, i32, vp]
-            lib.phl_compat_mu_grad_workspace_bytes.argtypes = [i64, i32]
-            lib.phl_compat_mu_grad_workspace_bytes.restype = C.c_size_t
-            lib.phl_compat_mu_grad.argtypes = [vp, i64, vp, i64, C.c_float, i64, i32, vp, vp, i32, vp]
-        if hasattr(lib, "phl_box_blur"):               # (an older build loaded through PHL_LIB lacks the blur)
-            lib.phl_box_blur.argtypes = [vp, vp, i64, i64, i64, i32, i32, vp]
-            lib.phl_box_blur_grad.argtypes = [vp, vp, i64, i64, i64, i32, C.c_double, vp, vp, vp]
-            lib.phl_box_blur_fused_max_r.argtypes = [i32, i32, i32]
-        if hasattr(lib, "phl_guided_filter"):          # (an older build loaded through PHL_LIB lacks the guided filter)
-            lib.phl_guided_filter.argtypes = [vp, vp, vp, vp] + [i32] * 8 + [vp, vp, vp, vp, vp, C.c_float, vp]
-        if hasattr(lib, "phl_guided_filter_grad"):     # (an older build loaded through PHL_LIB lacks its backward)
-            lib.phl_guided_filter_grad.argtypes = [vp] * 6 + [i32] * 8 + [vp, vp, vp, vp, vp, C.c_float, i32, vp]
-        if hasattr(lib, "phl_guided_filter_labels_per_chunk"):     # (an older build loaded through PHL_LIB lacks the query)
-            lib.phl_guided_filter_labels_per_chunk.argtypes = [i32] * 7
-        lib.phl_stream_copy.argtypes = [vp, vp, i64, vp]
-        lib.phl_copy2d.argtypes = [vp, i64, i64, vp, i64, i64, i64, i32, vp]
-        lib.phl_cost_volume.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]
-        if hasattr(lib, "phl_cost_volume_nchw"):       # (an older build loaded through PHL_LIB lacks the channel-major sweep)
-            lib.phl_cost_volume_nchw.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, u32, vp, i64, i64, i64, vp]
-            lib.phl_disparity_wta.argtypes = [vp, vp, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, i64, i64, vp]
-        lib.phl_get_keys.argtypes = [vp, vp]
-        lib.phl_get_vertex_order.argtypes = [vp, vp]
-        lib.phl_get_replay.argtypes = [vp, vp, vp]
-        lib.phl_get_neighbors.argtypes = [vp, vp]
-        lib.phl_get_splat_lists.argtypes = [vp, vp, vp, vp]
+        for name, ret, args in _ABI:
+            fn = getattr(lib, name, None)       # (an older build loaded through PHL_LIB lacks the newer entry points)
+            if fn is not None:
+                fn.restype, fn.argtypes = _KINDS[ret], [_KINDS[k] for k in args]
         _lib = lib
         return lib
 
@@ -156,7 +158,38 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-_STAGE_BYTES = 2 << 20       # piece size of the staged form below
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _host(a):
+    """A numpy array the library reads or fills on the host."""
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _launch(device, name, *args):
+    """Library function ``name`` on ``device`` with its current stream as the last argument; raises on a failed status.
+    Looked up on every call, so that a replaced attribute of the library (a test's spy) is the one that runs."""
+    with torch.cuda.device(device):
+        _check(getattr(load_library(), name)(*args, _stream(device)))
+
+
+def _call(name, *args, value=False):
+    """Library function ``name`` that takes no stream (sizes, host readers, settings), looked up like _launch's: raises on
+    a failed status, or with ``value`` returns what the function returned."""
+    rv = getattr(load_library(), name)(*args)
+    if value:
+        return rv
+    _check(rv)
+
+
+def _flags(subtract_input=False, exact=False, no_tiles=False):
+    return (SUBTRACT_INPUT if subtract_input else 0) | (EXACT if exact else 0) | (NO_TILES if no_tiles else 0)
+
+
+def _default_device(t):
+    """The device a result is built on when the caller names none: ``t``'s own GPU, or the current one for anything else."""
+    return t.device if (torch.is_tensor(t) and t.is_cuda) else torch.device("cuda", torch.cuda.current_device())
 
 
 def to_device(t, device):
@@ -167,22 +200,11 @@ def to_device(t, device):
     at 7 MB ... 1 GB -- it pins the user's pages for the DMA); copying through pinned staging pieces first, as rounds 3-4 did,
     is bound by the host memcpy and by the caching host allocator handing out fresh pinned blocks while earlier pieces are
     still in flight (3-4 GB/s at 128 MB and up, 20 GB/s at 7 MB on the same box; box to box the notebook-sized call swung
-    between 1.2 and 5 ms).  PHL_H2D=staged brings the staged form back."""
+    between 1.2 and 5 ms)."""
     device = torch.device(device)
     if t.device == device:
         return t
-    if (os.environ.get("PHL_H2D") != "staged" or t.is_cuda or t.is_pinned() or not t.is_contiguous()
-            or t.numel() * t.element_size() < (1 << 20)):
-        return t.to(device, non_blocking=(not t.is_cuda and t.is_pinned()))
-    out = torch.empty(t.shape, dtype=t.dtype, device=device)
-    src, dst = t.reshape(-1), out.view(-1)
-    step = max(1, _STAGE_BYTES // t.element_size())
-    for a in range(0, src.numel(), step):
-        b = min(src.numel(), a + step)
-        stage = torch.empty(b - a, dtype=t.dtype, pin_memory=True)
-        stage.copy_(src[a:b])
-        dst[a:b].copy_(stage, non_blocking=True)     # (the host allocator keeps the piece until this copy has run)
-    return out
+    return t.to(device, non_blocking=(not t.is_cuda and t.is_pinned()))
 
 
 def to_host(t):
@@ -221,22 +243,25 @@ class Lattice:
         vertices above M = 16383, see PHL_BUILD_REFERENCE_TABLE in include/phl.h) -- with ``exact=True`` the
         filter is then bit-identical to the reference's CPU path at any size."""
         _require_gpu()
-        lib = load_library()
+        load_library()
         if ref.dim() != 2:
             raise ValueError(f"ref must be [n, d], got {tuple(ref.shape)}")
-        if device is None:
-            device = ref.device if ref.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        ref_d = _as_device(ref.detach(), self.device)
-        self.n, self.d = int(ref_d.shape[0]), int(ref_d.shape[1])
+        device = torch.device(_default_device(ref) if device is None else device)
+        ref_d = _as_device(ref.detach(), device)
+        n, d = int(ref_d.shape[0]), int(ref_d.shape[1])
         handle = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(lib.phl_build_ex(C.byref(handle), C.c_void_p(ref_d.data_ptr()), self.n, self.d, ref_d.stride(0),
-                                    ref_d.stride(1), self.device.index or 0, _stream(self.device),
-                                    BUILD_REFERENCE_TABLE if reference_table else 0))
+        with torch.cuda.device(device):
+            _call("phl_build_ex", C.byref(handle), _ptr(ref_d), n, d, ref_d.stride(0), ref_d.stride(1), device.index or 0,
+                  _stream(device), BUILD_REFERENCE_TABLE if reference_table else 0)
+        self._adopt(handle, device, n, d, reference_table)
+
+    def _adopt(self, handle, device, n, d, reference_table):
+        """Take ownership of a built lattice: everything a Lattice knows about its handle."""
+        self.device, self.n, self.d = device, n, d
         self.reference_table = bool(reference_table)
         self._h = handle
-        self.M = int(lib.phl_num_vertices(handle))
+        self.M = int(_call("phl_num_vertices", handle, value=True))
+        return self
 
     # ---- a band cut out of the whole image's lattice (row-band multi-GPU, phl/rowtile.py) ---------------------
     @classmethod
@@ -246,33 +271,21 @@ class Lattice:
 
     def vertices_of_pixels(self, p0, p1):
         """bool numpy [M]: first-touch vertices touched by pixels [p0, p1)."""
-        lib = load_library()
-        lib.phl_vertices_of_pixels.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         mask = np.zeros(self.M, np.uint8)
-        with torch.cuda.device(self.device):
-            _check(lib.phl_vertices_of_pixels(self._h, int(p0), int(p1), mask.ctypes.data_as(C.c_void_p), _stream(self.device)))
+        _launch(self.device, "phl_vertices_of_pixels", self._h, int(p0), int(p1), _host(mask))
         return mask.astype(bool)
 
     def sub_lattice(self, p0, p1, sel, n_own, ref_band):
         """Lattice of pixels [p0, p1) on the selected vertices ``sel`` (first-touch ids; the first n_own = every vertex those
         pixels touch, then ghosts in the caller's order): phl_sub_lattice in include/phl.h.  The new lattice numbers its
         vertices by position in ``sel``; rows of ghost vertices are M_own + position among the ghosts."""
-        lib = load_library()
-        lib.phl_sub_lattice.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
-                                        C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         sel = np.ascontiguousarray(sel, np.int32)
         ref_d = _as_device(ref_band.detach(), self.device)
         assert ref_d.shape == (p1 - p0, self.d)
         handle = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _check(lib.phl_sub_lattice(C.byref(handle), self._h, int(p0), int(p1), sel.ctypes.data_as(C.c_void_p), len(sel), int(n_own),
-                                       C.c_void_p(ref_d.data_ptr()), ref_d.stride(0), ref_d.stride(1), _stream(self.device)))
-        sub = Lattice.__new__(Lattice)
-        sub.device, sub.n, sub.d = self.device, int(p1 - p0), self.d
-        sub.reference_table = self.reference_table
-        sub._h = handle
-        sub.M = int(lib.phl_num_vertices(handle))
-        return sub
+        _launch(self.device, "phl_sub_lattice", C.byref(handle), self._h, int(p0), int(p1), _host(sel), len(sel), int(n_own),
+                _ptr(ref_d), ref_d.stride(0), ref_d.stride(1))
+        return Lattice.__new__(Lattice)._adopt(handle, self.device, int(p1 - p0), self.d, self.reference_table)
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -293,14 +306,14 @@ class Lattice:
 
     @property
     def device_bytes(self):
-        return int(load_library().phl_device_bytes(self._h))
+        return int(_call("phl_device_bytes", self._h, value=True))
 
     def reserve(self, vd, strided_io=False, exact=False):
         """Pre-size everything a ``filter`` over ``vd`` channels needs, so that the next call -- on any stream,
         e.g. inside a HIP-graph capture -- allocates nothing.  strided_io: also the staging copies channel-major
         (NCHW) views -- and, from 128 channels on, pixel-major rows off the 16-byte grid such as column slices -- go
         through; exact: prepare for ``exact=True`` calls."""
-        _check(load_library().phl_reserve_ex(self._h, int(vd), (1 if strided_io else 0) | (2 if exact else 0)))
+        _call("phl_reserve_ex", self._h, int(vd), (1 if strided_io else 0) | (2 if exact else 0))
 
     # ---- hot path ---------------------------------------------------------------------------
     def filter(self, src, subtract_input=False, out=None, exact=False, no_tiles=False):
@@ -316,11 +329,8 @@ class Lattice:
         vd = int(src_d.shape[1])
         res = out if (out is not None and out.device == self.device) else torch.empty(
             (self.n, vd), dtype=torch.float32, device=self.device)
-        flags = (SUBTRACT_INPUT if subtract_input else 0) | (EXACT if exact else 0) | (NO_TILES if no_tiles else 0)
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_filter(self._h, C.c_void_p(src_d.data_ptr()), vd, src_d.stride(0),
-                                             src_d.stride(1), C.c_void_p(res.data_ptr()), res.stride(0),
-                                             res.stride(1), flags, _stream(self.device)))
+        _launch(self.device, "phl_filter", self._h, _ptr(src_d), vd, src_d.stride(0), src_d.stride(1), _ptr(res), res.stride(0),
+                res.stride(1), _flags(subtract_input, exact, no_tiles))
         if out is not None and out is not res:
             out.copy_(res)
             return out
@@ -335,27 +345,20 @@ class Lattice:
         vd = int(src_d.shape[1])
         vert = torch.empty((self.M, vd), dtype=torch.float32, device=self.device) if out is None else out
         assert vert.shape == (self.M, vd) and vert.is_contiguous()
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_splat(self._h, C.c_void_p(src_d.data_ptr()), vd, src_d.stride(0),
-                                            C.c_void_p(vert.data_ptr()),
-                                            (EXACT if exact else 0) | (NO_TILES if no_tiles else 0),
-                                            _stream(self.device)))
+        _launch(self.device, "phl_splat", self._h, _ptr(src_d), vd, src_d.stride(0), _ptr(vert), _flags(False, exact, no_tiles))
         return vert
 
     # ---- splat in parts (row-band exchange overlap, see phl_splat_part in include/phl.h) ------------------
     def chunks_touching(self, rows):
         """bool numpy mask [#chunks]: pixel chunks that contribute to any of the vertex rows (int64 device tensor)."""
-        lib = load_library()
-        mask = np.zeros(int(lib.phl_num_chunks(self._h)), np.int32)
+        mask = np.zeros(int(_call("phl_num_chunks", self._h, value=True)), np.int32)
         rows = rows.to(self.device, torch.int64).contiguous()
-        with torch.cuda.device(self.device):
-            _check(lib.phl_chunks_touching(self._h, C.c_void_p(rows.data_ptr()), int(rows.numel()),
-                                           mask.ctypes.data_as(C.c_void_p), _stream(self.device)))
+        _launch(self.device, "phl_chunks_touching", self._h, _ptr(rows), int(rows.numel()), _host(mask))
         return mask.astype(bool)
 
     @property
     def partial_rows(self):
-        return int(load_library().phl_partial_rows(self._h))
+        return int(_call("phl_partial_rows", self._h, value=True))
 
     def splat_part(self, src, out, partial, chunks, rows, pack_pos=None, pack=None):
         """Run the chunk splat for the listed chunks (int32 device tensor) and complete the listed vertex rows
@@ -366,39 +369,31 @@ class Lattice:
         assert src.stride(1) == 1 and out.is_contiguous() and out.shape == (self.M, vd)
         assert chunks.dtype == torch.int32 and rows.dtype == torch.int32 and chunks.is_contiguous() and rows.is_contiguous()
         assert partial.is_contiguous() and partial.shape[0] >= self.partial_rows and partial.shape[1] == vd
-        lib = load_library()
-        with torch.cuda.device(self.device):
-            if pack_pos is None:
-                _check(lib.phl_splat_part(self._h, C.c_void_p(src.data_ptr()), vd, src.stride(0), C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(partial.data_ptr()), C.c_void_p(chunks.data_ptr()), int(chunks.numel()),
-                                          C.c_void_p(rows.data_ptr()), int(rows.numel()), _stream(self.device)))
-            else:
-                assert pack_pos.dtype == torch.int32 and pack_pos.is_contiguous() and pack_pos.numel() == rows.numel()
-                assert pack.stride(1) == 1 and pack.shape[1] == vd and pack.dtype == torch.float32
-                _check(lib.phl_splat_part_pack(self._h, C.c_void_p(src.data_ptr()), vd, src.stride(0), C.c_void_p(out.data_ptr()),
-                                               C.c_void_p(partial.data_ptr()), C.c_void_p(chunks.data_ptr()), int(chunks.numel()),
-                                               C.c_void_p(rows.data_ptr()), int(rows.numel()), C.c_void_p(pack_pos.data_ptr()),
-                                               C.c_void_p(pack.data_ptr()), pack.stride(0), _stream(self.device)))
+        part = (self._h, _ptr(src), vd, src.stride(0), _ptr(out), _ptr(partial), _ptr(chunks), int(chunks.numel()), _ptr(rows),
+                int(rows.numel()))
+        if pack_pos is None:
+            _launch(self.device, "phl_splat_part", *part)
+        else:
+            assert pack_pos.dtype == torch.int32 and pack_pos.is_contiguous() and pack_pos.numel() == rows.numel()
+            assert pack.stride(1) == 1 and pack.shape[1] == vd and pack.dtype == torch.float32
+            _launch(self.device, "phl_splat_part_pack", *part, _ptr(pack_pos), _ptr(pack), pack.stride(0))
         return out
 
     def set_blur_rows(self, ranges):
         """Row-band lattices: per blur axis the rows whose output of that axis is read later, as three ascending
         {begin, end} row ranges (numpy / list [d+1][3][2]); None: all rows.  See phl_set_blur_rows in include/phl.h."""
-        lib = load_library()
         if ranges is None:
-            _check(lib.phl_set_blur_rows(self._h, None, 0))
+            _call("phl_set_blur_rows", self._h, None, 0)
             return
         r = np.ascontiguousarray(ranges, np.int64)
         assert r.shape == (self.d + 1, 3, 2), r.shape
-        _check(lib.phl_set_blur_rows(self._h, r.ctypes.data_as(C.c_void_p), self.d + 1))
+        _call("phl_set_blur_rows", self._h, _host(r), self.d + 1)
 
     def blur_axis(self, axis, vin, vout=None):
         vd = int(vin.shape[1])
         vout = torch.empty_like(vin) if vout is None else vout
         assert vin.is_contiguous() and vout.is_contiguous()
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_blur_axis(self._h, int(axis), C.c_void_p(vin.data_ptr()),
-                                                C.c_void_p(vout.data_ptr()), vd, _stream(self.device)))
+        _launch(self.device, "phl_blur_axis", self._h, int(axis), _ptr(vin), _ptr(vout), vd)
         return vout
 
     def blur(self, vert, scratch=None):
@@ -406,9 +401,7 @@ class Lattice:
         other = torch.empty_like(vert) if scratch is None else scratch
         assert vert.is_contiguous() and other.is_contiguous() and other.shape == vert.shape
         which = C.c_int(0)
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_blur(self._h, C.c_void_p(vert.data_ptr()), C.c_void_p(other.data_ptr()),
-                                           int(vert.shape[1]), C.byref(which), _stream(self.device)))
+        _launch(self.device, "phl_blur", self._h, _ptr(vert), _ptr(other), int(vert.shape[1]), C.byref(which))
         return other if which.value else vert
 
     def gather_rows(self, vert, idx, out=None):
@@ -416,30 +409,21 @@ class Lattice:
         k, vd = int(idx.numel()), int(vert.shape[1])
         out = torch.empty((k, vd), dtype=torch.float32, device=self.device) if out is None else out
         assert vert.is_contiguous() and idx.dtype == torch.int64 and idx.is_contiguous() and out.stride(1) == 1
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_gather_rows(C.c_void_p(vert.data_ptr()), vd, C.c_void_p(idx.data_ptr()), k,
-                                                  C.c_void_p(out.data_ptr()), out.stride(0) if k else vd, _stream(self.device)))
+        _launch(self.device, "phl_gather_rows", _ptr(vert), vd, _ptr(idx), k, _ptr(out), out.stride(0) if k else vd)
         return out
 
     def scatter_add_rows(self, vert, idx, rows):
         """vert[idx[r]] += rows[r]; idx must hold distinct vertex ids."""
         k, vd = int(idx.numel()), int(vert.shape[1])
         assert vert.is_contiguous() and idx.dtype == torch.int64 and idx.is_contiguous() and (k == 0 or rows.stride(1) == 1)
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_scatter_add_rows(C.c_void_p(vert.data_ptr()), vd, C.c_void_p(idx.data_ptr()), k,
-                                                       C.c_void_p(rows.data_ptr()), rows.stride(0) if k else vd,
-                                                       _stream(self.device)))
+        _launch(self.device, "phl_scatter_add_rows", _ptr(vert), vd, _ptr(idx), k, _ptr(rows), rows.stride(0) if k else vd)
         return vert
 
     def slice(self, vert, sub=None, exact=False, out=None, no_tiles=False):
         vd = int(vert.shape[1])
         out = torch.empty((self.n, vd), dtype=torch.float32, device=self.device) if out is None else out
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_slice(self._h, C.c_void_p(vert.data_ptr()), vd, C.c_void_p(out.data_ptr()),
-                                            out.stride(0), C.c_void_p(sub.data_ptr()) if sub is not None else None,
-                                            sub.stride(0) if sub is not None else 0,
-                                            (EXACT if exact else 0) | (NO_TILES if no_tiles else 0),
-                                            _stream(self.device)))
+        _launch(self.device, "phl_slice", self._h, _ptr(vert), vd, _ptr(out), out.stride(0), _ptr(sub),
+                sub.stride(0) if sub is not None else 0, _flags(False, exact, no_tiles))
         return out
 
     def filter_grad(self, src, g, ref, need_src=True):
@@ -453,19 +437,14 @@ class Lattice:
         L = int(src_d.shape[1])
         grad_ref = torch.empty((self.n, self.d), dtype=torch.float32, device=self.device)
         grad_src = torch.empty((self.n, L), dtype=torch.float32, device=self.device) if need_src else None
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_filter_grad(self._h, C.c_void_p(src_d.data_ptr()), src_d.stride(0),
-                                                  C.c_void_p(g_d.data_ptr()), g_d.stride(0), L,
-                                                  C.c_void_p(ref_d.data_ptr()), ref_d.stride(0), ref_d.stride(1),
-                                                  C.c_void_p(grad_ref.data_ptr()),
-                                                  C.c_void_p(grad_src.data_ptr()) if need_src else None, L,
-                                                  _stream(self.device)))
+        _launch(self.device, "phl_filter_grad", self._h, _ptr(src_d), src_d.stride(0), _ptr(g_d), g_d.stride(0), L, _ptr(ref_d),
+                ref_d.stride(0), ref_d.stride(1), _ptr(grad_ref), _ptr(grad_src), L)
         return grad_src, grad_ref
 
     def tile_stats(self, vd):
         """Chunk statistics of the LDS-staged path (see phl_tile_stats in include/phl.h)."""
         out = np.zeros(7, np.int64)
-        _check(load_library().phl_tile_stats(self._h, int(vd), out.ctypes.data_as(C.c_void_p)))
+        _call("phl_tile_stats", self._h, int(vd), _host(out))
         keys = ("pixels_per_chunk", "chunks", "max_local_vertices", "slots", "multi_chunk_slots", "staged_splat",
                 "staged_slice")
         return dict(zip(keys, (int(x) for x in out)))
@@ -475,16 +454,14 @@ class Lattice:
         ghosts; returns, for every key, its ROW in the vertex buffers (int32 [K]).  Updates ``M``."""
         keys = np.ascontiguousarray(keys, np.int16).reshape(-1, self.d)
         vid = np.empty(len(keys), np.int32)
-        with torch.cuda.device(self.device):
-            _check(load_library().phl_add_vertices(self._h, keys.ctypes.data_as(C.c_void_p), len(keys),
-                                                   vid.ctypes.data_as(C.c_void_p), _stream(self.device)))
-        self.M = int(load_library().phl_num_vertices(self._h))
+        _launch(self.device, "phl_add_vertices", self._h, _host(keys), len(keys), _host(vid))
+        self.M = int(_call("phl_num_vertices", self._h, value=True))
         self._rows = None
         return vid
 
     @property
     def M_local(self):
-        return int(load_library().phl_num_local_vertices(self._h))
+        return int(_call("phl_num_local_vertices", self._h, value=True))
 
     # ---- vertex numbering ---------------------------------------------------------------------
     # keys() / replay() / neighbors() / splat_lists() speak the reference's first-touch vertex ids.  The ROWS of
@@ -494,7 +471,7 @@ class Lattice:
         hit = getattr(self, "_rows", None)
         if hit is None or hit.numel() != self.M:
             out = np.empty(self.M, np.int32)
-            _check(load_library().phl_get_vertex_order(self._h, out.ctypes.data_as(C.c_void_p)))
+            _call("phl_get_vertex_order", self._h, _host(out))
             hit = self._rows = torch.from_numpy(out.astype(np.int64)).to(self.device)
         return hit
 
@@ -512,33 +489,30 @@ class Lattice:
     def pixel_order(self):
         """int32 [n]: pixels in chunk order (chunk c = pixel_order()[c*P:(c+1)*P], P = tile_stats()['pixels_per_chunk'])."""
         out = np.empty(self.n, np.int32)
-        lib = load_library()
-        lib.phl_get_pixel_order.argtypes = [C.c_void_p, C.c_void_p]
-        _check(lib.phl_get_pixel_order(self._h, out.ctypes.data_as(C.c_void_p)))
+        _call("phl_get_pixel_order", self._h, _host(out))
         return out
 
     def keys(self):
         out = np.empty((self.M, self.d), np.int16)
-        _check(load_library().phl_get_keys(self._h, out.ctypes.data_as(C.c_void_p)))
+        _call("phl_get_keys", self._h, _host(out))
         return out
 
     def replay(self):
         vid = np.empty((self.n, self.d + 1), np.int32)
         w = np.empty((self.n, self.d + 1), np.float32)
-        _check(load_library().phl_get_replay(self._h, vid.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p)))
+        _call("phl_get_replay", self._h, _host(vid), _host(w))
         return vid, w
 
     def neighbors(self):
         out = np.empty((self.d + 1, self.M, 2), np.int32)
-        _check(load_library().phl_get_neighbors(self._h, out.ctypes.data_as(C.c_void_p)))
+        _call("phl_get_neighbors", self._h, _host(out))
         return out
 
     def splat_lists(self):
         ptr = np.empty(self.M + 1, np.int32)
         pix = np.empty(self.n * (self.d + 1), np.int32)
         w = np.empty(self.n * (self.d + 1), np.float32)
-        _check(load_library().phl_get_splat_lists(self._h, ptr.ctypes.data_as(C.c_void_p),
-                                                  pix.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p)))
+        _call("phl_get_splat_lists", self._h, _host(ptr), _host(pix), _host(w))
         return ptr, pix, w
 
 
@@ -551,17 +525,6 @@ def _rowmajor(t):
 def _aligned(t):
     """A row operand the compat kernels take as it is: fp32 CUDA [n, L], unit channel stride, 16-byte aligned rows."""
     return _rowmajor(t) and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _launch(device, name, *args):
-    """Library function ``name`` on ``device`` with its current stream as the last argument; raises on a failed status.
-    Looked up on every call, so that a replaced attribute of the library (a test's spy) is the one that runs."""
-    with torch.cuda.device(device):
-        _check(getattr(load_library(), name)(*args, _stream(device)))
 
 
 def softmax_neg_add(E0, G=None, out=None):
@@ -628,7 +591,7 @@ class _MuForms:
         """Mu as the split kernels read it (phl_compat_prepare)."""
         def make():
             L = self.Mu.shape[0]
-            planes = torch.empty((load_library().phl_compat_planes_bytes(L),), dtype=torch.uint8, device=device)
+            planes = torch.empty((_call("phl_compat_planes_bytes", L, value=True),), dtype=torch.uint8, device=device)
             _launch(device, "phl_compat_prepare", _ptr(self.mu_t(device)), L, _ptr(planes))
             return planes
         return self._form(("planes", str(device)), device, make)
@@ -681,7 +644,7 @@ def _compat_route(L, operands, Mu, uniform=None, structure=True, arith="f32"):
         uniform = None
     if uniform is not None:
         return "uniform", uniform
-    if aligned and L <= 512 and arith == "split" and load_library().phl_compat_planes_bytes(L):
+    if aligned and L <= 512 and arith == "split" and _call("phl_compat_planes_bytes", L, value=True):
         return "split", None
     return ("f32" if aligned and L <= 256 else "gemm"), None
 
@@ -1021,7 +984,7 @@ def compat_mu_grad(X, dE, scale=1.0, out=None, accumulate=False):
         accumulate = False
     elif not (out.is_contiguous() and out.dtype == torch.float32 and out.shape == (L, L)):
         raise TypeError("compat_mu_grad: out must be a contiguous fp32 [L, L] tensor")
-    ws = torch.empty((max(1, load_library().phl_compat_mu_grad_workspace_bytes(n, L)),), dtype=torch.uint8, device=dE.device)
+    ws = torch.empty((max(1, _call("phl_compat_mu_grad_workspace_bytes", n, L, value=True)),), dtype=torch.uint8, device=dE.device)
     _launch(dE.device, "phl_compat_mu_grad", _ptr(X), X.stride(0), _ptr(dE), dE.stride(0), C.c_float(scale), n, L, _ptr(ws), _ptr(out),
             1 if accumulate else 0)
     return out
@@ -1195,7 +1158,7 @@ def _sweep_operands(a, b, dev):
 
 def _sweep_device(img1):
     _require_gpu()
-    return img1.device if (torch.is_tensor(img1) and img1.is_cuda) else torch.device("cuda", torch.cuda.current_device())
+    return _default_device(img1)
 
 
 def _sweep_request(w, max_disp, criterion):
@@ -1257,8 +1220,7 @@ def _blur_view(x, dim):
 
 
 def _blur_operand(t):
-    if not (t.is_cuda and t.dtype == torch.float32):
-        raise TypeError(f"box_blur: takes fp32 CUDA tensors, got {t.dtype} on {t.device}")
+    _fp32_cuda("box_blur", t)
     return t if t.is_contiguous() else t.contiguous()
 
 
@@ -1267,17 +1229,14 @@ def box_blur(x, r, dim, passes=3, out=None):
     its LDS fits, one launch per pass above that.  fp32 CUDA; any strides (copied contiguous)."""
     x = _blur_operand(x)
     outer, h, inner = _blur_view(x, dim)
-    if out is None:
-        out = torch.empty_like(x, memory_format=torch.contiguous_format)
-    elif not (out.is_contiguous() and out.dtype == torch.float32 and out.shape == x.shape and out.device == x.device):
-        raise TypeError("box_blur: out must be a contiguous fp32 tensor of the input's shape and device")
+    out = _out_or_empty("box_blur", out, x.shape, x.device, "the input's shape and device")
     _launch(x.device, "phl_box_blur", _ptr(x), _ptr(out), outer, h, inner, int(r), int(passes))
     return out
 
 
 def box_blur_fused_max_r(inner_is_one, passes=3, grad=False):
     """Largest r that the fused cascade kernel (grad=True: the fused sigma-gradient) takes."""
-    return int(load_library().phl_box_blur_fused_max_r(1 if inner_is_one else 0, int(passes), 1 if grad else 0))
+    return int(_call("phl_box_blur_fused_max_r", 1 if inner_is_one else 0, int(passes), 1 if grad else 0, value=True))
 
 
 def box_blur_grad(v, g, r, dim, sigma, need_x=True, need_sigma=True):
@@ -1343,11 +1302,7 @@ def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=No
     tensors of any strides (copied contiguous); any radius (above phl_guided_filter_max_r at the solving resolution the
     kernels read the image from memory instead of LDS tiles); PhlError status 7 for more than 16 guide channels."""
     _, e, dims, maps = _guided_launch_args("guided_filter", y, x, subtract, "subtract", r, eps, subsample)
-    if out is None:
-        out = torch.empty(y.shape, dtype=torch.float32, device=y.device)
-    elif not (torch.is_tensor(out) and out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == y.shape
-              and out.device == y.device):
-        raise TypeError("guided_filter: out must be a contiguous fp32 tensor of y's shape and device")
+    out = _out_or_empty("guided_filter", out, y.shape, y.device, "y's shape and device")
     if dims is None:
         return out
     yc, xc = y.contiguous(), x.contiguous()
@@ -1364,17 +1319,15 @@ def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False,
     needs = (1 if need_y else 0) | (2 if need_x else 0) | (4 if need_eps else 0)
     if grad is None:
         grad = needs != 0
-    return int(load_library().phl_guided_filter_labels_per_chunk(int(B), int(cy), int(cx), int(h), int(w), 1 if full else 0,
-                                                                 needs if grad else -1))
+    return int(_call("phl_guided_filter_labels_per_chunk", int(B), int(cy), int(cx), int(h), int(w), 1 if full else 0,
+                     needs if grad else -1, value=True))
 
 
 def _guided_launch_args(name, y, x, third, third_name, r, eps, subsample, launch=True):
     """What guided_filter and guided_filter_grad (``name``) share: the checks of y, x and ``third`` (subtract or g: y's
     shape, may be None), of subsample and r; then (cx, eps as the kernels read it, the launch's (B, cy, cx, H, W, h, w,
     r // s), its four index maps).  The last two are None when y has no elements or the caller launches nothing."""
-    for t in (y, x) + (() if third is None else (third,)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32):
-            raise TypeError(f"{name}: takes fp32 CUDA tensors, got {getattr(t, 'dtype', type(t))} on {getattr(t, 'device', '?')}")
+    _fp32_cuda(name, y, x, *(() if third is None else (third,)))
     if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:] or x.device != y.device:
         raise ValueError(f"{name}: y [B, cy, H, W] and x [B, cx, H, W] on one device, got {tuple(y.shape)} and {tuple(x.shape)}")
     if third is not None and (third.shape != y.shape or third.device != y.device):
@@ -1491,9 +1444,7 @@ _REFERENCE_TABLE = os.environ.get("PHL_REFERENCE_TABLE", "1") not in ("", "0")
 def _cache_key(ref, device=None):
     # device=None means what Lattice() resolves it to (ref's own GPU, or the current one for a CPU tensor): the same
     # lattice must be found whether a caller names that device or not (forward with device=dev, backward without)
-    if device is None:
-        device = ref.device if ref.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
+    device = torch.device(_default_device(ref) if device is None else device)
     idx = device.index if device.index is not None else (torch.cuda.current_device() if device.type == "cuda" else None)
     return (ref.device.type, ref.device.index, ref.data_ptr(), tuple(ref.shape), tuple(ref.stride()), ref._version,
             (device.type, idx))
@@ -1549,6 +1500,32 @@ def batch_devices(t=None):
 _batch_streams = {}
 
 
+def _deal(bs, devices, inputs, outputs, item):
+    """Deal the items 0 .. bs-1 of a batch over ``devices``, item i on devices[i % len(devices)], every device on its own
+    side stream: the side stream waits for the current stream of every device that holds one of ``inputs`` (they may
+    still be in flight on the caller's stream), ``item(i, device)`` runs under the device and stream guards, and at the
+    end the current stream of every device that holds one of ``outputs`` waits for the side streams; CPU outputs are
+    complete on return."""
+    sources = list(dict.fromkeys(t.device for t in inputs if t.is_cuda))
+    homes = list(dict.fromkeys(t.device for t in outputs if t.is_cuda))
+    used = []
+    for i in range(bs):
+        dev = devices[i % len(devices)]
+        st = _batch_streams.get(dev)
+        if st is None:
+            st = _batch_streams[dev] = torch.cuda.Stream(device=dev)
+        for d in sources:
+            st.wait_stream(torch.cuda.current_stream(d))
+        with torch.cuda.device(dev), torch.cuda.stream(st):
+            item(i, dev)
+        used.append(st)
+    for st in used:
+        for d in homes:
+            torch.cuda.current_stream(d).wait_stream(st)
+        if any(not t.is_cuda for t in outputs):
+            st.synchronize()
+
+
 def batched_filter(srcs, refs, devices=None, subtract_input=False):
     """Independent lattice per batch item: srcs [bs, n, vd], refs [bs, n, d] (any strides) -> [bs, n, vd] on
     srcs' device.  Item i runs on devices[i % len(devices)], each device on its own side stream, so that with
@@ -1557,27 +1534,15 @@ def batched_filter(srcs, refs, devices=None, subtract_input=False):
     assert refs.shape[0] == bs and srcs.shape[1] == refs.shape[1], "Incompatible shapes {}, and {}".format(tuple(srcs.shape), tuple(refs.shape))
     devices = [torch.device(d) for d in (devices or batch_devices(srcs))]
     _cache_floor[0] = max(_cache_floor[0], min(bs, 64))
-    home = srcs.device
-    out = torch.empty((bs,) + tuple(srcs.shape[1:]), dtype=torch.float32, device=home)
-    used = []
-    for i in range(bs):
-        dev = devices[i % len(devices)]
-        st = _batch_streams.get(dev)
-        if st is None:
-            st = _batch_streams[dev] = torch.cuda.Stream(device=dev)
-        if home.type == "cuda":
-            st.wait_stream(torch.cuda.current_stream(home))      # inputs may still be in flight on the caller's stream
-        with torch.cuda.device(dev), torch.cuda.stream(st):
-            lat = lattice_for(refs[i].detach(), device=dev)
-            s = srcs[i].detach()
-            res = lat.filter(s.to(dev, non_blocking=True) if s.device != dev else s, subtract_input=subtract_input)
-            out[i].copy_(res, non_blocking=True)
-        used.append((dev, st))
-    for dev, st in used:
-        if home.type == "cuda":
-            torch.cuda.current_stream(home).wait_stream(st)
-        else:
-            st.synchronize()
+    out = torch.empty((bs,) + tuple(srcs.shape[1:]), dtype=torch.float32, device=srcs.device)
+
+    def item(i, dev):
+        lat = lattice_for(refs[i].detach(), device=dev)
+        s = srcs[i].detach()
+        res = lat.filter(s.to(dev, non_blocking=True) if s.device != dev else s, subtract_input=subtract_input)
+        out[i].copy_(res, non_blocking=True)
+
+    _deal(bs, devices, (srcs, refs), (out,), item)
     return out
 
 
@@ -1588,34 +1553,19 @@ def batched_filter_grad(srcs, refs, g, need_src=True, devices=None):
     lattice its forward pass cached.  Raises PhlError(status 7) if the fused kernels do not take the shape."""
     bs = srcs.shape[0]
     devices = [torch.device(d) for d in (devices or batch_devices(srcs))]
-    home = srcs.device
     grad_refs = torch.empty(tuple(refs.shape), dtype=torch.float32, device=refs.device)
-    grad_srcs = torch.empty(tuple(srcs.shape), dtype=torch.float32, device=home) if need_src else None
-    used = []
-    for i in range(bs):
-        dev = devices[i % len(devices)]
-        st = _batch_streams.get(dev)
-        if st is None:
-            st = _batch_streams[dev] = torch.cuda.Stream(device=dev)
-        for t in (srcs, refs, g):
-            if t.is_cuda:
-                st.wait_stream(torch.cuda.current_stream(t.device))
-        with torch.cuda.device(dev), torch.cuda.stream(st):
-            r = refs[i].detach()
-            lat = lattice_for(r, device=dev)
-            gs, gr = lat.filter_grad(srcs[i].detach().to(dev, non_blocking=True), g[i].detach().to(dev, non_blocking=True),
-                                     r.to(dev, non_blocking=True), need_src=need_src)
-            grad_refs[i].copy_(gr, non_blocking=True)
-            if need_src:
-                grad_srcs[i].copy_(gs, non_blocking=True)
-        used.append((dev, st))
-    outs = [t for t in (grad_refs, grad_srcs) if t is not None]
-    for dev, st in used:
-        for t in outs:
-            if t.is_cuda:
-                torch.cuda.current_stream(t.device).wait_stream(st)
-        if any(not t.is_cuda for t in outs):
-            st.synchronize()
+    grad_srcs = torch.empty(tuple(srcs.shape), dtype=torch.float32, device=srcs.device) if need_src else None
+
+    def item(i, dev):
+        r = refs[i].detach()
+        lat = lattice_for(r, device=dev)
+        gs, gr = lat.filter_grad(srcs[i].detach().to(dev, non_blocking=True), g[i].detach().to(dev, non_blocking=True),
+                                 r.to(dev, non_blocking=True), need_src=need_src)
+        grad_refs[i].copy_(gr, non_blocking=True)
+        if need_src:
+            grad_srcs[i].copy_(gs, non_blocking=True)
+
+    _deal(bs, devices, (srcs, refs, g), (grad_refs, grad_srcs) if need_src else (grad_refs,), item)
     return grad_srcs, grad_refs
 
 

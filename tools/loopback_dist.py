@@ -108,7 +108,6 @@ class WireDist(LoopbackDist):
         import phl
 
         self.lib = phl.load_library()
-        self.lib.phl_debug_slow_copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
         self.c = ctypes
         import os
 
