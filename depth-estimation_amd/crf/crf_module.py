@@ -287,31 +287,39 @@ _NCHW_STEP = os.environ.get("PHL_NCHW_STEP", "1") not in ("", "0")
 def _mean_field_nchw_step_fused(E0, refs, W, M, niters, expect=False, values=None):
     """The same iteration for any other W (the default guided filter), without autograd, in the reference's order
     E = E0 + W(Mu(Q)) (crf_module.py:97-99): everything between two W calls -- the add, the negation, the softmax over
-    the label channels and the compatibility product -- is ONE channel-major kernel (phl.nchw_softmax_compat), so Q and E
-    never exist in memory and nothing is transposed.  W is called once per iteration as the module it is, on whatever
+    the label channels and the compatibility product -- is ONE channel-major kernel (phl.nchw_softmax_compat; its wide form
+    phl.nchw_softmax_compat_wide for a general Mu above 256 labels), so Q and E never exist in memory and nothing is transposed.  W is called once per iteration as the module it is, on whatever
     engine it picks.  M: _compat_matrix of the Mu module.  Gives the logits -E of the last iteration -- or, with
     ``expect``, their expected label [B, 1, H, W] under ``values`` (None: 0 .. L-1) straight from E0 and G
     (phl.nchw_expected_value), the logits never written."""
     import phl
 
     uniform = (phl._mu_uniform(M) or False) if M.shape[0] <= phl.NCHW_UNIFORM_MAX_L else False   # one read per forward
-    Y = phl.nchw_softmax_compat(E0, None, M, uniform=uniform)
+    wide = not uniform and M.shape[0] > phl.NCHW_PRODUCT_MAX_L       # a general Mu above 256 labels: the 32-pixel tile
+
+    def step(G, out=None):
+        if wide:
+            return phl.nchw_softmax_compat_wide(E0, G, M, out=out)
+        return phl.nchw_softmax_compat(E0, G, M, uniform=uniform, out=out)
+
+    Y = step(None)
     for it in range(niters):
         G = W(Y, refs)
         if it == niters - 1:
             if expect:
                 return phl.nchw_expected_value(E0, G, values, negate=True)
             return phl.nchw_softmax_compat(E0, G, logits=True)
-        Y = phl.nchw_softmax_compat(E0, G, M, uniform=uniform, out=Y)
+        Y = step(G, out=Y)
 
 
 def _nchw_step_matrix(mu, E0, labels):
-    """_compat_matrix of ``mu`` if phl.nchw_softmax_compat takes it at this label count, else None."""
+    """_compat_matrix of ``mu`` if phl.nchw_softmax_compat (a general Mu above 256 labels: phl.nchw_softmax_compat_wide)
+    takes it at this label count, else None."""
     import phl
 
     L = E0.shape[1]
     M = _compat_matrix(mu, L, labels, E0.device) if L <= phl.NCHW_UNIFORM_MAX_L else None
-    if M is not None and L > phl.NCHW_PRODUCT_MAX_L and not phl._mu_uniform(M):
+    if M is not None and L > phl.NCHW_WIDE_MAX_L and not phl._mu_uniform(M):
         return None
     return M
 
@@ -419,8 +427,9 @@ class CRFasRNN(nn.Module):
     ``lattice=True`` selects the permutohedral W (BatchedAdjacency, the MI355X path); the default
     stays the reference's guided-filter W.  With that W, a forward on fp32 CUDA tensors that autograd does not record
     (no gradient asked of the logits, the guide, Mu's or W's parameters) and a Mu that is a matrix (``charb``, a
-    bias-free 1x1 conv: at most 256 labels, 1024 for the Potts family) runs _mean_field_nchw_step_fused: per iteration W
-    and one channel-major kernel for everything else (phl.nchw_softmax_compat); PHL_NCHW_STEP=0 in the environment
+    bias-free 1x1 conv: at most 512 labels, 1024 for the Potts family) runs _mean_field_nchw_step_fused: per iteration W
+    and one channel-major kernel for everything else (phl.nchw_softmax_compat; phl.nchw_softmax_compat_wide for a general
+    Mu at 257 to 512 labels, the reference's 341 at 2048 columns among them); PHL_NCHW_STEP=0 in the environment
     keeps the plain loop.  Anything else -- training, CPU tensors, float64, another Mu -- is the plain NCHW loop.
     ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with: on
     that route the loop's last call is phl.nchw_expected_value on E0 and G, and the logits are never written.

@@ -88,6 +88,7 @@ _ABI = (
     ("phl_compat_softmax_split", "i", "PqPqPPPqqiIS"),
     ("phl_uniform_compat_softmax", "i", "PqPqffPqqiIS"),
     ("phl_nchw_softmax_compat", "i", "PPPffPiiqiS"),
+    ("phl_nchw_softmax_compat_wide", "i", "PPPPiiqS"),
     ("phl_nchw_expected_value", "i", "PPPPiiqiS"),
     ("phl_nchw_expected_value_grad", "i", "PPPPPiiqiS"),
     ("phl_nchw_scalar_unaries", "i", "PPPPPiiiiiiddS"),
@@ -754,6 +755,28 @@ def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=
             mode, M, ab = NCHW_PRODUCT, _mu_forms(Mu).dense(dev), (0.0, 0.0)
     e, g = E0.contiguous(), None if G is None else G.contiguous()        # (named: a copy must outlive the launch)
     _launch(dev, "phl_nchw_softmax_compat", _ptr(e), _ptr(g), _ptr(M), C.c_float(ab[0]), C.c_float(ab[1]), _ptr(out), B, L, n, mode)
+    return out
+
+
+NCHW_WIDE_MAX_L = 512                # a general Mu: phl_nchw_softmax_compat_wide's range
+
+
+def nchw_softmax_compat_wide(E0, G=None, Mu=None, *, out=None):
+    """``nchw_softmax_compat(E0, G, Mu, uniform=False)`` for up to NCHW_WIDE_MAX_L = 512 labels, one kernel
+    (phl_nchw_softmax_compat_wide): ``out[:, c] = sum_a Mu[a, c] * softmax(-(E0 + G), dim=1)[:, a]`` for fp32 CUDA E0, G
+    [B, L, H, W] (or [B, L, n]; G optional) and Mu [L, L] in the _compat_matrix convention, always as a product (a Mu of
+    the Potts family is not looked for).  Up to 256 labels it runs nchw_softmax_compat's kernels and gives their bits;
+    above, the same scheme on a tile of 32 pixels.  Inputs that are not contiguous are made so.
+    out: a contiguous fp32 tensor of E0's shape, returned.  Raises PhlError with the library's status: 1 for out aliasing
+    E0 or G, 7 for more than 512 labels."""
+    B, L, n = _nchw_operands("nchw_softmax_compat_wide", E0, G, "E0")
+    dev = E0.device
+    out = _out_or_empty("nchw_softmax_compat_wide", out, E0.shape, dev, "E0's shape and device")
+    if not torch.is_tensor(Mu) or tuple(Mu.shape) != (L, L):
+        raise ValueError(f"nchw_softmax_compat_wide: Mu must be an [L, L] = [{L}, {L}] tensor")
+    M = _mu_forms(Mu).dense(dev)
+    e, g = E0.contiguous(), None if G is None else G.contiguous()        # (named: a copy must outlive the launch)
+    _launch(dev, "phl_nchw_softmax_compat_wide", _ptr(e), _ptr(g), _ptr(M), _ptr(out), B, L, n)
     return out
 
 

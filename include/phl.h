@@ -316,6 +316,19 @@ int phl_uniform_compat_softmax(const float *E0_dev, int64_t e0_row_stride, const
 enum phl_nchw_mode { PHL_NCHW_PRODUCT = 0, PHL_NCHW_UNIFORM = 1, PHL_NCHW_SOFTMAX = 2, PHL_NCHW_LOGITS = 3 };
 int phl_nchw_softmax_compat(const float *E0_dev, const float *G_dev, const float *mu_dev, float alpha, float beta,
                             float *out_dev, int B, int L, int64_t n, int mode, phl_stream stream);
+/* PHL_NCHW_PRODUCT for 1 <= L <= 512: what a general mu needs at the reference's label counts above 256 (max_disp =
+ * w / 6: 341 at 2048 columns, 480 at 2880).  Up to 256 labels it runs the code of phl_nchw_softmax_compat(...,
+ * PHL_NCHW_PRODUCT) and gives its bits; for 256 < L <= 512 the same scheme on an LDS-staged [L][32 pixels] block (64 KiB
+ * at 512 labels, two workgroups per CU): the max-subtracted column softmax with eight partials per pixel combined in a
+ * fixed order, then the product on the f32-input matrix cores, mu read from global memory / L2: an fma chain in a order
+ * over each block of 32 labels, the blocks' sums added in an order that is a function of the workgroup's index alone (a
+ * third of one long chain's rounding at 341 labels; equal columns at different pixels may differ in the last bits).
+ * Operands, the float4 / dword rule and the order of the checks are phl_nchw_softmax_compat's: PHL_ERR_INVALID for
+ * B < 0, n < 0 or L < 1; then B == 0 or n == 0 is PHL_OK with nothing launched; then PHL_ERR_INVALID for NULL E0 / out /
+ * mu or out aliasing E0 or G; PHL_ERR_TOO_LARGE when B*L*n*4 bytes leave int64 or the workgroups (64 pixels each; 32
+ * above 256 labels) leave 2^31 - 1; PHL_ERR_UNSUPPORTED for L > 512.  No atomics: the same bits on every run. */
+int phl_nchw_softmax_compat_wide(const float *E0_dev, const float *G_dev, const float *mu_dev, float *out_dev, int B,
+                                 int L, int64_t n, phl_stream stream);
 /* ---- the expected label of a channel-major column: the end of the CRFasRNN heads (crf/mb_stereo_crf.py) -----------
  * Every head finishes with logits2average_depth(CRF(...)): a softmax over the label channels, a broadcast product with
  * the labels and a sum.  Here that is one kernel, and with negate != 0 it takes the loop's E0 and G as they are, so the
