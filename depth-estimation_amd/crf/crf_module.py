@@ -312,6 +312,23 @@ def _mean_field_nchw_step_fused(E0, refs, W, M, niters, expect=False, values=Non
         Y = step(G, out=Y)
 
 
+def _mean_field_nchw_step_grad(E0, refs, W, M, niters, expect=False, values=None):
+    """The loop of _mean_field_nchw_step_fused under autograd, at most phl.NCHW_TRAIN_MAX_L labels: everything between two
+    W calls is phl.NchwStepTrain -- one kernel forward, one call backward (dE, and Mu's gradient through the
+    differentiable M), which saves E0, G and M and nothing it computed, so no [B, L, H, W] intermediate of the add, the
+    negation, the softmax or the product lives until the backward.  W is called as the module it is (``fused_grad``
+    still chooses its engine) and keeps its own graph.  Gives the logits -(E0 + G) of the last iteration, or with
+    ``expect`` their expected label straight from E0 and G (phl.NchwExpectedValue), the logits never written."""
+    import phl
+
+    Y = phl.nchw_step_train_fn(E0, None, M)
+    for it in range(niters):
+        G = W(Y, refs)
+        if it == niters - 1:
+            return phl.nchw_expected_value_fn(E0, G, values, True) if expect else -(E0 + G)
+        Y = phl.nchw_step_train_fn(E0, G, M)
+
+
 def _nchw_step_matrix(mu, E0, labels):
     """_compat_matrix of ``mu`` if phl.nchw_softmax_compat (a general Mu above 256 labels: phl.nchw_softmax_compat_wide)
     takes it at this label count, else None."""
@@ -434,10 +451,15 @@ class CRFasRNN(nn.Module):
     ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with: on
     that route the loop's last call is phl.nchw_expected_value on E0 and G, and the logits are never written.
     ``fused_grad=True`` keeps W on the library's kernels under autograd: the lattice W through _mean_field_nchw_grad, the
-    guided W through phl.GuidedFilterFn inside the plain NCHW loop (Mu and the softmax stay torch ops there)."""
+    guided W through phl.GuidedFilterFn inside the plain NCHW loop (Mu and the softmax stay torch ops there).
+    ``fused_step=True`` takes Mu and the softmax of that training loop onto the kernels as well, for a W that is not the
+    lattice, fp32 CUDA tensors, at most 64 labels and a Mu that is a matrix: _mean_field_nchw_step_grad, where everything
+    between two W calls is phl.NchwStepTrain (one kernel forward, one call backward, float64 inside, nothing of the step
+    saved but its inputs) and ``expected_depth`` ends in phl.NchwExpectedValue.  Anything else under the keyword keeps the
+    route and the bits it has without it; without recording autograd that is the no-grad fused route."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
-                 fused_grad=False):
+                 fused_grad=False, fused_step=False):
         super().__init__()
         self.Mu, self.niters = mu_init, niters
         if notrain_mu:
@@ -446,7 +468,7 @@ class CRFasRNN(nn.Module):
         # backward, crf.guided.GaussianBlur, and ignores the flag)
         self.W = BatchedAdjacency() if lattice else BatchedGuidedAdjacency(gchannels, r, eps, gaussian=gaussian,
                                                                              fused_grad=fused_grad and not gaussian)
-        self.fused_grad = fused_grad
+        self.fused_grad, self.fused_step = fused_grad, fused_step
 
     def forward(self, refs, logits, confidence=None, labels=None, energies=None):
         """refs [B, C, H, W], logits [B, L, H, W].  energies: the unaries E0 [B, L, H, W] themselves in place of
@@ -496,6 +518,14 @@ class CRFasRNN(nn.Module):
             if M is not None:
                 out = _mean_field_nchw_step_fused(E0.contiguous(), refs, self.W, M, self.niters, expect, values)
                 return out, bool(expect)                                                  # already -E
+            if grad and self.fused_step:
+                import phl
+
+                L = E0.shape[1]
+                M = _compat_matrix(self.Mu, L, labels, E0.device, detach=False) if L <= phl.NCHW_TRAIN_MAX_L else None
+                if M is not None:
+                    out = _mean_field_nchw_step_grad(E0, refs, self.W, M, self.niters, expect, values)
+                    return out, bool(expect)                                              # already -E
         return -_mean_field_nchw(E0, lambda Q: self.W(self.Mu(Q, *extra), refs), self.niters), False
 
 

@@ -48,10 +48,10 @@ class _CoordConv(nn.Module):
 
 
 class CRFdepthRefiner(nn.Module):
-    def __init__(self, d_in=64, d_guide=16, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False):
+    def __init__(self, d_in=64, d_guide=16, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False, fused_step=False):
         super().__init__()
         self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
-                            fused_grad=fused_grad)
+                            fused_grad=fused_grad, fused_step=fused_step)
         self.projection = nn.Conv2d(d_in, d_guide - 3, kernel_size=1)
 
     def _guide(self, imgrgb, features):
@@ -91,10 +91,10 @@ def _scalar_unaries_routable(disp, mu):
 
 
 class CRFdepthUpsampler(nn.Module):
-    def __init__(self, d_in=64, d_guide=3, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False):
+    def __init__(self, d_in=64, d_guide=3, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False, fused_step=False):
         super().__init__()
         self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
-                            fused_grad=fused_grad)
+                            fused_grad=fused_grad, fused_step=fused_step)
 
     def forward(self, inputs):
         """fp32 CUDA inputs (_scalar_unaries_routable) get E0 and the labels from phl.nchw_scalar_unaries -- two launches,

@@ -8,7 +8,8 @@
 //   VEC   n % 4 == 0 and every pointer 16-byte aligned: the pixels are 4 t .. 4 t + 3 of the tile, one float4 per plane,
 //         which lies inside the image or outside
 //   else  the pixels are t, t + 256, t + 512, t + 768, one dword each: a wave still reads 256 contiguous bytes per plane
-// k_nchw_tile's 64-pixel LDS tile (phl_nchw.hip) is another layout; that file shares the host side only.
+// k_nchw_tile's 64-pixel LDS tile (phl_nchw.hip) is another layout; that file shares the host side only, and so does
+// phl_nchw_train.hip (the training step and its backward, the same tile with Q in float64).
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>

@@ -89,6 +89,9 @@ _ABI = (
     ("phl_uniform_compat_softmax", "i", "PqPqffPqqiIS"),
     ("phl_nchw_softmax_compat", "i", "PPPffPiiqiS"),
     ("phl_nchw_softmax_compat_wide", "i", "PPPPiiqS"),
+    ("phl_nchw_step_train", "i", "PPPPiiqS"),
+    ("phl_nchw_step_train_grad", "i", "PPPPPPiiqS"),
+    ("phl_nchw_step_train_partials", "i", "iiq"),
     ("phl_nchw_expected_value", "i", "PPPPiiqiS"),
     ("phl_nchw_expected_value_grad", "i", "PPPPPiiqiS"),
     ("phl_nchw_scalar_unaries", "i", "PPPPPiiiiiiddS"),
@@ -778,6 +781,86 @@ def nchw_softmax_compat_wide(E0, G=None, Mu=None, *, out=None):
     e, g = E0.contiguous(), None if G is None else G.contiguous()        # (named: a copy must outlive the launch)
     _launch(dev, "phl_nchw_softmax_compat_wide", _ptr(e), _ptr(g), _ptr(M), _ptr(out), B, L, n)
     return out
+
+
+NCHW_TRAIN_MAX_L = 64                # PHL_NCHW_TRAIN_MAX_L: the label range of the training step and its backward
+
+
+def _train_operands(name, E0, G, Mu):
+    """(E0, G contiguous, Mu detached as a dense fp32 [L, L] on E0's device, B, L, n) of the training-step entry points.
+    Nothing is read back to the host."""
+    B, L, n = _nchw_operands(name, E0, G, "E0")
+    if not torch.is_tensor(Mu) or tuple(Mu.shape) != (L, L):
+        raise ValueError(f"{name}: Mu must be an [L, L] = [{L}, {L}] tensor")
+    M = Mu.detach().to(E0.device, torch.float32).contiguous()
+    return E0.detach().contiguous(), None if G is None else G.detach().contiguous(), M, B, L, n
+
+
+def nchw_step_train(E0, G=None, Mu=None, *, out=None):
+    """The step of ``nchw_softmax_compat`` as training wants it, one kernel (phl_nchw_step_train), at most
+    NCHW_TRAIN_MAX_L = 64 labels: ``out[:, c] = sum_a Mu[a, c] * softmax(-(E0 + G), dim=1)[:, a]`` for fp32 CUDA E0, G
+    [B, L, H, W] (or [B, L, n]; G optional) and Mu [L, L] in the _compat_matrix convention, always as a product, float64
+    between the fp32 loads and the one fp32 store.  Inputs that are not contiguous are made so; Mu is read on the device.
+    out: a contiguous fp32 tensor of E0's shape, returned.  Raises PhlError with the library's status: 1 for out aliasing
+    an input, 7 for more than 64 labels."""
+    e, g, M, B, L, n = _train_operands("nchw_step_train", E0, G, Mu)
+    out = _out_or_empty("nchw_step_train", out, E0.shape, E0.device, "E0's shape and device")
+    _launch(E0.device, "phl_nchw_step_train", _ptr(e), _ptr(g), _ptr(M), _ptr(out), B, L, n)
+    return out
+
+
+def nchw_step_train_grad(E0, G, Mu, gY, *, need_e=True, need_mu=True):
+    """(dE, gMu) of ``nchw_step_train(E0, G, Mu)`` for the upstream gradient gY of E0's shape, one call
+    (phl_nchw_step_train_grad): with Q = softmax(-(E0 + G), 1), t = Mu gY and s = sum_a Q_a t_a per pixel, ``dE = Q * (s -
+    t)`` -- the gradient of E0 and of G alike -- and ``gMu[a, c] = sum over images and pixels of Q_a * gY_c``.  Only E0, G,
+    Mu and gY are read: Q is recomputed.  need_e / need_mu: a part that is not needed is neither computed nor stored and
+    comes back as None; the other part's bits do not depend on it.  gY that is not contiguous (autograd hands over
+    expanded gradients) is made so.  Float64 sums in a fixed order: the same bits on every call."""
+    e, g, M, B, L, n = _train_operands("nchw_step_train_grad", E0, G, Mu)
+    _fp32_cuda("nchw_step_train_grad", gY, device=E0.device)
+    if gY.shape != E0.shape:
+        raise ValueError(f"nchw_step_train_grad: gY must have E0's shape {tuple(E0.shape)}, got {tuple(gY.shape)}")
+    if not (need_e or need_mu):
+        raise ValueError("nchw_step_train_grad: nothing is asked for (need_e and need_mu are both false)")
+    gy = gY.detach().contiguous()
+    dE = torch.empty(E0.shape, dtype=torch.float32, device=E0.device) if need_e else None
+    # (no tile, no launch: the sum over nothing)
+    gMu = (torch.zeros if B * n == 0 else torch.empty)((L, L), dtype=torch.float32, device=E0.device) if need_mu else None
+    _launch(E0.device, "phl_nchw_step_train_grad", _ptr(e), _ptr(g), _ptr(M), _ptr(gy), _ptr(dE), _ptr(gMu), B, L, n)
+    return dE, gMu
+
+
+def nchw_step_train_partials(B, L, n):
+    """The number of workgroups, and of [L, L] float64 partials, of a ``nchw_step_train_grad`` that computes gMu
+    (phl_nchw_step_train_partials): the 64-pixel tiles of the volume, at most 1024 -- a function of (B, L, n) alone."""
+    return int(_call("phl_nchw_step_train_partials", int(B), int(L), int(n), value=True))
+
+
+class NchwStepTrain(torch.autograd.Function):
+    """``nchw_step_train(E0, G, Mu)`` with its backward on phl_nchw_step_train_grad.  Saves E0, G and Mu, nothing the
+    forward computed.  One call per backward computes only what ``ctx.needs_input_grad`` asks for; E0 and G get the same
+    gradient (one tensor, computed when either asks)."""
+
+    @staticmethod
+    def forward(ctx, E0, G, Mu):
+        ctx.save_for_backward(E0, G, Mu)
+        return nchw_step_train(E0, G, Mu)
+
+    @staticmethod
+    def backward(ctx, gY):
+        E0, G, Mu = ctx.saved_tensors
+        need_e, need_mu = any(ctx.needs_input_grad[:2]), ctx.needs_input_grad[2]
+        dE = gMu = None
+        if need_e or need_mu:
+            dE, gMu = nchw_step_train_grad(E0, G, Mu, gY, need_e=need_e, need_mu=need_mu)
+            if need_mu:
+                gMu = gMu.to(Mu.dtype)
+        return (dE if ctx.needs_input_grad[0] else None), (dE if ctx.needs_input_grad[1] else None), gMu
+
+
+def nchw_step_train_fn(E0, G=None, Mu=None):
+    """Differentiable ``nchw_step_train``: NchwStepTrain.apply(E0, G, Mu)."""
+    return NchwStepTrain.apply(E0, G, Mu)
 
 
 NCHW_EXPECT_PIXELS = 1024            # PHL_NCHW_EXPECT_PIXELS: pixels of a workgroup of the expected-label kernels

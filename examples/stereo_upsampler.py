@@ -6,7 +6,10 @@ left image at full resolution go through the head's forward, then one training s
     E0, labels = phl.nchw_scalar_unaries(disp_lowres, (H, W), 18, gamma, s)      -> phl_nchw_scalar_unaries, two launches
     depth      = CRFasRNN(charb(.05), niters=2, r, gchannels=3).expected_depth(img, None, energies=E0, labels=labels, values=labels)
 
-    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8]
+    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8] [--fused-step]
+
+--fused-step runs the training step with ``CRFdepthUpsampler(fused_grad=True, fused_step=True)``: W on phl.GuidedFilterFn
+and everything between two W calls on phl.NchwStepTrain.
 
 Prints the mean absolute disparity error of the plain bilinear enlargement and of the head's output against the known
 disparity, and the loss before and after the step.
@@ -23,7 +26,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from stereo_crf import synthetic_pair  # noqa: E402
 
 
-def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False):
+def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=False):
     import torch
     import torch.nn.functional as F
 
@@ -35,7 +38,7 @@ def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False):
     truth = torch.from_numpy(truth).to(dev).float()[None, None]
     low = F.interpolate(truth, size=(h // factor, w // factor), mode="bilinear", align_corners=False)
     low[:, :, 2:6, 3:9] = 0                                                   # no measurement there
-    net = CRFdepthUpsampler(r=r, niters=2).to(dev)
+    net = CRFdepthUpsampler(r=r, niters=2, fused_grad=fused_step, fused_step=fused_step).to(dev)
     torch.cuda.synchronize()
     t0 = time.time()
     with torch.no_grad():
@@ -57,6 +60,8 @@ def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False):
     if not quiet:
         print(f"{w}x{h} from {w // factor}x{h // factor}, 18 labels, guided-filter radius {r}: forward {dt * 1e3:.1f} ms on the device")
         print(f"mean |disparity error|: bilinear enlargement {err_plain:.3f} px, CRFdepthUpsampler {err_head:.3f} px")
+        if fused_step:
+            print("training step with fused_step=True: W, Mu and the softmax on the HIP kernels under autograd")
         print(f"one SGD step: loss {before:.4f} -> {after:.4f}; gamma.grad = {float(net.CRF.Mu.gamma.grad):.4g}, "
               f"s.grad = {float(net.CRF.Mu.s.grad):.4g}")
     return err_plain, err_head, before, after
@@ -68,8 +73,9 @@ if __name__ == "__main__":
     ap.add_argument("--w", type=int, default=384)
     ap.add_argument("--r", type=int, default=8)
     ap.add_argument("--factor", type=int, default=8)
+    ap.add_argument("--fused-step", action="store_true", help="the training step on phl.NchwStepTrain / phl.GuidedFilterFn")
     a = ap.parse_args()
-    run(a.h, a.w, a.r, a.factor)     # first run of the process: library load, first launches, first allocations
+    run(a.h, a.w, a.r, a.factor, fused_step=a.fused_step)     # first run of the process: library load, first launches, first allocations
     t1 = time.time()
-    run(a.h, a.w, a.r, a.factor, quiet=True)
+    run(a.h, a.w, a.r, a.factor, quiet=True, fused_step=a.fused_step)
     print(f"the same again, warm: {(time.time() - t1) * 1e3:.1f} ms end to end (synthetic pair generated on the CPU included)")

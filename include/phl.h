@@ -329,6 +329,36 @@ int phl_nchw_softmax_compat(const float *E0_dev, const float *G_dev, const float
  * above 256 labels) leave 2^31 - 1; PHL_ERR_UNSUPPORTED for L > 512.  No atomics: the same bits on every run. */
 int phl_nchw_softmax_compat_wide(const float *E0_dev, const float *G_dev, const float *mu_dev, float *out_dev, int B,
                                  int L, int64_t n, phl_stream stream);
+/* The same step for TRAINING, 1 <= L <= PHL_NCHW_TRAIN_MAX_L = 64 labels (the reference trains at 18 and at w / 6 = 60),
+ * with its backward; the arithmetic between the fp32 loads and the fp32 stores is float64, so every output is the
+ * float64 result rounded once.  Per pixel column, with Q_a = softmax_a(-(E0_a + G_a)):
+ *   phl_nchw_step_train        out[b,c,p] = sum_a mu[a*L + c] * Q_a
+ *   phl_nchw_step_train_grad   for the upstream gradient gY of out:  t_a = sum_c mu[a*L + c] * gY_c,  s = sum_a Q_a t_a,
+ *                              dE[b,a,p] = Q_a * (s - t_a)              -- the gradient of E0 and of G alike
+ *                              gmu[a*L + c] = sum over b, p of Q_a[b,p] * gY_c[b,p]
+ *                              Nothing but the forward's inputs and gY is read: Q is recomputed.
+ * E0, G, gY, out, dE: contiguous fp32 [B][L][n] on the device, n = H*W; G may be NULL.  mu, gmu: dense fp32 [L][L], row
+ * stride L, NOT transposed.  Either of dE / gmu may be NULL, and that part is then neither computed nor stored; both
+ * NULL is PHL_ERR_INVALID.  A workgroup owns tiles of 64 consecutive pixels and all L labels of them in LDS (Q as
+ * doubles, at most 52.25 KiB: two workgroups per CU): a max-subtracted softmax, then fma chains in label order on the
+ * vector unit, the four partials of a pixel combined in a fixed order; mu is laid out once per call as doubles in a
+ * stream-ordered scratch of at most 32 KiB and read through scalar loads.  float4 accesses along the pixel axis when
+ * n % 4 == 0 and every volume pointer is 16-byte aligned, dwords otherwise.  gmu: R =
+ * phl_nchw_step_train_partials(B, L, n) workgroups -- a function of its arguments alone, never of the device: the
+ * number of 64-pixel tiles B * ceil(n / 64), at most 1024; 0 for B < 1, L < 1 or n < 1 -- walk the tiles w, w + R, ..
+ * with their share of every gmu element in registers, write one [L][L] double partial each to a stream-ordered scratch
+ * (at most 32 MiB), and a second kernel adds the R partials in index order and stores fp32.  No atomics: the same bits
+ * on every call, and dE's bits do not depend on whether gmu is asked for (nor gmu's on dE).
+ * Status, checked before any HIP call: PHL_ERR_INVALID for negative sizes or L < 1; then B == 0 or n == 0 is PHL_OK
+ * with nothing launched; then PHL_ERR_INVALID for NULL E0 / mu / out (gY; both of dE and gmu) or an output that is one
+ * of the inputs or the other output; PHL_ERR_TOO_LARGE when B*L*n*4 bytes leave int64 or the 64-pixel tiles leave
+ * 2^31 - 1; PHL_ERR_UNSUPPORTED for L > PHL_NCHW_TRAIN_MAX_L (the caller keeps its torch ops). */
+#define PHL_NCHW_TRAIN_MAX_L 64
+int phl_nchw_step_train(const float *E0_dev, const float *G_dev, const float *mu_dev, float *out_dev, int B, int L,
+                        int64_t n, phl_stream stream);
+int phl_nchw_step_train_grad(const float *E0_dev, const float *G_dev, const float *mu_dev, const float *gY_dev,
+                             float *dE_dev, float *gmu_dev, int B, int L, int64_t n, phl_stream stream);
+int phl_nchw_step_train_partials(int B, int L, int64_t n);
 /* ---- the expected label of a channel-major column: the end of the CRFasRNN heads (crf/mb_stereo_crf.py) -----------
  * Every head finishes with logits2average_depth(CRF(...)): a softmax over the label channels, a broadcast product with
  * the labels and a sum.  Here that is one kernel, and with negate != 0 it takes the loop's E0 and G as they are, so the
