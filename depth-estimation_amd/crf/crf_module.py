@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+import phl
 from crf.gaussian_matrix import BatchedAdjacency, BatchedGuidedAdjacency  # noqa: F401  (crf_module.py:5)
 
 
@@ -75,8 +76,6 @@ def _pad_labels(E_0, Mu, differentiable=False, channel_major=False, structure=Tr
     Potts-family test and its device -> host read (uniform None), for a caller that does not run phl.compat_softmax.
     Otherwise one padded copy of E_0 and the padded Mu cached per Mu (phl._mu_forms); channel_major: E_0 is an image's
     [L, n] (NCHW) plane, always transposed into a fresh pixel-major buffer by phl.copy2d."""
-    import phl
-
     L = E_0.shape[0] if channel_major else E_0.shape[-1]
     Lp = _label_pad(L)
     if differentiable:
@@ -115,8 +114,6 @@ def mean_field_step(E_0, W, Mu, Q, out=None):
 
     ``W`` is an operator (``@``) or a callable.  The raw-pointer kernels below know nothing of autograd, so
     the caller must have established that no gradient flows (``mean_field_infer`` does)."""
-    import phl
-
     X = W(Q) if callable(W) and not hasattr(W, "__matmul__") else W @ Q
     return phl.compat_softmax(E_0, _kernel_operand(X, E_0.device), Mu, out=out)
 
@@ -130,8 +127,6 @@ def _device_loop(E_0, apply_W, Mu, niters, uniform=None, differentiable=False, l
     saved for backward: from there on the loop continues on the differentiable Functions (fused_grad) or on plain torch
     ops.  differentiable=True: phl.SoftmaxNegAdd / phl.CompatSoftmax, every tensor fresh -- nothing autograd saved is
     written again."""
-    import phl
-
     plain = False
     Q = phl.softmax_neg_add_fn(E_0) if differentiable else phl.softmax_neg_add(E_0)
     for it in range(niters):
@@ -203,8 +198,6 @@ def _mean_field_infer_staged(E_0, W, Mu, niters):
     the lattice of ``W.ref`` is built once (cached per ``ref``), every iteration is one lattice filter with ``- Q`` fused
     and one fused compatibility + softmax kernel, and Q crosses PCIe once at the end -- instead of Q making the round
     trip inside every ``W @ Q`` with the compatibility product and the softmax on the host."""
-    import phl
-
     dev = W.ref.device if W.ref.is_cuda else torch.device("cuda", torch.cuda.current_device())
     lat = phl.lattice_for(W.ref.detach())                 # CPU ref: built on the current device; GPU ref: where it lives
     E0d = phl.to_device(E_0.detach().contiguous(), dev)
@@ -221,16 +214,21 @@ def potts(num_classes):
     return conv
 
 
+def _mu_is_matrix(mu, L):
+    """Whether ``mu`` is a compatibility module that is an [L, L] matrix: ``charb``, or a bias-free 1x1 conv (``potts``)."""
+    return isinstance(mu, charb) or (isinstance(mu, nn.Conv2d) and mu.kernel_size == (1, 1) and mu.bias is None
+                                     and mu.groups == 1 and mu.weight.shape[:2] == (L, L))
+
+
 def _compat_matrix(mu, L, labels, device, detach=True):
-    """[L, L] matrix M with ``mu(Q)[:, c] = sum_b M[b, c] Q[:, b]`` for the compatibility modules CRFasRNN is
-    used with (``charb``, or a bias-free 1x1 conv such as ``potts``); None for anything else.  detach=False keeps
-    the graph to the module's parameters (the differentiable path of CRFasRNN)."""
+    """[L, L] matrix M with ``mu(Q)[:, c] = sum_b M[b, c] Q[:, b]`` for a ``mu`` that is one (_mu_is_matrix); None for
+    anything else.  detach=False keeps the graph to the module's parameters (the differentiable path of CRFasRNN)."""
+    if not _mu_is_matrix(mu, L):
+        return None
     if isinstance(mu, charb):
         return mu.matrix(L, labels, device, detach=detach)
-    if isinstance(mu, nn.Conv2d) and mu.kernel_size == (1, 1) and mu.bias is None and mu.groups == 1 and mu.weight.shape[:2] == (L, L):
-        w = mu.weight.detach() if detach else mu.weight
-        return w[:, :, 0, 0].t().to(device, torch.float32)      # conv: out[c] = sum_b w[c, b] q[b]
-    return None
+    w = mu.weight.detach() if detach else mu.weight
+    return w[:, :, 0, 0].t().to(device, torch.float32)          # conv: out[c] = sum_b w[c, b] q[b]
 
 
 def _maybe_learnable(value, trainable):
@@ -284,61 +282,77 @@ def _mean_field_nchw(E0, message, niters):
 _NCHW_STEP = os.environ.get("PHL_NCHW_STEP", "1") not in ("", "0")
 
 
-def _mean_field_nchw_step_fused(E0, refs, W, M, niters, expect=False, values=None):
-    """The same iteration for any other W (the default guided filter), without autograd, in the reference's order
-    E = E0 + W(Mu(Q)) (crf_module.py:97-99): everything between two W calls -- the add, the negation, the softmax over
-    the label channels and the compatibility product -- is ONE channel-major kernel (phl.nchw_softmax_compat; its wide form
-    phl.nchw_softmax_compat_wide for a general Mu above 256 labels), so Q and E never exist in memory and nothing is transposed.  W is called once per iteration as the module it is, on whatever
-    engine it picks.  M: _compat_matrix of the Mu module.  Gives the logits -E of the last iteration -- or, with
-    ``expect``, their expected label [B, 1, H, W] under ``values`` (None: 0 .. L-1) straight from E0 and G
-    (phl.nchw_expected_value), the logits never written."""
-    import phl
-
-    uniform = (phl._mu_uniform(M) or False) if M.shape[0] <= phl.NCHW_UNIFORM_MAX_L else False   # one read per forward
-    wide = not uniform and M.shape[0] > phl.NCHW_PRODUCT_MAX_L       # a general Mu above 256 labels: the 32-pixel tile
-
-    def step(G, out=None):
-        if wide:
-            return phl.nchw_softmax_compat_wide(E0, G, M, out=out)
-        return phl.nchw_softmax_compat(E0, G, M, uniform=uniform, out=out)
-
-    Y = step(None)
+def _mean_field_nchw_step(E0, refs, W, niters, step, last):
+    """The same iteration for any other W (the default guided filter), in the reference's order E = E0 + W(Mu(Q))
+    (crf_module.py:97-99): ``Y = step(None, None)``, then per iteration ``G = W(Y, refs)`` and ``Y = step(G, Y)``, which
+    may write over Y -- on the last one ``last(G)`` instead, which is what the loop gives.  Everything between two W
+    calls -- the add, the negation, the softmax over the label channels and the compatibility product -- is the one
+    channel-major kernel behind ``step``, so Q and E never exist in memory and nothing is transposed.  W is called once
+    per iteration as the module it is, on whatever engine it picks, and keeps its own graph."""
+    Y = step(None, None)
     for it in range(niters):
         G = W(Y, refs)
         if it == niters - 1:
-            if expect:
-                return phl.nchw_expected_value(E0, G, values, negate=True)
-            return phl.nchw_softmax_compat(E0, G, logits=True)
-        Y = step(G, out=Y)
+            return last(G)
+        Y = step(G, Y)
 
 
-def _mean_field_nchw_step_grad(E0, refs, W, M, niters, expect=False, values=None):
-    """The loop of _mean_field_nchw_step_fused under autograd, at most phl.NCHW_TRAIN_MAX_L labels: everything between two
-    W calls is phl.NchwStepTrain -- one kernel forward, one call backward (dE, and Mu's gradient through the
-    differentiable M), which saves E0, G and M and nothing it computed, so no [B, L, H, W] intermediate of the add, the
-    negation, the softmax or the product lives until the backward.  W is called as the module it is (``fused_grad``
-    still chooses its engine) and keeps its own graph.  Gives the logits -(E0 + G) of the last iteration, or with
-    ``expect`` their expected label straight from E0 and G (phl.NchwExpectedValue), the logits never written."""
-    import phl
-
-    Y = phl.nchw_step_train_fn(E0, None, M)
-    for it in range(niters):
-        G = W(Y, refs)
-        if it == niters - 1:
-            return phl.nchw_expected_value_fn(E0, G, values, True) if expect else -(E0 + G)
-        Y = phl.nchw_step_train_fn(E0, G, M)
+def _nchw_step_kernels(E0, M, uniform, expect, values):
+    """(step, last) of _mean_field_nchw_step without autograd: phl.nchw_softmax_compat in place (out=Y: nothing is allocated
+    per iteration), and the logits -(E0 + G) -- or with ``expect`` their expected label [B, 1, H, W] under ``values`` (None:
+    0 .. L-1) straight from E0 and G, the logits never written.  uniform: M's Potts-family structure, or False."""
+    if not uniform and M.shape[0] > phl.NCHW_PRODUCT_MAX_L:          # a general Mu above 256 labels: the 32-pixel tile
+        step = lambda G, Y: phl.nchw_softmax_compat_wide(E0, G, M, out=Y)                      # noqa: E731
+    else:
+        step = lambda G, Y: phl.nchw_softmax_compat(E0, G, M, uniform=uniform, out=Y)          # noqa: E731
+    if expect:
+        return step, lambda G: phl.nchw_expected_value(E0, G, values, negate=True)
+    return step, lambda G: phl.nchw_softmax_compat(E0, G, logits=True)
 
 
-def _nchw_step_matrix(mu, E0, labels):
-    """_compat_matrix of ``mu`` if phl.nchw_softmax_compat (a general Mu above 256 labels: phl.nchw_softmax_compat_wide)
-    takes it at this label count, else None."""
-    import phl
+def _nchw_step_train_kernels(E0, M, expect, values):
+    """(step, last) of _mean_field_nchw_step under autograd: phl.NchwStepTrain -- one kernel forward, one call backward (dE,
+    and Mu's gradient through the differentiable M), which saves E0, G and M and nothing it computed, so no [B, L, H, W]
+    intermediate of the step lives until the backward -- and the logits or phl.NchwExpectedValue, as above."""
+    step = lambda G, Y: phl.nchw_step_train_fn(E0, G, M)                                       # noqa: E731
+    if expect:
+        return step, lambda G: phl.nchw_expected_value_fn(E0, G, values, True)
+    return step, lambda G: -(E0 + G)
 
-    L = E0.shape[1]
-    M = _compat_matrix(mu, L, labels, E0.device) if L <= phl.NCHW_UNIFORM_MAX_L else None
-    if M is not None and L > phl.NCHW_WIDE_MAX_L and not phl._mu_uniform(M):
-        return None
-    return M
+
+# The label ranges of the routes: each is the range of the kernels the route runs on.
+_STEP_MAX_L = phl.NCHW_WIDE_MAX_L            # 512: the step route with a general Mu
+_STEP_POTTS_MAX_L = phl.NCHW_UNIFORM_MAX_L   # 1024: the step route with a Mu of the Potts family
+_STEP_GRAD_MAX_L = phl.NCHW_TRAIN_MAX_L      # 64: the step route under autograd
+_LATTICE_GRAD_MAX_L = 512                    # the backward kernels of the lattice route, on _label_pad(L)
+
+
+def _nchw_route(lattice, niters, e0_fp32_cuda, e0_4d, refs_fp32_cuda, grad, grad_w, fused_grad, fused_step, L, mu_matrix,
+                mu_potts, step=True):
+    """The route of one CRFasRNN call, from plain values:
+
+        W        | preconditions                                                                         | route
+        lattice  | niters > 0, E0 fp32 CUDA, no grad, Mu a matrix                                        | "lattice"
+        lattice  | the same under grad, fused_grad, refs fp32 CUDA, _label_pad(L) <= 512                 | "lattice_grad"
+        another  | step, niters > 0, E0 fp32 CUDA 4-D, no grad_w, Mu a matrix, L <= 512 (Potts: <= 1024) | "step"
+        another  | the same head under grad_w, fused_step, L <= 64                                       | "step_grad"
+        anything else                                                                                    | "plain"
+
+    A lattice W (BatchedAdjacency) that misses its rows is "plain", never a step route.  grad: autograd records and E0,
+    refs or a parameter of Mu asks for a gradient; grad_w: the same with W's parameters.  mu_potts decides only "step"
+    between 513 and 1024 labels, so CRFasRNN._run reads it (phl._mu_uniform: one cached device -> host read per Mu) only
+    where everything else already says "step".  step: the module switch _NCHW_STEP."""
+    if not (niters > 0 and e0_fp32_cuda and mu_matrix):
+        return "plain"
+    if lattice:
+        if not grad:
+            return "lattice"
+        return "lattice_grad" if fused_grad and refs_fp32_cuda and _label_pad(L) <= _LATTICE_GRAD_MAX_L else "plain"
+    if not (step and e0_4d):
+        return "plain"
+    if not grad_w:
+        return "step" if L <= (_STEP_POTTS_MAX_L if mu_potts else _STEP_MAX_L) else "plain"
+    return "step_grad" if fused_step and L <= _STEP_GRAD_MAX_L else "plain"
 
 
 def _expect_routable(logits, labels):
@@ -370,8 +384,6 @@ def _mean_field_nchw_fused(E0, refs, M, niters):
     dealt over phl.batch_devices (the tensors' own GPU, or all GPUs with PHL_BATCH_DEVICES=all / CPU inputs), two
     side streams per device, so that image b+1's lattice build and transposes run under image b's iterations; both
     transposes go through the library's LDS-tiled phl_copy2d."""
-    import phl
-
     bs, L, h, w = E0.shape
     d = refs.shape[1]
     n = h * w
@@ -419,7 +431,6 @@ def _mean_field_nchw_grad(E0, refs, M, niters):
     module).  W and Mu commute in the forward, not in the backward: the lattice filter is not exactly symmetric, its
     backward is the filter itself (LatticeFilter, as the reference's), so only this order gives Mu the reference's
     gradient; the (W Q) Mu order of mean_field_infer would give the exact gradient of the forward instead."""
-    import phl
     from crf.gaussian_matrix import LatticeFilter
 
     bs, L, h, w = E0.shape
@@ -441,22 +452,15 @@ def _mean_field_nchw_grad(E0, refs, M, niters):
 class CRFasRNN(nn.Module):
     """Batched NCHW mean field (crf_module.py:81-104); returns logits -E of the LAST iteration.
 
-    ``lattice=True`` selects the permutohedral W (BatchedAdjacency, the MI355X path); the default
-    stays the reference's guided-filter W.  With that W, a forward on fp32 CUDA tensors that autograd does not record
-    (no gradient asked of the logits, the guide, Mu's or W's parameters) and a Mu that is a matrix (``charb``, a
-    bias-free 1x1 conv: at most 512 labels, 1024 for the Potts family) runs _mean_field_nchw_step_fused: per iteration W
-    and one channel-major kernel for everything else (phl.nchw_softmax_compat; phl.nchw_softmax_compat_wide for a general
-    Mu at 257 to 512 labels, the reference's 341 at 2048 columns among them); PHL_NCHW_STEP=0 in the environment
-    keeps the plain loop.  Anything else -- training, CPU tensors, float64, another Mu -- is the plain NCHW loop.
-    ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with: on
-    that route the loop's last call is phl.nchw_expected_value on E0 and G, and the logits are never written.
-    ``fused_grad=True`` keeps W on the library's kernels under autograd: the lattice W through _mean_field_nchw_grad, the
-    guided W through phl.GuidedFilterFn inside the plain NCHW loop (Mu and the softmax stay torch ops there).
-    ``fused_step=True`` takes Mu and the softmax of that training loop onto the kernels as well, for a W that is not the
-    lattice, fp32 CUDA tensors, at most 64 labels and a Mu that is a matrix: _mean_field_nchw_step_grad, where everything
-    between two W calls is phl.NchwStepTrain (one kernel forward, one call backward, float64 inside, nothing of the step
-    saved but its inputs) and ``expected_depth`` ends in phl.NchwExpectedValue.  Anything else under the keyword keeps the
-    route and the bits it has without it; without recording autograd that is the no-grad fused route."""
+    ``lattice=True`` selects the permutohedral W (BatchedAdjacency, the MI355X path); the default stays the reference's
+    guided-filter W.  _nchw_route holds the table of routes: on fp32 CUDA tensors with a Mu that is a matrix (``charb``, a
+    bias-free 1x1 conv), a call that autograd does not record runs on the fused kernels -- _mean_field_nchw_fused for the
+    lattice W, _mean_field_nchw_step for any other (PHL_NCHW_STEP=0 in the environment switches that one off) -- and one
+    it records does so on request: ``fused_grad=True`` for the lattice W (_mean_field_nchw_grad; it also puts the guided
+    W itself on phl.GuidedFilterFn), ``fused_step=True`` for any other W.  Everything else -- CPU tensors, float64,
+    another Mu, a label count out of a route's range -- is the plain NCHW loop, with the bits it always had.
+    ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with; on
+    the step routes the loop itself ends in the expected label, and the logits are never written."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
                  fused_grad=False, fused_step=False):
@@ -480,8 +484,8 @@ class CRFasRNN(nn.Module):
         the softmax of the returned logits.  values: None = 0 .. L-1, a tensor with one value per label ([L] or
         [1, L, 1, 1]), or anything ``probs * values`` broadcasts.  A tensor of fewer than four dimensions with exactly L
         elements always means one value per label -- also a [W] tensor when W == L, which ``probs * values`` alone would
-        spread along the width; hand such values over as [1, 1, 1, W].  Where forward takes _mean_field_nchw_step_fused,
-        the loop itself ends with the expected value; everything else goes through forward.  energies: as in forward
+        spread along the width; hand such values over as [1, 1, 1, W].  Where forward takes _mean_field_nchw_step, the
+        loop itself ends with the expected value; everything else goes through forward.  energies: as in forward
         (``expected_depth(refs, None, energies=E0, ...)``)."""
         from crf.mb_stereo_crf import logits2average_depth
 
@@ -493,39 +497,36 @@ class CRFasRNN(nn.Module):
         return out if done else logits2average_depth(out, values)
 
     def _run(self, refs, logits, confidence, labels, expect=False, values=None, energies=None):
-        """(forward's logits, False) -- or, with ``expect`` on the _mean_field_nchw_step_fused route, (their expected label
-        under ``values``, True).  energies: E0 itself, on every route."""
+        """(forward's logits, False) -- or, with ``expect`` on the _mean_field_nchw_step routes, (their expected label under
+        ``values``, True).  energies: E0 itself, on every route.  Gathers what _nchw_route decides on, then dispatches."""
         if energies is not None and (logits is not None or confidence is not None):
             raise ValueError("CRFasRNN: energies are E0 itself; logits and confidence must be None with them")
         E0 = energies if energies is not None else -logits if confidence is None else -logits * confidence
+        L, recording = E0.shape[1], torch.is_grad_enabled()
+        grad = recording and (E0.requires_grad or refs.requires_grad or any(p.requires_grad for p in self.Mu.parameters()))
+        facts = (isinstance(self.W, BatchedAdjacency), self.niters, E0.is_cuda and E0.dtype == torch.float32, E0.dim() == 4,
+                 refs.is_cuda and refs.dtype == torch.float32, grad,
+                 grad or (recording and any(p.requires_grad for p in self.W.parameters())), self.fused_grad, self.fused_step,
+                 L, _mu_is_matrix(self.Mu, L))
+        route = _nchw_route(*facts, mu_potts=True, step=_NCHW_STEP)
+        if route in ("lattice", "lattice_grad"):                       # (every route but "plain" gives -E already)
+            M = _compat_matrix(self.Mu, L, labels, E0.device, detach=route == "lattice")
+            if route == "lattice":
+                return _mean_field_nchw_fused(E0.contiguous(), refs, M, self.niters), False
+            return _mean_field_nchw_grad(E0, refs, M, self.niters), False
+        if route in ("step", "step_grad"):
+            M = _compat_matrix(self.Mu, L, labels, E0.device, detach=route == "step")
+            if route == "step":
+                uniform = phl._mu_uniform(M) or False                  # the route's one read of Mu's structure, cached per Mu
+                route = _nchw_route(*facts, mu_potts=bool(uniform), step=_NCHW_STEP)     # a general Mu above 512 labels: "plain"
+            if route == "step":
+                E0 = E0.contiguous()
+                kernels = _nchw_step_kernels(E0, M, uniform, expect, values)
+            elif route == "step_grad":
+                kernels = _nchw_step_train_kernels(E0, M, expect, values)
+            if route != "plain":
+                return _mean_field_nchw_step(E0, refs, self.W, self.niters, *kernels), bool(expect)
         extra = () if labels is None else (labels,)
-        if isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda and E0.dtype == torch.float32:
-            grad = torch.is_grad_enabled() and (E0.requires_grad or refs.requires_grad
-                                                or any(p.requires_grad for p in self.Mu.parameters()))
-            if not grad:
-                M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device)
-                if M is not None:
-                    return _mean_field_nchw_fused(E0.contiguous(), refs, M, self.niters), False   # already -E
-            elif self.fused_grad and refs.is_cuda and refs.dtype == torch.float32 and _label_pad(E0.shape[1]) <= 512:
-                M = _compat_matrix(self.Mu, E0.shape[1], labels, E0.device, detach=False)
-                if M is not None:
-                    return _mean_field_nchw_grad(E0, refs, M, self.niters), False                 # already -E
-        elif (_NCHW_STEP and not isinstance(self.W, BatchedAdjacency) and self.niters > 0 and E0.is_cuda
-              and E0.dtype == torch.float32 and E0.dim() == 4):
-            params = list(self.Mu.parameters()) + list(self.W.parameters())
-            grad = torch.is_grad_enabled() and (E0.requires_grad or refs.requires_grad or any(p.requires_grad for p in params))
-            M = None if grad else _nchw_step_matrix(self.Mu, E0, labels)
-            if M is not None:
-                out = _mean_field_nchw_step_fused(E0.contiguous(), refs, self.W, M, self.niters, expect, values)
-                return out, bool(expect)                                                  # already -E
-            if grad and self.fused_step:
-                import phl
-
-                L = E0.shape[1]
-                M = _compat_matrix(self.Mu, L, labels, E0.device, detach=False) if L <= phl.NCHW_TRAIN_MAX_L else None
-                if M is not None:
-                    out = _mean_field_nchw_step_grad(E0, refs, self.W, M, self.niters, expect, values)
-                    return out, bool(expect)                                              # already -E
         return -_mean_field_nchw(E0, lambda Q: self.W(self.Mu(Q, *extra), refs), self.niters), False
 
 

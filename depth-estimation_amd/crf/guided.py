@@ -7,7 +7,7 @@ constructor / call signatures.  Their torch form below is pinned to the referenc
 that autograd does not record runs on the HIP kernels instead (phl.guided_filter, phl_guided.hip: fp64 window sums over
 LDS tiles, the ``* k - src`` of the adjacency fused); CPU tensors, float64, training, ``mode != 'nearest'`` and
 ``gaussian=True`` stay on the torch form.  Around such a forward, CRFasRNN runs the rest of its iteration -- Mu, the add and
-the softmax -- as one channel-major kernel (phl.nchw_softmax_compat, crf_module._mean_field_nchw_step_fused), whichever
+the softmax -- as one channel-major kernel (phl.nchw_softmax_compat, crf_module._mean_field_nchw_step), whichever
 form W itself takes.  Training leaves the torch form only on request: with the keyword ``fused_grad=True`` a forward
 that autograd records goes through phl.GuidedFilterFn, whose backward runs on the library's kernels as well
 (phl.guided_filter_grad: y, x and eps are all that is saved) and gives y, x and omega their gradients.

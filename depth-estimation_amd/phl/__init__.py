@@ -727,6 +727,19 @@ def _out_or_empty(name, out, shape, device, what):
     return out
 
 
+def _step_operands(name, E0, G, Mu, out=None, *, mu_optional=False, training=False):
+    """(e, g, B, L, n, out) of the channel-major step's entry points: E0 and G checked and contiguous (the caller names them:
+    a copy must outlive the launch), ``out`` checked or made (_out_or_empty), Mu checked to be an [L, L] tensor (mu_optional:
+    or None).  training: the operands are cut from their graph and ``out`` is left alone.  Nothing is read back."""
+    B, L, n = _nchw_operands(name, E0, G, "E0")
+    if not training:
+        out = _out_or_empty(name, out, E0.shape, E0.device, "E0's shape and device")
+    if not (Mu is None and mu_optional) and (not torch.is_tensor(Mu) or tuple(Mu.shape) != (L, L)):
+        raise ValueError(f"{name}: Mu must be an [L, L] = [{L}, {L}] tensor")
+    e, g = (E0.detach(), None if G is None else G.detach()) if training else (E0, G)
+    return e.contiguous(), None if g is None else g.contiguous(), B, L, n, out
+
+
 def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=None):
     """The non-W half of a CRFasRNN iteration on channel-major tensors, one kernel (phl_nchw_softmax_compat):
     ``out[:, c] = sum_a Mu[a, c] * softmax(-(E0 + G), dim=1)[:, a]`` for fp32 CUDA E0, G [B, L, H, W] (or [B, L, n]; G
@@ -738,16 +751,12 @@ def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=
     logits=True: ``out = -(E0 + G)``, CRFasRNN's return value; G is required, Mu is not read.
     out: a contiguous fp32 tensor of E0's shape, returned.  Raises PhlError with the library's status: 1 for out aliasing
     E0 or G, 7 for more than 256 labels with a general Mu or more than 1024 with a uniform one."""
-    B, L, n = _nchw_operands("nchw_softmax_compat", E0, G, "E0")
-    dev = E0.device
-    out = _out_or_empty("nchw_softmax_compat", out, E0.shape, dev, "E0's shape and device")
+    e, g, B, L, n, out = _step_operands("nchw_softmax_compat", E0, G, None if logits else Mu, out, mu_optional=True)
     if logits:
         if G is None:
             raise ValueError("nchw_softmax_compat: logits=True needs G")
         mode, M, ab = NCHW_LOGITS, None, (0.0, 0.0)
     else:
-        if Mu is not None and (not torch.is_tensor(Mu) or tuple(Mu.shape) != (L, L)):
-            raise ValueError(f"nchw_softmax_compat: Mu must be an [L, L] = [{L}, {L}] tensor")
         if uniform is None and Mu is not None and L <= NCHW_UNIFORM_MAX_L:
             uniform = _mu_forms(Mu).uniform()
         if uniform:
@@ -755,9 +764,8 @@ def nchw_softmax_compat(E0, G=None, Mu=None, *, uniform=None, logits=False, out=
         elif Mu is None:
             mode, M, ab = NCHW_SOFTMAX, None, (0.0, 0.0)
         else:
-            mode, M, ab = NCHW_PRODUCT, _mu_forms(Mu).dense(dev), (0.0, 0.0)
-    e, g = E0.contiguous(), None if G is None else G.contiguous()        # (named: a copy must outlive the launch)
-    _launch(dev, "phl_nchw_softmax_compat", _ptr(e), _ptr(g), _ptr(M), C.c_float(ab[0]), C.c_float(ab[1]), _ptr(out), B, L, n, mode)
+            mode, M, ab = NCHW_PRODUCT, _mu_forms(Mu).dense(E0.device), (0.0, 0.0)
+    _launch(E0.device, "phl_nchw_softmax_compat", _ptr(e), _ptr(g), _ptr(M), C.c_float(ab[0]), C.c_float(ab[1]), _ptr(out), B, L, n, mode)
     return out
 
 
@@ -772,28 +780,13 @@ def nchw_softmax_compat_wide(E0, G=None, Mu=None, *, out=None):
     above, the same scheme on a tile of 32 pixels.  Inputs that are not contiguous are made so.
     out: a contiguous fp32 tensor of E0's shape, returned.  Raises PhlError with the library's status: 1 for out aliasing
     E0 or G, 7 for more than 512 labels."""
-    B, L, n = _nchw_operands("nchw_softmax_compat_wide", E0, G, "E0")
-    dev = E0.device
-    out = _out_or_empty("nchw_softmax_compat_wide", out, E0.shape, dev, "E0's shape and device")
-    if not torch.is_tensor(Mu) or tuple(Mu.shape) != (L, L):
-        raise ValueError(f"nchw_softmax_compat_wide: Mu must be an [L, L] = [{L}, {L}] tensor")
-    M = _mu_forms(Mu).dense(dev)
-    e, g = E0.contiguous(), None if G is None else G.contiguous()        # (named: a copy must outlive the launch)
-    _launch(dev, "phl_nchw_softmax_compat_wide", _ptr(e), _ptr(g), _ptr(M), _ptr(out), B, L, n)
+    e, g, B, L, n, out = _step_operands("nchw_softmax_compat_wide", E0, G, Mu, out)
+    M = _mu_forms(Mu).dense(E0.device)
+    _launch(E0.device, "phl_nchw_softmax_compat_wide", _ptr(e), _ptr(g), _ptr(M), _ptr(out), B, L, n)
     return out
 
 
 NCHW_TRAIN_MAX_L = 64                # PHL_NCHW_TRAIN_MAX_L: the label range of the training step and its backward
-
-
-def _train_operands(name, E0, G, Mu):
-    """(E0, G contiguous, Mu detached as a dense fp32 [L, L] on E0's device, B, L, n) of the training-step entry points.
-    Nothing is read back to the host."""
-    B, L, n = _nchw_operands(name, E0, G, "E0")
-    if not torch.is_tensor(Mu) or tuple(Mu.shape) != (L, L):
-        raise ValueError(f"{name}: Mu must be an [L, L] = [{L}, {L}] tensor")
-    M = Mu.detach().to(E0.device, torch.float32).contiguous()
-    return E0.detach().contiguous(), None if G is None else G.detach().contiguous(), M, B, L, n
 
 
 def nchw_step_train(E0, G=None, Mu=None, *, out=None):
@@ -803,7 +796,8 @@ def nchw_step_train(E0, G=None, Mu=None, *, out=None):
     between the fp32 loads and the one fp32 store.  Inputs that are not contiguous are made so; Mu is read on the device.
     out: a contiguous fp32 tensor of E0's shape, returned.  Raises PhlError with the library's status: 1 for out aliasing
     an input, 7 for more than 64 labels."""
-    e, g, M, B, L, n = _train_operands("nchw_step_train", E0, G, Mu)
+    e, g, B, L, n, _ = _step_operands("nchw_step_train", E0, G, Mu, training=True)
+    M = Mu.detach().to(E0.device, torch.float32).contiguous()      # (uncached: a parameter that changes every step)
     out = _out_or_empty("nchw_step_train", out, E0.shape, E0.device, "E0's shape and device")
     _launch(E0.device, "phl_nchw_step_train", _ptr(e), _ptr(g), _ptr(M), _ptr(out), B, L, n)
     return out
@@ -816,7 +810,8 @@ def nchw_step_train_grad(E0, G, Mu, gY, *, need_e=True, need_mu=True):
     Mu and gY are read: Q is recomputed.  need_e / need_mu: a part that is not needed is neither computed nor stored and
     comes back as None; the other part's bits do not depend on it.  gY that is not contiguous (autograd hands over
     expanded gradients) is made so.  Float64 sums in a fixed order: the same bits on every call."""
-    e, g, M, B, L, n = _train_operands("nchw_step_train_grad", E0, G, Mu)
+    e, g, B, L, n, _ = _step_operands("nchw_step_train_grad", E0, G, Mu, training=True)
+    M = Mu.detach().to(E0.device, torch.float32).contiguous()      # (uncached: a parameter that changes every step)
     _fp32_cuda("nchw_step_train_grad", gY, device=E0.device)
     if gY.shape != E0.shape:
         raise ValueError(f"nchw_step_train_grad: gY must have E0's shape {tuple(E0.shape)}, got {tuple(gY.shape)}")

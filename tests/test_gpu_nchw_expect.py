@@ -6,13 +6,12 @@ Accuracy rule, forward and backward alike: the yardstick is the float64 torch tr
 err_hip = max|hip - f64| and err_t32 = max|the same transcription in fp32 on the GPU - f64| over all elements,
 err_hip <= 2 * err_t32, and err_hip == 0 where err_t32 == 0.  No absolute tolerance.  Every pair of errors is printed; the
 largest of each per test is printed last."""
-import contextlib
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 import _guided_util
+from _nchw_util import binding_spy, old_loop
 
 DEV = _guided_util.DEV
 pytestmark = pytest.mark.gpu
@@ -213,34 +212,15 @@ def test_both_entry_points_repeat_their_bits():
                            phl.nchw_expected_value_grad(X, G, labels, g, negate=True))
 
 
-@contextlib.contextmanager
 def _binding_spy():
-    """Calls of the binding: [name, negate] of nchw_expected_value / _fn / _grad, and of nchw_softmax_compat(logits=True)."""
-    import phl
+    """Calls of the binding: (name, negate) of nchw_expected_value / _fn / _grad, and of nchw_softmax_compat(logits=True)."""
+    def negate(name, at=None):
+        return lambda a, kw: (name, bool(a[at]) if at is not None and len(a) > at else bool(kw.get("negate", False)))
 
-    seen = []
-    names = ("nchw_expected_value", "nchw_expected_value_fn", "nchw_expected_value_grad", "nchw_softmax_compat")
-    real = {k: getattr(phl, k) for k in names}
-
-    def wrap(k):
-        def f(*a, **kw):
-            if k == "nchw_softmax_compat":
-                if kw.get("logits"):
-                    seen.append(("logits", None))
-            elif k == "nchw_expected_value_fn":
-                seen.append((k, bool(a[3]) if len(a) > 3 else bool(kw.get("negate", False))))
-            else:
-                seen.append((k, bool(kw.get("negate", False))))
-            return real[k](*a, **kw)
-        return f
-
-    for k in names:
-        setattr(phl, k, wrap(k))
-    try:
-        yield seen
-    finally:
-        for k in names:
-            setattr(phl, k, real[k])
+    return binding_spy({"nchw_expected_value": negate("nchw_expected_value"),
+                        "nchw_expected_value_fn": negate("nchw_expected_value_fn", at=3),
+                        "nchw_expected_value_grad": negate("nchw_expected_value_grad"),
+                        "nchw_softmax_compat": lambda a, kw: ("logits", None) if kw.get("logits") else None})
 
 
 def test_autograd_function():
@@ -272,18 +252,6 @@ def test_autograd_function():
 
 
 # ---- the surface ------------------------------------------------------------------------------------------------------
-@contextlib.contextmanager
-def _torch_form():
-    """The module switch behind PHL_NCHW_STEP=0: the plain loop and the torch lines of logits2average_depth."""
-    from crf import crf_module as cm
-
-    was, cm._NCHW_STEP = cm._NCHW_STEP, False
-    try:
-        yield
-    finally:
-        cm._NCHW_STEP = was
-
-
 def _head(kind, gen):
     """(head, inputs) of a small call of each head of crf/mb_stereo_crf.py.  The modules draw their parameters from the
     global generator: it is seeded here, so that a test computes the same numbers whatever ran before it."""
@@ -344,7 +312,7 @@ def test_heads_end_in_the_kernel(kind):
         assert seen == [("nchw_expected_value", True)], seen                      # once, on E0 and G; the logits never written
         values = kw.get("values")
         mid = _transcription(net.CRF(*a, **{k: v for k, v in kw.items() if k != "values"}), None, values, False, torch.float32)
-        with _torch_form(), _binding_spy() as seen:                               # the same operands on the torch form
+        with old_loop(), _binding_spy() as seen:                                  # the same operands on the torch form
             old = net.CRF.expected_depth(*a, **kw)
             want = _expected_depth_f64(net, a, kw)
             assert torch.equal(first(net(inputs)), old)                           # ... which is what the head then gives
@@ -384,7 +352,7 @@ def test_head_under_autograd():
     with _binding_spy() as seen:
         out_new, new = grad_of(torch.float32)
     assert seen == [("nchw_expected_value_fn", False), ("nchw_expected_value", False), ("nchw_expected_value_grad", False)], seen
-    with _torch_form(), _binding_spy() as seen:
+    with old_loop(), _binding_spy() as seen:
         out_old, old = grad_of(torch.float32)
         out_want, want = grad_of(torch.float64)
     assert seen == [], seen
@@ -413,7 +381,7 @@ def test_what_never_reaches_the_binding():
                         (logits, per_channel.clone().requires_grad_())):
             got = logits2average_depth(lg, lab)
             assert torch.equal(got.detach(), formula(lg, lab).detach()), (lg.dtype, lg.device)
-        with _torch_form():
+        with old_loop():
             assert torch.equal(logits2average_depth(logits, per_channel), formula(logits, per_channel))
     assert seen == [], seen
     with _binding_spy() as seen:                                                    # ... and what does

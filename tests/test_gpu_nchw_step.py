@@ -6,13 +6,13 @@ e_hip <= max(2e-6 * max(1, |Y64|.max()), 2 * e_torch).  Softmax mode: <= 2e-6 an
 mode: <= 1e-4 * |E|.max() (the bounds of phl.softmax_neg_add's test).  The loop is held to e_new <= 2 * e_old against the
 float64 fixture / the float64 module, e_old being the plain loop in the same tree (the factor test_golden_crfasrnn_default_w
 grants the multi-iteration fixtures).  Every pair of errors is printed."""
-import contextlib
-
 import pytest
 import torch
 import torch.nn.functional as F
 
-from _guided_util import DEV, load_case, spy
+from _guided_util import DEV, load_case
+from _nchw_util import (B, LOGITS, PRODUCT, SOFTMAX, UNIFORM, both_loops, check_product, energy, inputs, launch_spy, loop_spy,
+                        old_loop, on_float4_path, report_loop, shifted)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,57 +21,7 @@ SIZES = [(7, 9), (13, 17), (16, 24)]         # n = 63 (one short tile, planes of
 # the float4 path (n % 4 == 0, 16-byte aligned bases) with a short last tile: n = 100 (a full tile + 36 pixels), 12 (one
 # short tile), 4 (one float4), 260 (four pixels past the streaming kernel's 256-pixel workgroup as well)
 VEC_SIZES = [(5, 20), (2, 6), (1, 4), (4, 65)]
-B = 2
 TP = 64                                      # pixels of a tile of k_nchw_tile
-PRODUCT, UNIFORM, SOFTMAX, LOGITS = 0, 1, 2, 3
-
-
-def _inputs(L, H, W, seed, B=B):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    E0 = torch.rand((B, L, H, W), device=DEV, generator=g) * 30 - 5
-    G = torch.randn((B, L, H, W), device=DEV, generator=g) * 5
-    Mu = torch.rand((L, L), device=DEV, generator=g) * 4 + torch.arange(L, device=DEV, dtype=torch.float32)[:, None] * 0.05
-    return E0, G, Mu
-
-
-def _energy(E0, G):
-    return E0 if G is None else E0 + G
-
-
-def _truth(E0, G, Mu64):
-    return torch.einsum("ac,bahw->bchw", Mu64, F.softmax(-_energy(E0.double(), None if G is None else G.double()), 1))
-
-
-def _torch32(E0, G, Mu):
-    return F.conv2d(F.softmax(-_energy(E0, G), 1), Mu.t()[..., None, None])
-
-
-def _check_product(name, hip, E0, G, Mu, Mu64=None):
-    want = _truth(E0, G, Mu.double() if Mu64 is None else Mu64)
-    e_hip = float((hip.double() - want).abs().max())
-    e_torch = float((_torch32(E0, G, Mu) .double() - want).abs().max())
-    bound = max(2e-6 * max(1.0, float(want.abs().max())), 2 * e_torch)
-    print(f"{name}: e_hip = {e_hip:.3e}  e_torch = {e_torch:.3e}  |Y| <= {float(want.abs().max()):.4g}")
-    assert torch.isfinite(hip).all(), name
-    assert e_hip <= bound, (name, e_hip, e_torch)
-
-
-@contextlib.contextmanager
-def _launch_spy():
-    """(entry point, mode) of every library launch made through phl._launch."""
-    import phl
-
-    real, seen = phl._launch, []
-
-    def launch(device, name, *args):
-        seen.append((name, args[-1]))
-        return real(device, name, *args)
-
-    phl._launch = launch
-    try:
-        yield seen
-    finally:
-        phl._launch = real
 
 
 @pytest.mark.parametrize("L", LS)
@@ -79,15 +29,15 @@ def test_product_parity(L):
     import phl
 
     for H, W in SIZES:
-        E0, G, Mu = _inputs(L, H, W, seed=L + H)
+        E0, G, Mu = inputs(L, H, W, seed=L + H)
         if L > 1:
             assert not torch.equal(Mu, Mu.t())                 # a transposed operand cannot pass
         for g in (G, None):
-            with _launch_spy() as seen:
+            with launch_spy() as seen:
                 hip = phl.nchw_softmax_compat(E0, g, Mu)
             assert seen == [("phl_nchw_softmax_compat", PRODUCT)]
             assert hip.shape == E0.shape
-            _check_product(f"product L{L} {H}x{W} G={'yes' if g is not None else 'none'}", hip, E0, g, Mu)
+            check_product(f"product L{L} {H}x{W} G={'yes' if g is not None else 'none'}", hip, E0, g, Mu)
 
 
 @pytest.mark.parametrize("L", [18, 64])
@@ -95,10 +45,10 @@ def test_product_needs_the_max_subtraction(L):
     """Energies near +80 and -80 in one column: exp(80) ** 2 leaves fp32 without the subtraction of the column maximum."""
     import phl
 
-    E0, G, Mu = _inputs(L, 13, 17, seed=3)
+    E0, G, Mu = inputs(L, 13, 17, seed=3)
     E0 = torch.where(torch.arange(L, device=DEV)[None, :, None, None] % 2 == 0, E0 * 0.1 + 80, E0 * 0.1 - 80)
     hip = phl.nchw_softmax_compat(E0, G * 0.1, Mu)
-    _check_product(f"product L{L} energies +-80", hip, E0, G * 0.1, Mu)
+    check_product(f"product L{L} energies +-80", hip, E0, G * 0.1, Mu)
 
 
 @pytest.mark.parametrize("L", [1, 5, 18, 64, 256, 300])         # 300: columns longer than an LDS tile
@@ -106,16 +56,16 @@ def test_softmax_and_logits_modes(L):
     import phl
 
     for H, W in SIZES:
-        E0, G, _ = _inputs(L, H, W, seed=2 * L + W)
+        E0, G, _ = inputs(L, H, W, seed=2 * L + W)
         for g in (G, None):
-            with _launch_spy() as seen:
+            with launch_spy() as seen:
                 q = phl.nchw_softmax_compat(E0, g)
             assert seen == [("phl_nchw_softmax_compat", SOFTMAX)]
-            want = F.softmax(-_energy(E0.double(), None if g is None else g.double()), 1)
+            want = F.softmax(-energy(E0.double(), None if g is None else g.double()), 1)
             err, colsum = float((q.double() - want).abs().max()), float((q.sum(1) - 1).abs().max())
             print(f"softmax L{L} {H}x{W} G={'yes' if g is not None else 'none'}: err = {err:.3e}  |colsum - 1| = {colsum:.3e}")
             assert err <= 2e-6 and colsum <= 1e-5
-        with _launch_spy() as seen:
+        with launch_spy() as seen:
             lg = phl.nchw_softmax_compat(E0, G, logits=True)
         assert seen == [("phl_nchw_softmax_compat", LOGITS)]
         want = -(E0.double() + G.double())
@@ -132,26 +82,22 @@ def test_uniform_mode(L):
     from crf.crf_module import _compat_matrix, potts
 
     for H, W in SIZES[::2]:
-        E0, G, _ = _inputs(L, H, W, seed=L + 7)
+        E0, G, _ = inputs(L, H, W, seed=L + 7)
         Mp = _compat_matrix(potts(L).to(DEV), L, None, DEV)
-        with _launch_spy() as seen:
+        with launch_spy() as seen:
             hip = phl.nchw_softmax_compat(E0, G, Mp)                     # detected
         assert seen == [("phl_nchw_softmax_compat", UNIFORM)]
-        _check_product(f"uniform potts L{L} {H}x{W}", hip, E0, G, Mp)
+        check_product(f"uniform potts L{L} {H}x{W}", hip, E0, G, Mp)
         M64 = 0.3 * torch.ones((L, L), dtype=torch.float64, device=DEV) - 1.7 * torch.eye(L, dtype=torch.float64, device=DEV)
-        with _launch_spy() as seen:
+        with launch_spy() as seen:
             hip = phl.nchw_softmax_compat(E0, None, uniform=(0.3, -1.7))
         assert seen == [("phl_nchw_softmax_compat", UNIFORM)]
-        _check_product(f"uniform (0.3, -1.7) L{L} {H}x{W}", hip, E0, None, M64.float(), M64)
+        check_product(f"uniform (0.3, -1.7) L{L} {H}x{W}", hip, E0, None, M64.float(), M64)
         if L <= 256:                                                      # the same matrix through the product
-            with _launch_spy() as seen:
+            with launch_spy() as seen:
                 prod = phl.nchw_softmax_compat(E0, G, Mp, uniform=False)
             assert seen == [("phl_nchw_softmax_compat", PRODUCT)]
-            _check_product(f"potts as a product L{L} {H}x{W}", prod, E0, G, Mp)
-
-
-def _on_float4_path(*tensors):
-    return all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0 and t[0, 0].numel() % 4 == 0) for t in tensors)
+            check_product(f"potts as a product L{L} {H}x{W}", prod, E0, G, Mp)
 
 
 @pytest.mark.parametrize("batch", [1, 2, 3])
@@ -160,13 +106,13 @@ def test_product_parity_short_float4_tiles(L, batch):
     import phl
 
     for H, W in VEC_SIZES:
-        E0, G, Mu = _inputs(L, H, W, seed=L + W + batch, B=batch)
-        assert _on_float4_path(E0, G) and (H * W) % TP != 0
+        E0, G, Mu = inputs(L, H, W, seed=L + W + batch, B=batch)
+        assert on_float4_path(E0, G) and (H * W) % TP != 0
         for g in (G, None):
-            with _launch_spy() as seen:
+            with launch_spy() as seen:
                 hip = phl.nchw_softmax_compat(E0, g, Mu)
-            assert seen == [("phl_nchw_softmax_compat", PRODUCT)] and _on_float4_path(hip)
-            _check_product(f"product L{L} B{batch} {H}x{W} G={'yes' if g is not None else 'none'}", hip, E0, g, Mu)
+            assert seen == [("phl_nchw_softmax_compat", PRODUCT)] and on_float4_path(hip)
+            check_product(f"product L{L} B{batch} {H}x{W} G={'yes' if g is not None else 'none'}", hip, E0, g, Mu)
 
 
 @pytest.mark.parametrize("L", [5, 64, 300])                      # 300: the streaming kernel, a thread per pixel
@@ -174,31 +120,22 @@ def test_uniform_and_softmax_short_float4_tiles(L):
     import phl
 
     for H, W in VEC_SIZES:
-        E0, G, _ = _inputs(L, H, W, seed=3 * L + W)
-        assert _on_float4_path(E0, G)
+        E0, G, _ = inputs(L, H, W, seed=3 * L + W)
+        assert on_float4_path(E0, G)
         M64 = 0.3 * torch.ones((L, L), dtype=torch.float64, device=DEV) - 1.7 * torch.eye(L, dtype=torch.float64, device=DEV)
         for g in (G, None):
             name = f"L{L} {H}x{W} G={'yes' if g is not None else 'none'}"
-            with _launch_spy() as seen:
+            with launch_spy() as seen:
                 hip = phl.nchw_softmax_compat(E0, g, uniform=(0.3, -1.7))
             assert seen == [("phl_nchw_softmax_compat", UNIFORM)]
-            _check_product("uniform (0.3, -1.7) " + name, hip, E0, g, M64.float(), M64)
-            with _launch_spy() as seen:
+            check_product("uniform (0.3, -1.7) " + name, hip, E0, g, M64.float(), M64)
+            with launch_spy() as seen:
                 q = phl.nchw_softmax_compat(E0, g)
             assert seen == [("phl_nchw_softmax_compat", SOFTMAX)]
-            want = F.softmax(-_energy(E0.double(), None if g is None else g.double()), 1)
+            want = F.softmax(-energy(E0.double(), None if g is None else g.double()), 1)
             err, colsum = float((q.double() - want).abs().max()), float((q.sum(1) - 1).abs().max())
             print(f"softmax {name}: err = {err:.3e}  |colsum - 1| = {colsum:.3e}")
             assert torch.isfinite(q).all() and err <= 2e-6 and colsum <= 1e-5
-
-
-def _shifted(t):
-    """A contiguous copy of t whose base lies 4 bytes past the 16-byte grid."""
-    buf = torch.zeros((t.numel() + 5,), device=DEV)
-    v = buf[1:1 + t.numel()].view(t.shape)
-    v.copy_(t)
-    assert v.is_contiguous() and v.data_ptr() % 16 == 4
-    return v
 
 
 @pytest.mark.parametrize("L", [18, 64])                          # VALU, matrix cores
@@ -208,14 +145,14 @@ def test_dword_fallback_for_a_base_off_the_16_byte_grid(L):
     import phl
 
     H, W = VEC_SIZES[0]
-    E0, G, Mu = _inputs(L, H, W, seed=L + 40)
+    E0, G, Mu = inputs(L, H, W, seed=L + 40)
     want = phl.nchw_softmax_compat(E0, G, Mu)
-    assert _on_float4_path(E0, G, want)
-    assert torch.equal(phl.nchw_softmax_compat(_shifted(E0), G, Mu), want)
-    assert torch.equal(phl.nchw_softmax_compat(E0, _shifted(G), Mu), want)
-    out = _shifted(torch.full(E0.shape, float("nan"), device=DEV))
+    assert on_float4_path(E0, G, want)
+    assert torch.equal(phl.nchw_softmax_compat(shifted(E0), G, Mu), want)
+    assert torch.equal(phl.nchw_softmax_compat(E0, shifted(G), Mu), want)
+    out = shifted(torch.full(E0.shape, float("nan"), device=DEV))
     assert phl.nchw_softmax_compat(E0, G, Mu, out=out) is out and torch.equal(out, want)
-    _check_product(f"product L{L} {H}x{W}, out off the 16-byte grid", out, E0, G, Mu)
+    check_product(f"product L{L} {H}x{W}, out off the 16-byte grid", out, E0, G, Mu)
 
 
 @pytest.mark.parametrize("L", [18, 64])
@@ -224,12 +161,12 @@ def test_nothing_written_behind_out(H, W, L):
     """``out`` as a view at the front of a larger buffer: a short last tile leaves the 4096 floats behind it alone."""
     import phl
 
-    E0, G, Mu = _inputs(L, H, W, seed=L + 50)
+    E0, G, Mu = inputs(L, H, W, seed=L + 50)
     want = phl.nchw_softmax_compat(E0, G, Mu)
     sentinel, pad = -12345.5, 4096
     buf = torch.full((E0.numel() + pad,), sentinel, device=DEV)
     out = buf[:E0.numel()].view(E0.shape)
-    assert _on_float4_path(E0, G, out)
+    assert on_float4_path(E0, G, out)
     assert phl.nchw_softmax_compat(E0, G, Mu, out=out) is out
     assert torch.equal(out, want)
     assert torch.equal(buf[E0.numel():], torch.full((pad,), sentinel, device=DEV))
@@ -238,7 +175,7 @@ def test_nothing_written_behind_out(H, W, L):
 def test_label_ranges():
     import phl
 
-    E0, G, Mu = _inputs(257, 7, 9, seed=1)
+    E0, G, Mu = inputs(257, 7, 9, seed=1)
     with pytest.raises(phl.PhlError) as e:
         phl.nchw_softmax_compat(E0, G, Mu)
     assert e.value.status == phl.ERR_UNSUPPORTED
@@ -256,17 +193,17 @@ def test_arguments():
     g = torch.Generator(device=DEV).manual_seed(11)
     E0 = (torch.rand((B, H, W, L), device=DEV, generator=g) * 30 - 5).permute(0, 3, 1, 2)       # a permuted view
     G = (torch.randn((B, L, H, 2 * W), device=DEV, generator=g) * 5)[..., ::2]                  # a strided slice
-    Mu = _inputs(L, 1, 1, seed=5)[2]
+    Mu = inputs(L, 1, 1, seed=5)[2]
     assert not E0.is_contiguous() and not G.is_contiguous()
     hip = phl.nchw_softmax_compat(E0, G, Mu)
-    _check_product("non-contiguous inputs", hip, E0, G, Mu)
+    check_product("non-contiguous inputs", hip, E0, G, Mu)
     out = torch.full((B, L, H, W), float("nan"), device=DEV)
     again = phl.nchw_softmax_compat(E0, G, Mu, out=out)
     assert again is out and torch.equal(out, hip)                           # two calls, the same bits
     flat = phl.nchw_softmax_compat(E0.reshape(B, L, H * W), G.reshape(B, L, H * W), Mu)      # [B, L, n]
     assert flat.shape == (B, L, H * W) and torch.equal(flat.reshape(B, L, H, W), hip)
     for L2 in (64, 256):                                                    # ... on the matrix cores as well
-        E2, G2, Mu2 = _inputs(L2, 16, 24, seed=L2)
+        E2, G2, Mu2 = inputs(L2, 16, 24, seed=L2)
         assert torch.equal(phl.nchw_softmax_compat(E2, G2, Mu2), phl.nchw_softmax_compat(E2, G2, Mu2))
     Gc = G.contiguous()
     with pytest.raises(phl.PhlError) as e:
@@ -279,77 +216,6 @@ def test_arguments():
 
 
 # ---- the loop ---------------------------------------------------------------------------------------------------------
-class _CountingF:
-    """torch.nn.functional as crf.crf_module sees it, with softmax and conv2d counted."""
-
-    def __init__(self, calls):
-        self._calls = calls
-
-    def __getattr__(self, name):
-        return getattr(F, name)
-
-    def softmax(self, *a, **k):
-        self._calls["softmax"] += 1
-        return F.softmax(*a, **k)
-
-    def conv2d(self, *a, **k):
-        self._calls["conv2d"] += 1
-        return F.conv2d(*a, **k)
-
-
-@contextlib.contextmanager
-def _loop_spy():
-    """Counts of F.softmax / F.conv2d calls made from crf.crf_module, and of phl.nchw_softmax_compat calls."""
-    import phl
-    from crf import crf_module as cm
-
-    calls = {"softmax": 0, "conv2d": 0, "step": 0}
-    real_f, real_step = cm.F, phl.nchw_softmax_compat
-
-    def step(*a, **k):
-        calls["step"] += 1
-        return real_step(*a, **k)
-
-    cm.F, phl.nchw_softmax_compat = _CountingF(calls), step
-    try:
-        yield calls
-    finally:
-        cm.F, phl.nchw_softmax_compat = real_f, real_step
-
-
-@contextlib.contextmanager
-def _old_loop():
-    """The module switch behind PHL_NCHW_STEP=0."""
-    from crf import crf_module as cm
-
-    was, cm._NCHW_STEP = cm._NCHW_STEP, False
-    try:
-        yield
-    finally:
-        cm._NCHW_STEP = was
-
-
-def _both_loops(net, *args, **kw):
-    """(new loop, old loop) outputs of one no-grad forward, with the call counts of the new one checked."""
-    niters = net.niters
-    with torch.no_grad():
-        with _loop_spy() as calls, spy() as wcalls:
-            new = net(*args, **kw)
-        assert calls == {"softmax": 0, "conv2d": 0, "step": niters + 1}, calls
-        assert wcalls == {"hip": niters, "box_sum": 0}, wcalls
-        with _old_loop(), _loop_spy() as calls:
-            old = net(*args, **kw)
-        assert calls["step"] == 0 and calls["softmax"] == niters + 1, calls
-    return new, old
-
-
-def _report_loop(name, new, old, want):
-    e_new, e_old = float((new.double() - want).abs().max()), float((old.double() - want).abs().max())
-    print(f"{name}: e_new = {e_new:.3e}  e_old = {e_old:.3e}  |out| <= {float(want.abs().max()):.4g}")
-    assert torch.isfinite(new).all()
-    assert e_new <= 2 * e_old, (name, e_new, e_old)
-
-
 def test_loop_on_the_crfasrnn_fixture():
     from crf.crf_module import CRFasRNN, charb
 
@@ -360,8 +226,8 @@ def test_loop_on_the_crfasrnn_fixture():
         net.W.omega.copy_(torch.from_numpy(z["omega"]))
     net = net.to(DEV)
     refs, logits, labels = (torch.from_numpy(z[k]).to(DEV) for k in ("x", "logits", "labels"))
-    new, old = _both_loops(net, refs, logits, labels=labels)
-    _report_loop("crfasrnn_guided", new, old, torch.from_numpy(z["out"]).to(DEV))
+    new, old = both_loops(lambda: net(refs, logits, labels=labels), net.niters)
+    report_loop("crfasrnn_guided", new, old, torch.from_numpy(z["out"]).to(DEV))
 
 
 def test_loop_on_the_upsampler_call_shape():
@@ -378,11 +244,11 @@ def test_loop_on_the_upsampler_call_shape():
         logits = -10 * net.Mu.get_energies_from_scalar(up, labels[None, :, None, None])
     confidence = (up > 1e-2).float()
     assert tuple(logits.shape) == (1, 18, 45, 83) and 0 < float(confidence.mean()) < 1
-    new, old = _both_loops(net, img, logits, confidence=confidence, labels=labels)
+    new, old = both_loops(lambda: net(img, logits, confidence=confidence, labels=labels), net.niters)
     with torch.no_grad():
         want = net.double()(img.double(), logits.double(), confidence=confidence.double(), labels=labels.double())
     net.float()
-    _report_loop("upsampler shape L18", new, old, want)
+    report_loop("upsampler shape L18", new, old, want)
 
 
 def test_loop_with_potts():
@@ -392,14 +258,14 @@ def test_loop_with_potts():
     net = CRFasRNN(potts(8), niters=3, notrain_mu=True).to(DEV)
     refs = torch.rand((2, 1, 40, 50), device=DEV, generator=g)
     logits = torch.randn((2, 8, 40, 50), device=DEV, generator=g) * 3
-    with _launch_spy() as seen:
-        new, old = _both_loops(net, refs, logits)
+    with launch_spy() as seen:
+        new, old = both_loops(lambda: net(refs, logits), net.niters)
     modes = [m for name, m in seen if name == "phl_nchw_softmax_compat"]
     assert modes == [UNIFORM] * 3 + [LOGITS], modes
     with torch.no_grad():
         want = net.double()(refs.double(), logits.double())
     net.float()
-    _report_loop("potts(8)", new, old, want)
+    report_loop("potts(8)", new, old, want)
 
 
 def test_routing_keeps_the_plain_loop():
@@ -413,10 +279,10 @@ def test_routing_keeps_the_plain_loop():
 
     def run(net, refs, logits):
         labels = torch.arange(5, dtype=logits.dtype, device=logits.device)    # charb's own default labels are fp32
-        with _loop_spy() as calls:
+        with loop_spy() as calls:
             out = net(refs, logits, labels=labels)
         assert calls["step"] == 0 and calls["softmax"] == 3, calls
-        with _old_loop():
+        with old_loop():
             assert torch.equal(out.detach(), net(refs, logits, labels=labels).detach())
 
     run(net, refs, logits.clone().requires_grad_())           # a gradient of the logits
