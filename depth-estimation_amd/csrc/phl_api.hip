@@ -145,6 +145,14 @@ hipError_t phl_dev_free(void *p)
     return hipSuccess;
 }
 
+// test hook: blocks handed out and not yet given back
+extern "C" int64_t phl_debug_live_blocks(void)
+{
+    dev_cache_t &c = dev_cache();
+    std::lock_guard<std::mutex> lk(c.mu);
+    return (int64_t)c.live.size();
+}
+
 // ---- value workspaces --------------------------------------------------------------------------------
 // SURVEY 8(b), threading row: "re-entrant; autograd may call from any thread".  A lattice's tables are
 // read-only after the build; what a filter call WRITES (the [M][vd] ping-pong pair, partial rows, staging
@@ -481,18 +489,18 @@ int phl_raise_lds_limit(const void *kernel, size_t bytes)
     return PHL_OK;
 }
 
-// an empty handle (phl_sub_lattice fills it): same initial state phl_build_ex gives one
-int phl_lattice_blank(phl_lattice **out, int device, int d, int64_t n)
+// an empty handle: the initial state of every lattice (phl_build_ex and phl_sub_lattice fill it)
+phl_lattice *phl_lattice_blank(int device, int d, int64_t n, unsigned build_flags)
 {
     phl_lattice *lat = new phl_lattice();
     memset(lat, 0, sizeof(*lat));
     lat->device = device;
     lat->d = d;
     lat->n = n;
+    lat->build_flags = build_flags;
     lat->nbr00_override = -2;
     lat->shared = new phl_shared();
-    *out = lat;
-    return PHL_OK;
+    return lat;
 }
 
 // ---- the plan of a filter call ----------------------------------------------------------------------------------------
@@ -656,14 +664,7 @@ int phl_build_ex(phl_lattice **out, const float *ref_dev, int64_t n, int d, int6
     device_guard g(device);
     if (!g.ok) { phl_set_error("phl_build: cannot select device %d", device); return PHL_ERR_NO_DEVICE; }
 
-    phl_lattice *lat = new phl_lattice();
-    memset(lat, 0, sizeof(*lat));
-    lat->device = device;
-    lat->d = d;
-    lat->n = n;
-    lat->build_flags = build_flags;
-    lat->nbr00_override = -2;
-    lat->shared = new phl_shared();
+    phl_lattice *lat = phl_lattice_blank(device, d, n, build_flags);
     static const bool dbg_t = getenv("PHL_DEBUG") != nullptr;
     const auto tb0 = std::chrono::steady_clock::now();
     int rc = phl_build_device(lat, ref_dev, rs, cs, (hipStream_t)stream);
@@ -687,9 +688,7 @@ int phl_destroy(phl_lattice *lat)
     (void)hipDeviceSynchronize();      // what hipFree would do: nothing may still be using the arrays (they are cached, not freed)
     phl_tiles_free(lat);
     phl_release_build_tables(lat);                 // (only a build that failed half-way leaves any)
-    void *ptrs[] = {lat->vkeys, lat->replay, lat->csr_ptr, lat->csr, lat->nbr, lat->nbr2, lat->table, lat->ft_of_int, lat->int_of_ft, lat->vfirst};
-    for (void *p : ptrs)
-        if (p) (void)phl_dev_free(p);
+    phl_lat_free_persistent(lat);
     if (lat->shared) {
         for (phl_workspace *w : lat->shared->ws) {
             ws_free_buffers(w);

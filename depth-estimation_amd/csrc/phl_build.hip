@@ -511,12 +511,12 @@ __global__ __launch_bounds__(256) void k_neighbors(const uint32_t *__restrict__ 
 }
 
 template <int D>
-int launch_neighbors(const int16_t *vkeys, int M, const int *table, uint32_t mask, int *nbr, void **scratch_out, hipStream_t st)
+int launch_neighbors(const int16_t *vkeys, int M, const int *table, uint32_t mask, int *nbr, phl_dev_block<uint32_t> &scratch,
+                     hipStream_t st)
 {
     using K = packed_key<D>;
-    uint32_t *vkp;
-    PHL_HIP(phl_dev_malloc((void **)&vkp, sizeof(uint32_t) * ((size_t)M * K::PW + 4)));
-    *scratch_out = vkp;
+    PHL_TRY(scratch.alloc((size_t)M * K::PW + 4));
+    uint32_t *const vkp = scratch.get();
     hipLaunchKernelGGL(k_pack_keys<D>, dim3((M + 255) / 256), dim3(256), 0, st, vkeys, M, vkp);
     const int64_t tot = (int64_t)M * (D + 1);
     hipLaunchKernelGGL(k_neighbors<D>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, vkp, M, table, mask, nbr);
@@ -705,24 +705,18 @@ __global__ void k_override_nbr00(int *nbr, const int *__restrict__ int_of_ft, in
 }  // namespace
 
 // Persistent compact table (capacity >= 2M) + blur neighbour ids for ALL current vertices.
-// *scratch_out: a device block the launches read (packed keys); the caller releases it with phl_dev_free once the
-// stream has been synchronised (the block cache may hand a freed block to another thread's build at once).
-int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, void **scratch_out)
+// scratch: the caller's empty holder.  It leaves with the device block the launches read (packed keys); the caller drops
+// it once the stream has been synchronised (the block cache may hand a freed block to another thread's build at once).
+int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, phl_dev_block<uint32_t> &scratch)
 {
-    *scratch_out = nullptr;
     const int d = lat->d;
     const int M = (int)lat->M;
-    if (lat->table) PHL_HIP(phl_dev_free(lat->table));
-    if (lat->nbr) PHL_HIP(phl_dev_free(lat->nbr));
-    if (lat->nbr2) PHL_HIP(phl_dev_free(lat->nbr2));
-    lat->table = nullptr;
-    lat->nbr = nullptr;
-    lat->nbr2 = nullptr;
+    PHL_HIP(phl_lat_free(lat->nbr2));            // (made again below only where there are vertices)
     uint64_t cap = 1024;
     while (cap < (uint64_t)M * 2) cap <<= 1;
     lat->table_mask = (uint32_t)(cap - 1);
-    PHL_HIP(phl_dev_malloc((void **)&lat->table, sizeof(int) * cap));
-    PHL_HIP(phl_dev_malloc((void **)&lat->nbr, sizeof(int32_t) * (size_t)(M ? M : 1) * (d + 1) * 2));
+    PHL_HIP(phl_lat_alloc(lat->table, cap));
+    PHL_HIP(phl_lat_alloc(lat->nbr, (size_t)M * (d + 1) * 2));
     hipLaunchKernelGGL(k_fill_i32, dim3(1024), dim3(256), 0, st, lat->table, (int64_t)cap, PHL_EMPTY);
     if (M > 0) {
         hidden_t hidden;
@@ -732,7 +726,7 @@ int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, void **scr
                            lat->table_mask, hidden, lat->int_of_ft);
         int rcn = PHL_OK;
         switch (d) {
-#define PHL_CASE(D) case D: rcn = launch_neighbors<D>(lat->vkeys, M, lat->table, lat->table_mask, lat->nbr, scratch_out, st); break;
+#define PHL_CASE(D) case D: rcn = launch_neighbors<D>(lat->vkeys, M, lat->table, lat->table_mask, lat->nbr, scratch, st); break;
             PHL_FOR_D(PHL_CASE)
 #undef PHL_CASE
         }
@@ -740,24 +734,13 @@ int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, void **scr
         if (lat->nbr00_override != -2)    // a table doubling inside the reference's blur(): phl_reftable.hip
             hipLaunchKernelGGL(k_override_nbr00, dim3(1), dim3(1), 0, st, lat->nbr, lat->int_of_ft, lat->nbr00_override);
         const int npairs = (d + 1) / 2;
-        PHL_HIP(phl_dev_malloc((void **)&lat->nbr2, sizeof(int32_t) * (size_t)M * npairs * 8));
+        PHL_HIP(phl_lat_alloc(lat->nbr2, (size_t)M * npairs * 8));
         const int64_t totp = (int64_t)M * npairs;
         hipLaunchKernelGGL(k_compose_pairs, dim3((unsigned)((totp + 255) / 256)), dim3(256), 0, st,
                            reinterpret_cast<const int2 *>(lat->nbr), M, npairs, reinterpret_cast<int4 *>(lat->nbr2));
     }
     PHL_HIP(hipGetLastError());
     return PHL_OK;
-}
-
-void phl_release_build_tables(phl_lattice *lat)
-{
-    // (bt_seg_e / bt_seg_id point into bt_dup_ptr's block: phl_apply_reference_table)
-    int32_t **p[] = {&lat->bt_slot_of, &lat->bt_table, &lat->bt_remap, &lat->bt_dup_ptr, &lat->bt_cell};
-    for (int32_t **q : p) {
-        if (*q) (void)phl_dev_free(*q);
-        *q = nullptr;
-    }
-    lat->bt_seg_e = lat->bt_seg_id = nullptr;
 }
 
 int phl_write_final_vids(phl_lattice *lat, hipStream_t st)
@@ -781,6 +764,30 @@ struct side_t {
 };
 constexpr int MAX_SIDE_DEV = 64;
 thread_local side_t t_sides[MAX_SIDE_DEV];
+
+// The calling thread's side stream on the current device, or null.  One per (thread, device): a thread that deals builds
+// over several GPUs (phl.batched_filter, the NCHW mean field) comes back to each device's own stream instead of dropping
+// and re-creating it.  (never destroyed: a thread's exit may come after the runtime has shut down)
+side_t *replay_side_stream()
+{
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_SIDE_DEV) { (void)hipGetLastError(); return nullptr; }
+    side_t *const side = &t_sides[dev];
+    if (side->dev == dev) return side;
+    side_t fresh;                            // first build of this thread on this device
+    if (hipStreamCreateWithFlags(&fresh.s, hipStreamNonBlocking) == hipSuccess &&
+        hipEventCreateWithFlags(&fresh.fork, hipEventDisableTiming) == hipSuccess &&
+        hipEventCreateWithFlags(&fresh.join, hipEventDisableTiming) == hipSuccess) {
+        fresh.dev = dev;
+        *side = fresh;
+        return side;
+    }
+    (void)hipGetLastError();                 // nothing half-made is kept
+    if (fresh.s) (void)hipStreamDestroy(fresh.s);
+    if (fresh.fork) (void)hipEventDestroy(fresh.fork);
+    if (fresh.join) (void)hipEventDestroy(fresh.join);
+    return nullptr;
+}
 }  // namespace
 
 // test hook: side streams the calling thread holds (one per device it has built reference-table lattices on)
@@ -825,7 +832,7 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
     if (cap > cap_full || !small_table) cap = cap_full;
     uint32_t mask = (uint32_t)(cap - 1);
 
-    temp_pool tmp;
+    temp_pool tmp(st);
     uint32_t *recs;                                  // per-pixel records the candidate keys are rebuilt from (pix_rec)
     int *table, *slot_of, *wcount, *wrank, *tile_sums, *err;
     unsigned long long *fbits;
@@ -833,8 +840,8 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
     const int NW = (int)gN * 4;                      // 64-candidate words of the first-touch mask
     PHL_HIP(tmp.get(&recs, (size_t)n * rec_words(d) + 4));
     phl_release_build_tables(lat);
-    PHL_HIP(phl_dev_malloc((void **)&lat->bt_table, sizeof(int) * (size_t)cap));       // (outlive this function: bt_*)
-    PHL_HIP(phl_dev_malloc((void **)&lat->bt_slot_of, sizeof(int) * (size_t)N));
+    PHL_HIP(phl_lat_alloc(lat->bt_table, (size_t)cap));       // (outlive this function: bt_*)
+    PHL_HIP(phl_lat_alloc(lat->bt_slot_of, (size_t)N));
     table = lat->bt_table;
     slot_of = lat->bt_slot_of;
     PHL_HIP(tmp.get(&fbits, (size_t)NW));
@@ -853,7 +860,7 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
     int *info_pinned = (int *)phl_pinned_alloc(sizeof(int) * INFO_N);
     int info_host[INFO_N];
     PHL_HIP(tmp.get(&info_dev, (size_t)INFO_N));
-    PHL_HIP(phl_dev_malloc((void **)&lat->replay, sizeof(phl_replay_t) * (size_t)N));
+    PHL_HIP(phl_lat_alloc(lat->replay, (size_t)N));
     PHL_HIP(hipMemsetAsync(err, 0, sizeof(int), st));
 
     switch (d) {
@@ -875,8 +882,7 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
         hipLaunchKernelGGL(k_flag_bits, dim3((unsigned)((cap / 4 + 255) / 256)), dim3(256), 0, st, table, (int64_t)cap, fbits);
         hipLaunchKernelGGL(k_word_counts, dim3((unsigned)((NW + 255) / 256)), dim3(256), 0, st, fbits, NW, wcount);
         PHL_HIP(hipGetLastError());
-        rc = exclusive_scan(wcount, wrank, NW, tile_sums, st);
-        if (rc) return rc;
+        PHL_TRY(exclusive_scan(wcount, wrank, NW, tile_sums, st));
         // one read-back: the kernel writes straight into pinned host memory where there is some
         if (nblk > 4 * MM2) {
             hipLaunchKernelGGL(k_minmax_stage, dim3(MM2), dim3(256), 0, st, mm, nblk, d, mm2);
@@ -899,9 +905,7 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
         // the small table overflowed (little sharing: most candidates are vertices of their own): full size
         cap = cap_full;
         mask = (uint32_t)(cap - 1);
-        PHL_HIP(phl_dev_free(lat->bt_table));             // (the stream has been synchronised)
-        lat->bt_table = nullptr;
-        PHL_HIP(phl_dev_malloc((void **)&lat->bt_table, sizeof(int) * (size_t)cap));
+        PHL_HIP(phl_lat_alloc(lat->bt_table, (size_t)cap));      // (the stream has been synchronised)
         table = lat->bt_table;
         PHL_HIP(hipMemsetAsync(err, 0, sizeof(int), st));
     }
@@ -913,11 +917,9 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
     const int M = host[0];
     lat->M = M;
 
-    PHL_HIP(phl_dev_malloc((void **)&lat->vkeys, sizeof(int16_t) * (size_t)M * d));
-    if (lat->vfirst) PHL_HIP(phl_dev_free(lat->vfirst));
-    lat->vfirst = nullptr;
+    PHL_HIP(phl_lat_alloc(lat->vkeys, (size_t)M * d));
     lat->vfirst_valid_for_M = 0;
-    PHL_HIP(phl_dev_malloc((void **)&lat->vfirst, sizeof(int) * ((size_t)M + 1)));
+    PHL_HIP(phl_lat_alloc(lat->vfirst, (size_t)M + 1));
     switch (d) {
 #define PHL_CASE(D) case D: launch_assign<D>(fbits, wrank, recs, (int64_t)cap, table, lat->vkeys, lat->vfirst, st); break;
         PHL_FOR_D(PHL_CASE)
@@ -947,39 +949,13 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
         char *arena2 = nullptr;
         under.bytes = phl_tiles_pixel_order_scratch_bytes(n);
         // (a second stream: on the caller's the replay's device queries would queue behind these launches)
-        // one side stream per (thread, device): a thread that deals builds over several GPUs (phl.batched_filter, the NCHW
-        // mean field) comes back to each device's own stream instead of dropping and re-creating it
-        // (never destroyed: a thread's exit may come after the runtime has shut down)
-        side_t *const sides = t_sides;
-        side_t none;
-        side_t *sidep = &none;
         if (early) {
-            int dev = -1;
-            if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_SIDE_DEV) {
-                sidep = &sides[dev];
-                if (sidep->dev != dev) {                 // first build of this thread on this device
-                    side_t fresh;
-                    if (hipStreamCreateWithFlags(&fresh.s, hipStreamNonBlocking) == hipSuccess &&
-                        hipEventCreateWithFlags(&fresh.fork, hipEventDisableTiming) == hipSuccess &&
-                        hipEventCreateWithFlags(&fresh.join, hipEventDisableTiming) == hipSuccess) {
-                        fresh.dev = dev;
-                        *sidep = fresh;
-                    } else {                             // nothing half-made is kept
-                        (void)hipGetLastError();
-                        if (fresh.s) (void)hipStreamDestroy(fresh.s);
-                        if (fresh.fork) (void)hipEventDestroy(fresh.fork);
-                        if (fresh.join) (void)hipEventDestroy(fresh.join);
-                    }
-                }
-            } else {
-                (void)hipGetLastError();
-            }
-            side_t &side = *sidep;
-            if (side.dev == dev && dev >= 0 && tmp.get(&arena2, under.bytes) == hipSuccess) {
+            const side_t *const side = replay_side_stream();
+            if (side && tmp.get(&arena2, under.bytes) == hipSuccess) {
                 under.arena = arena2;
-                under.aux = side.s;
-                under.fork = side.fork;
-                under.join = side.join;
+                under.aux = side->s;
+                under.fork = side->fork;
+                under.join = side->join;
             } else {
                 (void)hipGetLastError();
             }
@@ -988,9 +964,9 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
             under_t *u = (under_t *)a;
             PHL_HIP(hipEventRecord(u->fork, u->st));                 // everything enqueued so far (vertex keys, first touches)
             PHL_HIP(hipStreamWaitEvent(u->aux, u->fork, 0));
+            u->launched = true;          // (before the first launch: an error below still has the side stream drained)
             const int rcp = phl_tiles_pixel_order(u->lat, u->ref, u->rs, u->cs, u->arena, u->bytes, u->aux);
             PHL_HIP(hipEventRecord(u->join, u->aux));
-            u->launched = true;
             return rcp;
         };
         rc = phl_apply_reference_table(lat, st, arena, arena ? arena_bytes : 0, under.arena ? +hook : nullptr, &under);
@@ -1001,8 +977,7 @@ int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs,
         if (rc) return rc;
     }
     if (lat->M != M && lat->vfirst_valid_for_M != lat->M) {     // duplicate vertices inserted without a list of their own
-        PHL_HIP(phl_dev_free(lat->vfirst));
-        lat->vfirst = nullptr;
+        PHL_HIP(phl_lat_free(lat->vfirst));
     }
     lat->M_local = lat->M;
     // (locality renumbering, key -> vertex table and blur neighbours follow in phl_tiles_build)
@@ -1019,8 +994,7 @@ int phl_ensure_csr(phl_lattice *lat, hipStream_t st)
 {
     std::lock_guard<std::mutex> once(*phl_csr_mutex(lat));     // several threads may filter through one lattice
     if (!(lat->csr_ptr && lat->csr)) {
-        const int rc = build_csr(lat, st);
-        if (rc) return rc;
+        PHL_TRY(build_csr(lat, st));
     }
     return phl_tiles_ensure_vorder(lat, st);  // (the gather splat's vertex order: same first use, same lock)
 }
@@ -1028,18 +1002,14 @@ int phl_ensure_csr(phl_lattice *lat, hipStream_t st)
 static int build_csr(phl_lattice *lat, hipStream_t st)
 {
     const int M = (int)lat->M, N = (int)lat->N, dp1 = lat->d + 1;
-    if (lat->csr_ptr) PHL_HIP(phl_dev_free(lat->csr_ptr));
-    if (lat->csr) PHL_HIP(phl_dev_free(lat->csr));
-    lat->csr_ptr = nullptr;
-    lat->csr = nullptr;
-    PHL_HIP(phl_dev_malloc((void **)&lat->csr_ptr, sizeof(int32_t) * ((size_t)M + 1)));
-    PHL_HIP(phl_dev_malloc((void **)&lat->csr, sizeof(phl_contrib_t) * (size_t)(N ? N : 1)));
+    PHL_HIP(phl_lat_alloc(lat->csr_ptr, (size_t)M + 1));
+    PHL_HIP(phl_lat_alloc(lat->csr, (size_t)N));
     if (N == 0 || M == 0) {
         PHL_HIP(hipMemsetAsync(lat->csr_ptr, 0, sizeof(int32_t) * ((size_t)M + 1), st));
         PHL_HIP(hipStreamSynchronize(st));
         return PHL_OK;
     }
-    temp_pool tmp;
+    temp_pool tmp(st);
     int *cnt, *tile_sums, *vkey, *perm;
     PHL_HIP(tmp.get(&cnt, (size_t)M));
     PHL_HIP(tmp.get(&tile_sums, (size_t)M / SCAN_TILE + 2));
@@ -1049,14 +1019,12 @@ static int build_csr(phl_lattice *lat, hipStream_t st)
     const unsigned gN = (unsigned)((N + 255) / 256);
     hipLaunchKernelGGL(k_count_vid, dim3(gN), dim3(256), 0, st, lat->replay, N, cnt);
     PHL_HIP(hipGetLastError());
-    int rc = exclusive_scan(cnt, lat->csr_ptr, M, tile_sums, st);
-    if (rc) return rc;
+    PHL_TRY(exclusive_scan(cnt, lat->csr_ptr, M, tile_sums, st));
     // a pixel holds a vertex at most once (the d+1 vertices of a simplex are distinct), so a STABLE sort of the
     // candidates by vertex id leaves every list in ascending pixel order; O(N) for any list lengths
     hipLaunchKernelGGL(k_replay_vids, dim3(gN), dim3(256), 0, st, lat->replay, N, vkey);
     PHL_HIP(hipGetLastError());
-    rc = stable_sort_perm(vkey, N, M, perm, tmp, st);
-    if (rc) return rc;
+    PHL_TRY(stable_sort_perm(vkey, N, M, perm, tmp, st));
     hipLaunchKernelGGL(k_fill_sorted, dim3(gN), dim3(256), 0, st, lat->replay, perm, N, dp1, lat->csr);
     PHL_HIP(hipGetLastError());
     PHL_HIP(hipStreamSynchronize(st));  // temporaries go back to the scratch cache
@@ -1067,12 +1035,12 @@ static int build_csr(phl_lattice *lat, hipStream_t st)
 // distinct.  Used by the row-band multi-GPU path; rebuilds the table and the neighbour ids.
 int phl_add_vertices_device(phl_lattice *lat, const int16_t *keys_host, int64_t count, int32_t *vid_host, hipStream_t st)
 {
-    void *nbr_scratch = nullptr;
     if (count == 0) return PHL_OK;
     const int d = lat->d;
     const int K = (int)count;
     const int M_old = (int)lat->M;
-    temp_pool tmp;
+    phl_dev_block<uint32_t> nbr_scratch(st);
+    temp_pool tmp(st);
     int16_t *qkeys;
     int *vid, *missing, *mrank, *tile_sums;
     PHL_HIP(tmp.get(&qkeys, (size_t)K * d));
@@ -1084,51 +1052,46 @@ int phl_add_vertices_device(phl_lattice *lat, const int16_t *keys_host, int64_t 
     hipLaunchKernelGGL(k_table_lookup, dim3((K + 255) / 256), dim3(256), 0, st, qkeys, d, K, lat->vkeys, lat->table,
                        lat->table_mask, vid, missing);
     PHL_HIP(hipGetLastError());
-    int rc = exclusive_scan(missing, mrank, K, tile_sums, st);
-    if (rc) return rc;
+    PHL_TRY(exclusive_scan(missing, mrank, K, tile_sums, st));
     int n_new = 0;
     PHL_HIP(hipMemcpyAsync(&n_new, mrank + K, sizeof(int), hipMemcpyDeviceToHost, st));
     PHL_HIP(hipStreamSynchronize(st));
     if (n_new > 0) {
         const int M_new = M_old + n_new;
-        int16_t *vkeys_new;
-        PHL_HIP(phl_dev_malloc((void **)&vkeys_new, sizeof(int16_t) * (size_t)M_new * d));
+        phl_dev_block<int16_t> vkeys_new(st);
+        PHL_TRY(vkeys_new.alloc((size_t)M_new * d));
         if (M_old > 0)
-            PHL_HIP(hipMemcpyAsync(vkeys_new, lat->vkeys, sizeof(int16_t) * (size_t)M_old * d, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_append_missing, dim3((K + 255) / 256), dim3(256), 0, st, qkeys, d, K, mrank, M_old, vkeys_new,
-                           vid);
+            PHL_HIP(hipMemcpyAsync(vkeys_new.get(), lat->vkeys, sizeof(int16_t) * (size_t)M_old * d, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_append_missing, dim3((K + 255) / 256), dim3(256), 0, st, qkeys, d, K, mrank, M_old,
+                           vkeys_new.get(), vid);
         PHL_HIP(hipGetLastError());
         PHL_HIP(hipStreamSynchronize(st));
         if (lat->int_of_ft) {        // ghosts are appended at the end in both numberings
-            int32_t *a, *b;
-            PHL_HIP(phl_dev_malloc((void **)&a, sizeof(int32_t) * (size_t)M_new));
-            PHL_HIP(phl_dev_malloc((void **)&b, sizeof(int32_t) * (size_t)M_new));
-            PHL_HIP(hipMemcpyAsync(a, lat->ft_of_int, sizeof(int32_t) * (size_t)M_old, hipMemcpyDeviceToDevice, st));
-            PHL_HIP(hipMemcpyAsync(b, lat->int_of_ft, sizeof(int32_t) * (size_t)M_old, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_iota_from, dim3((n_new + 255) / 256), dim3(256), 0, st, a + M_old, n_new, M_old);
-            hipLaunchKernelGGL(k_iota_from, dim3((n_new + 255) / 256), dim3(256), 0, st, b + M_old, n_new, M_old);
+            phl_dev_block<int32_t> a(st), b(st);
+            PHL_TRY(a.alloc((size_t)M_new));
+            PHL_TRY(b.alloc((size_t)M_new));
+            PHL_HIP(hipMemcpyAsync(a.get(), lat->ft_of_int, sizeof(int32_t) * (size_t)M_old, hipMemcpyDeviceToDevice, st));
+            PHL_HIP(hipMemcpyAsync(b.get(), lat->int_of_ft, sizeof(int32_t) * (size_t)M_old, hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(k_iota_from, dim3((n_new + 255) / 256), dim3(256), 0, st, a.get() + M_old, n_new, M_old);
+            hipLaunchKernelGGL(k_iota_from, dim3((n_new + 255) / 256), dim3(256), 0, st, b.get() + M_old, n_new, M_old);
             PHL_HIP(hipGetLastError());
             PHL_HIP(hipStreamSynchronize(st));
-            PHL_HIP(phl_dev_free(lat->ft_of_int));
-            PHL_HIP(phl_dev_free(lat->int_of_ft));
-            lat->ft_of_int = a;
-            lat->int_of_ft = b;
+            PHL_HIP(phl_lat_free(lat->ft_of_int));
+            PHL_HIP(phl_lat_free(lat->int_of_ft));
+            lat->ft_of_int = a.release();
+            lat->int_of_ft = b.release();
         }
-        if (lat->vkeys) PHL_HIP(phl_dev_free(lat->vkeys));
+        PHL_HIP(phl_lat_free(lat->vkeys));
         // the per-vertex contribution lists are indexed by M: drop them, they are rebuilt on demand
         // (ghosts get empty lists)
-        if (lat->csr_ptr) PHL_HIP(phl_dev_free(lat->csr_ptr));
-        if (lat->csr) PHL_HIP(phl_dev_free(lat->csr));
-        lat->csr_ptr = nullptr;
-        lat->csr = nullptr;
-        lat->vkeys = vkeys_new;
+        PHL_HIP(phl_lat_free(lat->csr_ptr));
+        PHL_HIP(phl_lat_free(lat->csr));
+        lat->vkeys = vkeys_new.release();
         lat->M = M_new;
-        rc = phl_rebuild_table_and_neighbors(lat, st, &nbr_scratch);
-        if (rc) return rc;
+        PHL_TRY(phl_rebuild_table_and_neighbors(lat, st, nbr_scratch));
         // (the value workspaces are sized by M: phl_add_vertices drops them)
     }
     PHL_HIP(hipMemcpyAsync(vid_host, vid, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost, st));
     PHL_HIP(hipStreamSynchronize(st));
-    if (nbr_scratch) PHL_HIP(phl_dev_free(nbr_scratch));
-    return PHL_OK;
+    return nbr_scratch.drop();
 }

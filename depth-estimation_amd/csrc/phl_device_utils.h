@@ -184,16 +184,23 @@ __attribute__((unused)) int exclusive_scan(const int *in, int *out /* n+1 */, in
 // block (phl_scratch_*, phl_api.hip) so that a warm build performs no hipMalloc/hipFree for its
 // ~25 work arrays; whatever does not fit falls back to hipMalloc, and the block is re-sized to the
 // phase's total on release so the next build fits.
+// `st`: the stream whose launches use the temporaries.  The scratch block's next user may be another thread's build, so a
+// pool that holds it waits for `st` before it gives it back: microseconds behind the synchronisation every success path
+// ends in, the whole queue on an early error return.  A pool that does not hold it never waits.
 struct temp_pool {
     std::vector<void *> ptrs;
     char *base = nullptr;
     size_t cap = 0, off = 0, wanted = 0;
-    bool have_cache = false;
-    temp_pool() { have_cache = phl_scratch_acquire((void **)&base, &cap); }
+    bool have_cache;
+    hipStream_t st;
+    explicit temp_pool(hipStream_t s, bool use_cache = true) : have_cache(use_cache && phl_scratch_acquire((void **)&base, &cap)), st(s) {}
     ~temp_pool()
     {
         for (void *p : ptrs) (void)hipFree(p);
-        if (have_cache) phl_scratch_release(wanted);
+        if (!have_cache) return;
+        (void)hipStreamSynchronize(st);
+        (void)hipGetLastError();
+        phl_scratch_release(wanted);
     }
     template <typename T>
     hipError_t get(T **out, size_t count)
@@ -294,11 +301,12 @@ __attribute__((unused)) __global__ __launch_bounds__(256) void k_iota(int *p, in
 
 // Requests served from a caller's arena first (device bytes out of the caller's temp_pool, handed across translation
 // units as a plain pointer), from a pool of its own when that is missing or full -- which means hipMalloc / hipFree
-// while the caller holds the scratch block.
+// while the caller holds the scratch block.  The fallback therefore never asks for that block and never waits for a
+// stream: phl_tiles_pixel_order runs launch-only on a side stream under the host's table replay.
 struct arena_pool {
     char *base;
     size_t cap, off = 0;
-    temp_pool fallback;
+    temp_pool fallback{nullptr, false};
     arena_pool(void *b, size_t c) : base((char *)b), cap(b ? c : 0) {}
     template <typename T>
     hipError_t get(T **out, size_t count)

@@ -7,11 +7,23 @@
 #include "phl.h"
 
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #define PHL_WAVE 64
 #define PHL_MAX_HIDDEN 64   // duplicate vertices of the reference-table mode (<= 2 per table doubling)
 #define PHL_EMPTY 0x7FFFFFFF  // empty hash slot (larger than any candidate index)
+
+// thread-local error message
+void phl_set_error(const char *fmt, ...);
+int phl_hip_fail(hipError_t e, const char *what, const char *file, int line);
+#define PHL_HIP(call)                                                              \
+    do {                                                                           \
+        hipError_t e__ = (call);                                                   \
+        if (e__ != hipSuccess) return phl_hip_fail(e__, #call, __FILE__, __LINE__); \
+    } while (0)
+#define PHL_TRY(call) \
+    do { const int rc__ = (call); if (rc__ != PHL_OK) return rc__; } while (0)
 
 // (vertex, weight) per (pixel, remainder): the sparse n x M splat matrix, d+1 entries per
 // row.  Same content as the reference's ReplayEntry (permutohedral.h:558-561) with a vertex
@@ -103,6 +115,51 @@ struct phl_lattice {
     int32_t nbr00_override;
 };
 
+// ---- who owns a device block ----
+// Cached device blocks (phl_api.hip).  Called from three places only: the lattice's replace call and member list here, the
+// holder (phl_dev_block, below) and the value workspaces of phl_api.hip.
+hipError_t phl_dev_malloc(void **p, size_t bytes);
+hipError_t phl_dev_free(void *p);
+
+// The replace call for an array the lattice owns: the old block goes back, the member is nulled, the new block is typed (a
+// zero count allocates one element).  The member is null whenever it fails, so phl_destroy is safe after any failed build.
+// The caller guarantees that no launch still reads the old block.
+template <typename T>
+inline hipError_t phl_lat_free(T *&member) { return phl_dev_free(std::exchange(member, nullptr)); }
+template <typename T>
+inline hipError_t phl_lat_alloc(T *&member, size_t count)
+{
+    hipError_t e = phl_lat_free(member);
+    void *p = nullptr;
+    if (e == hipSuccess) e = phl_dev_malloc(&p, sizeof(T) * (count ? count : (size_t)1));
+    if (e == hipSuccess) member = (T *)p;
+    return e;
+}
+
+// The member list: every device array a lattice owns is named here, once, in the group that is released together
+// (persistent tables, chunk arrays, build-time tables).  phl_destroy frees all three.
+template <typename... T>
+inline void phl_lat_free_all(T *&...member) { ((void)phl_lat_free(member), ...); }
+inline void phl_lat_free_persistent(phl_lattice *lat)
+{
+    phl_lat_free_all(lat->vkeys, lat->replay, lat->csr_ptr, lat->csr, lat->nbr, lat->nbr2, lat->table, lat->ft_of_int, lat->int_of_ft,
+                     lat->vfirst);
+}
+inline void phl_tiles_free(phl_lattice *lat)
+{
+    phl_lat_free_all(lat->pix_order, lat->chunk_vptr, lat->slot_vert, lat->slot_pidx, lat->seg_rng, lat->seg, lat->lidx, lat->vs_ptr,
+                     lat->vs, lat->vorder, lat->chunk_by_nv, lat->vlong);
+    free(lat->nv_cum);
+    lat->nv_cum = nullptr;
+    lat->n_long = lat->S = lat->S_multi = 0;
+    lat->nchunks = lat->nv_max = 0;
+}
+inline void phl_release_build_tables(phl_lattice *lat)      // (after a stream synchronisation)
+{
+    phl_lat_free_all(lat->bt_slot_of, lat->bt_table, lat->bt_remap, lat->bt_dup_ptr, lat->bt_cell);
+    lat->bt_seg_e = lat->bt_seg_id = nullptr;      // (not owned: they point into bt_dup_ptr's block)
+}
+
 // host replay of the reference's hash table (phl_reftable.hip)
 struct phl_reftable_query {
     virtual int vid_at(int64_t candidate) = 0;                          // clean vertex id of a candidate
@@ -161,7 +218,6 @@ int phl_apply_reference_table(phl_lattice *lat, hipStream_t st, void *arena, siz
 //  do not depend on the replay run under it)
 // replay[].vid from the build-time tables (see bt_* above), mapped through int_of_ft if there is one; releases nothing
 int phl_write_final_vids(phl_lattice *lat, hipStream_t st);
-void phl_release_build_tables(phl_lattice *lat);          // (after a stream synchronisation)
 // steps 1-2 of phl_tiles_build (grid over the two widest features, pixels in cell-major order), launches only:
 // lat->pix_order, bt_cell, grid_*.  Temporaries out of `arena` (phl_tiles_pixel_order_scratch_bytes(n) device bytes).
 size_t phl_tiles_pixel_order_scratch_bytes(int64_t n);
@@ -198,14 +254,6 @@ int phl_ws_acquire(phl_lattice *lat, hipStream_t st, int64_t buf_elems, int64_t 
                    phl_workspace **out);
 void phl_ws_release(phl_lattice *lat, phl_workspace *ws, hipStream_t st, bool idle);
 
-// thread-local error message
-void phl_set_error(const char *fmt, ...);
-int phl_hip_fail(hipError_t e, const char *what, const char *file, int line);
-#define PHL_HIP(call)                                                              \
-    do {                                                                           \
-        hipError_t e__ = (call);                                                   \
-        if (e__ != hipSuccess) return phl_hip_fail(e__, #call, __FILE__, __LINE__); \
-    } while (0)
 // after a group of launches: rc takes the launch error unless it already holds an earlier one (the first error wins)
 inline void phl_launched(int &rc, const char *what)
 {
@@ -256,6 +304,34 @@ struct phl_temps {
     }
 };
 
+// A device block that is not (or no longer) the lattice's: a new array until the lattice takes it, an old one that queued
+// launches still read, the scratch of a group of launches.  `st` is the stream whose launches use the block.  A success
+// path ends in release(), or in drop() behind the caller's own stream synchronisation, and costs nothing more; the
+// destructor finds a block only on an early error return, and then waits for the stream before the block goes back to
+// the cache (which may hand it to another thread's build at once).  Move-only.
+template <typename T>
+class phl_dev_block {
+    T *p = nullptr;
+    hipStream_t st;
+
+public:
+    explicit phl_dev_block(hipStream_t s) : st(s) {}
+    phl_dev_block(phl_dev_block &&o) : p(o.release()), st(o.st) {}
+    ~phl_dev_block()
+    {
+        if (!p) return;
+        (void)hipStreamSynchronize(st);
+        (void)hipGetLastError();
+        (void)phl_lat_free(p);
+    }
+    // (alloc and adopt: an empty holder only)
+    int alloc(size_t count) { PHL_HIP(phl_lat_alloc(p, count)); return PHL_OK; }
+    void adopt(T *&member) { p = std::exchange(member, nullptr); }     // a block the lattice gives up: the member is nulled
+    T *get() const { return p; }
+    T *release() { return std::exchange(p, nullptr); }                 // the lattice owns the block from here on
+    int drop() { PHL_HIP(phl_lat_free(p)); return PHL_OK; }            // the caller has synchronised `st` behind the block's last user
+};
+
 // Raise kernel K's dynamic-LDS limit on the current device to at least `bytes` (phl_api.hip).  A no-op at or below the
 // default 64 KiB; at most one attribute call per (device, kernel, larger size), never per launch: the call is not a stream
 // operation, and a launch may sit inside a stream capture.
@@ -299,15 +375,11 @@ inline unsigned phl_xcd_grid(int64_t blocks, int *xcd_chunk)
 inline bool phl_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool phl_rows16(const void *p, int64_t rs) { return rs % 4 == 0 && phl_al16(p); }
 
-// cached device blocks for the arrays a lattice owns (phl_api.hip)
-hipError_t phl_dev_malloc(void **p, size_t bytes);
-hipError_t phl_dev_free(void *p);
-
 // cached device scratch for build temporaries (phl_api.hip); one user at a time per process
 bool phl_scratch_acquire(void **base, size_t *cap);
 void phl_scratch_release(size_t wanted_bytes);
 
-int phl_lattice_blank(phl_lattice **out, int device, int d, int64_t n);      // phl_api.hip (extern "C" there)
+phl_lattice *phl_lattice_blank(int device, int d, int64_t n, unsigned build_flags);   // the one initial state (phl_api.hip)
 
 // ---- launchers implemented in phl_build.hip ----
 int phl_build_device(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, hipStream_t st);
@@ -315,7 +387,7 @@ int phl_ensure_csr(phl_lattice *lat, hipStream_t st);  // pixel-sorted lists, bu
 namespace std { class mutex; }
 std::mutex *phl_csr_mutex(phl_lattice *lat);
 int phl_add_vertices_device(phl_lattice *lat, const int16_t *keys_host, int64_t count, int32_t *vid_host, hipStream_t st);
-int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, void **scratch_out);
+int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, phl_dev_block<uint32_t> &scratch);
 
 // ---- side streams for launches that are independent of their neighbours in a call (phl_api.hip) ----
 // A forked chain: work enqueued on stream() starts behind everything enqueued on `st` before fork(st), runs beside what
@@ -341,7 +413,6 @@ public:
 // ---- the chunk build, implemented in phl_tiles_build.hip (once per lattice) ----
 int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, hipStream_t st);   // + renumbering, tables
 int phl_tiles_link_vertices(phl_lattice *lat, hipStream_t st);
-int phl_tiles_free(phl_lattice *lat);
 // a vertex fed by more chunks than this is listed in lat->vlong by the build and summed by k_splat_reduce_long
 constexpr int LONG_LIST = 24;
 

@@ -1386,28 +1386,16 @@ int phl_apply_reference_table(phl_lattice *lat, hipStream_t st, void *arena, siz
         std::copy(dv_id.begin(), dv_id.end(), pack.begin() + (ptrdiff_t)o_dvid);
         std::copy(dv_e.begin(), dv_e.end(), pack.begin() + (ptrdiff_t)o_dve);
         // (kept until the candidates' vertex ids are written: lat->bt_*, k_final_vid)
-        PHL_HIP(phl_dev_malloc((void **)&lat->bt_remap, sizeof(int) * (size_t)M));
-        PHL_HIP(phl_dev_malloc((void **)&lat->bt_dup_ptr, sizeof(int) * total));
+        PHL_HIP(phl_lat_alloc(lat->bt_remap, (size_t)M));
+        PHL_HIP(phl_lat_alloc(lat->bt_dup_ptr, total));
         lat->bt_seg_e = lat->bt_dup_ptr + o_se;
         lat->bt_seg_id = lat->bt_dup_ptr + o_si;
         remap_dev = lat->bt_remap;
         int *const blk = lat->bt_dup_ptr;
-        // The guard: on ANY early return it synchronises the stream first (the copies of the host vectors above may still
-        // be queued; it is destroyed before them) and releases what the lattice does not own yet.
-        struct apply_guard {
-            hipStream_t st;
-            int16_t *vkeys_new = nullptr;
-            int *vfirst_clean = nullptr;
-            bool done = false;
-            ~apply_guard()
-            {
-                if (done) return;
-                (void)hipStreamSynchronize(st);
-                (void)hipGetLastError();
-                if (vkeys_new) (void)phl_dev_free(vkeys_new);
-                if (vfirst_clean) (void)phl_dev_free(vfirst_clean);
-            }
-        } guard{st};
+        // The holders: on ANY early return they wait for the stream first (the copies of the host vectors above may still
+        // be queued; they are destroyed before them) and give back what the lattice does not own.
+        phl_dev_block<int16_t> vkeys_new(st);
+        phl_dev_block<int32_t> vfirst_clean(st);
         PHL_HIP(hipMemcpyAsync(blk, pack.data(), sizeof(int32_t) * total, hipMemcpyHostToDevice, st));
         if (R.compact) {
             hipLaunchKernelGGL(k_ref_remap, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (int)M, ex, remap_dev);
@@ -1417,27 +1405,23 @@ int phl_apply_reference_table(phl_lattice *lat, hipStream_t st, void *arena, siz
         } else {
             PHL_HIP(hipMemcpyAsync(remap_dev, R.remap.data(), sizeof(int) * (size_t)M, hipMemcpyHostToDevice, st));
         }
-        int16_t *vkeys_new;
-        PHL_HIP(phl_dev_malloc((void **)&vkeys_new, sizeof(int16_t) * (size_t)R.M_ref * d));
-        guard.vkeys_new = vkeys_new;
+        PHL_TRY(vkeys_new.alloc((size_t)R.M_ref * d));
         if (R.compact)
-            hipLaunchKernelGGL(k_ref_keys, dim3((unsigned)((R.M_ref + 255) / 256)), dim3(256), 0, st, lat->vkeys, d, (int)R.M_ref, ex, vkeys_new);
+            hipLaunchKernelGGL(k_ref_keys, dim3((unsigned)((R.M_ref + 255) / 256)), dim3(256), 0, st, lat->vkeys, d, (int)R.M_ref, ex,
+                               vkeys_new.get());
         else
-            PHL_HIP(hipMemcpyAsync(vkeys_new, R.keys.data(), sizeof(int16_t) * (size_t)R.M_ref * d, hipMemcpyHostToDevice, st));
-        int *vfirst_clean = lat->vfirst;              // (= efirst_dev: read by the launch below, released behind the sync)
-        lat->vfirst = nullptr;
-        guard.vfirst_clean = vfirst_clean;
-        PHL_HIP(phl_dev_malloc((void **)&lat->vfirst, sizeof(int) * (size_t)R.M_ref));
+            PHL_HIP(hipMemcpyAsync(vkeys_new.get(), R.keys.data(), sizeof(int16_t) * (size_t)R.M_ref * d, hipMemcpyHostToDevice, st));
+        vfirst_clean.adopt(lat->vfirst);              // (= efirst_dev: read by the launch below, dropped behind the sync)
+        PHL_HIP(phl_lat_alloc(lat->vfirst, (size_t)R.M_ref));
         PHL_HIP(hipMemsetAsync(lat->vfirst, 0, sizeof(int) * (size_t)R.M_ref, st));
         hipLaunchKernelGGL(k_vfirst_ref, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, remap_dev, efirst_dev, (int)M, lat->vfirst);
         if (n_dv)
             hipLaunchKernelGGL(k_set_pairs, dim3((unsigned)((n_dv + 63) / 64)), dim3(64), 0, st, blk + o_dvid, blk + o_dve, (int)n_dv, lat->vfirst);
         PHL_HIP(hipGetLastError());
         PHL_HIP(hipStreamSynchronize(st));            // host vectors and pool temporaries die on return
-        guard.done = true;                            // from here on the lattice owns vkeys_new; vfirst_clean goes now
-        (void)phl_dev_free(vfirst_clean);
-        (void)phl_dev_free(lat->vkeys);
-        lat->vkeys = vkeys_new;
+        (void)vfirst_clean.drop();
+        (void)phl_lat_free(lat->vkeys);
+        lat->vkeys = vkeys_new.release();             // from here on the lattice owns it
         lat->M = R.M_ref;
         lat->vfirst_valid_for_M = R.M_ref;
     }
@@ -1574,7 +1558,7 @@ extern "C" int phl_debug_probe_paths(const int16_t *keys_clean, int64_t n_clean,
         *result_out = q.probe_paths_do_not_wrap(n_clean, ex, sc, cap, ck);
         return PHL_OK;
     }
-    temp_pool tmp;
+    temp_pool tmp(nullptr);                           // (everything below runs on the null stream)
     device_query q;
     int16_t *kd;
     PHL_HIP(tmp.get(&kd, (size_t)n_clean * d + 1));

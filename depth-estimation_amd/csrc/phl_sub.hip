@@ -76,7 +76,7 @@ int phl_vertices_of_pixels(phl_lattice *lat, int64_t p0, int64_t p1, unsigned ch
     if (M == 0) return PHL_OK;
     device_sel g(lat->device);
     hipStream_t st = (hipStream_t)stream;
-    temp_pool tmp;
+    temp_pool tmp(st);
     unsigned char *mask;
     PHL_HIP(tmp.get(&mask, (size_t)M));
     PHL_HIP(hipMemsetAsync(mask, 0, (size_t)M, st));
@@ -122,13 +122,10 @@ int phl_sub_lattice(phl_lattice **out, phl_lattice *g, int64_t p0, int64_t p1, c
     const int64_t n = p1 - p0, N = n * dp1;
     const int K = (int)n_sel;
 
-    phl_lattice *lat = nullptr;
-    int rc = phl_lattice_blank(&lat, g->device, d, n);
-    if (rc) return rc;
+    phl_lattice *lat = phl_lattice_blank(g->device, d, n, g->build_flags);
     lat->N = N;
     lat->M = K;
     lat->M_local = n_own;
-    lat->build_flags = g->build_flags;
     auto fail = [&](int code) {
         (void)hipStreamSynchronize(st);
         phl_destroy(lat);
@@ -140,7 +137,7 @@ int phl_sub_lattice(phl_lattice **out, phl_lattice *g, int64_t p0, int64_t p1, c
         if (e__ != hipSuccess) return fail(phl_hip_fail(e__, #call, __FILE__, __LINE__)); \
     } while (0)
     {
-        temp_pool tmp;
+        temp_pool tmp(st);
         int *sel_dev, *g2l, *err;
         SUB_HIP(tmp.get(&sel_dev, (size_t)K + 1));
         SUB_HIP(tmp.get(&g2l, (size_t)g->M + 1));
@@ -148,8 +145,8 @@ int phl_sub_lattice(phl_lattice **out, phl_lattice *g, int64_t p0, int64_t p1, c
         SUB_HIP(hipMemsetAsync(err, 0, sizeof(int), st));
         SUB_HIP(hipMemsetAsync(g2l, 0xFF, sizeof(int) * (size_t)g->M, st));       // -1
         SUB_HIP(hipMemcpyAsync(sel_dev, sel_host, sizeof(int) * (size_t)K, hipMemcpyHostToDevice, st));
-        SUB_HIP(phl_dev_malloc((void **)&lat->vkeys, sizeof(int16_t) * (size_t)(K ? K : 1) * d));
-        SUB_HIP(phl_dev_malloc((void **)&lat->replay, sizeof(phl_replay_t) * (size_t)N));
+        SUB_HIP(phl_lat_alloc(lat->vkeys, (size_t)K * d));
+        SUB_HIP(phl_lat_alloc(lat->replay, (size_t)N));
         if (K > 0)
             hipLaunchKernelGGL(k_sub_select, dim3((K + 255) / 256), dim3(256), 0, st, sel_dev, K, g->int_of_ft, g->vkeys, d, g2l, lat->vkeys);
         hipLaunchKernelGGL(k_sub_replay, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g->replay, p0 * dp1, (int)N, g2l, (int)n_own,
@@ -173,7 +170,7 @@ int phl_sub_lattice(phl_lattice **out, phl_lattice *g, int64_t p0, int64_t p1, c
                 if (lat->n_hidden < PHL_MAX_HIDDEN) lat->hidden[lat->n_hidden++] = (int32_t)i;
                 break;
             }
-    rc = phl_tiles_build(lat, ref_dev, rs, cs, st);
+    const int rc = phl_tiles_build(lat, ref_dev, rs, cs, st);
     if (rc) return fail(rc);
     *out = lat;
     return PHL_OK;

@@ -24,7 +24,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include <memory>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -1168,10 +1167,7 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
     int rc = PHL_OK;
     const int nrun = o.subset ? o.nlist : lat->nchunks;
     static const char *tl_path = getenv("PHL_TIMELINE");     // debug: dump per-workgroup time stamps of the main launch
-    struct dev_free {
-        void operator()(void *p) const { (void)phl_dev_free(p); }
-    };
-    std::unique_ptr<unsigned long long, dev_free> tl;       // (every exit frees it)
+    phl_dev_block<unsigned long long> tl(st);               // (an early exit waits for the stream, then frees it)
     size_t tl_n = 0;
     // the small classes go first, on a forked high-priority stream, and run beside the main grid (see phl_fork_guard);
     // any early return below drains that stream and gives the slot back (the guard's destructor)
@@ -1198,10 +1194,10 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
         int xcd_chunk;
         const unsigned cgrid = phl_xcd_grid(cnt, &xcd_chunk);
         unsigned long long *tlc = nullptr;
-        if (tl_path && c.full_grid && !tl) {
+        if (tl_path && c.full_grid && !tl.get()) {
             tl_n = (size_t)cgrid * 8;
-            PHL_HIP(phl_dev_malloc((void **)&tlc, tl_n * 8));
-            tl.reset(tlc);
+            PHL_TRY(tl.alloc(tl_n));
+            tlc = tl.get();
             PHL_HIP(hipMemsetAsync(tlc, 0, tl_n * 8, st));
         }
         const char *env1 = getenv("PHL_WIDE_ONE_PHASE");            // read per call: the parity test toggles it
@@ -1233,11 +1229,11 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
         const hipError_t e = fk.join(st);                     // the reduction below needs every class's sums
         if (e != hipSuccess) return phl_hip_fail(e, "joining the side stream of the chunk classes", __FILE__, __LINE__);
     }
-    if (tl) {                                                 // debug only
+    if (tl.get()) {                                           // debug only
         std::vector<unsigned long long> h(tl_n);
         PHL_HIP(hipMemcpyAsync(h.data(), tl.get(), tl_n * 8, hipMemcpyDeviceToHost, st));
         PHL_HIP(hipStreamSynchronize(st));
-        tl.reset();
+        PHL_TRY(tl.drop());
         if (FILE *f = fopen(tl_path, "wb")) {
             fwrite(h.data(), 8, tl_n, f);
             fclose(f);

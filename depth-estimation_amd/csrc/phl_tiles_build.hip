@@ -624,28 +624,6 @@ __global__ __launch_bounds__(256) void k_strip_marks(int *slot_vert, int S)
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-int phl_tiles_free(phl_lattice *lat)
-{
-    void *ptrs[] = {lat->pix_order, lat->chunk_vptr, lat->slot_vert, lat->slot_pidx, lat->seg_rng, lat->seg,
-                    lat->lidx, lat->vs_ptr, lat->vs, lat->vorder, lat->chunk_by_nv, lat->vlong};
-    for (void *p : ptrs)
-        if (p) (void)phl_dev_free(p);
-    free(lat->nv_cum);
-    lat->nv_cum = nullptr;
-    lat->chunk_by_nv = nullptr;
-    lat->vlong = nullptr;
-    lat->n_long = 0;
-    lat->pix_order = lat->chunk_vptr = lat->slot_vert = lat->slot_pidx = lat->vs_ptr = nullptr;
-    lat->seg_rng = nullptr;
-    lat->vorder = nullptr;
-    lat->seg = lat->vs = nullptr;
-    lat->lidx = nullptr;
-    lat->nchunks = 0;
-    lat->S = lat->S_multi = 0;
-    lat->nv_max = 0;
-    return PHL_OK;
-}
-
 // vertex -> slots lists (ascending slot = ascending chunk), sole marks and partial-row indices.
 // Also called after ghost vertices were appended (M grew, the slots did not change).
 // Vertex processing order of the gather splat (exact arithmetic, shapes the chunk kernels do not take): made on first
@@ -655,24 +633,23 @@ int phl_tiles_ensure_vorder(phl_lattice *lat, hipStream_t st)
     if (lat->vorder || !lat->vs_ptr || !lat->vs || !lat->slot_vert) return PHL_OK;
     const int M = (int)lat->M, S = (int)lat->S;
     if (M == 0 || S == 0) return PHL_OK;
-    temp_pool tmp;
+    phl_dev_block<int32_t> vorder(st);      // (the lattice's only once it is filled)
+    temp_pool tmp(st);
     int *first, *frank, *tile_sums;
     PHL_HIP(tmp.get(&first, (size_t)S + 1));
     PHL_HIP(tmp.get(&frank, (size_t)S + 2));
     PHL_HIP(tmp.get(&tile_sums, (size_t)S / SCAN_TILE + 2));
-    int *vorder = nullptr;
-    PHL_HIP(phl_dev_malloc((void **)&vorder, sizeof(int) * ((size_t)M + 1)));
+    PHL_TRY(vorder.alloc((size_t)M + 1));
     const unsigned gS = (unsigned)((S + 255) / 256);
     hipLaunchKernelGGL(k_first_slot, dim3(gS), dim3(256), 0, st, lat->slot_vert, S, lat->vs_ptr, lat->vs, first);
     PHL_HIP(hipGetLastError());
-    const int rc = exclusive_scan(first, frank, S, tile_sums, st);
-    if (rc) return rc;
+    PHL_TRY(exclusive_scan(first, frank, S, tile_sums, st));
     const int span = S > M ? S : M;
     hipLaunchKernelGGL(k_fill_vorder, dim3((span + 255) / 256), dim3(256), 0, st, lat->slot_vert, S, first, frank,
-                       (int)lat->M_local, M, vorder);
+                       (int)lat->M_local, M, vorder.get());
     PHL_HIP(hipGetLastError());
     PHL_HIP(hipStreamSynchronize(st));      // temporaries go back to the scratch cache
-    lat->vorder = vorder;
+    lat->vorder = vorder.release();
     return PHL_OK;
 }
 
@@ -680,22 +657,16 @@ int phl_tiles_link_vertices(phl_lattice *lat, hipStream_t st)
 {
     const int M = (int)lat->M, S = (int)lat->S;
     phl_pinned_reset();                       // (callers have synchronised the stream: nothing of the arena is in flight)
-    if (lat->vs_ptr) PHL_HIP(phl_dev_free(lat->vs_ptr));
-    if (lat->vs) PHL_HIP(phl_dev_free(lat->vs));
-    if (lat->slot_pidx) PHL_HIP(phl_dev_free(lat->slot_pidx));
-    lat->vs_ptr = nullptr;
-    lat->vs = nullptr;
-    lat->slot_pidx = nullptr;
     lat->S_multi = 0;
-    PHL_HIP(phl_dev_malloc((void **)&lat->vs_ptr, sizeof(int) * ((size_t)M + 1)));
-    PHL_HIP(phl_dev_malloc((void **)&lat->vs, sizeof(phl_contrib_t) * ((size_t)S + 1)));
-    PHL_HIP(phl_dev_malloc((void **)&lat->slot_pidx, sizeof(int) * ((size_t)S + 1)));
+    PHL_HIP(phl_lat_alloc(lat->vs_ptr, (size_t)M + 1));
+    PHL_HIP(phl_lat_alloc(lat->vs, (size_t)S + 1));
+    PHL_HIP(phl_lat_alloc(lat->slot_pidx, (size_t)S + 1));
     if (S == 0) {
         PHL_HIP(hipMemsetAsync(lat->vs_ptr, 0, sizeof(int) * ((size_t)M + 1), st));
         PHL_HIP(hipStreamSynchronize(st));
         return PHL_OK;
     }
-    temp_pool tmp;
+    temp_pool tmp(st);
     int *cnt, *multi, *tile_sums, *sperm;
     PHL_HIP(tmp.get(&cnt, (size_t)M + 1));
     PHL_HIP(tmp.get(&multi, (size_t)S + 1));
@@ -706,16 +677,13 @@ int phl_tiles_link_vertices(phl_lattice *lat, hipStream_t st)
     hipLaunchKernelGGL(k_strip_marks, dim3(gS), dim3(256), 0, st, lat->slot_vert, S);
     hipLaunchKernelGGL(k_count_slots, dim3(gS), dim3(256), 0, st, lat->slot_vert, S, cnt);
     PHL_HIP(hipGetLastError());
-    int rc = exclusive_scan(cnt, lat->vs_ptr, M, tile_sums, st);
-    if (rc) return rc;
+    PHL_TRY(exclusive_scan(cnt, lat->vs_ptr, M, tile_sums, st));
     // slots grouped by vertex, ascending slot (= ascending chunk) inside a vertex: a stable sort by vertex id (the
     // marks are stripped: slot_vert itself is the key array)
-    rc = stable_sort_perm(lat->slot_vert, S, M, sperm, tmp, st);
-    if (rc) return rc;
+    PHL_TRY(stable_sort_perm(lat->slot_vert, S, M, sperm, tmp, st));
     hipLaunchKernelGGL(k_contrib_and_sole, dim3(gS), dim3(256), 0, st, sperm, lat->slot_vert, S, lat->vs_ptr, lat->vs, multi);
     PHL_HIP(hipGetLastError());
-    rc = exclusive_scan(multi, lat->slot_pidx, S, tile_sums, st);
-    if (rc) return rc;
+    PHL_TRY(exclusive_scan(multi, lat->slot_pidx, S, tile_sums, st));
     hipLaunchKernelGGL(k_fill_vs_rows, dim3(gS), dim3(256), 0, st, lat->vs, S, lat->slot_pidx);
     PHL_HIP(hipGetLastError());
     int pageable_counts[2] = {0, 0};
@@ -724,21 +692,18 @@ int phl_tiles_link_vertices(phl_lattice *lat, hipStream_t st)
     PHL_HIP(hipMemcpyAsync(&counts[0], lat->slot_pidx + S, sizeof(int), hipMemcpyDeviceToHost, st));
     // vertices with long slot lists (k_splat_reduce_long)
     int n_long = 0;
-    if (lat->vlong) PHL_HIP(phl_dev_free(lat->vlong));
-    lat->vlong = nullptr;
     lat->n_long = 0;
     {
         int *lcount;
         PHL_HIP(tmp.get(&lcount, 1));
         PHL_HIP(hipMemsetAsync(lcount, 0, sizeof(int), st));
-        PHL_HIP(phl_dev_malloc((void **)&lat->vlong, sizeof(int) * ((size_t)M + 1)));      // worst case; usually almost empty
+        PHL_HIP(phl_lat_alloc(lat->vlong, (size_t)M + 1));      // worst case; usually almost empty
         hipLaunchKernelGGL(k_append_long, dim3((M + 255) / 256), dim3(256), 0, st, lat->vs_ptr, M, LONG_LIST, lat->vlong, lcount);
         PHL_HIP(hipGetLastError());
         PHL_HIP(hipMemcpyAsync(&counts[1], lcount, sizeof(int), hipMemcpyDeviceToHost, st));
     }
     // (the chunk-major vertex order of the gather splat is made on first use: phl_tiles_ensure_vorder)
-    if (lat->vorder) PHL_HIP(phl_dev_free(lat->vorder));
-    lat->vorder = nullptr;
+    PHL_HIP(phl_lat_free(lat->vorder));
     PHL_HIP(hipStreamSynchronize(st));
     const int s_multi = counts[0];
     n_long = counts[1];
@@ -755,8 +720,7 @@ int phl_tiles_link_vertices(phl_lattice *lat, hipStream_t st)
         const int kmax = lat->nchunks + 1;
         hipLaunchKernelGGL(k_long_keys, dim3(gl), dim3(256), 0, st, lat->vlong, n_long, lat->vs_ptr, kmax, lkey);
         PHL_HIP(hipGetLastError());
-        rc = stable_sort_perm(lkey, n_long, (int64_t)kmax + 1, lperm, tmp, st);
-        if (rc) return rc;
+        PHL_TRY(stable_sort_perm(lkey, n_long, (int64_t)kmax + 1, lperm, tmp, st));
         hipLaunchKernelGGL(k_gather_i32, dim3(gl), dim3(256), 0, st, lat->vlong, lperm, n_long, lsorted);
         PHL_HIP(hipGetLastError());
         PHL_HIP(hipMemcpyAsync(lat->vlong, lsorted, sizeof(int) * (size_t)n_long, hipMemcpyDeviceToDevice, st));
@@ -816,7 +780,7 @@ int pixel_order(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, int 
     hipLaunchKernelGGL(k_cell_ids, dim3(gn), dim3(256), 0, st, ref, rs, cs, (int64_t)n, da, db, lo[da],
                        db >= 0 ? lo[db] : 0.f, inv_t, nca, ncb, cell);
     PHL_HIP(hipGetLastError());
-    PHL_HIP(phl_dev_malloc((void **)&lat->pix_order, sizeof(int) * (size_t)n));
+    PHL_HIP(phl_lat_alloc(lat->pix_order, (size_t)n));
     *nca_out = nca;
     *ncb_out = ncb;
     return stable_sort_perm(cell, n, ncell, lat->pix_order, tmp, st);
@@ -835,15 +799,14 @@ int phl_tiles_pixel_order(phl_lattice *lat, const float *ref, int64_t rs, int64_
     const int n = (int)lat->n;
     if (n == 0 || !lat->feat_range_valid || lat->pix_order || lat->bt_cell) return PHL_OK;     // (phl_tiles_build does it)
     arena_pool tmp(arena, arena_bytes);
-    PHL_HIP(phl_dev_malloc((void **)&lat->bt_cell, sizeof(int) * (size_t)n));
+    PHL_HIP(phl_lat_alloc(lat->bt_cell, (size_t)n));
     return pixel_order(lat, ref, rs, cs, tile_pixels(lat->d + 1), lat->feat_lo, lat->feat_hi, lat->bt_cell, &lat->grid_nca,
                        &lat->grid_ncb, tmp, st);
 }
 
 int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, hipStream_t st)
 {
-    int *pix_ready = lat->bt_cell ? lat->pix_order : nullptr;        // made ahead (phl_tiles_pixel_order): keep it
-    if (pix_ready) lat->pix_order = nullptr;
+    int *const pix_ready = lat->bt_cell ? std::exchange(lat->pix_order, nullptr) : nullptr;   // made ahead (phl_tiles_pixel_order): keep it
     phl_tiles_free(lat);
     lat->pix_order = pix_ready;
     const int d = lat->d, dp1 = d + 1;
@@ -851,11 +814,9 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
     const int P = tile_pixels(dp1);
     lat->P = P;
     if (n == 0) {
-        void *scratch = nullptr;
-        const int rc0 = phl_rebuild_table_and_neighbors(lat, st, &scratch);
-        const int rc1 = rc0 ? rc0 : phl_tiles_link_vertices(lat, st);      // (synchronises the stream)
-        if (scratch) { (void)hipStreamSynchronize(st); (void)phl_dev_free(scratch); }
-        return rc1;
+        phl_dev_block<uint32_t> scratch(st);        // (stays empty: no vertices, no packed keys)
+        PHL_TRY(phl_rebuild_table_and_neighbors(lat, st, scratch));
+        return phl_tiles_link_vertices(lat, st);   // (synchronises the stream)
     }
     int sortn = 512;
     while (sortn < P * dp1) sortn <<= 1;
@@ -864,15 +825,14 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
     int nchunks = 0;
     int64_t S = 0;
     const int64_t N = lat->N;
-    // arrays replaced while launches that read them may still be in flight: released only behind the stream
+    // arrays replaced while launches that read them may still be in flight: dropped only behind the stream
     // synchronisation at the end of this phase (the block cache may hand a freed block to another thread's build)
-    struct deferred_t {
-        void *p[3] = {nullptr, nullptr, nullptr};
-        ~deferred_t() { for (void *q : p) if (q) (void)phl_dev_free(q); }
-    } deferred;
-    phl_fork_guard nbr_chain;                        // (declared behind `deferred`: drained before those blocks are released)
+    phl_dev_block<int16_t> vkeys_old(st);
+    phl_dev_block<int32_t> vfirst_old(st);
+    phl_dev_block<uint32_t> nbr_scratch(st);
+    phl_fork_guard nbr_chain;                        // (declared behind the holders: its stream is drained before they wait for `st`)
     {   // temporaries of the chunk build go back to the scratch cache before the vertex lists are linked
-    temp_pool tmp;
+    temp_pool tmp(st);
     // 1.-2. the pixel order (pixel_order above), unless it has been made under the table replay already
     int nca = 1, ncb = 1;
     int *cell, *tile_sums;
@@ -901,8 +861,7 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
                 }
         }
         PHL_HIP(tmp.get(&cell, (size_t)n));
-        rc = pixel_order(lat, ref, rs, cs, P, lo.data(), hi.data(), cell, &nca, &ncb, tmp, st);
-        if (rc) return rc;
+        PHL_TRY(pixel_order(lat, ref, rs, cs, P, lo.data(), hi.data(), cell, &nca, &ncb, tmp, st));
     }
     const int ncell = nca * ncb;
 
@@ -936,41 +895,36 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
             const int stripw = (nca + nstrips - 1) / nstrips;
             hipLaunchKernelGGL(k_strip_key, dim3((M + 255) / 256), dim3(256), 0, st, vhome, M, nca, ncb, stripw, vkey);
             PHL_HIP(hipGetLastError());
-            PHL_HIP(phl_dev_malloc((void **)&lat->ft_of_int, sizeof(int) * (size_t)M_all));
-            PHL_HIP(phl_dev_malloc((void **)&lat->int_of_ft, sizeof(int) * (size_t)M_all));
-            rc = stable_sort_perm(vkey, M, (int64_t)(nstrips + 1) * ncb * stripw, lat->ft_of_int, tmp, st);
-            if (rc) return rc;
+            PHL_HIP(phl_lat_alloc(lat->ft_of_int, (size_t)M_all));
+            PHL_HIP(phl_lat_alloc(lat->int_of_ft, (size_t)M_all));
+            PHL_TRY(stable_sort_perm(vkey, M, (int64_t)(nstrips + 1) * ncb * stripw, lat->ft_of_int, tmp, st));
             if (M_all > M)        // ghosts: identity
                 hipLaunchKernelGGL(k_iota_tail, dim3((M_all - M + 255) / 256), dim3(256), 0, st, lat->ft_of_int, M, M_all);
             hipLaunchKernelGGL(k_invert_perm, dim3((M_all + 255) / 256), dim3(256), 0, st, lat->ft_of_int, M_all, lat->int_of_ft);
-            int16_t *vkeys_new;
-            PHL_HIP(phl_dev_malloc((void **)&vkeys_new, sizeof(int16_t) * (size_t)M_all * d));
+            phl_dev_block<int16_t> vkeys_new(st);
+            PHL_TRY(vkeys_new.alloc((size_t)M_all * d));
             hipLaunchKernelGGL(k_permute_keys, dim3((unsigned)(((int64_t)M_all * d + 255) / 256)), dim3(256), 0, st, lat->vkeys,
-                               lat->ft_of_int, M_all, d, vkeys_new);
+                               lat->ft_of_int, M_all, d, vkeys_new.get());
             if (from_tables) {
-                rc = phl_write_final_vids(lat, st);
-                if (rc) return rc;
+                PHL_TRY(phl_write_final_vids(lat, st));
                 wrote_vids = true;
             } else {
                 hipLaunchKernelGGL(k_relabel_replay, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, lat->replay, (int)N,
                                    lat->int_of_ft);
             }
             PHL_HIP(hipGetLastError());
-            deferred.p[0] = lat->vkeys;              // still being read by the gather above
-            lat->vkeys = vkeys_new;
+            vkeys_old.adopt(lat->vkeys);             // still being read by the gather above
+            lat->vkeys = vkeys_new.release();
         }
         if (from_tables && !wrote_vids) {            // no locality numbering: first-touch (reference) ids as they are
-            rc = phl_write_final_vids(lat, st);
-            if (rc) return rc;
+            PHL_TRY(phl_write_final_vids(lat, st));
         }
-        deferred.p[1] = lat->vfirst;                 // build-time only
-        lat->vfirst = nullptr;
+        vfirst_old.adopt(lat->vfirst);               // build-time only
         // key -> vertex table, packed keys, blur neighbours, composed pairs: ~100 us of small dependent launches that
         // nothing in the chunk build below depends on -- on a forked stream beside it, joined before this phase ends
         static const bool side_nbr = !(getenv("PHL_SIDE_NEIGHBORS") && atoi(getenv("PHL_SIDE_NEIGHBORS")) == 0);
         if (side_nbr) nbr_chain.fork(st);
-        rc = phl_rebuild_table_and_neighbors(lat, nbr_chain ? nbr_chain.stream() : st, &deferred.p[2]);
-        if (rc) return rc;
+        PHL_TRY(phl_rebuild_table_and_neighbors(lat, nbr_chain ? nbr_chain.stream() : st, nbr_scratch));
     }
 
     // 3. per-chunk local vertex lists, segments and local indices
@@ -978,7 +932,7 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
     lat->nchunks = nchunks;
     int *nv;
     PHL_HIP(tmp.get(&nv, (size_t)nchunks + 1));
-    PHL_HIP(phl_dev_malloc((void **)&lat->chunk_vptr, sizeof(int) * ((size_t)nchunks + 1)));
+    PHL_HIP(phl_lat_alloc(lat->chunk_vptr, (size_t)nchunks + 1));
 #define PHL_CHUNK_MASKS_X(HTX_, ...)                                                                                    \
     switch (sortn) {                                                                                                     \
         case 512: hipLaunchKernelGGL((k_chunk_masks<512, HTX_>), dim3(nchunks), dim3(256), 0, st, __VA_ARGS__); break;    \
@@ -1002,8 +956,8 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
     int2 *t_rng;
     PHL_HIP(tmp.get(&t_vert, (size_t)nchunks * SLOT_STRIDE));
     PHL_HIP(tmp.get(&t_rng, (size_t)nchunks * SLOT_STRIDE));
-    PHL_HIP(phl_dev_malloc((void **)&lat->seg, sizeof(phl_contrib_t) * (size_t)N));
-    PHL_HIP(phl_dev_malloc((void **)&lat->lidx, sizeof(unsigned short) * (size_t)N));
+    PHL_HIP(phl_lat_alloc(lat->seg, (size_t)N));
+    PHL_HIP(phl_lat_alloc(lat->lidx, (size_t)N));
     // k_chunk_masks does every chunk with at most NVC local vertices; heavier ones only report their count here and
     // are done by k_chunk_group below, once the counts are on the host
     static const bool use_masks = !(getenv("PHL_CHUNK_MASKS") && atoi(getenv("PHL_CHUNK_MASKS")) == 0);
@@ -1015,8 +969,7 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
                        lat->seg, lat->lidx, (const int *)nullptr, 0)
     }
     PHL_HIP(hipGetLastError());
-    rc = exclusive_scan(nv, lat->chunk_vptr, nchunks, tile_sums, st);
-    if (rc) return rc;
+    PHL_TRY(exclusive_scan(nv, lat->chunk_vptr, nchunks, tile_sums, st));
     // (pinned staging where there is some: a copy into pageable memory would block the host twice)
     std::vector<int> nv_pageable, by_nv_pageable;
     int *nv_host = (int *)phl_pinned_alloc(sizeof(int) * (size_t)nchunks);
@@ -1043,11 +996,11 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
         for (int b = 0; b <= nv_max; b++) start[(size_t)b + 1] += start[(size_t)b];
         for (int x = 0; x <= nv_max; x++) lat->nv_cum[x] = nchunks - start[(size_t)(nv_max - x)];   // #chunks with nv <= x
         for (int c = 0; c < nchunks; c++) by_nv[start[(size_t)(nv_max - nv_host[c])]++] = c;
-        PHL_HIP(phl_dev_malloc((void **)&lat->chunk_by_nv, sizeof(int) * ((size_t)nchunks + 1)));
+        PHL_HIP(phl_lat_alloc(lat->chunk_by_nv, (size_t)nchunks + 1));
         PHL_HIP(hipMemcpyAsync(lat->chunk_by_nv, by_nv, sizeof(int) * (size_t)nchunks, hipMemcpyHostToDevice, st));
     }
-    PHL_HIP(phl_dev_malloc((void **)&lat->slot_vert, sizeof(int) * ((size_t)S + 1)));
-    PHL_HIP(phl_dev_malloc((void **)&lat->seg_rng, sizeof(int2) * ((size_t)S + 1)));
+    PHL_HIP(phl_lat_alloc(lat->slot_vert, (size_t)S + 1));
+    PHL_HIP(phl_lat_alloc(lat->seg_rng, (size_t)S + 1));
     if (nv_max <= SLOT_STRIDE) {
         if (use_masks && nv_max > NVC) {     // the chunks k_chunk_masks left out (first-pass form: slot records to the scratch)
             PHL_CHUNK_SORT(true, lat->pix_order, n, P, dp1, lat->replay, (int *)nullptr, (const int *)nullptr, SLOT_STRIDE, t_vert,
@@ -1076,8 +1029,10 @@ int phl_tiles_build(phl_lattice *lat, const float *ref, int64_t rs, int64_t cs, 
     PHL_HIP(hipStreamSynchronize(st));
     }
     phl_release_build_tables(lat);                 // (read by k_final_vid: behind the synchronisation)
-    rc = phl_tiles_link_vertices(lat, st);
-    if (rc) return rc;
+    PHL_TRY(phl_tiles_link_vertices(lat, st));
+    PHL_TRY(vkeys_old.drop());                     // (the stream has been synchronised since their last readers)
+    PHL_TRY(vfirst_old.drop());
+    PHL_TRY(nbr_scratch.drop());
     lat->table_bytes = (int64_t)(sizeof(int16_t) * (size_t)lat->M * d + sizeof(phl_replay_t) * (size_t)N +
                                  sizeof(int32_t) * (size_t)lat->M * (d + 1) * 2 + sizeof(int32_t) * (size_t)lat->M * ((d + 1) / 2) * 8 +
                                  sizeof(int) * ((size_t)lat->table_mask + 1) + (lat->int_of_ft ? 2 * sizeof(int) * (size_t)lat->M : 0));
@@ -1110,7 +1065,7 @@ int phl_tiles_chunks_touching(phl_lattice *lat, const int64_t *rows_dev, int64_t
 {
     const int nchunks = lat->nchunks;
     if (nchunks == 0) return PHL_OK;
-    temp_pool tmp;
+    temp_pool tmp(st);
     int *mask;
     PHL_HIP(tmp.get(&mask, (size_t)nchunks));
     PHL_HIP(hipMemsetAsync(mask, 0, sizeof(int) * (size_t)nchunks, st));

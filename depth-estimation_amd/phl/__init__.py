@@ -126,6 +126,7 @@ _ABI = (
     ("phl_debug_probe_paths", "i", "PqiPiPiQPiiP"),
     ("phl_debug_slow_copy", "i", "PPqiiS"),
     ("phl_debug_side_streams", "i", ""),
+    ("phl_debug_live_blocks", "q", ""),
 )
 
 

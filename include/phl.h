@@ -619,6 +619,9 @@ int phl_debug_slow_copy(const float *src_dev, float *dst_dev, int64_t n_floats, 
 /* Test hook: side streams the calling thread holds for the reference-table build (one per device the thread has
  * built such a lattice on; building on devices A, B, A, B ... must not create more than two). */
 int phl_debug_side_streams(void);
+/* Test hook: device blocks the block cache has handed out and not yet got back, over all lattices, workspaces and builds
+ * in flight in the process.  Building, using and destroying lattices leaves it where it was; so does a build that fails. */
+int64_t phl_debug_live_blocks(void);
 
 #ifdef __cplusplus
 }
