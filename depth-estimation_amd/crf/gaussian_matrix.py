@@ -52,7 +52,7 @@ def _ref_gradient(src, ref, g, wall):
 
 
 def _fused_shape_ok(src, ref, g):
-    return (g.shape == src.shape and src.shape[-1] > 0 and ref.shape[-1] <= 7 and torch.cuda.is_available()
+    return (g.shape == src.shape and src.shape[-1] > 0 and ref.shape[-1] <= phl.FILTER_GRAD_MAX_D and torch.cuda.is_available()
             and src.dtype == torch.float32 and ref.dtype == torch.float32
             and os.environ.get("PHL_FUSED_GRAD", "1") != "0")         # A/B switch: the reference's formulation
 

@@ -979,15 +979,23 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
         return PHL_OK;
     }
     if (!src || !g || !ref) { phl_set_error("phl_filter_grad: NULL src / g / ref"); return PHL_ERR_INVALID; }
-    const int64_t vdw = (int64_t)L * (d + 1);
+    // Feature groups: column k of the result needs only block 0 (W x) and block 1 + k (W(x f_k)) of the wide rows, so the
+    // d features are contracted in ceil(d / 7) groups of at most 7 columns, as even as possible (8 -> 4+4, 16 -> 6+5+5),
+    // each a wide splat / blur / slice of (group size + 1) blocks.  d <= 7 is one group of all features: the kernels with
+    // d + 1 built in.  PHL_GRAD_FEATURES_PER_GROUP (1..7, read per call like PHL_GRAD_WS_MB) caps the group size at any d.
+    const char *fg_env = getenv("PHL_GRAD_FEATURES_PER_GROUP");
+    const int fg_cap = fg_env && atoi(fg_env) >= 1 && atoi(fg_env) <= 7 ? atoi(fg_env) : 7;
+    const int ngroups = d > 0 ? (d + fg_cap - 1) / fg_cap : 1;
+    const int nb_max = (d + ngroups - 1) / ngroups + 1;             // blocks of the widest group
+    const int64_t vdw = (int64_t)L * nb_max;
     const phl_operand g_rows = {g, g_rs, 1};
-    if (d > 7 || L % 4 != 0 || !plan_call(lat, L, 0, {src, src_rs, 1}, {}, &g_rows).chunk_splat || vdw > (1 << 20) ||
-        (grad_src && !phl_rows16(grad_src, grad_src_rs))) {
-        phl_set_error("phl_filter_grad: shape not covered by the fused path (d <= 7, L %% 4 == 0, 16-byte aligned pixel-major rows, "
-                      "chunk splat available); filter the 2L(1+d)-channel operand instead");
+    if (d < 1 || d > PHL_FILTER_GRAD_MAX_D || L % 4 != 0 || !plan_call(lat, L, 0, {src, src_rs, 1}, {}, &g_rows).chunk_splat ||
+        vdw > (1 << 20) || (grad_src && !phl_rows16(grad_src, grad_src_rs))) {
+        phl_set_error("phl_filter_grad: shape not covered by the fused path (d <= %d, L %% 4 == 0, 16-byte aligned pixel-major rows, "
+                      "chunk splat available); filter the 2L(1+d)-channel operand instead", PHL_FILTER_GRAD_MAX_D);
         return PHL_ERR_UNSUPPORTED;
     }
-    // Workspace: the wide vertex rows (two ping-pong buffers) and the wide partial rows, (2M + S_multi) * (1+d) * Lg floats
+    // Workspace: the wide vertex rows (two ping-pong buffers) and the wide partial rows, (2M + S_multi) * nb_max * Lg floats
     // for a group of Lg channels.  The contraction is a sum over channels, so the call runs in CHANNEL GROUPS whenever
     // all L at once would exceed the budget (PHL_GRAD_WS_MB, default 24576): features with little sharing push S_multi
     // towards 2n, and (2M + S_multi)(1+d)L floats would then be as large as the reference's wide operand that this
@@ -997,7 +1005,7 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
     const int64_t rows_ws = 2 * lat->M + lat->S_multi;
     int Lg = L;
     if (rows_ws * vdw * (int64_t)sizeof(float) > ws_budget) {
-        const int64_t per_ch = rows_ws * (d + 1) * (int64_t)sizeof(float);
+        const int64_t per_ch = rows_ws * nb_max * (int64_t)sizeof(float);
         int64_t fit = ws_budget / (per_ch > 0 ? per_ch : 1);
         fit = fit >= 64 ? fit / 64 * 64 : fit / 4 * 4;
         if (fit < 4) {
@@ -1007,28 +1015,36 @@ int phl_filter_grad(phl_lattice *lat, const float *src, int64_t src_rs, const fl
         }
         Lg = (int)(fit < L ? fit : L);
     }
-    const int64_t vdg = (int64_t)Lg * (d + 1);
+    const int64_t vdg = (int64_t)Lg * nb_max;
     ws_lease w(lat, st);
     int rc = w.acquire(lat->M * vdg, lat->S_multi * vdg, 0);
     if (rc) return rc;
-    // Two passes of the same three stages, each over (1+d) L channels instead of the reference's 2 (1+d) L at once:
+    // Two passes of the same three stages per feature group, each over (1+cols) L channels instead of the reference's
+    // 2 (1+d) L at once:
     //   pass 1  x = g,   y = src:  T  = -2 sum_l src (f Wg - W(g f))      (+ Wg itself = the gradient w.r.t. src)
     //   pass 2  x = src, y = g:    T += -2 sum_l g   (f Ws - W(s f))
+    // Feature groups write disjoint columns of grad_ref, so `accumulate` does not depend on the group; W g is block 0 of
+    // every group and is written once, by the first.
     const float *xs[2] = {g, src}, *ys[2] = {src, g};
     const int64_t xrs[2] = {g_rs, src_rs}, yrs[2] = {src_rs, g_rs};
     for (int c0 = 0; c0 < L && rc == PHL_OK; c0 += Lg) {
         const int Lc = L - c0 < Lg ? L - c0 : Lg;
         for (int pass = 0; pass < 2 && rc == PHL_OK; pass++) {
-            const phl_splat_wide wide = {d + 1, ref, ref_rs, ref_cs};
-            phl_splat_opts o;
-            o.wide = &wide;
-            rc = phl_launch_splat_tiled(lat, xs[pass] + c0, xrs[pass], Lc, w->buf[0], w->partial, st, o);
-            if (rc) break;
-            int cur = 0;
-            rc = blur_all(lat, w->buf, Lc * (d + 1), st, &cur);
-            if (rc) break;
-            rc = phl_launch_slice_grad(lat, w->buf[cur], Lc, ys[pass] + c0, yrs[pass], ref, ref_rs, ref_cs, grad_ref, (pass || c0) ? 1 : 0,
-                                       (pass == 0 && grad_src) ? grad_src + c0 : nullptr, grad_src_rs, st);
+            for (int fg = 0, k0 = 0; fg < ngroups && rc == PHL_OK; fg++) {
+                const int cols = d / ngroups + (fg < d % ngroups ? 1 : 0);
+                const phl_splat_wide wide = {cols + 1, ref + (int64_t)k0 * ref_cs, ref_rs, ref_cs};
+                phl_splat_opts o;
+                o.wide = &wide;
+                rc = phl_launch_splat_tiled(lat, xs[pass] + c0, xrs[pass], Lc, w->buf[0], w->partial, st, o);
+                if (rc) break;
+                int cur = 0;
+                rc = blur_all(lat, w->buf, Lc * (cols + 1), st, &cur);
+                if (rc) break;
+                rc = phl_launch_slice_grad(lat, w->buf[cur], Lc, ys[pass] + c0, yrs[pass], ref, ref_rs, ref_cs, grad_ref, k0, cols,
+                                           (pass || c0) ? 1 : 0, (pass == 0 && fg == 0 && grad_src) ? grad_src + c0 : nullptr,
+                                           grad_src_rs, st);
+                k0 += cols;
+            }
         }
     }
     return rc;

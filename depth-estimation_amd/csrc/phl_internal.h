@@ -440,10 +440,11 @@ struct phl_splat_opts {
 };
 int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, int vd, float *vert, float *partial,
                            hipStream_t st, const phl_splat_opts &o = {});
-// slice of a wide vertex buffer contracted to the feature gradient (phl_tiles.hip, k_slice_grad)
+// slice of a wide vertex buffer of ncols + 1 blocks contracted to columns [k0, k0 + ncols) of the feature gradient
+// (phl_tiles.hip: k_slice_grad for all d <= 7 columns at once, k_slice_grad_group for a feature group)
 int phl_launch_slice_grad(const phl_lattice *lat, const float *vertw, int L, const float *y, int64_t y_rs, const float *ref,
-                          int64_t ref_rs, int64_t ref_cs, float *grad_ref, int accumulate, float *wx_out, int64_t wx_rs,
-                          hipStream_t st);
+                          int64_t ref_rs, int64_t ref_cs, float *grad_ref, int k0, int ncols, int accumulate, float *wx_out,
+                          int64_t wx_rs, hipStream_t st);
 int phl_tiles_chunks_touching(phl_lattice *lat, const int64_t *rows_dev, int64_t k, int32_t *mask_host, hipStream_t st);   // (phl_tiles_build.hip)
 int phl_launch_slice_tiled(const phl_lattice *lat, const float *vert, int vd, float *out, int64_t out_rs, const float *sub,
                            int64_t sub_rs, unsigned flags, hipStream_t st);

@@ -373,17 +373,20 @@ __device__ __forceinline__ void sum4w(float4 (&acc)[NS], const uint2 e, const fl
     wide_entry<K0 + 3, NS>(acc, q3, w3, f);
 }
 
-template <int NS>
+// DP1 = 0 (phl_filter_grad's feature groups): the NS sets are block 0 and NS - 1 of the d features (fref points at the
+// group's first column) while an entry list still has dp1_rt = d + 1 entries per pixel; DP1 = NS: all d features.
+template <int NS, int DP1 = NS>
 __global__ __launch_bounds__(TPB_S) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_splat_wide(const float *__restrict__ src, int64_t src_rs, int vd, int n, int P,
                                                     int nv_cap, const int *__restrict__ pix_order, const int *__restrict__ vptr,
                                                     const int *__restrict__ slot_vert, const int *__restrict__ slot_pidx,
                                                     const int2 *__restrict__ seg_rng, const phl_contrib_t *__restrict__ seg,
                                                     float *__restrict__ vert, float *__restrict__ partial, int nchunks, int xcd_chunk,
                                                     const int *__restrict__ chunk_list, int nv_lo, int nv_hi, int long_seg,
-                                                    const float *__restrict__ fref, int64_t fref_rs, int64_t fref_cs)
+                                                    const float *__restrict__ fref, int64_t fref_rs, int64_t fref_cs, int dp1_rt)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int LPRS = 16, SL = 64, G = TPB_S / LPRS, Q = 4, NW = TPB_S / 64, PF = 8, NF = NS - 1, dp1 = NS;
+    constexpr int LPRS = 16, SL = 64, G = TPB_S / LPRS, Q = 4, NW = TPB_S / 64, PF = 8, NF = NS - 1;
+    const int dp1 = DP1 ? DP1 : dp1_rt;
     const int g = threadIdx.x / LPRS, l = threadIdx.x % LPRS;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = lane / LPRS;
@@ -947,6 +950,176 @@ __global__ __launch_bounds__(TPB) void k_slice_grad(const float *__restrict__ ve
                                       wx_out, wx_rs, rcdiv);
 }
 
+// ---- the same contraction for a GROUP of features (d = 8..16, or a forced split) ----------------------------------------
+// k_slice_grad uses one number, NS = d + 1, for two things: the simplex vertices of a pixel and the blocks of a staged
+// row.  phl_filter_grad runs d > 7 in feature groups [k0, k0 + NB - 1): the wide rows then hold NB = 1 + (group size)
+// <= 8 blocks (block 0 = W x, block t = W(x f_{k0+t-1})) while a pixel still has nvp = d + 1 vertices.  NB stays a
+// compile-time value (the accumulators), nvp is a run-time one: the loop over a pixel's vertices is the OUTER one --
+// one entry read per vertex -- and feeds NB running rows v[t]; the NB dots with y follow.  That is NB float4 of row
+// sums per pixel and PPG * NB accumulators per lane, and no table of NS x NS row addresses for the compiler to hoist:
+// 98 .. 246 registers at NB = 2 .. 8, no scratch.  Block 0 sums the vertices in the order k_slice_grad does: W x has
+// the same bits.
+// Same LDS layout ([nv][NB][4 LG] floats after the index data, entries [P][nvp]) and the same three forms.
+template <int NB, int LG, bool DIRECT>
+__device__ __forceinline__ void slice_grad_group_chunk(const float *__restrict__ vertw, int L, int cnt, int nv, int nvp,
+                                                       const uint2 *ent, const int *pixl, const int *vl, float *rows,   // (one LDS
+                                                       // block, not restrict: see slice_grad_chunk)
+                                                       const float *__restrict__ y, int64_t y_rs, const float *__restrict__ ref,
+                                                       int64_t ref_rs, int64_t ref_cs, float *__restrict__ grad_ref, int d, int k0,
+                                                       int accumulate, float *__restrict__ wx_out, int64_t wx_rs, float rcdiv)
+{
+    constexpr int SLG = LG * 4;              // channels per slab
+    constexpr int G = TPB / LG;              // lane groups
+    constexpr int PPG = 256 / G;             // pixels per group (P <= 256)
+    constexpr int PITCH = NB * SLG;          // floats per staged local vertex
+    const int g = threadIdx.x / LG, l = threadIdx.x % LG;
+    const int64_t vdw = (int64_t)NB * L;
+    float acc[PPG][NB];
+#pragma unroll
+    for (int u = 0; u < PPG; u++)
+#pragma unroll
+        for (int t = 0; t < NB; t++) acc[u][t] = 0.f;
+    const int kclamp = cnt - 1;
+    for (int c0 = 0; c0 < L; c0 += SLG) {
+        const int ch = c0 + l * 4;
+        const bool chok = ch < L;
+        const int chc = chok ? ch : 0;
+        float4 yv[PPG];
+#pragma unroll
+        for (int u = 0; u < PPG; u++) yv[u] = ld4(y + (int64_t)pixl[min(g + u * G, kclamp)] * y_rs + chc);
+        if (!DIRECT) {
+            // [nv][NB][LG] 16-byte pieces, LG consecutive threads on LG consecutive pieces of one (vertex, block)
+            const int total = nv * NB * LG;
+            for (int i0 = threadIdx.x; i0 < total; i0 += 4 * TPB) {
+                float4 q[4];
+                int dsto[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int idx = min(i0 + u * TPB, total - 1);
+                    const int i = idx / (NB * LG), rem = idx - i * (NB * LG);
+                    const int set = rem / LG, ll = rem - set * LG;
+                    const int cc = c0 + ll * 4 < L ? c0 + ll * 4 : 0;
+                    q[u] = ld4(vertw + (int64_t)vl[i] * vdw + (int64_t)set * L + cc);
+                    dsto[u] = i * PITCH + set * SLG + ll * 4;
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (i0 + u * TPB < total) st4(rows + dsto[u], q[u]);
+            }
+            __syncthreads();
+        }
+        const char *rbase = reinterpret_cast<const char *>(rows) + l * 16;
+#pragma unroll
+        for (int u = 0; u < PPG; u++) {
+            const int k = min(g + u * G, kclamp);
+            const bool live = chok && g + u * G < cnt;
+            const uint2 *pe = ent + k * nvp;   // the pixel's d+1 simplex vertices {row offset | vertex id, weight}
+            float4 v[NB];
+#pragma unroll
+            for (int t = 0; t < NB; t++) v[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+            uint2 en = pe[0];
+#pragma unroll 1
+            for (int r = 0; r < nvp; r++) {
+                const uint2 e = en;
+                en = pe[min(r + 1, nvp - 1)];      // the next vertex's entry, under this one's row reads
+                const float w = __uint_as_float(e.y);
+                const char *pr = rbase + e.x;
+                const float *gr = vertw + (int64_t)e.x * vdw + chc;
+#pragma unroll
+                for (int t = 0; t < NB; t++) {
+                    const float4 q0 = DIRECT ? ld4(gr + (int64_t)t * L) : *reinterpret_cast<const float4 *>(pr + t * (SLG * 4));
+                    v[t] = fma4(v[t], w, q0);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < NB; t++) {
+                const float dot = yv[u].x * v[t].x + yv[u].y * v[t].y + yv[u].z * v[t].z + yv[u].w * v[t].w;
+                acc[u][t] += live ? dot : 0.f;
+            }
+            if (wx_out && live)
+                st4(wx_out + (int64_t)pixl[k] * wx_rs + ch, make_float4(v[0].x * rcdiv, v[0].y * rcdiv, v[0].z * rcdiv, v[0].w * rcdiv));
+            // (no scheduling barrier between the pixels, unlike slice_grad_chunk: the compiler runs the PPG vertex loops
+            // side by side -- 246 registers at NB = 8, no scratch -- and that is the faster form where most chunks
+            // gather from memory: 28.5 against 30.6 ms for a d = 8 backward at 1110 x 1390 x 64, equal at d = 16)
+        }
+        if (!DIRECT) __syncthreads();
+    }
+    // the LG lanes of a group hold a slab's channels between them: add their dot products
+#pragma unroll
+    for (int u = 0; u < PPG; u++)
+#pragma unroll
+        for (int t = 0; t < NB; t++) {
+            float a = acc[u][t];
+#pragma unroll
+            for (int o = LG / 2; o > 0; o >>= 1) a += __shfl_xor(a, o, LG);
+            acc[u][t] = a;
+        }
+    if (l == 0) {
+#pragma unroll
+        for (int u = 0; u < PPG; u++) {
+            const int k = g + u * G;
+            if (k >= cnt) continue;
+            const int64_t p = pixl[k];
+#pragma unroll
+            for (int t = 1; t < NB; t++) {
+                const float f = ref[p * ref_rs + (int64_t)(k0 + t - 1) * ref_cs];
+                const float val = -2.f * rcdiv * (f * acc[u][0] - acc[u][t]);
+                float *dst = grad_ref + p * d + (k0 + t - 1);
+                *dst = accumulate ? *dst + val : val;
+            }
+        }
+    }
+}
+
+template <int NB>
+__global__ __launch_bounds__(TPB) void k_slice_grad_group(const float *__restrict__ vertw, int L, int n, int P, int dp1, int k0,
+                                                          int lds_bytes, const int *__restrict__ pix_order,
+                                                          const int *__restrict__ vptr, const int *__restrict__ slot_vert,
+                                                          const unsigned short *__restrict__ lidx,
+                                                          const phl_replay_t *__restrict__ replay, const float *__restrict__ y,
+                                                          int64_t y_rs, const float *__restrict__ ref, int64_t ref_rs, int64_t ref_cs,
+                                                          float *__restrict__ grad_ref, int accumulate, float *__restrict__ wx_out,
+                                                          int64_t wx_rs, float rcdiv, int nchunks, int xcd_chunk)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int c = xcd_chunk > 0 ? (int)(blockIdx.x & 7) * xcd_chunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    if (c >= nchunks) return;
+    const int base = c * P;
+    const int cnt = min(P, n - base);
+    const int E = cnt * dp1;
+    const int64_t ebase = (int64_t)base * dp1;
+    const int vbase = vptr[c], nv = vptr[c + 1] - vbase;
+    uint2 *ent = reinterpret_cast<uint2 *>(lds);
+    int *pixl = reinterpret_cast<int *>(ent + P * dp1);
+    int *vl = pixl + P;
+    const int fixed = (P * dp1 * 8 + P * 4 + nv * 4 + 15) & ~15;      // (the launcher gives at least this much)
+    float *rows = reinterpret_cast<float *>(reinterpret_cast<char *>(lds) + fixed);
+    // workgroup-uniform choice: 32-channel slabs, 16-channel slabs, or no staging
+    const int mode = fixed + (int64_t)nv * (NB * 128) <= lds_bytes ? 8 : (fixed + (int64_t)nv * (NB * 64) <= lds_bytes ? 4 : 0);
+    const unsigned pitch_bytes = (unsigned)NB * (mode == 8 ? 128u : 64u);
+    for (int k = threadIdx.x; k < cnt; k += TPB) pixl[k] = pix_order[base + k];
+    if (mode)
+        for (int i = threadIdx.x; i < nv; i += TPB) vl[i] = slot_vert[vbase + i] & 0x7FFFFFFF;
+    for (int e = threadIdx.x; e < E; e += TPB) {
+        const int k = e / dp1, r = e - k * dp1;
+        const int p = pix_order[base + k];
+        const unsigned li = lidx[ebase + e];
+        ent[e] = make_uint2(mode ? li * pitch_bytes : (unsigned)(slot_vert[vbase + li] & 0x7FFFFFFF),
+                            __float_as_uint(replay[(int64_t)p * dp1 + r].w));
+    }
+    __syncthreads();
+    const int d = dp1 - 1;
+    if (mode == 8)
+        slice_grad_group_chunk<NB, 8, false>(vertw, L, cnt, nv, dp1, ent, pixl, vl, rows, y, y_rs, ref, ref_rs, ref_cs, grad_ref, d, k0,
+                                             accumulate, wx_out, wx_rs, rcdiv);
+    else if (mode == 4)
+        slice_grad_group_chunk<NB, 4, false>(vertw, L, cnt, nv, dp1, ent, pixl, vl, rows, y, y_rs, ref, ref_rs, ref_cs, grad_ref, d, k0,
+                                             accumulate, wx_out, wx_rs, rcdiv);
+    else
+        slice_grad_group_chunk<NB, 8, true>(vertw, L, cnt, nv, dp1, ent, pixl, vl, rows, y, y_rs, ref, ref_rs, ref_cs, grad_ref, d, k0,
+                                            accumulate, wx_out, wx_rs, rcdiv);
+}
+
 // LDS per workgroup: default 80 KiB -> two workgroups per CU (160 KiB LDS per CU on gfx950)
 int lds_budget()
 {
@@ -1204,13 +1377,19 @@ int phl_launch_splat_tiled(phl_lattice *lat, const float *src, int64_t src_rs, i
         const bool one_phase = !(env1 && atoi(env1) == 0);
         if (wide && one_phase && c.cfg.lprs == 16 && wide->nsets >= 2 && wide->nsets <= 8 && lat->P <= 256) {
             // every LDS row read feeds all nsets accumulators (k_splat_wide)
+            // (all d features: the instantiation with d + 1 entries per pixel built in; a feature group: the run-time one)
+            const bool all_sets = wide->nsets == lat->d + 1;
             dispatch_int<2, 3, 4, 5, 6, 7, 8>(wide->nsets, [&](auto N) {
                 constexpr int NS = decltype(N)::value;
-                if ((rc = allow_lds(k_splat_wide<NS>, c.cfg.lds)) != PHL_OK) return;
-                k_splat_wide<NS><<<dim3(cgrid), dim3(TPB_S), c.cfg.lds, st>>>(
-                    src, src_rs, vd, (int)lat->n, lat->P, c.cfg.cap, lat->pix_order, lat->chunk_vptr, lat->slot_vert, lat->slot_pidx,
-                    lat->seg_rng, lat->seg, vert, partial, cnt, xcd_chunk, list, c.lo, c.hi, long_seg(), wide->fref, wide->rs,
-                    wide->cs);
+                auto launch = [&](auto kernel) {
+                    if ((rc = allow_lds(kernel, c.cfg.lds)) != PHL_OK) return;
+                    kernel<<<dim3(cgrid), dim3(TPB_S), c.cfg.lds, st>>>(
+                        src, src_rs, vd, (int)lat->n, lat->P, c.cfg.cap, lat->pix_order, lat->chunk_vptr, lat->slot_vert, lat->slot_pidx,
+                        lat->seg_rng, lat->seg, vert, partial, cnt, xcd_chunk, list, c.lo, c.hi, long_seg(), wide->fref, wide->rs,
+                        wide->cs, lat->d + 1);
+                };
+                if (all_sets) launch(k_splat_wide<NS, NS>);
+                else launch(k_splat_wide<NS, 0>);
             });
             continue;
         }
@@ -1302,15 +1481,51 @@ int phl_launch_slice_tiled(const phl_lattice *lat, const float *vert, int vd, fl
     return PHL_OK;
 }
 
-// phl_filter_grad's last stage (see k_slice_grad).  d <= 7; P <= 256 (eight pixels per 16-lane group).
+// phl_filter_grad's last stage for the feature group [k0, k0 + ncols) (see k_slice_grad_group): the wide rows hold
+// ncols + 1 <= 8 blocks, a pixel has d + 1 <= 17 vertices.  LDS is sized from the blocks, and never below the index data.
+static int launch_slice_grad_group(const phl_lattice *lat, const float *vertw, int L, const float *y, int64_t y_rs, const float *ref,
+                                   int64_t ref_rs, int64_t ref_cs, float *grad_ref, int k0, int ncols, int accumulate, float *wx_out,
+                                   int64_t wx_rs, hipStream_t st)
+{
+    const int dp1 = lat->d + 1, nb = ncols + 1;
+    const int64_t fixed = (((int64_t)lat->P * dp1 * 8 + (int64_t)lat->P * 4 + (int64_t)lat->nv_max * 4 + 15) & ~(int64_t)15);
+    if (nb < 2 || nb > 8 || k0 < 0 || k0 + ncols > lat->d || dp1 > PHL_FILTER_GRAD_MAX_D + 1 || lat->P > 256 || lat->nchunks == 0 ||
+        fixed > lds_big()) {
+        phl_set_error("fused feature gradient: features [%d, %d) of d = %d not supported (groups of 1..7, d <= %d)", k0, k0 + ncols,
+                      lat->d, PHL_FILTER_GRAD_MAX_D);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    int64_t lds = fixed + (int64_t)lat->nv_max * nb * 128;      // every chunk on 32-channel slabs, if the budget allows
+    if (lds > lds_budget()) lds = lds_budget() > fixed ? lds_budget() : fixed;      // (fixed alone: every chunk DIRECT)
+    const float rcdiv = 1.0f / (1 + powf(2, -lat->d));      // permutohedral.h:480
+    int xcd_chunk;
+    const unsigned cgrid = phl_xcd_grid(lat->nchunks, &xcd_chunk);
+    int rc = PHL_OK;
+    dispatch_int<2, 3, 4, 5, 6, 7, 8>(nb, [&](auto N) {          // (nb outside 2..8 was rejected above)
+        constexpr int NB = decltype(N)::value;
+        if ((rc = allow_lds(k_slice_grad_group<NB>, (size_t)lds)) != PHL_OK) return;
+        k_slice_grad_group<NB><<<dim3(cgrid), dim3(TPB), (size_t)lds, st>>>(
+            vertw, L, (int)lat->n, lat->P, dp1, k0, (int)lds, lat->pix_order, lat->chunk_vptr, lat->slot_vert, lat->lidx, lat->replay, y,
+            y_rs, ref, ref_rs, ref_cs, grad_ref, accumulate, wx_out, wx_rs, rcdiv, lat->nchunks, xcd_chunk);
+    });
+    if (rc) return rc;
+    PHL_HIP(hipGetLastError());
+    return PHL_OK;
+}
+
+// phl_filter_grad's last stage (see k_slice_grad): columns [k0, k0 + ncols) of grad_ref from wide rows of ncols + 1
+// blocks.  All d <= 7 columns at once: k_slice_grad<d + 1>; a feature group: k_slice_grad_group.  P <= 256 (eight
+// pixels per 16-lane group).
 int phl_launch_slice_grad(const phl_lattice *lat, const float *vertw, int L, const float *y, int64_t y_rs, const float *ref,
-                          int64_t ref_rs, int64_t ref_cs, float *grad_ref, int accumulate, float *wx_out, int64_t wx_rs,
-                          hipStream_t st)
+                          int64_t ref_rs, int64_t ref_cs, float *grad_ref, int k0, int ncols, int accumulate, float *wx_out,
+                          int64_t wx_rs, hipStream_t st)
 {
     if (lat->n == 0 || L == 0) return PHL_OK;
+    if (k0 != 0 || ncols != lat->d)
+        return launch_slice_grad_group(lat, vertw, L, y, y_rs, ref, ref_rs, ref_cs, grad_ref, k0, ncols, accumulate, wx_out, wx_rs, st);
     const int dp1 = lat->d + 1;
     if (dp1 < 2 || dp1 > 8 || lat->P > 256 || lat->nchunks == 0) {
-        phl_set_error("fused feature gradient: d = %d not supported (1..7)", lat->d);
+        phl_set_error("fused feature gradient: d = %d not supported in one group (1..7)", lat->d);
         return PHL_ERR_UNSUPPORTED;
     }
     const int64_t fixed = (((int64_t)lat->P * dp1 * 8 + (int64_t)lat->P * 4 + (int64_t)lat->nv_max * 4 + 15) & ~(int64_t)15);

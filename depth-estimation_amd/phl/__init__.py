@@ -28,6 +28,7 @@ SUBTRACT_INPUT = 1
 EXACT = 4
 NO_TILES = 8
 ERR_UNSUPPORTED = 7          # PHL_ERR_UNSUPPORTED: the kernels do not take this shape, the caller keeps its own path
+FILTER_GRAD_MAX_D = 16       # PHL_FILTER_GRAD_MAX_D: most feature dimensions phl_filter_grad takes (tests hold it to the header)
 BUILD_REFERENCE_TABLE = 1
 
 _lib = None
@@ -434,7 +435,10 @@ class Lattice:
     def filter_grad(self, src, g, ref, need_src=True):
         """Gradients of ``sum(g * filter(src, ref))``: returns (grad_src or None, grad_ref [n, d]) -- the body of
         LatticeFilter.backward (crf/gaussian_matrix.py:435-468) in two fused passes (phl_filter_grad in
-        include/phl.h).  Raises PhlError(status UNSUPPORTED) for shapes the fused path does not take."""
+        include/phl.h).  d <= FILTER_GRAD_MAX_D = 16: above d = 7 the features are contracted in ceil(d / 7) groups of at
+        most 7 columns (8 -> 4+4, 16 -> 6+5+5), each with a wide vertex buffer of (columns + 1) L channels, so the
+        workspace is that of the widest group; PHL_GRAD_FEATURES_PER_GROUP (1..7) caps the group size at any d.  Raises
+        PhlError(status UNSUPPORTED) for shapes the fused path does not take."""
         src_d = _as_device(src.detach(), self.device).contiguous()
         g_d = _as_device(g.detach(), self.device).contiguous()
         ref_d = _as_device(ref.detach(), self.device)
@@ -1652,7 +1656,8 @@ def batched_filter_grad(srcs, refs, g, need_src=True, devices=None):
     """Per-item Lattice.filter_grad for a batch (the body of BatchedLatticeFilter.backward, crf/gaussian_matrix.py:402-421):
     srcs, g [bs, n, L], refs [bs, n, d] (any strides) -> (grad_srcs [bs, n, L] or None, grad_refs [bs, n, d]) on the
     inputs' devices.  Items are dealt over the same devices and side streams as batched_filter, so every item meets the
-    lattice its forward pass cached.  Raises PhlError(status 7) if the fused kernels do not take the shape."""
+    lattice its forward pass cached.  d <= FILTER_GRAD_MAX_D = 16, in feature groups above d = 7 (Lattice.filter_grad).
+    Raises PhlError(status 7) if the fused kernels do not take the shape."""
     bs = srcs.shape[0]
     devices = [torch.device(d) for d in (devices or batch_devices(srcs))]
     grad_refs = torch.empty(tuple(refs.shape), dtype=torch.float32, device=refs.device)

@@ -183,8 +183,15 @@ int phl_filter_once(const float *src_dev, int vd, int64_t src_row_stride, int64_
  * filters it and contracts the 2L(1+d)-channel result; here the products are formed on the weights inside the
  * splat and the contraction inside the slice, so HBM sees src and g twice, the wide vertex buffer
  * [M][(1+d)L] (two passes) and [n][d] -- never a wide per-pixel tensor.  ref must be the array the lattice was
- * built from.  src, g, grad_src: pixel-major rows (unit channel stride), 16-byte aligned, L % 4 == 0; d <= 7.
- * grad_ref: dense [n][d].  PHL_ERR_UNSUPPORTED for shapes outside that (callers then filter the wide operand). */
+ * built from.  src, g, grad_src: pixel-major rows (unit channel stride), 16-byte aligned, L % 4 == 0;
+ * d <= PHL_FILTER_GRAD_MAX_D = 16.  grad_ref: dense [n][d].  PHL_ERR_UNSUPPORTED for shapes outside that (callers then
+ * filter the wide operand).
+ * Feature groups: column k needs only block 0 (W x) and block 1+k (W(x f_k)) of the wide vertex rows, so the d features
+ * are contracted in ceil(d / 7) groups of at most 7 columns, sized as evenly as possible (8 -> 4+4, 15 -> 5+5+5,
+ * 16 -> 6+5+5); every group is a wide splat, blur and contracting slice of (columns + 1) L channels, and the workspace
+ * is that of the widest group, not of d + 1 blocks.  d <= 7 is one group holding every feature.  The environment
+ * variable PHL_GRAD_FEATURES_PER_GROUP (1..7, read on every call) caps the group size at any d. */
+#define PHL_FILTER_GRAD_MAX_D 16
 int phl_filter_grad(phl_lattice *lat, const float *src_dev, int64_t src_row_stride, const float *g_dev,
                     int64_t g_row_stride, int L, const float *ref_dev, int64_t ref_row_stride, int64_t ref_col_stride,
                     float *grad_ref_dev, float *grad_src_dev, int64_t grad_src_row_stride, phl_stream stream);
