@@ -12,6 +12,14 @@ form W itself takes.  Training leaves the torch form only on request: with the k
 that autograd records goes through phl.GuidedFilterFn, whose backward runs on the library's kernels as well
 (phl.guided_filter_grad: y, x and eps are all that is saved) and gives y, x and omega their gradients.
 
+``full_cov=True`` (keyword of all four classes) solves the guide channels together, A = cov_yx (cov_xx + diag(eps))^-1,
+the model the reference keeps as commented lines (gaussian_matrix.py:204, 209-212) beside a memory print: its torch form
+needs [n, h, w, cx, cx] tensors and a batched inverse.  Here the forward that autograd does not record runs on
+phl.guided_filter(full_cov=True) for up to phl.GUIDED_FULL_MAX_CX guide channels (the inverse once per image, in
+registers); a forward that autograd records runs the torch form of get_coeffs, ``fused_grad`` or not -- this model has no
+backward kernel -- as do more guide channels, CPU tensors, float64 and ``mode != 'nearest'``.  The Gaussian window does
+not take the flag.
+
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
     box_filter(x, r, dim)            one normalised box pass (window of 2r samples, divisor of 2r+1: see _box_torch)
@@ -138,11 +146,15 @@ def _box_sum(x, r):
 
 class GuidedFilter(nn.Module):
     """y filtered by guide x with per-guide-channel (diagonal covariance) linear model,
-    eps = softplus(omega) as in the reference's parametrisation (:161-232)."""
+    eps = softplus(omega) as in the reference's parametrisation (:161-232); with ``full_cov`` one linear model over all
+    guide channels, through their covariance matrix (:204, :209-212)."""
 
-    def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False, *, fused_grad=False):
+    def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False, *, fused_grad=False, full_cov=False):
         super().__init__()
+        if gaussian and full_cov:
+            raise NotImplementedError("GuidedFilter(gaussian=True, full_cov=True): the full covariance has the box window only")
         self.fused_grad = fused_grad
+        self.full_cov = full_cov
         self.omega = nn.Parameter(torch.log(torch.expm1(torch.tensor(float(eps)))).expand(channels).clone())
         if gaussian:
             # pinned to the reference (tests/golden/blur_guided.npz): its fp32 log(exp(eps) - 1), not expm1 (:166)
@@ -179,8 +191,14 @@ class GuidedFilter(nn.Module):
         mean = lambda t: blur(t) / N  # noqa: E731
         mx, my = mean(x), mean(y)
         cov = mean((y[:, :, None] * x[:, None]).reshape(n, cy * cx, h, w)).reshape(n, cy, cx, h, w) - my[:, :, None] * mx[:, None]
-        var = mean(x * x) - mx * mx
-        A = cov / (var[:, None] + self.eps.view(1, 1, -1, 1, 1))          # [n, cy, cx, h, w]
+        if self.full_cov:
+            # A = cov_yx @ inverse(cov_xx + eps * I), per pixel (:204, :209-212); eps * I broadcasts to diag(eps)
+            cov_xx = mean((x[:, :, None] * x[:, None]).reshape(n, cx * cx, h, w)).reshape(n, cx, cx, h, w) - mx[:, :, None] * mx[:, None]
+            P = torch.linalg.inv(cov_xx.permute(0, 3, 4, 1, 2) + torch.diag_embed(self.eps.expand(cx)))     # [n, h, w, cx, cx]
+            A = (cov.permute(0, 3, 4, 1, 2) @ P).permute(0, 3, 4, 1, 2)
+        else:
+            var = mean(x * x) - mx * mx
+            A = cov / (var[:, None] + self.eps.view(1, 1, -1, 1, 1))      # [n, cy, cx, h, w]
         b = my - (A * mx[:, None]).sum(2)
         mean_A = mean(A.reshape(n, cy * cx, h, w)).reshape(n, cy, cx, h, w)
         return mean_A, mean(b)
@@ -188,17 +206,19 @@ class GuidedFilter(nn.Module):
     def _fused(self, y, x, subsample=1, scale=1.0, subtract=None):
         """The forward on the HIP kernels (phl.guided_filter), or None where the torch form has to run: a Gaussian
         window, an interpolation other than nearest, tensors that are not fp32 CUDA, autograd recording without
-        ``fused_grad``, or a shape the kernels do not take (PHL_ERR_UNSUPPORTED: more than 16 guide channels).  With
-        ``fused_grad`` a recorded forward is phl.GuidedFilterFn (eps = softplus(omega) keeps its graph); ``subtract`` is
-        None or y itself."""
+        ``fused_grad`` (with ``full_cov``: any recording), or a shape the kernels do not take (PHL_ERR_UNSUPPORTED: more
+        than 16 guide channels, with ``full_cov`` more than phl.GUIDED_FULL_MAX_CX).  With ``fused_grad`` a recorded forward
+        is phl.GuidedFilterFn (eps = softplus(omega) keeps its graph); ``subtract`` is None or y itself."""
         if self.gaussian or getattr(self, "mode", "nearest") != "nearest" or not (_hip_ok(y) and _hip_ok(x)):
             return None
         if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
             return None
         recording = torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad)
-        if recording and not self.fused_grad:
+        if recording and (self.full_cov or not self.fused_grad):
             return None
         try:
+            if self.full_cov:
+                return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract, full_cov=True)
             if recording:
                 return phl.GuidedFilterFn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract)
@@ -255,8 +275,8 @@ class BatchedGuidedAdjacency(FastGuidedFilter):
 class GuidedAdjacency(GuidedFilter):
     """Flat ``W @ U`` form used by Experiments/DenseCrf.ipynb cell 9: guide [1, C, H, W], U [n, L]."""
 
-    def __init__(self, guide_img, r, eps):
-        super().__init__(guide_img.shape[1], r, eps)
+    def __init__(self, guide_img, r, eps, *, full_cov=False):
+        super().__init__(guide_img.shape[1], r, eps, full_cov=full_cov)
         self.guide_img = guide_img.float()
 
     def __matmul__(self, U):

@@ -20,12 +20,16 @@
 //   k_guide_apply   per (image x label, tile): window means of the cx + 1 planes into LDS, four planes at a time, then
 //                   the full-resolution pixels that map into the tile: fp64 sum over the channels, * scale - src, one
 //                   rounding into out (with more than four planes the partial sum passes through out between groups)
+// (phl_guided_filter_full, the model over the whole covariance matrix of the guide channels: k_guide_stats_full and
+// k_guide_coef_full in the places of the first two, after run() below.)
 // Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
 // routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.  The
 // kernels of both directions reach the two forms through one front end (plane_sums, square_sums, product_sums).
 // The coefficient planes are a stream-ordered temporary; labels are processed in chunks whose planes stay within
 // kChunkBytes, so that k_guide_apply finds them in the Infinity Cache.
 #include <math.h>
+
+#include <utility>
 
 #include "phl_internal.h"
 
@@ -474,6 +478,189 @@ int run(const float *y, const float *x, const float *src, float *out, int B, int
     return tmp.release();
 }
 
+// ---- full covariance (forward only) --------------------------------------------------------------------------------
+// The model the reference kept as commented lines (crf/gaussian_matrix.py:204-212): the guide channels are solved for
+// together, through their whole covariance matrix instead of its diagonal.  At the solving resolution:
+//   S_cd = mean(x_c x_d) - mx_c mx_d      P = (S + diag(eps))^-1 (symmetric)      A_lc = sum_d cov_ld P_dc
+// b_l and out as in the header, so k_guide_apply and the chunks are those of run().  P belongs to the image, not to the
+// label: the two kernels below take the places of k_guide_stats and k_guide_coef, the channel count a template parameter
+// (1 .. PHL_GUIDED_FULL_MAX_CX), so that every matrix element is a register of a constant index.
+//   k_guide_stats_full  per (image, tile): mx_c and the window sums of the cx (cx + 1) / 2 products x_c x_d (two halo
+//                       tiles, as k_guide_coef) -> S + diag(eps) = L D L^T in fp64 registers, M = L^-1,
+//                       P = M^T D^-1 M -> mx (fp64 planes) and the upper triangle of P (fp64 planes, row-major)
+//   k_guide_coef_full   per (image x label, tile): the sums of y and y x_c as k_guide_coef, all cx covariances kept ->
+//                       A_lc through P in fp64, rounded to fp32 once; b_l from the rounded values
+// No pivot search and no loop whose trip count depends on the data: a non-positive pivot (eps <= 0 on a flat window)
+// gives inf or nan, as 1 / (var + eps) does in k_guide_stats.
+constexpr int npairs(int cx) { return cx * (cx + 1) / 2; }
+// plane of P_cd, c <= d, among the npairs(cx) of an image
+__host__ __device__ constexpr int pair_plane(int c, int d, int cx) { return c * cx - c * (c - 1) / 2 + (d - c); }
+
+// f(std::integral_constant<int, I>) for I = 0 .. N - 1: a loop whose index is a constant in every body
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_seq(F f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F f) { static_for_seq(f, std::make_integer_sequence<int, N>{}); }
+
+template <bool ST, int CX>
+__global__ __launch_bounds__(NT) void k_guide_stats_full(const float *__restrict__ x, const int *__restrict__ rmap,
+                                                        const int *__restrict__ cmap, const float *__restrict__ eps,
+                                                        double *__restrict__ mx, double *__restrict__ P, int H, int W, int h, int w,
+                                                        int r)
+{
+    constexpr int NP = npairs(CX);
+    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_COEF);
+    const int b = blockIdx.z;
+    const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
+    const float *xb = x + (int64_t)b * CX * HWf;
+    double m[CX][RPT], S[NP][RPT], rn[RPT], s[RPT];
+    recip_counts(t, rn);
+    // (static_for, not a loop with an unroll pragma: around bodies of this size the pragma is not always honoured, and a
+    // channel that is not a constant puts S into scratch)
+    static_for<CX>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        plane_sums<ST>(t, t.in, xb + c * HWf, s);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) m[c][k] = s[k] * rn[k];
+        square_sums<ST>(t, xb + c * HWf, s);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) S[pair_plane(c, c, CX)][k] = s[k] * rn[k];          // mean(x_c x_d) for now
+        static_for<CX>([&](auto dd) {
+            constexpr int d = decltype(dd)::value;
+            if constexpr (d > c) {
+                product_sums<ST>(t, xb + c * HWf, xb + d * HWf, s);
+#pragma unroll
+                for (int k = 0; k < RPT; k++) S[pair_plane(c, d, CX)][k] = s[k] * rn[k];
+            }
+        });
+    });
+    double e[CX];
+#pragma unroll
+    for (int c = 0; c < CX; c++) e[c] = (double)eps[c];
+    double *mp = mx + (int64_t)b * CX * hw, *pp = P + (int64_t)b * NP * hw;
+    for_pixels(t, [&](int k, int64_t q) {
+        // a[d][c], c <= d: the lower triangle of S + diag(eps), then L below the diagonal; D and 1 / D beside it
+        double a[CX][CX], M[CX][CX], D[CX], rD[CX];
+#pragma unroll
+        for (int d = 0; d < CX; d++)
+#pragma unroll
+            for (int c = 0; c <= d; c++) a[d][c] = S[pair_plane(c, d, CX)][k] - m[c][k] * m[d][k] + (c == d ? e[c] : 0.0);
+#pragma unroll
+        for (int j = 0; j < CX; j++) {
+            double dj = a[j][j];
+#pragma unroll
+            for (int p = 0; p < j; p++) dj -= a[j][p] * a[j][p] * D[p];
+            D[j] = dj, rD[j] = 1.0 / dj;
+#pragma unroll
+            for (int i = j + 1; i < CX; i++) {
+                double v = a[i][j];
+#pragma unroll
+                for (int p = 0; p < j; p++) v -= a[i][p] * a[j][p] * D[p];
+                a[i][j] = v * rD[j];
+            }
+        }
+        // M = L^-1, unit lower triangular
+#pragma unroll
+        for (int j = 0; j < CX; j++) {
+            M[j][j] = 1.0;
+#pragma unroll
+            for (int i = j + 1; i < CX; i++) {
+                double v = 0.0;
+#pragma unroll
+                for (int p = j; p < i; p++) v -= a[i][p] * M[p][j];
+                M[i][j] = v;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CX; c++) {
+            mp[c * hw + q] = m[c][k];
+#pragma unroll
+            for (int d = c; d < CX; d++) {
+                double v = 0.0;
+#pragma unroll
+                for (int p = d; p < CX; p++) v += M[p][c] * M[p][d] * rD[p];
+                pp[pair_plane(c, d, CX) * hw + q] = v;
+            }
+        }
+    });
+}
+
+template <bool ST, int CX>
+__global__ __launch_bounds__(NT) void k_guide_coef_full(const float *__restrict__ y, const float *__restrict__ x,
+                                                       const int *__restrict__ rmap, const int *__restrict__ cmap,
+                                                       const double *__restrict__ mx, const double *__restrict__ P,
+                                                       float *__restrict__ coef, int n0, int cy, int H, int W, int h, int w, int r)
+{
+    constexpr int NP = npairs(CX);
+    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_COEF);
+    const int n = n0 + blockIdx.z, b = n / cy;                     // n = image * cy + label
+    const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
+    const float *yp = y + (int64_t)n * HWf, *xb = x + (int64_t)b * CX * HWf;
+    const double *mp = mx + (int64_t)b * CX * hw, *pp = P + (int64_t)b * NP * hw;
+    float *cp = coef + (int64_t)blockIdx.z * (CX + 1) * hw;
+
+    double my[RPT], rn[RPT], s[RPT], cov[CX][RPT];
+    recip_counts(t, rn);
+    plane_sums<ST>(t, t.in, yp, s);                                 // (tiled form: y stays in LDS for the products below)
+#pragma unroll
+    for (int k = 0; k < RPT; k++) my[k] = s[k] * rn[k];
+    static_for<CX>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        product_sums<ST>(t, yp, xb + c * HWf, s);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) cov[c][k] = s[k] * rn[k];       // mean(y x_c) for now
+    });
+    for_pixels(t, [&](int k, int64_t o) {
+        double m[CX], cv[CX], p[NP], bacc = my[k];
+#pragma unroll
+        for (int c = 0; c < CX; c++) m[c] = mp[c * hw + o], cv[c] = cov[c][k] - my[k] * m[c];
+#pragma unroll
+        for (int i = 0; i < NP; i++) p[i] = pp[i * hw + o];
+#pragma unroll
+        for (int c = 0; c < CX; c++) {
+            double v = 0.0;
+#pragma unroll
+            for (int d = 0; d < CX; d++) v += cv[d] * p[pair_plane(min(c, d), max(c, d), CX)];
+            const float a = (float)v;
+            cp[c * hw + o] = a;
+            bacc -= (double)a * m[c];
+        }
+        cp[CX * hw + o] = (float)bacc;
+    });
+}
+
+template <bool ST, int CX>
+int run_full(const Plan &p, const float *y, const float *x, const float *src, float *out, int B, int cy, int H, int W, int h, int w,
+             int re, const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col, const float *eps,
+             float scale, hipStream_t st)
+{
+    const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
+    auto stats = k_guide_stats_full<ST, CX>;
+    auto coefk = k_guide_coef_full<ST, CX>;
+    auto apply = k_guide_apply<ST>;
+    if (int rc = phl_allow_lds(stats, p.lds_coef)) return rc;
+    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
+    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
+
+    const int64_t chunk = Plan::chunk(nimg, Plan::per_forward(CX, hw));
+    phl_temps tmp(st);
+    double *mx = tmp.get<double>((size_t)B * CX * hw), *P = tmp.get<double>((size_t)B * npairs(CX) * hw);
+    float *coef = tmp.get<float>((size_t)chunk * (CX + 1) * hw);
+    int &rc = tmp.rc;
+    if (rc == PHL_OK) {
+        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(x, row_of_low, col_of_low, eps, mx, P, H, W, h, w, re);
+        phl_launched(rc, "k_guide_stats_full");
+    }
+    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
+        const unsigned nz = (unsigned)min(chunk, nimg - n0);
+        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, row_of_low, col_of_low, mx, P, coef, (int)n0, cy, H, W, h, w, re);
+        apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(coef, x, src, out, low_of_row, low_of_col, (int)n0, cy, CX, H, W, h, w, re,
+                                                        scale);
+        phl_launched(rc, "k_guide_coef_full / k_guide_apply");
+    }
+    return tmp.release();
+}
+
 // ---- backward ------------------------------------------------------------------------------------------------------
 // With g the gradient of out [B][cy][H][W], N = S(1), and the forward's mx_c, my_l, inv_c = 1 / (var_c + eps_c), A_lc
 // recomputed (nothing but y, x, eps and g comes in):
@@ -891,7 +1078,34 @@ int phl_guided_filter(const float *y, const float *x, const float *src, float *o
     return run(y, x, src, out, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps, scale, (hipStream_t)stream);
 }
 
-int phl_guided_filter_grad_max_r(void) { return phl_guided_filter_max_r(); }      // the same two LDS layouts as the forward
+int phl_guided_filter_full(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h,
+                           int w, int r, const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col,
+                           const float *eps, float scale, phl_stream stream)
+{
+    if (int rc = check_guided_args("phl_guided_filter_full", y, x, out, "out", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low,
+                                   low_of_row, low_of_col, eps, scale))
+        return rc;
+    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;          // (as check_guided_args: before the channel bound)
+    if (cx > PHL_GUIDED_FULL_MAX_CX) {
+        phl_set_error("phl_guided_filter_full: %d guide channels, at most %d (PHL_GUIDED_FULL_MAX_CX)", cx, PHL_GUIDED_FULL_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (out == y || out == x || out == src) {
+        phl_set_error("phl_guided_filter_full: out aliases an input");
+        return PHL_ERR_INVALID;
+    }
+    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
+    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, int, int, int, int, int, int, int, const int *,
+                        const int *, const int *, const int *, const float *, float, hipStream_t);
+    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX] = {{run_full<false, 1>, run_full<false, 2>, run_full<false, 3>, run_full<false, 4>},
+                                                        {run_full<true, 1>, run_full<true, 2>, run_full<true, 3>, run_full<true, 4>}};
+    const int re = min(r, max(h, w));
+    const Plan p(re, h, w);
+    return runs[p.tiled ? 0 : 1][cx - 1](p, y, x, src, out, B, cy, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps,
+                                        scale, (hipStream_t)stream);
+}
+
+int phl_guided_filter_grad_max_r(void) { return phl_guided_filter_max_r(); }     // the same two LDS layouts as the forward
 
 int phl_guided_filter_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B, int cy,
                            int cx, int H, int W, int h, int w, int r, const int *row_of_low, const int *col_of_low,

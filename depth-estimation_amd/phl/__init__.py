@@ -29,6 +29,7 @@ EXACT = 4
 NO_TILES = 8
 ERR_UNSUPPORTED = 7          # PHL_ERR_UNSUPPORTED: the kernels do not take this shape, the caller keeps its own path
 FILTER_GRAD_MAX_D = 16       # PHL_FILTER_GRAD_MAX_D: most feature dimensions phl_filter_grad takes (tests hold it to the header)
+GUIDED_FULL_MAX_CX = 4       # PHL_GUIDED_FULL_MAX_CX: most guide channels phl_guided_filter_full takes
 BUILD_REFERENCE_TABLE = 1
 
 _lib = None
@@ -110,6 +111,7 @@ _ABI = (
     ("phl_box_blur_grad", "i", "PPqqqidPPS"),
     ("phl_box_blur_fused_max_r", "i", "iii"),
     ("phl_guided_filter", "i", "PPPPiiiiiiiiPPPPPfS"),
+    ("phl_guided_filter_full", "i", "PPPPiiiiiiiiPPPPPfS"),
     ("phl_guided_filter_max_r", "i", ""),
     ("phl_guided_filter_labels_per_chunk", "i", "iiiiiii"),
     ("phl_guided_filter_grad", "i", "PPPPPPiiiiiiiiPPPPPfiS"),
@@ -1400,21 +1402,24 @@ def _nearest_index_maps(H, W, s, device):
     return maps
 
 
-def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=None):
+def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=None, full_cov=False):
     """The box-window guided filter of ``y`` [B, cy, H, W] by the guide ``x`` [B, cx, H, W] (phl_guided_filter; forward
     only): ``out = guided(y, x) * scale - subtract``.  ``r`` is the full-resolution radius; with ``subsample = s > 1`` the
     linear model is solved on nearest samples at (H // s, W // s) with radius r // s and upsampled by nearest
     (FastGuidedFilter).  ``eps``: a number or a tensor of cx values (softplus(omega) stays on the device).  fp32 CUDA
     tensors of any strides (copied contiguous); any radius (above phl_guided_filter_max_r at the solving resolution the
-    kernels read the image from memory instead of LDS tiles); PhlError status 7 for more than 16 guide channels."""
+    kernels read the image from memory instead of LDS tiles); PhlError status 7 for more than 16 guide channels.
+    ``full_cov``: the linear model over the whole covariance matrix of the guide channels, A = cov_yx (cov_xx + diag(eps))^-1
+    (phl_guided_filter_full; PhlError status 7 for more than GUIDED_FULL_MAX_CX guide channels), instead of one model per
+    channel."""
     _, e, dims, maps = _guided_launch_args("guided_filter", y, x, subtract, "subtract", r, eps, subsample)
     out = _out_or_empty("guided_filter", out, y.shape, y.device, "y's shape and device")
     if dims is None:
         return out
     yc, xc = y.contiguous(), x.contiguous()
     sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
-    _launch(y.device, "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims, *(_ptr(m) for m in maps), _ptr(e),
-            C.c_float(float(scale)))
+    _launch(y.device, "phl_guided_filter_full" if full_cov else "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims,
+            *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)))
     return out
 
 

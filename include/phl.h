@@ -548,7 +548,20 @@ int phl_box_blur_fused_max_r(int inner_is_one, int passes, int grad);
 int phl_guided_filter(const float *y_dev, const float *x_dev, const float *src_dev, float *out_dev, int B, int cy, int cx, int H,
                       int W, int h, int w, int r, const int *row_of_low_dev, const int *col_of_low_dev, const int *low_of_row_dev,
                       const int *low_of_col_dev, const float *eps_dev, float scale, phl_stream stream);
-int phl_guided_filter_max_r(void);   /* largest window radius (at the solving resolution) of the LDS-tiled form */
+/* The same filter with the full covariance of the guide channels (the model the reference keeps as commented lines,
+ * crf/gaussian_matrix.py:204-212), forward only; arguments, maps, window sums and out exactly as phl_guided_filter, but
+ *   S_cd = mean(xl_c xl_d) - mean(xl_c) mean(xl_d)      P = (S + diag(eps))^-1      A_lc = sum_d cov_ld P_dc
+ * with cov_ld = mean(yl_l xl_d) - mean(yl_l) mean(xl_d); cx = 1 is the model above.  P is computed once per image in fp64
+ * (L D L^T without pivoting; a non-positive pivot, eps <= 0 on a flat window, gives inf or nan) and kept as
+ * cx (cx + 1) / 2 fp64 planes at the solving resolution; A is rounded to fp32 once.  No atomics: the same bits on every run.
+ * Status as phl_guided_filter, then PHL_ERR_UNSUPPORTED for cx > PHL_GUIDED_FULL_MAX_CX (the caller keeps its torch
+ * path), all before any HIP call.  The tiled radius and the labels per chunk are those of phl_guided_filter. */
+#define PHL_GUIDED_FULL_MAX_CX 4
+int phl_guided_filter_full(const float *y_dev, const float *x_dev, const float *src_dev, float *out_dev, int B, int cy, int cx, int H,
+                           int W, int h, int w, int r, const int *row_of_low_dev, const int *col_of_low_dev,
+                           const int *low_of_row_dev, const int *low_of_col_dev, const float *eps_dev, float scale,
+                           phl_stream stream);
+int phl_guided_filter_max_r(void);  /* largest window radius (at the solving resolution) of the LDS-tiled form */
 /* Labels (planes of y) per chunk of a call: the labels B * cy are processed in chunks whose per-label temporaries stay
  * within a fixed budget.  h x w is the solving resolution; needs = -1 asks for phl_guided_filter, otherwise for
  * phl_guided_filter_grad with the bit mask 1 = grad_y, 2 = grad_x, 4 = grad_eps, and full != 0 for h x w = H x W (the
