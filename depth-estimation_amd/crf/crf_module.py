@@ -458,16 +458,19 @@ class CRFasRNN(nn.Module):
     lattice W, _mean_field_nchw_step for any other (PHL_NCHW_STEP=0 in the environment switches that one off) -- and one
     it records does so on request: ``fused_grad=True`` for the lattice W (_mean_field_nchw_grad; it also puts the guided
     W itself on phl.GuidedFilterFn), ``fused_step=True`` for any other W.  ``full_cov=True`` gives the guided W the full
-    covariance of the guide channels (crf.guided; its recorded forward is the torch form).  Everything else -- CPU tensors, float64,
+    covariance of the guide channels (crf.guided; its recorded forward is the torch form, or with ``full_cov_grad=True``
+    phl.GuidedFilterFullFn, which trains that W on the library's kernels for up to four guide channels).  Everything else -- CPU tensors, float64,
     another Mu, a label count out of a route's range -- is the plain NCHW loop, with the bits it always had.
     ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with; on
     the step routes the loop itself ends in the expected label, and the logits are never written."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
-                 fused_grad=False, fused_step=False, full_cov=False):
+                 fused_grad=False, fused_step=False, full_cov=False, full_cov_grad=False):
         super().__init__()
         if lattice and full_cov:
             raise ValueError("CRFasRNN: full_cov belongs to the guided-filter W; lattice=True has no covariance model")
+        if full_cov_grad and not full_cov:
+            raise ValueError("CRFasRNN: full_cov_grad=True is the backward of the full-covariance W: it needs full_cov=True")
         self.Mu, self.niters = mu_init, niters
         if notrain_mu:
             self.Mu.requires_grad_(False)
@@ -475,7 +478,7 @@ class CRFasRNN(nn.Module):
         # backward, crf.guided.GaussianBlur, and ignores the flag)
         self.W = BatchedAdjacency() if lattice else BatchedGuidedAdjacency(gchannels, r, eps, gaussian=gaussian,
                                                                              fused_grad=fused_grad and not gaussian,
-                                                                             full_cov=full_cov)
+                                                                             full_cov=full_cov, full_cov_grad=full_cov_grad)
         self.fused_grad, self.fused_step = fused_grad, fused_step
 
     def forward(self, refs, logits, confidence=None, labels=None, energies=None):

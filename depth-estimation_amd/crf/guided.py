@@ -16,9 +16,12 @@ that autograd records goes through phl.GuidedFilterFn, whose backward runs on th
 the model the reference keeps as commented lines (gaussian_matrix.py:204, 209-212) beside a memory print: its torch form
 needs [n, h, w, cx, cx] tensors and a batched inverse.  Here the forward that autograd does not record runs on
 phl.guided_filter(full_cov=True) for up to phl.GUIDED_FULL_MAX_CX guide channels (the inverse once per image, in
-registers); a forward that autograd records runs the torch form of get_coeffs, ``fused_grad`` or not -- this model has no
-backward kernel -- as do more guide channels, CPU tensors, float64 and ``mode != 'nearest'``.  The Gaussian window does
-not take the flag.
+registers); a forward that autograd records runs the torch form of get_coeffs, ``fused_grad`` or not, as do more guide
+channels, CPU tensors, float64 and ``mode != 'nearest'``.  The Gaussian window does not take the flag.  The model trains
+on the kernels under a keyword of its own, ``full_cov_grad=True`` (it needs ``full_cov=True``, and no ``fused_grad``): a
+recorded forward is then phl.GuidedFilterFullFn, whose backward (phl.guided_filter_full_grad) recomputes the statistics
+and the inverse from y, x and eps and gives y, x and omega their gradients; what the kernels do not take stays on the
+torch form as before.
 
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
@@ -149,12 +152,15 @@ class GuidedFilter(nn.Module):
     eps = softplus(omega) as in the reference's parametrisation (:161-232); with ``full_cov`` one linear model over all
     guide channels, through their covariance matrix (:204, :209-212)."""
 
-    def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False, *, fused_grad=False, full_cov=False):
+    def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False, *, fused_grad=False, full_cov=False, full_cov_grad=False):
         super().__init__()
         if gaussian and full_cov:
             raise NotImplementedError("GuidedFilter(gaussian=True, full_cov=True): the full covariance has the box window only")
+        if full_cov_grad and not full_cov:
+            raise ValueError("full_cov_grad=True is the backward of the full-covariance model: it needs full_cov=True")
         self.fused_grad = fused_grad
         self.full_cov = full_cov
+        self.full_cov_grad = full_cov_grad
         self.omega = nn.Parameter(torch.log(torch.expm1(torch.tensor(float(eps)))).expand(channels).clone())
         if gaussian:
             # pinned to the reference (tests/golden/blur_guided.npz): its fp32 log(exp(eps) - 1), not expm1 (:166)
@@ -206,17 +212,20 @@ class GuidedFilter(nn.Module):
     def _fused(self, y, x, subsample=1, scale=1.0, subtract=None):
         """The forward on the HIP kernels (phl.guided_filter), or None where the torch form has to run: a Gaussian
         window, an interpolation other than nearest, tensors that are not fp32 CUDA, autograd recording without
-        ``fused_grad`` (with ``full_cov``: any recording), or a shape the kernels do not take (PHL_ERR_UNSUPPORTED: more
-        than 16 guide channels, with ``full_cov`` more than phl.GUIDED_FULL_MAX_CX).  With ``fused_grad`` a recorded forward
-        is phl.GuidedFilterFn (eps = softplus(omega) keeps its graph); ``subtract`` is None or y itself."""
+        ``fused_grad`` (with ``full_cov``: without ``full_cov_grad``), or a shape the kernels do not take
+        (PHL_ERR_UNSUPPORTED: more than 16 guide channels, with ``full_cov`` more than phl.GUIDED_FULL_MAX_CX).  With
+        ``fused_grad`` a recorded forward is phl.GuidedFilterFn, with ``full_cov_grad`` phl.GuidedFilterFullFn (eps =
+        softplus(omega) keeps its graph); ``subtract`` is None or y itself."""
         if self.gaussian or getattr(self, "mode", "nearest") != "nearest" or not (_hip_ok(y) and _hip_ok(x)):
             return None
         if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
             return None
         recording = torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad)
-        if recording and (self.full_cov or not self.fused_grad):
+        if recording and not (self.full_cov_grad if self.full_cov else self.fused_grad):
             return None
         try:
+            if self.full_cov and recording:
+                return phl.GuidedFilterFullFn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             if self.full_cov:
                 return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract, full_cov=True)
             if recording:

@@ -21,7 +21,7 @@
 //                   the full-resolution pixels that map into the tile: fp64 sum over the channels, * scale - src, one
 //                   rounding into out (with more than four planes the partial sum passes through out between groups)
 // (phl_guided_filter_full, the model over the whole covariance matrix of the guide channels: k_guide_stats_full and
-// k_guide_coef_full in the places of the first two, after run() below.)
+// k_guide_coef_full in the places of the first two, after run() below; its backward after run_grad().)
 // Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
 // routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.  The
 // kernels of both directions reach the two forms through one front end (plane_sums, square_sums, product_sums).
@@ -422,6 +422,8 @@ __global__ __launch_bounds__(NT) void k_guide_apply(const float *__restrict__ co
 // ---- host: what the forward and the backward derive from (re, h, w) -------------------------------------------------
 inline bool fits_tiled(int r) { return max_lds(r) <= kMaxLds && halo_stride(r) <= 64 * NCO; }
 
+constexpr int npairs(int cx) { return cx * (cx + 1) / 2; }     // elements of the upper triangle of a cx x cx matrix
+
 // The tiled form while its LDS fits the radius, else the streamed form; the tile grid; the dynamic LDS of the three
 // layouts (one halo tile, two, one + the window means); the labels of a chunk.
 struct Plan {
@@ -443,6 +445,11 @@ struct Plan {
     static int64_t per_backward(int cx, int64_t hw, bool full, bool need_x, bool need_xe)
     {
         return hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * kGradParts * cx : 0));
+    }
+    // ... and of the full-covariance backward: npairs(cx) + 2 cx fp64 terms a label in the place of NPART * cx
+    static int64_t per_backward_full(int cx, int64_t hw, bool full, bool need_x, bool need_xe)
+    {
+        return hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * (npairs(cx) + 2 * cx) : 0));
     }
 };
 
@@ -478,7 +485,7 @@ int run(const float *y, const float *x, const float *src, float *out, int B, int
     return tmp.release();
 }
 
-// ---- full covariance (forward only) --------------------------------------------------------------------------------
+// ---- full covariance: the forward ------------------------------------------------------------------------------------
 // The model the reference kept as commented lines (crf/gaussian_matrix.py:204-212): the guide channels are solved for
 // together, through their whole covariance matrix instead of its diagonal.  At the solving resolution:
 //   S_cd = mean(x_c x_d) - mx_c mx_d      P = (S + diag(eps))^-1 (symmetric)      A_lc = sum_d cov_ld P_dc
@@ -492,7 +499,6 @@ int run(const float *y, const float *x, const float *src, float *out, int B, int
 //                       A_lc through P in fp64, rounded to fp32 once; b_l from the rounded values
 // No pivot search and no loop whose trip count depends on the data: a non-positive pivot (eps <= 0 on a flat window)
 // gives inf or nan, as 1 / (var + eps) does in k_guide_stats.
-constexpr int npairs(int cx) { return cx * (cx + 1) / 2; }
 // plane of P_cd, c <= d, among the npairs(cx) of an image
 __host__ __device__ constexpr int pair_plane(int c, int d, int cx) { return c * cx - c * (c - 1) / 2 + (d - c); }
 
@@ -798,8 +804,9 @@ __global__ __launch_bounds__(NT) void k_grad_apply(const float *__restrict__ Q, 
                                                   const float *__restrict__ g, float *__restrict__ grad_y, float *__restrict__ mA,
                                                   double *__restrict__ part, const int *__restrict__ rmapS,
                                                   const int *__restrict__ cmapS, int n0, int cy, int cx, int H, int W, int h, int w,
-                                                  int r, int subtract_is_y)
+                                                  int r, int subtract_is_y, int pstride, int poff)
 {
+    // part: `pstride` planes a label, this kernel's ys_l U_lc from plane `poff` on
     Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_APPLY);
     double *G = reinterpret_cast<double *>(t.in2);                  // [TH][TW] gys (both forms; 8-byte aligned)
     const int z = blockIdx.z, n = n0 + z, b = n / cy;
@@ -813,7 +820,7 @@ __global__ __launch_bounds__(NT) void k_grad_apply(const float *__restrict__ Q, 
         plane_sums<ST>(t, t.in, qp + (int64_t)c * hw, s);
         for_pixels(t, [&](int k, int64_t o) {
             gys[k] += (double)xp[o] * s[k];
-            if (part) part[((int64_t)z * NPART * cx + (int64_t)PART_YU * cx + c) * hw + o] = (double)yp[o] * s[k];
+            if (part) part[((int64_t)z * pstride + poff + c) * hw + o] = (double)yp[o] * s[k];
         });
         if (mA) {
             plane_sums<ST>(t, t.in, A + ((int64_t)z * cx + c) * hw, s);
@@ -830,9 +837,10 @@ __global__ __launch_bounds__(NT) void k_grad_apply(const float *__restrict__ Q, 
                  [&](int64_t o, double v) { op[o] = (float)(subtract_is_y ? v - (double)gp[o] : v); });
 }
 
-// acc[sel][b][c] (+)= sum over the chunk's labels of image b, in index order, of part[label][sel][c]
+// acc[sel][b][c] (+)= sum over the chunk's labels of image b, in index order, of part[label][sel][c]; a label has
+// `pstride` planes (the diagonal form: NPART * cx; the full form: one selector of `cx` = all its planes)
 __global__ __launch_bounds__(NE) void k_grad_reduce(const double *__restrict__ part, double *__restrict__ acc, int n0, int nz, int cy,
-                                                   int cx, int B, int nsel, int64_t hw)
+                                                   int cx, int B, int nsel, int pstride, int64_t hw)
 {
     const int64_t q = (int64_t)blockIdx.x * NE + threadIdx.x;
     if (q >= hw) return;
@@ -840,7 +848,7 @@ __global__ __launch_bounds__(NE) void k_grad_reduce(const double *__restrict__ p
     const int na = max(n0, b * cy), nb = min(n0 + nz, (b + 1) * cy);
     for (int sel = 0; sel < nsel; sel++) {
         double s = 0.0;
-        for (int n = na; n < nb; n++) s += part[(((int64_t)(n - n0) * NPART + sel) * cx + c) * hw + q];
+        for (int n = na; n < nb; n++) s += part[((int64_t)(n - n0) * pstride + (int64_t)sel * cx + c) * hw + q];
         double *d = acc + (((int64_t)sel * B + b) * cx + c) * hw + q;
         *d = na == b * cy ? s : *d + s;
     }
@@ -908,17 +916,18 @@ __global__ __launch_bounds__(NT) void k_grad_x(const float *__restrict__ F, cons
 
 // grad_eps_c = sum over images and pixels of gvar_c = (gvar_c / N) N: stage 1, NEB workgroups per channel, each thread a
 // fixed strided share in index order, then a fixed tree in LDS; stage 2 adds the NEB partial sums in index order
+// (gvn: `stride` planes an image; channel c's is plane c, or with `pairs` plane pair_plane(c, c) of the full form's gS)
 __global__ __launch_bounds__(NE) void k_grad_eps1(const double *__restrict__ gvn, double *__restrict__ partial, int B, int cx, int h,
-                                                 int w, int r)
+                                                 int w, int r, int stride, int pairs)
 {
     __shared__ double sh[NE];
-    const int c = blockIdx.y;
+    const int c = blockIdx.y, pl = pairs ? pair_plane(c, c, cx) : c;
     const int64_t hw = (int64_t)h * w, total = (int64_t)B * hw;
     double s = 0.0;
     for (int64_t e = (int64_t)blockIdx.x * NE + threadIdx.x; e < total; e += (int64_t)NEB * NE) {
         const int64_t b = e / hw, q = e % hw;
         const double n = (double)win_count((int)(q / w), r, h) * (double)win_count((int)(q % w), r, w);
-        s += gvn[(b * cx + c) * hw + q] * n;
+        s += gvn[(b * stride + pl) * hw + q] * n;
     }
     sh[threadIdx.x] = s;
     __syncthreads();
@@ -987,9 +996,10 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
         coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(ys, xs, P, mx, inv, Q, A, part, (int)n0, cy, cx, h, w, re);
         if (need_apply)
             apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low, col_of_low,
-                                                            (int)n0, cy, cx, H, W, h, w, re, subtract_is_y);
+                                                            (int)n0, cy, cx, H, W, h, w, re, subtract_is_y, NPART * cx, PART_YU * cx);
         if (need_xe)
-            k_grad_reduce<<<dim3(nblo, (unsigned)cx, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, cx, B, need_x ? NPART : 2, hw);
+            k_grad_reduce<<<dim3(nblo, (unsigned)cx, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, cx, B, need_x ? NPART : 2,
+                                                                            NPART * cx, hw);
         if (need_x)
             k_grad_direct<<<dim3(nbfull, (unsigned)cx, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy, cx,
                                                                               H, W, h, w);
@@ -1002,8 +1012,213 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
         phl_launched(rc, "k_grad_finish / k_grad_x");
     }
     if (grad_eps && rc == PHL_OK) {
-        k_grad_eps1<<<dim3(NEB, (unsigned)cx), dim3(NE), 0, st>>>(acc, epart, B, cx, h, w, re);
+        k_grad_eps1<<<dim3(NEB, (unsigned)cx), dim3(NE), 0, st>>>(acc, epart, B, cx, h, w, re, cx, 0);
         k_grad_eps2<<<dim3(1), dim3(64), 0, st>>>(epart, grad_eps, cx);
+        phl_launched(rc, "k_grad_eps");
+    }
+    return tmp.release();
+}
+
+// ---- backward of the full-covariance model -------------------------------------------------------------------------
+// With m_c = mx_c, Sig = S (run_full's header), P = (Sig + diag(eps))^-1, cv_ld = cov_ld, and gA, gb, gA' as above:
+//   gcv_ld = sum_c gA'_lc P_cd      gSig_cd = -1/2 sum_l (A_lc gcv_ld + A_ld gcv_lc)      gmy_l = gb_l - sum_d gcv_ld m_d
+//   gm_c = -sum_l gb_l A_lc - sum_l gcv_lc my_l - 2 sum_d gSig_cd m_d
+//   U_l0 = S(gmy_l / N)   U_lc = S(gcv_lc / N)   V_cd = S(gSig_cd / N)
+//   gys_l = U_l0 + sum_c xs_c U_lc          gxs_c = sum_l ys_l U_lc + S(gm_c / N) + 2 sum_d xs_d V_cd
+//   grad_y, grad_x from gys, gxs and mean(A) as above          grad_eps_c = sum gSig_cc
+// (the diagonal form is the case of a diagonal P: gvar_c = gSig_cc).  U, gys and mean(A) have the diagonal form's shape, so
+// run_full_grad is run_grad with k_guide_stats_full for the statistics and three kernels of its own:
+//   k_grad_coef_full    per (label, tile), the channel count a template parameter as in the forward: the window sums of ys,
+//                       ys xs_c, gb and gA_c stay in registers; cv, A = cv P, gA', gcv = gA' P, gmy per pixel in fp64 ->
+//                       gcv_lc / N and gmy_l / N (the Q planes of k_grad_apply), A_lc (for grad_x), and as fp64 planes this
+//                       label's terms of gSig_cd / N (pair_plane order) and of gm_c / N without its gSig term
+//   k_grad_finish_full  once: gm_c / N with its - 2 sum_d gSig_cd m_d term and the gSig_cd / N, as fp32 planes
+//   k_grad_x_full       per (image, tile): gxs_c (cx + 1 window sums per channel) into LDS -> grad_x as k_grad_x
+// A label's fp64 planes: [npairs gSig][cx gm][cx ys_l U_lc]; k_grad_reduce sums them into acc [B][npairs + 2 cx][h][w].
+template <bool ST, int CX>
+__global__ __launch_bounds__(NT) void k_grad_coef_full(const float *__restrict__ ys, const float *__restrict__ xs,
+                                                      const float *__restrict__ Pd, const double *__restrict__ mx,
+                                                      const double *__restrict__ Pm, float *__restrict__ Q, float *__restrict__ A,
+                                                      double *__restrict__ part, int n0, int cy, int h, int w, int r)
+{
+    constexpr int NP = npairs(CX), NPL = NP + 2 * CX;
+    Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_COEF);
+    const int z = blockIdx.z, b = (n0 + z) / cy;
+    const int64_t hw = (int64_t)h * w;
+    const float *yp = ys + (int64_t)z * hw, *xb = xs + (int64_t)b * CX * hw, *gd = Pd + (int64_t)z * (CX + 1) * hw;
+    const double *mp = mx + (int64_t)b * CX * hw, *pp = Pm + (int64_t)b * NP * hw;
+    float *qp = Q + (int64_t)z * (CX + 1) * hw, *ap = A ? A + (int64_t)z * CX * hw : nullptr;
+    double *tp = part ? part + (int64_t)z * NPL * hw : nullptr;
+
+    double my[RPT], gb[RPT], rn[RPT], s[RPT], cov[CX][RPT], gA[CX][RPT];
+    recip_counts(t, rn);
+    plane_sums<ST>(t, t.in, yp, s);                                 // (tiled form: ys stays in LDS for the products below)
+#pragma unroll
+    for (int k = 0; k < RPT; k++) my[k] = s[k] * rn[k];
+    static_for<CX>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        product_sums<ST>(t, yp, xb + c * hw, s);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) cov[c][k] = s[k] * rn[k];       // mean(y x_c) for now
+    });
+    plane_sums<ST>(t, t.in2, gd + CX * hw, gb);
+    static_for<CX>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        plane_sums<ST>(t, t.in2, gd + c * hw, gA[c]);
+    });
+    for_pixels(t, [&](int k, int64_t o) {
+        double m[CX], p[NP], cv[CX], gap[CX], a[CX], gcv[CX], gmy = gb[k];
+#pragma unroll
+        for (int c = 0; c < CX; c++) m[c] = mp[c * hw + o], cv[c] = cov[c][k] - my[k] * m[c], gap[c] = gA[c][k] - gb[k] * m[c];
+#pragma unroll
+        for (int i = 0; i < NP; i++) p[i] = pp[i * hw + o];
+#pragma unroll
+        for (int c = 0; c < CX; c++) {
+            double va = 0.0, vg = 0.0;
+#pragma unroll
+            for (int d = 0; d < CX; d++) {
+                const double pcd = p[pair_plane(min(c, d), max(c, d), CX)];
+                va += cv[d] * pcd, vg += gap[d] * pcd;
+            }
+            a[c] = va, gcv[c] = vg;
+            gmy -= vg * m[c];
+            qp[c * hw + o] = (float)(vg * rn[k]);
+            if (ap) ap[c * hw + o] = (float)va;
+        }
+        qp[CX * hw + o] = (float)(gmy * rn[k]);
+        if (tp) {
+#pragma unroll
+            for (int c = 0; c < CX; c++) {
+#pragma unroll
+                for (int d = c; d < CX; d++) tp[pair_plane(c, d, CX) * hw + o] = -0.5 * (a[c] * gcv[d] + a[d] * gcv[c]) * rn[k];
+                tp[(NP + c) * hw + o] = -(gb[k] * a[c] + gcv[c] * my[k]) * rn[k];
+            }
+        }
+    });
+}
+
+// F[b][c] = gm_c / N, c < cx, and F[b][cx + i] = gSig / N of pair i, from acc [B][npl][h][w] (gSig first, then gm's terms)
+__global__ __launch_bounds__(NE) void k_grad_finish_full(const double *__restrict__ acc, const double *__restrict__ mx,
+                                                        float *__restrict__ F, int cx, int npl, int64_t hw)
+{
+    const int64_t q = (int64_t)blockIdx.x * NE + threadIdx.x;
+    if (q >= hw) return;
+    const int b = blockIdx.z, np = npairs(cx);
+    const double *ab = acc + (int64_t)b * npl * hw + q, *mb = mx + (int64_t)b * cx * hw + q;
+    float *fb = F + (int64_t)b * (cx + np) * hw + q;
+    for (int c = 0; c < cx; c++) {
+        double v = ab[(int64_t)(np + c) * hw];
+        for (int d = 0; d < cx; d++) v -= 2.0 * ab[(int64_t)pair_plane(min(c, d), max(c, d), cx) * hw] * mb[(int64_t)d * hw];
+        fb[(int64_t)c * hw] = (float)v;
+    }
+    for (int i = 0; i < np; i++) fb[(int64_t)(cx + i) * hw] = (float)ab[(int64_t)i * hw];
+}
+
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_grad_x_full(const float *__restrict__ F, const double *__restrict__ acc,
+                                                   const float *__restrict__ xs, const double *__restrict__ D,
+                                                   float *__restrict__ grad_x, const int *__restrict__ rmapS,
+                                                   const int *__restrict__ cmapS, int cx, int npl, int H, int W, int h, int w, int r,
+                                                   float scale)
+{
+    Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_APPLY);
+    double *G = reinterpret_cast<double *>(t.in2);
+    const int b = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i0 = t.ti + wave * RPT, j = t.tj + lane;
+    const int np = npairs(cx);
+    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W;
+    const float *fb = F + (int64_t)b * (cx + np) * hw, *xb = xs + (int64_t)b * cx * hw;
+    const double *yu = acc + ((int64_t)b * npl + np + cx) * hw;      // sum_l ys_l U_lc
+    for (int c = 0; c < cx; c++) {
+        double v[RPT], s[RPT];
+        plane_sums<ST>(t, t.in, fb + (int64_t)c * hw, v);
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            const bool in = i0 + k < h && j < w;
+            v[k] = in ? v[k] + yu[(int64_t)c * hw + (int64_t)(i0 + k) * w + j] : 0.0;
+        }
+        for (int d = 0; d < cx; d++) {
+            plane_sums<ST>(t, t.in, fb + (int64_t)(cx + pair_plane(min(c, d), max(c, d), cx)) * hw, s);
+#pragma unroll
+            for (int k = 0; k < RPT; k++)
+                if (i0 + k < h && j < w) v[k] += 2.0 * (double)xb[(int64_t)d * hw + (int64_t)(i0 + k) * w + j] * s[k];
+        }
+#pragma unroll
+        for (int k = 0; k < RPT; k++) G[(wave * RPT + k) * TW + lane] = v[k];
+        __syncthreads();
+        const double *dp = D + ((int64_t)b * cx + c) * HWf;
+        float *op = grad_x + ((int64_t)b * cx + c) * HWf;
+        scatter_tile(t, G, rmapS, cmapS, H, W, [&](int64_t o, double v) { op[o] = (float)((double)scale * dp[o] + v); });
+        // (the next channel's first write to G comes after the barriers of its plane_sums)
+    }
+}
+
+template <bool ST, int CX>
+int run_full_grad(const Plan &p, const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B,
+                  int cy, int H, int W, int h, int w, int re, const int *row_of_low, const int *col_of_low, const int *low_of_row,
+                  const int *low_of_col, const float *eps, float scale, int subtract_is_y, hipStream_t st)
+{
+    constexpr int NP = npairs(CX), NPL = NP + 2 * CX;
+    const bool full = h == H && w == W;
+    const bool need_x = grad_x != nullptr, need_xe = need_x || grad_eps != nullptr, need_apply = need_x || grad_y != nullptr;
+    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, nimg = (int64_t)B * cy;
+    const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
+    auto stats = k_guide_stats_full<ST, CX>;
+    auto coefk = k_grad_coef_full<ST, CX>;
+    auto apply = k_grad_apply<ST>;
+    auto gxk = k_grad_x_full<ST>;
+    if (int rc = phl_allow_lds(stats, p.lds_coef)) return rc;
+    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
+    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
+    if (int rc = phl_allow_lds(gxk, p.lds_apply)) return rc;
+
+    const int64_t chunk = Plan::chunk(nimg, Plan::per_backward_full(CX, hw, full, need_x, need_xe));
+    const size_t nstat = (size_t)B * CX * hw;
+    const int nred = need_x ? NPL : NP;                // planes of a label that anything reads after the sum over labels
+    phl_temps tmp(st);
+    double *mx = tmp.get<double>(nstat), *Pm = tmp.get<double>((size_t)B * NP * hw);
+    float *xsb = full ? nullptr : tmp.get<float>(nstat);
+    float *ysb = full ? nullptr : tmp.get<float>((size_t)chunk * hw);
+    float *Pd = tmp.get<float>((size_t)chunk * (CX + 1) * hw), *Q = tmp.get<float>((size_t)chunk * (CX + 1) * hw);
+    float *A = need_x ? tmp.get<float>((size_t)chunk * CX * hw) : nullptr, *mA = need_x ? tmp.get<float>((size_t)chunk * CX * hw) : nullptr;
+    double *part = need_xe ? tmp.get<double>((size_t)chunk * NPL * hw) : nullptr;
+    double *acc = need_xe ? tmp.get<double>((size_t)B * NPL * hw) : nullptr;
+    float *F = need_x ? tmp.get<float>((size_t)B * (CX + NP) * hw) : nullptr;
+    double *D = need_x ? tmp.get<double>((size_t)B * CX * HWf) : nullptr;
+    double *epart = grad_eps ? tmp.get<double>((size_t)CX * NEB) : nullptr;
+    int &rc = tmp.rc;
+    const float *xs = full ? x : xsb;
+    if (rc == PHL_OK) {
+        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(x, row_of_low, col_of_low, eps, mx, Pm, H, W, h, w, re);
+        if (!full)
+            k_grad_gather<<<dim3(nblo, (unsigned)CX, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
+        phl_launched(rc, "k_guide_stats_full / k_grad_gather");
+    }
+    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
+        const unsigned nz = (unsigned)min(chunk, nimg - n0);
+        const unsigned nb = (unsigned)((n0 + nz - 1) / cy - n0 / cy + 1);          // images the chunk touches
+        const float *ys = full ? y + n0 * HWf : ysb;
+        if (!full) k_grad_gather<<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
+        k_grad_down<<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, Pd, low_of_row, low_of_col, (int)n0, cy, CX, H, W, h, w, re, scale);
+        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(ys, xs, Pd, mx, Pm, Q, A, part, (int)n0, cy, h, w, re);
+        if (need_apply)
+            apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low, col_of_low,
+                                                            (int)n0, cy, CX, H, W, h, w, re, subtract_is_y, NPL, NP + CX);
+        if (need_xe)
+            k_grad_reduce<<<dim3(nblo, (unsigned)nred, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, NPL, B, 1, NPL, hw);
+        if (need_x)
+            k_grad_direct<<<dim3(nbfull, (unsigned)CX, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy, CX,
+                                                                              H, W, h, w);
+        phl_launched(rc, "the full backward's chunk kernels");
+    }
+    if (need_x && rc == PHL_OK) {
+        k_grad_finish_full<<<dim3(nblo, 1, (unsigned)B), dim3(NE), 0, st>>>(acc, mx, F, CX, NPL, hw);
+        gxk<<<p.grid((unsigned)B), dim3(NT), p.lds_apply, st>>>(F, acc, xs, D, grad_x, row_of_low, col_of_low, CX, NPL, H, W, h, w, re,
+                                                               scale);
+        phl_launched(rc, "k_grad_finish_full / k_grad_x_full");
+    }
+    if (grad_eps && rc == PHL_OK) {
+        k_grad_eps1<<<dim3(NEB, (unsigned)CX), dim3(NE), 0, st>>>(acc, epart, B, CX, h, w, re, NPL, 1);
+        k_grad_eps2<<<dim3(1), dim3(64), 0, st>>>(epart, grad_eps, CX);
         phl_launched(rc, "k_grad_eps");
     }
     return tmp.release();
@@ -1126,6 +1341,46 @@ int phl_guided_filter_grad(const float *y, const float *x, const float *g, float
     const int re = min(r, max(h, w));
     return run_grad(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps,
                     scale, subtract_is_y, (hipStream_t)stream);
+}
+
+int phl_guided_filter_full_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B,
+                                int cy, int cx, int H, int W, int h, int w, int r, const int *row_of_low, const int *col_of_low,
+                                const int *low_of_row, const int *low_of_col, const float *eps, float scale, int subtract_is_y,
+                                phl_stream stream)
+{
+    if (int rc = check_guided_args("phl_guided_filter_full_grad", y, x, g, "g", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low,
+                                   low_of_row, low_of_col, eps, scale))
+        return rc;
+    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
+    if (cx > PHL_GUIDED_FULL_MAX_CX) {
+        phl_set_error("phl_guided_filter_full_grad: %d guide channels, at most %d (PHL_GUIDED_FULL_MAX_CX)", cx,
+                      PHL_GUIDED_FULL_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    const void *ins[4] = {y, x, g, eps}, *outs[3] = {grad_y, grad_x, grad_eps};
+    for (int o = 0; o < 3; o++)
+        for (int i = 0; i < 4; i++)
+            if (outs[o] && (outs[o] == ins[i] || (i < o && outs[o] == outs[i]))) {
+                phl_set_error("phl_guided_filter_full_grad: a gradient aliases an input or another gradient");
+                return PHL_ERR_INVALID;
+            }
+    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
+    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, float *, float *, int, int, int, int, int, int,
+                        int, const int *, const int *, const int *, const int *, const float *, float, int, hipStream_t);
+    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX] = {
+        {run_full_grad<false, 1>, run_full_grad<false, 2>, run_full_grad<false, 3>, run_full_grad<false, 4>},
+        {run_full_grad<true, 1>, run_full_grad<true, 2>, run_full_grad<true, 3>, run_full_grad<true, 4>}};
+    const int re = min(r, max(h, w));
+    const Plan p(re, h, w);
+    return runs[p.tiled ? 0 : 1][cx - 1](p, y, x, g, grad_y, grad_x, grad_eps, B, cy, H, W, h, w, re, row_of_low, col_of_low, low_of_row,
+                                        low_of_col, eps, scale, subtract_is_y, (hipStream_t)stream);
+}
+
+int phl_guided_filter_full_grad_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs)
+{
+    if (B < 1 || cy < 1 || cx < 1 || cx > PHL_GUIDED_FULL_MAX_CX || h < 1 || w < 1 || needs < 0 || needs > 7) return 0;
+    const bool need_x = (needs & 2) != 0, need_xe = (needs & 6) != 0;
+    return (int)Plan::chunk((int64_t)B * cy, Plan::per_backward_full(cx, (int64_t)h * w, full != 0, need_x, need_xe));
 }
 
 }  // extern "C"

@@ -116,6 +116,8 @@ _ABI = (
     ("phl_guided_filter_labels_per_chunk", "i", "iiiiiii"),
     ("phl_guided_filter_grad", "i", "PPPPPPiiiiiiiiPPPPPfiS"),
     ("phl_guided_filter_grad_max_r", "i", ""),
+    ("phl_guided_filter_full_grad", "i", "PPPPPPiiiiiiiiPPPPPfiS"),
+    ("phl_guided_filter_full_grad_labels_per_chunk", "i", "iiiiiii"),
     ("phl_stream_copy", "i", "PPqS"),
     ("phl_copy2d", "i", "PqqPqqqiS"),
     ("phl_tile_stats", "i", "PiP"),
@@ -1423,13 +1425,19 @@ def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=No
     return out
 
 
-def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False, need_x=False, need_eps=False, grad=None):
+def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False, need_x=False, need_eps=False, grad=None,
+                                   full_cov=False):
     """Labels (of the B * cy planes of y) that one chunk of a guided_filter call holds at the solving resolution h x w,
     or, with any ``need_*`` flag or ``grad=True``, of the guided_filter_grad call that is asked for those gradients
-    (``full``: subsample == 1).  Host arithmetic of the library (phl_guided_filter_labels_per_chunk), no device needed."""
+    (``full``: subsample == 1; ``full_cov``: of the guided_filter_full_grad call -- the forward's chunks do not depend on
+    the model).  Host arithmetic of the library (phl_guided_filter_labels_per_chunk,
+    phl_guided_filter_full_grad_labels_per_chunk), no device needed."""
     needs = (1 if need_y else 0) | (2 if need_x else 0) | (4 if need_eps else 0)
     if grad is None:
         grad = needs != 0
+    if full_cov and grad:
+        return int(_call("phl_guided_filter_full_grad_labels_per_chunk", int(B), int(cy), int(cx), int(h), int(w), 1 if full else 0,
+                         needs, value=True))
     return int(_call("phl_guided_filter_labels_per_chunk", int(B), int(cy), int(cx), int(h), int(w), 1 if full else 0,
                      needs if grad else -1, value=True))
 
@@ -1474,7 +1482,21 @@ def guided_filter_grad(y, x, g, r, eps, *, subsample=1, scale=1.0, subtract_is_y
     grad_eps has cx values.  Nothing of the forward is needed: the kernels recompute it from y, x and eps.  The same tensor
     rules as guided_filter (fp32 CUDA, any strides, any radius; PhlError status 7 for more than 16 guide channels); the
     same bits on every run."""
-    cx, e, dims, maps = _guided_launch_args("guided_filter_grad", y, x, g, "g", r, eps, subsample, need_y or need_x or need_eps)
+    return _guided_grad("guided_filter_grad", "phl_guided_filter_grad", y, x, g, r, eps, subsample, scale, subtract_is_y, need_y, need_x,
+                        need_eps)
+
+
+def guided_filter_full_grad(y, x, g, r, eps, *, subsample=1, scale=1.0, subtract_is_y=False, need_y=True, need_x=False,
+                            need_eps=False):
+    """Backward of ``guided_filter(..., full_cov=True)`` (phl_guided_filter_full_grad): arguments, return value and rules
+    of guided_filter_grad; PhlError status 7 for more than GUIDED_FULL_MAX_CX guide channels."""
+    return _guided_grad("guided_filter_full_grad", "phl_guided_filter_full_grad", y, x, g, r, eps, subsample, scale, subtract_is_y,
+                        need_y, need_x, need_eps)
+
+
+def _guided_grad(name, entry, y, x, g, r, eps, subsample, scale, subtract_is_y, need_y, need_x, need_eps):
+    """guided_filter_grad and guided_filter_full_grad: one argument list, two entry points."""
+    cx, e, dims, maps = _guided_launch_args(name, y, x, g, "g", r, eps, subsample, need_y or need_x or need_eps)
     new = torch.zeros if y.numel() == 0 else torch.empty
     gy = new(y.shape, dtype=torch.float32, device=y.device) if need_y else None
     gx = new(x.shape, dtype=torch.float32, device=y.device) if need_x else None
@@ -1482,7 +1504,7 @@ def guided_filter_grad(y, x, g, r, eps, *, subsample=1, scale=1.0, subtract_is_y
     if dims is None:
         return gy, gx, ge
     yc, xc, gc = y.contiguous(), x.contiguous(), g.contiguous()         # (named: a copy must outlive the launch)
-    _launch(y.device, "phl_guided_filter_grad", _ptr(yc), _ptr(xc), _ptr(gc), _ptr(gy), _ptr(gx), _ptr(ge), *dims,
+    _launch(y.device, entry, _ptr(yc), _ptr(xc), _ptr(gc), _ptr(gy), _ptr(gx), _ptr(ge), *dims,
             *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)), 1 if subtract_is_y else 0)
     return gy, gx, ge
 
@@ -1506,6 +1528,30 @@ class GuidedFilterFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         gy, gx, ge = guided_filter_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0], need_x=need[1],
                                         need_eps=need[2])
+        if ge is not None:
+            ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
+        return gy, gx, ge, None, None, None, None
+
+
+class GuidedFilterFullFn(torch.autograd.Function):
+    """GuidedFilterFn for the full-covariance model: ``guided_filter(y, x, r, eps, full_cov=True) * scale - (y if
+    subtract_is_y else 0)`` with its backward on guided_filter_full_grad.  Only y, x and eps are saved, one backward call
+    computes the gradients that are asked for.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, y, x, eps, r, subsample, scale, subtract_is_y):
+        ctx.save_for_backward(y, x, eps)
+        ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
+        return guided_filter(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None, full_cov=True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        y, x, eps = ctx.saved_tensors
+        r, s, scale, sub = ctx.args
+        need = ctx.needs_input_grad
+        gy, gx, ge = guided_filter_full_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0],
+                                             need_x=need[1], need_eps=need[2])
         if ge is not None:
             ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
         return gy, gx, ge, None, None, None, None

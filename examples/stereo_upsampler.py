@@ -6,11 +6,12 @@ left image at full resolution go through the head's forward, then one training s
     E0, labels = phl.nchw_scalar_unaries(disp_lowres, (H, W), 18, gamma, s)      -> phl_nchw_scalar_unaries, two launches
     depth      = CRFasRNN(charb(.05), niters=2, r, gchannels=3).expected_depth(img, None, energies=E0, labels=labels, values=labels)
 
-    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8] [--fused-step] [--full-cov]
+    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8] [--fused-step] [--full-cov [--full-cov-grad]]
 
 --fused-step runs the training step with ``CRFdepthUpsampler(fused_grad=True, fused_step=True)``: W on phl.GuidedFilterFn
 and everything between two W calls on phl.NchwStepTrain.  --full-cov gives W the full covariance of the RGB guide
-(``CRFdepthUpsampler(full_cov=True)``): the forward on phl.guided_filter(full_cov=True), the training step on the torch form.
+(``CRFdepthUpsampler(full_cov=True)``): the forward on phl.guided_filter(full_cov=True), the training step on the torch form --
+or, with --full-cov-grad (``full_cov_grad=True``), on phl.GuidedFilterFullFn, the model's backward kernels.
 
 Prints the mean absolute disparity error of the plain bilinear enlargement and of the head's output against the known
 disparity, and the loss before and after the step.
@@ -27,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from stereo_crf import synthetic_pair  # noqa: E402
 
 
-def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=False, full_cov=False):
+def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=False, full_cov=False, full_cov_grad=False):
     import torch
     import torch.nn.functional as F
 
@@ -39,7 +40,8 @@ def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=Fals
     truth = torch.from_numpy(truth).to(dev).float()[None, None]
     low = F.interpolate(truth, size=(h // factor, w // factor), mode="bilinear", align_corners=False)
     low[:, :, 2:6, 3:9] = 0                                                   # no measurement there
-    net = CRFdepthUpsampler(r=r, niters=2, fused_grad=fused_step, fused_step=fused_step, full_cov=full_cov).to(dev)
+    net = CRFdepthUpsampler(r=r, niters=2, fused_grad=fused_step, fused_step=fused_step, full_cov=full_cov,
+                            full_cov_grad=full_cov_grad).to(dev)
     torch.cuda.synchronize()
     t0 = time.time()
     with torch.no_grad():
@@ -76,8 +78,10 @@ if __name__ == "__main__":
     ap.add_argument("--factor", type=int, default=8)
     ap.add_argument("--fused-step", action="store_true", help="the training step on phl.NchwStepTrain / phl.GuidedFilterFn")
     ap.add_argument("--full-cov", action="store_true", help="W with the full covariance of the RGB guide")
+    ap.add_argument("--full-cov-grad", action="store_true", help="with --full-cov: train that W on phl.GuidedFilterFullFn")
     a = ap.parse_args()
-    run(a.h, a.w, a.r, a.factor, fused_step=a.fused_step, full_cov=a.full_cov)     # first run of the process: library load, first launches, first allocations
+    kw = dict(fused_step=a.fused_step, full_cov=a.full_cov, full_cov_grad=a.full_cov_grad)
+    run(a.h, a.w, a.r, a.factor, **kw)     # first run of the process: library load, first launches, first allocations
     t1 = time.time()
-    run(a.h, a.w, a.r, a.factor, quiet=True, fused_step=a.fused_step, full_cov=a.full_cov)
+    run(a.h, a.w, a.r, a.factor, quiet=True, **kw)
     print(f"the same again, warm: {(time.time() - t1) * 1e3:.1f} ms end to end (synthetic pair generated on the CPU included)")

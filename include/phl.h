@@ -549,7 +549,7 @@ int phl_guided_filter(const float *y_dev, const float *x_dev, const float *src_d
                       int W, int h, int w, int r, const int *row_of_low_dev, const int *col_of_low_dev, const int *low_of_row_dev,
                       const int *low_of_col_dev, const float *eps_dev, float scale, phl_stream stream);
 /* The same filter with the full covariance of the guide channels (the model the reference keeps as commented lines,
- * crf/gaussian_matrix.py:204-212), forward only; arguments, maps, window sums and out exactly as phl_guided_filter, but
+ * crf/gaussian_matrix.py:204-212; its backward: phl_guided_filter_full_grad); arguments, maps, window sums and out exactly as phl_guided_filter, but
  *   S_cd = mean(xl_c xl_d) - mean(xl_c) mean(xl_d)      P = (S + diag(eps))^-1      A_lc = sum_d cov_ld P_dc
  * with cov_ld = mean(yl_l xl_d) - mean(yl_l) mean(xl_d); cx = 1 is the model above.  P is computed once per image in fp64
  * (L D L^T without pivoting; a non-positive pivot, eps <= 0 on a flat window, gives inf or nan) and kept as
@@ -584,6 +584,22 @@ int phl_guided_filter_grad(const float *y_dev, const float *x_dev, const float *
                            const int *row_of_low_dev, const int *col_of_low_dev, const int *low_of_row_dev,
                            const int *low_of_col_dev, const float *eps_dev, float scale, int subtract_is_y, phl_stream stream);
 int phl_guided_filter_grad_max_r(void);   /* largest radius of the backward's LDS-tiled form */
+/* Backward of phl_guided_filter_full: the argument list, the outputs, the maps and the rules of phl_guided_filter_grad.
+ * With P, A and cov_ld as there, gA_lc / gb_l the window-summed gradients of mean(A) / mean(b), gA'_lc = gA_lc - gb_l m_c:
+ *   gcov_ld = sum_c gA'_lc P_cd      gS_cd = -1/2 sum_l (A_lc gcov_ld + A_ld gcov_lc)      grad_eps_c = sum gS_cc
+ * and gS enters grad_x through all cx (cx + 1) / 2 products xl_c xl_d.  mx and P are recomputed once per call (fp64), the
+ * per-label terms of gS and of the gradient of mean(xl) are fp64 planes summed over the labels in index order; no atomics,
+ * the same bits on every run, every gradient rounded to fp32 once.
+ * Status as phl_guided_filter_grad, then (after the zero-element return) PHL_ERR_UNSUPPORTED for
+ * cx > PHL_GUIDED_FULL_MAX_CX, then the aliasing check; all before any HIP call.  The tiled radius is
+ * phl_guided_filter_grad_max_r(). */
+int phl_guided_filter_full_grad(const float *y_dev, const float *x_dev, const float *g_dev, float *grad_y_dev, float *grad_x_dev,
+                                float *grad_eps_dev, int B, int cy, int cx, int H, int W, int h, int w, int r,
+                                const int *row_of_low_dev, const int *col_of_low_dev, const int *low_of_row_dev,
+                                const int *low_of_col_dev, const float *eps_dev, float scale, int subtract_is_y, phl_stream stream);
+/* Labels per chunk of a phl_guided_filter_full_grad call; needs is the bit mask 1 = grad_y, 2 = grad_x, 4 = grad_eps, the
+ * other arguments as phl_guided_filter_labels_per_chunk.  0 for sizes below 1, cx > PHL_GUIDED_FULL_MAX_CX or another needs. */
+int phl_guided_filter_full_grad_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs);
 
 /* Plain float4 streaming copy dst <- src (n_floats % 4 == 0, 16-byte aligned): measures the
  * HBM read+write ceiling of the box that the roofline fractions are compared with. */
