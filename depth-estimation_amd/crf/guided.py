@@ -23,6 +23,11 @@ recorded forward is then phl.GuidedFilterFullFn, whose backward (phl.guided_filt
 and the inverse from y, x and eps and gives y, x and omega their gradients; what the kernels do not take stays on the
 torch form as before.
 
+``mode='bilinear'`` of FastGuidedFilter / BatchedGuidedAdjacency (coefficients solved on the bilinearly down-sampled
+images and interpolated back up) reaches the kernels under the keyword ``fused_bilinear=True``: a forward that autograd
+does not record is then phl.guided_filter_bilinear (either model; the taps are computed on the device).  Without the
+keyword, and for every recorded forward, the mode keeps the torch form.
+
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
     box_filter(x, r, dim)            one normalised box pass (window of 2r samples, divisor of 2r+1: see _box_torch)
@@ -215,15 +220,23 @@ class GuidedFilter(nn.Module):
         ``fused_grad`` (with ``full_cov``: without ``full_cov_grad``), or a shape the kernels do not take
         (PHL_ERR_UNSUPPORTED: more than 16 guide channels, with ``full_cov`` more than phl.GUIDED_FULL_MAX_CX).  With
         ``fused_grad`` a recorded forward is phl.GuidedFilterFn, with ``full_cov_grad`` phl.GuidedFilterFullFn (eps =
-        softplus(omega) keeps its graph); ``subtract`` is None or y itself."""
-        if self.gaussian or getattr(self, "mode", "nearest") != "nearest" or not (_hip_ok(y) and _hip_ok(x)):
+        softplus(omega) keeps its graph); ``subtract`` is None or y itself.  FastGuidedFilter's ``mode='bilinear'`` with
+        ``fused_bilinear=True`` is phl.guided_filter_bilinear for a forward that autograd does not record (at subsample 1
+        both interpolations are the identity: the nearest route); a recorded one keeps the torch form, ``fused_grad`` /
+        ``full_cov_grad`` or not."""
+        mode = getattr(self, "mode", "nearest")
+        bilinear = mode == "bilinear" and getattr(self, "fused_bilinear", False)
+        if self.gaussian or not (mode == "nearest" or bilinear) or not (_hip_ok(y) and _hip_ok(x)):
             return None
         if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
             return None
         recording = torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad)
-        if recording and not (self.full_cov_grad if self.full_cov else self.fused_grad):
+        if recording and (bilinear or not (self.full_cov_grad if self.full_cov else self.fused_grad)):
             return None
         try:
+            if bilinear and subsample >= 2:
+                return phl.guided_filter_bilinear(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract,
+                                                  full_cov=self.full_cov)
             if self.full_cov and recording:
                 return phl.GuidedFilterFullFn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             if self.full_cov:
@@ -248,13 +261,16 @@ class GuidedFilter(nn.Module):
 class FastGuidedFilter(GuidedFilter):
     """Coefficients solved at 1/subsample_ratio resolution and upsampled (:234-253)."""
 
-    def __init__(self, *args, subsample_ratio=2, mode="nearest", **kwargs):
+    def __init__(self, *args, subsample_ratio=2, mode="nearest", fused_bilinear=False, **kwargs):
         super().__init__(*args, **kwargs)
         if self.gaussian:
             # the reference's constructor reads self._r, which its gaussian form never sets (AttributeError, :238)
             raise NotImplementedError("FastGuidedFilter(gaussian=True) does not construct in the reference either")
+        if fused_bilinear and mode != "bilinear":
+            raise ValueError(f"fused_bilinear=True is the kernel route of mode='bilinear', got mode={mode!r}")
         self.subsample_ratio = subsample_ratio
         self.mode = mode
+        self.fused_bilinear = fused_bilinear
 
     def _window(self):
         return self._r // self.subsample_ratio

@@ -21,7 +21,9 @@
 //                   the full-resolution pixels that map into the tile: fp64 sum over the channels, * scale - src, one
 //                   rounding into out (with more than four planes the partial sum passes through out between groups)
 // (phl_guided_filter_full, the model over the whole covariance matrix of the guide channels: k_guide_stats_full and
-// k_guide_coef_full in the places of the first two, after run() below; its backward after run_grad().)
+// k_guide_coef_full in the places of the first two, after run() below; its backward after run_grad().
+// phl_guided_filter_bilinear, FastGuidedFilter(mode='bilinear'): the first two kernels of either model with a four-tap
+// tile fill, then k_guide_mean and k_guide_up in the place of k_guide_apply, after run_full().)
 // Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
 // routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.  The
 // kernels of both directions reach the two forms through one front end (plane_sums, square_sums, product_sums).
@@ -41,6 +43,7 @@ constexpr int RPT = TH / 4;         // rows per thread
 constexpr int HSP = TW + 1;         // row stride of the fp64 plane: 16 consecutive rows hit 16 different bank pairs
 constexpr int NCO = 3;              // halo columns per lane: a halo row is at most 64 * NCO words
 constexpr int FU = 8;               // halo rows per wave whose loads tile_fill issues together
+constexpr int FUB = 2;              // ... of its bilinear form, four taps an element
 constexpr int SR = 64;               // rows per strip of the streamed form
 constexpr int GRP = 4;              // coefficient planes per pass of k_guide_apply
 constexpr size_t kMaxLds = 160 << 10;
@@ -65,6 +68,23 @@ __device__ __forceinline__ int win_count(int i, int r, int n) { return min(i + r
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
+// torch's bilinear tap (align_corners=False) of output index o along an axis that maps n_in samples to n_out, sc =
+// (double)n_in / n_out: the two source indices and the weight of the second, all in fp64 as the float64 torch form.
+// (The intrinsics keep the compiler from contracting the product and the subtraction into one rounding.)
+__device__ __forceinline__ void bil_tap(int o, double sc, int n_in, int &i0, int &i1, double &lam)
+{
+    const double src = fmax(__dsub_rn(__dmul_rn((double)o + 0.5, sc), 0.5), 0.0);
+    i0 = min((int)src, n_in - 1);
+    i1 = min(i0 + 1, n_in - 1);
+    lam = fmin(fmax(src - (double)i0, 0.0), 1.0);
+}
+// the bilinear sample from its four taps, in fp64
+__device__ __forceinline__ double bil_mix(float v00, float v01, float v10, float v11, double ly, double lx)
+{
+    const double a = (1.0 - lx) * (double)v00 + lx * (double)v01, b = (1.0 - lx) * (double)v10 + lx * (double)v11;
+    return (1.0 - ly) * a + ly * b;
+}
+
 struct Tile {
     double *hs;     // [TH + 2r][HSP] horizontal window sums
     float *in;      // [TH + 2r][halo_stride] the tile and its halo
@@ -74,11 +94,26 @@ struct Tile {
     int r, ti, tj, h, w;
     const int *rmap, *cmap;     // low-resolution row / column -> row / column of a source plane (null: the identity)
     int ph, pw;                 // source planes are ph x pw
+    // the bilinear sampler (BL: the low-resolution image is F.interpolate(plane, (h, w), mode='bilinear'), no maps): the
+    // axis scales ph / h and pw / w and, beside co, the second tap of this lane's halo columns and its weight
+    double sy, sx;
+    int co1[NCO];
+    double clam[NCO];
     // element (i, j) of the low-resolution image in a source plane, straight from memory (the streamed form)
+    template <bool BL = false>
     __device__ __forceinline__ float ld(const float *__restrict__ plane, int i, int j) const
     {
-        const int I = rmap ? min(max(rmap[i], 0), ph - 1) : i, J = cmap ? min(max(cmap[j], 0), pw - 1) : j;
-        return plane[(int64_t)I * pw + J];
+        if constexpr (BL) {
+            int i0, i1, j0, j1;
+            double ly, lx;
+            bil_tap(i, sy, ph, i0, i1, ly);
+            bil_tap(j, sx, pw, j0, j1, lx);
+            const float *p0 = plane + (int64_t)i0 * pw, *p1 = plane + (int64_t)i1 * pw;
+            return (float)bil_mix(p0[j0], p0[j1], p1[j0], p1[j1], ly, lx);          // D(.) is held in fp32, as the tile holds it
+        } else {
+            const int I = rmap ? min(max(rmap[i], 0), ph - 1) : i, J = cmap ? min(max(cmap[j], 0), pw - 1) : j;
+            return plane[(int64_t)I * pw + J];
+        }
     }
     // this thread's pixels are (i0() + k, j()), k < RPT; count(k) is N of pixel k (an axis outside the image counts 1)
     __device__ __forceinline__ int i0() const { return ti + (threadIdx.x >> 6) * RPT; }
@@ -91,11 +126,38 @@ struct Tile {
 
 // in[ih][jh] = plane[rowoff[ih] + co] at the low-resolution pixel (ti - r + ih, tj - r + jh), 0 outside the image; the
 // row's padding word is filled as well.  The loads of FU rows are issued before the first store: a fill costs a few
-// memory latencies, not one per row.
+// memory latencies, not one per row.  BL: every element is the bilinear sample of four taps (the row taps from bil_tap,
+// the column taps from the tile), rounded to fp32 once; FUB rows together keep as many loads in flight as FU do.
+template <bool BL = false>
 __device__ __forceinline__ void tile_fill(const Tile &t, float *__restrict__ in, const float *__restrict__ plane)
 {
     const int HH = halo_rows(t.r), st = halo_stride(t.r);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if constexpr (BL) {
+        for (int ih0 = wave; ih0 < HH; ih0 += 4 * FUB) {
+            float v[FUB][NCO];
+#pragma unroll
+            for (int u = 0; u < FUB; u++) {
+                const int ih = ih0 + 4 * u, i = t.ti - t.r + ih;
+                const bool row = ih < HH && i >= 0 && i < t.h;
+                int i0, i1;
+                double ly;
+                bil_tap(row ? i : 0, t.sy, t.ph, i0, i1, ly);
+                const float *p0 = plane + (int64_t)i0 * t.pw, *p1 = plane + (int64_t)i1 * t.pw;
+#pragma unroll
+                for (int m = 0; m < NCO; m++)
+                    v[u][m] = row && t.co[m] >= 0 ? (float)bil_mix(p0[t.co[m]], p0[t.co1[m]], p1[t.co[m]], p1[t.co1[m]], ly, t.clam[m]) : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < FUB; u++) {
+                const int ih = ih0 + 4 * u;
+#pragma unroll
+                for (int m = 0; m < NCO; m++)
+                    if (ih < HH && lane + 64 * m < st) in[ih * st + lane + 64 * m] = v[u][m];
+            }
+        }
+        return;
+    }
     for (int ih0 = wave; ih0 < HH; ih0 += 4 * FU) {
         float v[FU][NCO];
 #pragma unroll
@@ -210,7 +272,7 @@ __device__ __forceinline__ void tile_sums_stream(const Tile &t, double (&res)[RP
 // The workgroup's tile over dynamic LDS (ST: the streamed form, which keeps no halo tile).  Source planes are ph x pw;
 // low-resolution row i / column j is their row rmap[i] / column cmap[j] (null maps: the identity).  Ends with a barrier
 // (rowoff is read by every wave).
-template <bool ST>
+template <bool ST, bool BL = false>
 __device__ __forceinline__ Tile make_tile(int r, int h, int w, const int *__restrict__ rmap, const int *__restrict__ cmap, int ph,
                                           int pw, int kind)
 {
@@ -220,6 +282,7 @@ __device__ __forceinline__ Tile make_tile(int r, int h, int w, const int *__rest
     t.r = r, t.h = h, t.w = w;
     t.ti = blockIdx.y * TH, t.tj = blockIdx.x * TW;
     t.rmap = rmap, t.cmap = cmap, t.ph = ph, t.pw = pw;
+    if constexpr (BL) t.sy = (double)ph / (double)h, t.sx = (double)pw / (double)w;
     if (ST) {
         t.in = nullptr;
         t.in2 = reinterpret_cast<float *>(lds_d + (size_t)SR * HSP);
@@ -237,7 +300,12 @@ __device__ __forceinline__ Tile make_tile(int r, int h, int w, const int *__rest
 #pragma unroll
     for (int m = 0; m < NCO; m++) {
         const int jh = (threadIdx.x & 63) + 64 * m, j = t.tj - r + jh;
-        t.co[m] = jh < st && j >= 0 && j < w ? clampi(cmap ? cmap[j] : j, 0, pw - 1) : -1;
+        if constexpr (BL) {
+            bil_tap(clampi(j, 0, w - 1), t.sx, pw, t.co[m], t.co1[m], t.clam[m]);
+            if (!(jh < st && j >= 0 && j < w)) t.co[m] = -1;
+        } else {
+            t.co[m] = jh < st && j >= 0 && j < w ? clampi(cmap ? cmap[j] : j, 0, pw - 1) : -1;
+        }
     }
     __syncthreads();
     return t;
@@ -246,35 +314,35 @@ __device__ __forceinline__ Tile make_tile(int r, int h, int w, const int *__rest
 // ---- the window-sum front end --------------------------------------------------------------------------------------
 // What the kernels below call, in the form they are built for (ST: streamed, through the tile's maps; else tiled, staged
 // through LDS).  Window sums of a plane, which the tiled form leaves in the halo tile `in` ...
-template <bool ST>
+template <bool ST, bool BL = false>
 __device__ __forceinline__ void plane_sums(const Tile &t, float *__restrict__ in, const float *__restrict__ pl, double (&s)[RPT])
 {
     if constexpr (ST) {
-        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(pl, i, jj); });
+        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.template ld<BL>(pl, i, jj); });
     } else {
-        tile_fill(t, in, pl);
+        tile_fill<BL>(t, in, pl);
         tile_sums(t, s, [&](int e) { return (double)in[e]; });
     }
 }
 // ... of the square of the plane pl that a plane_sums call has left in t.in ...
-template <bool ST>
+template <bool ST, bool BL = false>
 __device__ __forceinline__ void square_sums(const Tile &t, const float *__restrict__ pl, double (&s)[RPT])
 {
     if constexpr (ST) {
-        tile_sums_stream(t, s, [&](int i, int jj) { const double v = t.ld(pl, i, jj); return v * v; });
+        tile_sums_stream(t, s, [&](int i, int jj) { const double v = t.template ld<BL>(pl, i, jj); return v * v; });
     } else {
         tile_sums(t, s, [&](int e) { const double v = t.in[e]; return v * v; });
     }
 }
 // ... and of its product with a second plane, which goes into t.in2 (exact in fp64: 24 + 24 bits)
-template <bool ST>
+template <bool ST, bool BL = false>
 __device__ __forceinline__ void product_sums(const Tile &t, const float *__restrict__ pl, const float *__restrict__ pl2,
                                              double (&s)[RPT])
 {
     if constexpr (ST) {
-        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.ld(pl, i, jj) * (double)t.ld(pl2, i, jj); });
+        tile_sums_stream(t, s, [&](int i, int jj) { return (double)t.template ld<BL>(pl, i, jj) * (double)t.template ld<BL>(pl2, i, jj); });
     } else {
-        tile_fill(t, t.in2, pl2);
+        tile_fill<BL>(t, t.in2, pl2);
         tile_sums(t, s, [&](int e) { return (double)t.in[e] * (double)t.in2[e]; });
     }
 }
@@ -298,20 +366,22 @@ __device__ __forceinline__ void for_pixels(const Tile &t, F f)
 }
 
 // ---- guide statistics ----------------------------------------------------------------------------------------------
-template <bool ST>
+// (BL, here and in the three kernels that follow: the low-resolution image is the bilinear sample of the H x W planes,
+// taken while the tile is filled; the maps are null)
+template <bool ST, bool BL = false>
 __global__ __launch_bounds__(NT) void k_guide_stats(const float *__restrict__ x, const int *__restrict__ rmap,
                                                    const int *__restrict__ cmap, const float *__restrict__ eps,
                                                    double *__restrict__ mx, float *__restrict__ inv, int cx, int H, int W, int h,
                                                    int w, int r)
 {
-    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_STATS);
+    Tile t = make_tile<ST, BL>(r, h, w, rmap, cmap, H, W, KIND_STATS);
     const int b = blockIdx.z;
     const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
     for (int c = 0; c < cx; c++) {
         const float *xp = x + ((int64_t)b * cx + c) * HWf;
         double s1[RPT], s2[RPT];
-        plane_sums<ST>(t, t.in, xp, s1);
-        square_sums<ST>(t, xp, s2);
+        plane_sums<ST, BL>(t, t.in, xp, s1);
+        square_sums<ST, BL>(t, xp, s2);
         const double e = (double)eps[c];
         for_pixels(t, [&](int k, int64_t q) {
             const double n = t.count(k);
@@ -324,13 +394,13 @@ __global__ __launch_bounds__(NT) void k_guide_stats(const float *__restrict__ x,
 }
 
 // ---- coefficients --------------------------------------------------------------------------------------------------
-template <bool ST>
+template <bool ST, bool BL = false>
 __global__ __launch_bounds__(NT) void k_guide_coef(const float *__restrict__ y, const float *__restrict__ x,
                                                   const int *__restrict__ rmap, const int *__restrict__ cmap,
                                                   const double *__restrict__ mx, const float *__restrict__ inv,
                                                   float *__restrict__ coef, int n0, int cy, int cx, int H, int W, int h, int w, int r)
 {
-    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_COEF);
+    Tile t = make_tile<ST, BL>(r, h, w, rmap, cmap, H, W, KIND_COEF);
     const int n = n0 + blockIdx.z, b = n / cy;                     // n = image * cy + label
     const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
     const float *yp = y + (int64_t)n * HWf;
@@ -338,11 +408,11 @@ __global__ __launch_bounds__(NT) void k_guide_coef(const float *__restrict__ y, 
 
     double my[RPT], bacc[RPT], rn[RPT], s[RPT];
     recip_counts(t, rn);
-    plane_sums<ST>(t, t.in, yp, s);                                 // (tiled form: y stays in LDS for the products below)
+    plane_sums<ST, BL>(t, t.in, yp, s);                             // (tiled form: y stays in LDS for the products below)
 #pragma unroll
     for (int k = 0; k < RPT; k++) bacc[k] = my[k] = s[k] * rn[k];
     for (int c = 0; c < cx; c++) {
-        product_sums<ST>(t, yp, x + ((int64_t)b * cx + c) * HWf, s);
+        product_sums<ST, BL>(t, yp, x + ((int64_t)b * cx + c) * HWf, s);
         for_pixels(t, [&](int k, int64_t o) {
             const int64_t g = ((int64_t)b * cx + c) * hw + o;
             const double m = mx[g];
@@ -442,6 +512,8 @@ struct Plan {
     // `per` of the forward (the cx + 1 coefficient planes) and of the backward (ys unless full resolution, P and Q, A and
     // mA for grad_x, the NPART fp64 terms for grad_x / grad_eps): run(), run_grad() and the query below all come here
     static int64_t per_forward(int cx, int64_t hw) { return (int64_t)(cx + 1) * hw * (int64_t)sizeof(float); }
+    // ... of the bilinear forward: the cx + 1 window-mean planes beside the cx + 1 coefficient planes
+    static int64_t per_bilinear(int cx, int64_t hw) { return 2 * per_forward(cx, hw); }
     static int64_t per_backward(int cx, int64_t hw, bool full, bool need_x, bool need_xe)
     {
         return hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * kGradParts * cx : 0));
@@ -508,14 +580,14 @@ __device__ __forceinline__ void static_for_seq(F f, std::integer_sequence<int, I
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F f) { static_for_seq(f, std::make_integer_sequence<int, N>{}); }
 
-template <bool ST, int CX>
+template <bool ST, int CX, bool BL = false>
 __global__ __launch_bounds__(NT) void k_guide_stats_full(const float *__restrict__ x, const int *__restrict__ rmap,
                                                         const int *__restrict__ cmap, const float *__restrict__ eps,
                                                         double *__restrict__ mx, double *__restrict__ P, int H, int W, int h, int w,
                                                         int r)
 {
     constexpr int NP = npairs(CX);
-    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_COEF);
+    Tile t = make_tile<ST, BL>(r, h, w, rmap, cmap, H, W, KIND_COEF);
     const int b = blockIdx.z;
     const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
     const float *xb = x + (int64_t)b * CX * HWf;
@@ -525,16 +597,16 @@ __global__ __launch_bounds__(NT) void k_guide_stats_full(const float *__restrict
     // channel that is not a constant puts S into scratch)
     static_for<CX>([&](auto cc) {
         constexpr int c = decltype(cc)::value;
-        plane_sums<ST>(t, t.in, xb + c * HWf, s);
+        plane_sums<ST, BL>(t, t.in, xb + c * HWf, s);
 #pragma unroll
         for (int k = 0; k < RPT; k++) m[c][k] = s[k] * rn[k];
-        square_sums<ST>(t, xb + c * HWf, s);
+        square_sums<ST, BL>(t, xb + c * HWf, s);
 #pragma unroll
         for (int k = 0; k < RPT; k++) S[pair_plane(c, c, CX)][k] = s[k] * rn[k];          // mean(x_c x_d) for now
         static_for<CX>([&](auto dd) {
             constexpr int d = decltype(dd)::value;
             if constexpr (d > c) {
-                product_sums<ST>(t, xb + c * HWf, xb + d * HWf, s);
+                product_sums<ST, BL>(t, xb + c * HWf, xb + d * HWf, s);
 #pragma unroll
                 for (int k = 0; k < RPT; k++) S[pair_plane(c, d, CX)][k] = s[k] * rn[k];
             }
@@ -591,14 +663,14 @@ __global__ __launch_bounds__(NT) void k_guide_stats_full(const float *__restrict
     });
 }
 
-template <bool ST, int CX>
+template <bool ST, int CX, bool BL = false>
 __global__ __launch_bounds__(NT) void k_guide_coef_full(const float *__restrict__ y, const float *__restrict__ x,
                                                        const int *__restrict__ rmap, const int *__restrict__ cmap,
                                                        const double *__restrict__ mx, const double *__restrict__ P,
                                                        float *__restrict__ coef, int n0, int cy, int H, int W, int h, int w, int r)
 {
     constexpr int NP = npairs(CX);
-    Tile t = make_tile<ST>(r, h, w, rmap, cmap, H, W, KIND_COEF);
+    Tile t = make_tile<ST, BL>(r, h, w, rmap, cmap, H, W, KIND_COEF);
     const int n = n0 + blockIdx.z, b = n / cy;                     // n = image * cy + label
     const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
     const float *yp = y + (int64_t)n * HWf, *xb = x + (int64_t)b * CX * HWf;
@@ -607,12 +679,12 @@ __global__ __launch_bounds__(NT) void k_guide_coef_full(const float *__restrict_
 
     double my[RPT], rn[RPT], s[RPT], cov[CX][RPT];
     recip_counts(t, rn);
-    plane_sums<ST>(t, t.in, yp, s);                                 // (tiled form: y stays in LDS for the products below)
+    plane_sums<ST, BL>(t, t.in, yp, s);                             // (tiled form: y stays in LDS for the products below)
 #pragma unroll
     for (int k = 0; k < RPT; k++) my[k] = s[k] * rn[k];
     static_for<CX>([&](auto cc) {
         constexpr int c = decltype(cc)::value;
-        product_sums<ST>(t, yp, xb + c * HWf, s);
+        product_sums<ST, BL>(t, yp, xb + c * HWf, s);
 #pragma unroll
         for (int k = 0; k < RPT; k++) cov[c][k] = s[k] * rn[k];       // mean(y x_c) for now
     });
@@ -663,6 +735,118 @@ int run_full(const Plan &p, const float *y, const float *x, const float *src, fl
         apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(coef, x, src, out, low_of_row, low_of_col, (int)n0, cy, CX, H, W, h, w, re,
                                                         scale);
         phl_launched(rc, "k_guide_coef_full / k_guide_apply");
+    }
+    return tmp.release();
+}
+
+// ---- bilinear: FastGuidedFilter(mode='bilinear'), forward ----------------------------------------------------------
+// D = F.interpolate(., (h, w), mode='bilinear'), U = F.interpolate(., (H, W), mode='bilinear') (align_corners=False):
+//   (mean_A, mean_b) = the model above (either one) on D(y), D(x)      out_l = (sum_c U(mean_A_lc) x_c + U(mean_b_l)) * scale - src_l
+// D is taken inside the front end: the BL instances of the statistics and coefficient kernels fill their halo tiles with
+// the four-tap samples (fp64 taps and weights from bil_tap, the sample rounded to fp32 once, which is what fp32 torch
+// holds as well), so no low-resolution copy of y or x is written and everything after the fill is the nearest kernels'
+// code.  U needs the window means of up to four low-resolution pixels, which may lie in four tiles, so the means leave
+// k_guide_apply's LDS:
+//   k_guide_mean    per (image x label, tile): the window means of the cx + 1 coefficient planes (plane_sums, rounded to
+//                   fp32 as k_guide_apply rounds them) -> cx + 1 low-resolution planes
+//   k_guide_up      per full-resolution pixel (a thread takes UR rows of one column): the four-tap samples of the mean
+//                   planes and the sum over the channels in fp64, * scale - src, one rounding into out
+// Labels per chunk: kChunkBytes / (2 (cx + 1) h w sizeof(float)), at least 1, at most B cy and 65535 (Plan::per_bilinear):
+// the coefficient and the mean planes of a chunk stay in the Infinity Cache between the three kernels.
+constexpr int UR = 4;               // full-resolution rows per thread of k_guide_up: a workgroup covers 16 x 64 pixels
+
+template <bool ST>
+__global__ __launch_bounds__(NT) void k_guide_mean(const float *__restrict__ coef, float *__restrict__ mean, int np, int h, int w,
+                                                  int r)
+{
+    Tile t = make_tile<ST>(r, h, w, nullptr, nullptr, h, w, KIND_STATS);
+    const int64_t hw = (int64_t)h * w;
+    const float *cp = coef + (int64_t)blockIdx.z * np * hw;
+    float *mp = mean + (int64_t)blockIdx.z * np * hw;
+    double rn[RPT];
+    recip_counts(t, rn);
+    for (int q = 0; q < np; q++) {
+        double s[RPT];
+        plane_sums<ST>(t, t.in, cp + (int64_t)q * hw, s);
+        for_pixels(t, [&](int k, int64_t o) { mp[(int64_t)q * hw + o] = (float)(s[k] * rn[k]); });
+    }
+}
+
+__global__ __launch_bounds__(NT) void k_guide_up(const float *__restrict__ mean, const float *__restrict__ x,
+                                                const float *__restrict__ src, float *__restrict__ out, int n0, int cy, int cx,
+                                                int H, int W, int h, int w, int tilesx, float scale)
+{
+    const int bx = blockIdx.x % tilesx, by = blockIdx.x / tilesx;
+    const int J = bx * 64 + (threadIdx.x & 63), I0 = (by * 4 + (threadIdx.x >> 6)) * UR;
+    if (J >= W) return;
+    const int n = n0 + blockIdx.z, b = n / cy;
+    const int64_t HWf = (int64_t)H * W, hw = (int64_t)h * w;
+    const float *mp = mean + (int64_t)blockIdx.z * (cx + 1) * hw;
+    const float *xb = x + (int64_t)b * cx * HWf;
+    const float *sp = src ? src + (int64_t)n * HWf : nullptr;
+    float *op = out + (int64_t)n * HWf;
+    const double sy = (double)h / (double)H;
+    int j0, j1;
+    double lx;
+    bil_tap(J, (double)w / (double)W, w, j0, j1, lx);
+    for (int k = 0; k < UR && I0 + k < H; k++) {
+        int i0, i1;
+        double ly;
+        bil_tap(I0 + k, sy, h, i0, i1, ly);
+        const int64_t o = (int64_t)(I0 + k) * W + J, q0 = (int64_t)i0 * w, q1 = (int64_t)i1 * w;
+        double acc = 0.0;
+        for (int c = 0; c <= cx; c++) {
+            const float *m = mp + (int64_t)c * hw;
+            const double u = bil_mix(m[q0 + j0], m[q0 + j1], m[q1 + j0], m[q1 + j1], ly, lx);
+            acc += c < cx ? u * (double)xb[(int64_t)c * HWf + o] : u;
+        }
+        acc *= (double)scale;
+        if (sp) acc -= (double)sp[o];
+        op[o] = (float)acc;
+    }
+}
+
+// CX = 0: the diagonal model with cx guide channels; else the full covariance of CX (= cx) channels
+template <bool ST, int CX>
+int run_bilinear(const Plan &p, const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h,
+                 int w, int re, const float *eps, float scale, hipStream_t st)
+{
+    const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
+    const size_t lds_first = CX ? p.lds_coef : p.lds_stats;
+    auto meank = k_guide_mean<ST>;
+    if constexpr (CX == 0) {
+        if (int rc = phl_allow_lds(k_guide_stats<ST, true>, lds_first)) return rc;
+        if (int rc = phl_allow_lds(k_guide_coef<ST, true>, p.lds_coef)) return rc;
+    } else {
+        if (int rc = phl_allow_lds(k_guide_stats_full<ST, CX, true>, lds_first)) return rc;
+        if (int rc = phl_allow_lds(k_guide_coef_full<ST, CX, true>, p.lds_coef)) return rc;
+    }
+    if (int rc = phl_allow_lds(meank, p.lds_stats)) return rc;
+
+    const int64_t chunk = Plan::chunk(nimg, Plan::per_bilinear(cx, hw));
+    const size_t nstat = (size_t)B * cx * hw;
+    phl_temps tmp(st);
+    double *mx = tmp.get<double>(nstat), *P = CX ? tmp.get<double>((size_t)B * npairs(CX) * hw) : nullptr;
+    float *inv = CX ? nullptr : tmp.get<float>(nstat);
+    float *coef = tmp.get<float>((size_t)chunk * (cx + 1) * hw), *mean = tmp.get<float>((size_t)chunk * (cx + 1) * hw);
+    const int tilesx = (W + 63) / 64, tilesy = (H + 4 * UR - 1) / (4 * UR);
+    int &rc = tmp.rc;
+    if (rc == PHL_OK) {
+        if constexpr (CX == 0)
+            k_guide_stats<ST, true><<<p.grid((unsigned)B), dim3(NT), lds_first, st>>>(x, nullptr, nullptr, eps, mx, inv, cx, H, W, h, w, re);
+        else
+            k_guide_stats_full<ST, CX, true><<<p.grid((unsigned)B), dim3(NT), lds_first, st>>>(x, nullptr, nullptr, eps, mx, P, H, W, h, w, re);
+        phl_launched(rc, "k_guide_stats (bilinear)");
+    }
+    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
+        const unsigned nz = (unsigned)min(chunk, nimg - n0);
+        if constexpr (CX == 0)
+            k_guide_coef<ST, true><<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, nullptr, nullptr, mx, inv, coef, (int)n0, cy, cx, H, W, h, w, re);
+        else
+            k_guide_coef_full<ST, CX, true><<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, nullptr, nullptr, mx, P, coef, (int)n0, cy, H, W, h, w, re);
+        meank<<<p.grid(nz), dim3(NT), p.lds_stats, st>>>(coef, mean, cx + 1, h, w, re);
+        k_guide_up<<<dim3((unsigned)tilesx * (unsigned)tilesy, 1, nz), dim3(NT), 0, st>>>(mean, x, src, out, (int)n0, cy, cx, H, W, h, w, tilesx, scale);
+        phl_launched(rc, "k_guide_coef / k_guide_mean / k_guide_up (bilinear)");
     }
     return tmp.release();
 }
@@ -1224,11 +1408,12 @@ int run_full_grad(const Plan &p, const float *y, const float *x, const float *g,
     return tmp.release();
 }
 
-// The arguments the forward and the backward share (`third`: out or g); `who` names the entry point in the message.
+// The arguments the forward and the backward share (`third`: out or g; `maps` false: an entry point that takes no index
+// maps); `who` names the entry point in the message.
 // PHL_OK also for zero elements, which the caller then tests for.
 int check_guided_args(const char *who, const void *y, const void *x, const void *third, const char *third_name, int B, int cy, int cx,
                       int H, int W, int h, int w, int r, const int *row_of_low, const int *col_of_low, const int *low_of_row,
-                      const int *low_of_col, const float *eps, float scale)
+                      const int *low_of_col, const float *eps, float scale, bool maps = true)
 {
     if (B < 0 || cy < 0 || cx < 1 || H < 0 || W < 0 || h < 0 || w < 0 || r < 0 || h > H || w > W || !isfinite(scale)) {
         phl_set_error("%s: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", who, B, cy, cx, H, W, h, w, r,
@@ -1240,7 +1425,7 @@ int check_guided_args(const char *who, const void *y, const void *x, const void 
         phl_set_error("%s: empty solving resolution %d x %d for a %d x %d image", who, h, w, H, W);
         return PHL_ERR_INVALID;
     }
-    if (!y || !x || !third || !eps || !row_of_low || !col_of_low || !low_of_row || !low_of_col) {
+    if (!y || !x || !third || !eps || (maps && (!row_of_low || !col_of_low || !low_of_row || !low_of_col))) {
         phl_set_error("%s: null y / x / %s / eps / index map", who, third_name);
         return PHL_ERR_INVALID;
     }
@@ -1381,6 +1566,44 @@ int phl_guided_filter_full_grad_labels_per_chunk(int B, int cy, int cx, int h, i
     if (B < 1 || cy < 1 || cx < 1 || cx > PHL_GUIDED_FULL_MAX_CX || h < 1 || w < 1 || needs < 0 || needs > 7) return 0;
     const bool need_x = (needs & 2) != 0, need_xe = (needs & 6) != 0;
     return (int)Plan::chunk((int64_t)B * cy, Plan::per_backward_full(cx, (int64_t)h * w, full != 0, need_x, need_xe));
+}
+
+int phl_guided_filter_bilinear(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h,
+                               int w, int r, const float *eps, float scale, unsigned flags, phl_stream stream)
+{
+    if (int rc = check_guided_args("phl_guided_filter_bilinear", y, x, out, "out", B, cy, cx, H, W, h, w, r, nullptr, nullptr, nullptr,
+                                   nullptr, eps, scale, false))
+        return rc;
+    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
+    if (flags & ~PHL_GUIDED_BILINEAR_FULL_COV) {
+        phl_set_error("phl_guided_filter_bilinear: unknown flags 0x%x", flags);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    const bool full = (flags & PHL_GUIDED_BILINEAR_FULL_COV) != 0;
+    if (full && cx > PHL_GUIDED_FULL_MAX_CX) {
+        phl_set_error("phl_guided_filter_bilinear: %d guide channels with the full covariance, at most %d (PHL_GUIDED_FULL_MAX_CX)", cx,
+                      PHL_GUIDED_FULL_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (out == y || out == x || out == src) {
+        phl_set_error("phl_guided_filter_bilinear: out aliases an input");
+        return PHL_ERR_INVALID;
+    }
+    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
+    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, int, int, int, int, int, int, int, int,
+                        const float *, float, hipStream_t);
+    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX + 1] = {
+        {run_bilinear<false, 0>, run_bilinear<false, 1>, run_bilinear<false, 2>, run_bilinear<false, 3>, run_bilinear<false, 4>},
+        {run_bilinear<true, 0>, run_bilinear<true, 1>, run_bilinear<true, 2>, run_bilinear<true, 3>, run_bilinear<true, 4>}};
+    const int re = min(r, max(h, w));
+    const Plan p(re, h, w);
+    return runs[p.tiled ? 0 : 1][full ? cx : 0](p, y, x, src, out, B, cy, cx, H, W, h, w, re, eps, scale, (hipStream_t)stream);
+}
+
+int phl_guided_filter_bilinear_labels_per_chunk(int B, int cy, int cx, int h, int w)
+{
+    if (B < 1 || cy < 1 || cx < 1 || h < 1 || w < 1) return 0;
+    return (int)Plan::chunk((int64_t)B * cy, Plan::per_bilinear(cx, (int64_t)h * w));
 }
 
 }  // extern "C"

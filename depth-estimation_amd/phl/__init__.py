@@ -30,6 +30,7 @@ NO_TILES = 8
 ERR_UNSUPPORTED = 7          # PHL_ERR_UNSUPPORTED: the kernels do not take this shape, the caller keeps its own path
 FILTER_GRAD_MAX_D = 16       # PHL_FILTER_GRAD_MAX_D: most feature dimensions phl_filter_grad takes (tests hold it to the header)
 GUIDED_FULL_MAX_CX = 4       # PHL_GUIDED_FULL_MAX_CX: most guide channels phl_guided_filter_full takes
+GUIDED_BILINEAR_FULL_COV = 1 # PHL_GUIDED_BILINEAR_FULL_COV: flag of phl_guided_filter_bilinear
 BUILD_REFERENCE_TABLE = 1
 
 _lib = None
@@ -118,6 +119,8 @@ _ABI = (
     ("phl_guided_filter_grad_max_r", "i", ""),
     ("phl_guided_filter_full_grad", "i", "PPPPPPiiiiiiiiPPPPPfiS"),
     ("phl_guided_filter_full_grad_labels_per_chunk", "i", "iiiiiii"),
+    ("phl_guided_filter_bilinear", "i", "PPPPiiiiiiiiPfIS"),
+    ("phl_guided_filter_bilinear_labels_per_chunk", "i", "iiiii"),
     ("phl_stream_copy", "i", "PPqS"),
     ("phl_copy2d", "i", "PqqPqqqiS"),
     ("phl_tile_stats", "i", "PiP"),
@@ -1442,10 +1445,37 @@ def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False,
                      needs if grad else -1, value=True))
 
 
-def _guided_launch_args(name, y, x, third, third_name, r, eps, subsample, launch=True):
-    """What guided_filter and guided_filter_grad (``name``) share: the checks of y, x and ``third`` (subtract or g: y's
-    shape, may be None), of subsample and r; then (cx, eps as the kernels read it, the launch's (B, cy, cx, H, W, h, w,
-    r // s), its four index maps).  The last two are None when y has no elements or the caller launches nothing."""
+def guided_filter_bilinear(y, x, r, eps, *, subsample, scale=1.0, subtract=None, out=None, full_cov=False):
+    """FastGuidedFilter(mode='bilinear') (phl_guided_filter_bilinear; forward only): guided_filter with the linear model
+    solved on ``F.interpolate(., size=(H // s, W // s), mode='bilinear')`` of y and x, radius r // s, and its window means
+    interpolated back to (H, W) the same way, ``out = (sum_c U(mean_A_c) x_c + U(mean_b)) * scale - subtract``.  The taps
+    are computed on the device (no index maps).  Tensor rules of guided_filter; ``subsample`` >= 2 (at 1 both
+    interpolations are the identity: guided_filter).  ``full_cov``: the model over the whole covariance matrix, up to
+    GUIDED_FULL_MAX_CX guide channels (PhlError status 7 above, as above 16 channels without it)."""
+    if int(subsample) < 2:
+        raise ValueError(f"guided_filter_bilinear: needs subsample >= 2, got {subsample}")
+    _, e, dims, _ = _guided_launch_args("guided_filter_bilinear", y, x, subtract, "subtract", r, eps, subsample, maps=False)
+    out = _out_or_empty("guided_filter_bilinear", out, y.shape, y.device, "y's shape and device")
+    if dims is None:
+        return out
+    yc, xc = y.contiguous(), x.contiguous()
+    sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
+    _launch(y.device, "phl_guided_filter_bilinear", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims, _ptr(e), C.c_float(float(scale)),
+            GUIDED_BILINEAR_FULL_COV if full_cov else 0)
+    return out
+
+
+def guided_filter_bilinear_labels_per_chunk(B, cy, cx, h, w):
+    """Labels per chunk of a guided_filter_bilinear call at the solving resolution h x w
+    (phl_guided_filter_bilinear_labels_per_chunk: host arithmetic of the library, no device needed)."""
+    return int(_call("phl_guided_filter_bilinear_labels_per_chunk", int(B), int(cy), int(cx), int(h), int(w), value=True))
+
+
+def _guided_launch_args(name, y, x, third, third_name, r, eps, subsample, launch=True, maps=True):
+    """What guided_filter, guided_filter_bilinear and guided_filter_grad (``name``) share: the checks of y, x and ``third``
+    (subtract or g: y's shape, may be None), of subsample and r; then (cx, eps as the kernels read it, the launch's (B, cy,
+    cx, H, W, h, w, r // s), its four index maps -- None without ``maps``).  The last two are None when y has no elements or
+    the caller launches nothing."""
     _fp32_cuda(name, y, x, *(() if third is None else (third,)))
     if y.dim() != 4 or x.dim() != 4 or y.shape[0] != x.shape[0] or y.shape[2:] != x.shape[2:] or x.device != y.device:
         raise ValueError(f"{name}: y [B, cy, H, W] and x [B, cx, H, W] on one device, got {tuple(y.shape)} and {tuple(x.shape)}")
@@ -1461,7 +1491,7 @@ def _guided_launch_args(name, y, x, third, third_name, r, eps, subsample, launch
         return cx, e, None, None
     if H // s == 0 or W // s == 0:
         raise ValueError(f"{name}: a {H} x {W} image has no pixels at subsample {s}")
-    return cx, e, (B, cy, cx, H, W, H // s, W // s, r // s), _nearest_index_maps(H, W, s, y.device)
+    return cx, e, (B, cy, cx, H, W, H // s, W // s, r // s), _nearest_index_maps(H, W, s, y.device) if maps else None
 
 
 def _guided_eps(eps, cx, device, name):

@@ -601,6 +601,28 @@ int phl_guided_filter_full_grad(const float *y_dev, const float *x_dev, const fl
  * other arguments as phl_guided_filter_labels_per_chunk.  0 for sizes below 1, cx > PHL_GUIDED_FULL_MAX_CX or another needs. */
 int phl_guided_filter_full_grad_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs);
 
+/* FastGuidedFilter(mode='bilinear'), forward only: the tensors, eps, the window sums and the status rules of
+ * phl_guided_filter, but no index maps -- with D = F.interpolate(., size=(h, w), mode='bilinear') and
+ * U = F.interpolate(., size=(H, W), mode='bilinear') (align_corners=False, no antialias)
+ *   (mean(A), mean(b)) = the model of phl_guided_filter on D(y), D(x), r the radius at h x w
+ *   out_l = (sum_c U(mean(A_lc)) x_c + U(mean(b_l))) * scale - src_l
+ * and with PHL_GUIDED_BILINEAR_FULL_COV in flags the model of phl_guided_filter_full.  Per axis the taps of output
+ * index o, mapping n_in samples to n_out, are torch's, computed on the device in fp64:
+ *   s = max((o + 0.5) * (n_in / n_out) - 0.5, 0)   i0 = min(int(s), n_in - 1)   i1 = min(i0 + 1, n_in - 1)   lam = s - i0
+ * D(y) and D(x) are rounded to fp32 once (never written to memory); from there on the roundings are those of
+ * phl_guided_filter; U and the sum over the channels are fp64, out is rounded once.  No atomics: the same bits on
+ * every run.  Temporaries are stream-ordered: the statistics, and per chunk of labels 2 (cx + 1) fp32 planes at h x w.
+ * Status, before any HIP call: as phl_guided_filter (without the maps); then, after the zero-element return,
+ * PHL_ERR_UNSUPPORTED for unknown flag bits or, with the flag, cx > PHL_GUIDED_FULL_MAX_CX; then PHL_ERR_INVALID for
+ * out aliasing an input.  The tiled radius is phl_guided_filter_max_r(). */
+#define PHL_GUIDED_BILINEAR_FULL_COV 1u
+int phl_guided_filter_bilinear(const float *y_dev, const float *x_dev, const float *src_dev, float *out_dev, int B, int cy, int cx,
+                               int H, int W, int h, int w, int r, const float *eps_dev, float scale, unsigned flags,
+                               phl_stream stream);
+/* Labels per chunk of a phl_guided_filter_bilinear call (the window-mean planes join the coefficient planes in the
+ * budget); host arithmetic only.  0 for sizes below 1. */
+int phl_guided_filter_bilinear_labels_per_chunk(int B, int cy, int cx, int h, int w);
+
 /* Plain float4 streaming copy dst <- src (n_floats % 4 == 0, 16-byte aligned): measures the
  * HBM read+write ceiling of the box that the roofline fractions are compared with. */
 int phl_stream_copy(const float *src_dev, float *dst_dev, int64_t n_floats, phl_stream stream);
