@@ -877,7 +877,21 @@ int phl_blur_axis(phl_lattice *lat, int axis, const float *vin, float *vout, int
 static int blur_all(const phl_lattice *lat, float *const buf[2], int vd, hipStream_t st, int *cur_out)
 {
     static const bool pairs = !(getenv("PHL_BLUR_PAIRS") && atoi(getenv("PHL_BLUR_PAIRS")) == 0);
+    static const bool triples = !(getenv("PHL_BLUR_TRIPLES") && atoi(getenv("PHL_BLUR_TRIPLES")) == 0);
     int cur = 0;
+    // Three axes per pass where the lattice has the line lists and a wave owns a row: n3 triples (k_blur3), then the
+    // pairs behind them from their own tables -- ceil((d+1)/3) launches, same axis order, same bits.  Row-band
+    // lattices and narrow rows take the pair route below.
+    if (pairs && triples && phl_blur3_takes(lat, buf[0], buf[1], vd)) {
+        for (int slot = 0; slot < lat->np3; slot++) {
+            const int rc = slot < lat->n3 ? phl_launch_blur3(lat, slot, buf[cur], buf[cur ^ 1], vd, st)
+                                          : phl_launch_blur2_slot(lat, slot, buf[cur], buf[cur ^ 1], vd, st);
+            if (rc) return rc;
+            cur ^= 1;
+        }
+        *cur_out = cur;
+        return PHL_OK;
+    }
     for (int axis = 0; axis <= lat->d;) {  // axis order 0..d, Jacobi ping-pong (:498, :530-532)
         int rc;
         if (pairs && axis + 1 <= lat->d && lat->nbr2) {
@@ -1169,6 +1183,36 @@ int phl_get_neighbors(phl_lattice *lat, int32_t *nbr)
                 const int32_t x = h[((size_t)a * M + r[v]) * 2 + s2];
                 nbr[((size_t)a * M + v) * 2 + s2] = x < 0 ? x : f[x];
             }
+    return PHL_OK;
+}
+
+int phl_get_blur_lines(phl_lattice *lat, int group, int32_t *vertex, int32_t *flags, int32_t *item_start, int64_t info[3])
+{
+    if (!lat || !info) { phl_set_error("phl_get_blur_lines: bad arguments"); return PHL_ERR_INVALID; }
+    const bool have = lat->lines && lat->line_items && lat->n3 > 0;
+    info[0] = have ? lat->n3 : 0;
+    info[1] = have ? lat->nitems3 : 0;
+    info[2] = have ? lat->line_item_size : 0;
+    if (!vertex && !flags && !item_start) return PHL_OK;
+    if (!have || group < 0 || group >= lat->n3 || !vertex || !flags || !item_start) {
+        phl_set_error("phl_get_blur_lines: no line list for group %d", group);
+        return PHL_ERR_INVALID;
+    }
+    device_guard g(lat->device);
+    PHL_HIP(hipDeviceSynchronize());
+    std::vector<int32_t> f, r;
+    int rc = fetch_maps(lat, f, r);
+    if (rc) return rc;
+    const size_t M = (size_t)lat->M;
+    std::vector<uint32_t> h(M);
+    PHL_HIP(hipMemcpy(h.data(), lat->lines + (size_t)group * M, sizeof(uint32_t) * M, hipMemcpyDeviceToHost));
+    PHL_HIP(hipMemcpy(item_start, lat->line_items + (size_t)group * (lat->nitems3 + 1), sizeof(int32_t) * (size_t)(lat->nitems3 + 1),
+                      hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < M; i++) {
+        const uint32_t row = h[i] & PHL_LINE_VERTEX;
+        vertex[i] = (f.empty() || row >= M) ? (int32_t)row : f[row];
+        flags[i] = (int32_t)(h[i] >> 28);
+    }
     return PHL_OK;
 }
 

@@ -510,13 +510,16 @@ __global__ __launch_bounds__(256) void k_neighbors(const uint32_t *__restrict__ 
     nbr[idx * 2 + 1] = res[1];
 }
 
+// (extra_words: room behind the packed keys in the same scratch block, for the caller's own temporaries; *extra gets it)
 template <int D>
 int launch_neighbors(const int16_t *vkeys, int M, const int *table, uint32_t mask, int *nbr, phl_dev_block<uint32_t> &scratch,
-                     hipStream_t st)
+                     size_t extra_words, uint32_t **extra, hipStream_t st)
 {
     using K = packed_key<D>;
-    PHL_TRY(scratch.alloc((size_t)M * K::PW + 4));
+    const size_t own = ((size_t)M * K::PW + 4 + 3) / 4 * 4;
+    PHL_TRY(scratch.alloc(own + extra_words));
     uint32_t *const vkp = scratch.get();
+    *extra = vkp + own;
     hipLaunchKernelGGL(k_pack_keys<D>, dim3((M + 255) / 256), dim3(256), 0, st, vkeys, M, vkp);
     const int64_t tot = (int64_t)M * (D + 1);
     hipLaunchKernelGGL(k_neighbors<D>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, vkp, M, table, mask, nbr);
@@ -541,6 +544,97 @@ __global__ __launch_bounds__(256) void k_compose_pairs(const int2 *__restrict__ 
     const int2 ap = nb.y >= 0 ? na[nb.y] : none;
     nbr2[idx * 2 + 0] = make_int4(am.x, nb.x, am.y, a0.x);
     nbr2[idx * 2 + 1] = make_int4(a0.y, ap.x, nb.y, ap.y);
+}
+
+// ---- three axes per pass (k_blur3): tables of the axis groups (a, b | c) = (3g, 3g+1 | 3g+2) ----
+// The same composed ids for pairs that start at any axis: slot j of the table is the pair (ax.a[j], ax.a[j] + 1).
+struct pair_axes_t {
+    int a[PHL_MAX_D + 1];
+};
+__global__ __launch_bounds__(256) void k_compose_pairs_at(const int2 *__restrict__ nbr, int M, int nslots, pair_axes_t ax,
+                                                          int4 *__restrict__ out)
+{
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)M * nslots) return;
+    const int j = (int)(idx / M);
+    const int v = (int)(idx - (int64_t)j * M);
+    const int2 *na = nbr + (int64_t)ax.a[j] * M;
+    const int2 nb = nbr[(int64_t)(ax.a[j] + 1) * M + v];
+    const int2 none = make_int2(-1, -1);
+    const int2 am = nb.x >= 0 ? na[nb.x] : none;
+    const int2 a0 = na[v];
+    const int2 ap = nb.y >= 0 ? na[nb.y] : none;
+    out[idx * 2 + 0] = make_int4(am.x, nb.x, am.y, a0.x);
+    out[idx * 2 + 1] = make_int4(a0.y, ap.x, nb.y, ap.y);
+}
+
+// Along axis c the vertices form LINES: u -> w is a link of a line iff it is mutual, nbr[c][u].y == w and
+// nbr[c][w].x == u (the duplicate vertices of the reference-table mode make a few links one-sided: such a neighbour is
+// read, but no line runs over it).  A vertex has at most one mutual predecessor and one mutual successor, and keys move
+// strictly along the axis, so the lines are disjoint paths and every vertex is on exactly one.
+// len[g][v] = length of the line that STARTS at v, 0 for every other vertex.  One thread per vertex; the walk of a line
+// is its start's (at most the key range along the axis, 2^16 / (d + 1) steps).
+__global__ __launch_bounds__(256) void k_line_len(const int2 *__restrict__ nbr, int M, int n3, int *__restrict__ len)
+{
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)M * n3) return;
+    const int g = (int)(idx / M);
+    const int v = (int)(idx - (int64_t)g * M);
+    const int2 *nc = nbr + (int64_t)(3 * g + 2) * M;
+    const int p = nc[v].x;
+    int l = 0;
+    if (!(p >= 0 && nc[p].y == v)) {
+        int u = v;
+        for (l = 1; l < M; l++) {
+            const int w = nc[u].y;
+            if (w < 0 || nc[w].x != u) break;
+            u = w;
+        }
+    }
+    len[idx] = l;
+}
+
+// The line list and the work items.  pos = exclusive scan of len over all groups (every group's lengths add up to M, so
+// group g's positions are pos - g * M): lines in the order of their first member's row.
+// Work items: the entries are cut into buckets of K; an item starts at the first line start inside each bucket, or at
+// the bucket's first entry where one line covers the whole bucket.  So items are whole lines wherever a line is no
+// longer than K, an item has fewer than 2K entries, and there is exactly one per bucket (no compaction).  Where an item
+// starts inside a line, both sides of the cut get PHL_LINE_EVAL: each wave evaluates the other side's T itself.
+__device__ __forceinline__ bool line_cut_at(int p, int s, int l, int K, int M)
+{
+    return p > s && p % K == 0 && s + l >= (p + K < M ? p + K : M);
+}
+__global__ __launch_bounds__(256) void k_line_fill(const int2 *__restrict__ nbr, int M, int n3, int K, int nitems,
+                                                   const int *__restrict__ len, const int *__restrict__ pos,
+                                                   uint32_t *__restrict__ lines, int *__restrict__ items)
+{
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)M * n3) return;
+    const int l = len[idx];
+    if (l == 0) return;
+    const int g = (int)(idx / M);
+    const int2 *nc = nbr + (int64_t)(3 * g + 2) * M;
+    const int s = pos[idx] - g * M;
+    if (s < 0 || s + l > M) return;     // (cannot happen, see k_line_len; never write past the group's list)
+    atomicMin(&items[(int64_t)g * (nitems + 1) + s / K], s);
+    int u = (int)(idx - (int64_t)g * M);
+    for (int o = 0; o < l; o++) {
+        const int p = s + o;
+        const int2 nb = nc[u];
+        const uint32_t fm = nb.x < 0 ? PHL_LINE_ABSENT : ((o > 0 && !line_cut_at(p, s, l, K, M)) ? PHL_LINE_SLIDE : PHL_LINE_EVAL);
+        const uint32_t fp = nb.y < 0 ? PHL_LINE_ABSENT : ((o + 1 < l && !line_cut_at(p + 1, s, l, K, M)) ? PHL_LINE_SLIDE : PHL_LINE_EVAL);
+        lines[(int64_t)g * M + p] = (uint32_t)u | (fm << 28) | (fp << 30);
+        u = nb.y;
+    }
+}
+// buckets without a line start begin an item at their first entry; the closing entry of every group is M
+__global__ __launch_bounds__(256) void k_line_items_finish(int M, int n3, int K, int nitems, int *__restrict__ items)
+{
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (int64_t)(nitems + 1) * n3) return;
+    const int b = (int)(idx % (nitems + 1));
+    if (b == nitems) items[idx] = M;
+    else if (items[idx] == 0x7FFFFFFF) items[idx] = b * K;
 }
 
 struct hidden_t {
@@ -712,6 +806,22 @@ int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, phl_dev_bl
     const int d = lat->d;
     const int M = (int)lat->M;
     PHL_HIP(phl_lat_free(lat->nbr2));            // (made again below only where there are vertices)
+    PHL_HIP(phl_lat_free(lat->nbr3));
+    PHL_HIP(phl_lat_free(lat->lines));
+    PHL_HIP(phl_lat_free(lat->line_items));
+    lat->n3 = lat->np3 = 0;
+    lat->nitems3 = 0;
+    // Three axes per pass: d+1 = 3q + r axes go as q triples (r = 0), q triples + one pair (r = 2) or q-1 triples + two
+    // pairs (r = 1), ceil((d+1)/3) launches.  No tables where that is no triple at all (d+1 < 3, d+1 == 4), on a lattice
+    // with ghost vertices (row bands keep the pair route), or beyond the list entry's 28 vertex bits.
+    static const int line_item = getenv("PHL_BLUR3_ITEM") ? atoi(getenv("PHL_BLUR3_ITEM")) : 4;
+    const int naxes = d + 1;
+    const int n3 = naxes % 3 == 1 ? naxes / 3 - 1 : naxes / 3;
+    const bool ghosts = lat->M_local > 0 && lat->M_local < lat->M;
+    const bool triples = n3 > 0 && !ghosts && M > 0 && (int64_t)M <= (int64_t)PHL_LINE_VERTEX && (int64_t)M * n3 < ((int64_t)1 << 30) &&
+                         line_item >= 1 && line_item <= 32;       // (an item has fewer than 2 * line_item entries; k_blur3 takes up to 64)
+    const size_t line_words = triples ? 2 * (size_t)M * n3 + (size_t)M * n3 / SCAN_TILE + 16 : 0;
+    uint32_t *line_tmp = nullptr;
     uint64_t cap = 1024;
     while (cap < (uint64_t)M * 2) cap <<= 1;
     lat->table_mask = (uint32_t)(cap - 1);
@@ -726,7 +836,7 @@ int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, phl_dev_bl
                            lat->table_mask, hidden, lat->int_of_ft);
         int rcn = PHL_OK;
         switch (d) {
-#define PHL_CASE(D) case D: rcn = launch_neighbors<D>(lat->vkeys, M, lat->table, lat->table_mask, lat->nbr, scratch, st); break;
+#define PHL_CASE(D) case D: rcn = launch_neighbors<D>(lat->vkeys, M, lat->table, lat->table_mask, lat->nbr, scratch, line_words, &line_tmp, st); break;
             PHL_FOR_D(PHL_CASE)
 #undef PHL_CASE
         }
@@ -738,6 +848,33 @@ int phl_rebuild_table_and_neighbors(phl_lattice *lat, hipStream_t st, phl_dev_bl
         const int64_t totp = (int64_t)M * npairs;
         hipLaunchKernelGGL(k_compose_pairs, dim3((unsigned)((totp + 255) / 256)), dim3(256), 0, st,
                            reinterpret_cast<const int2 *>(lat->nbr), M, npairs, reinterpret_cast<int4 *>(lat->nbr2));
+        if (triples) {
+            pair_axes_t ax = {};
+            int np3 = 0;
+            for (int g = 0; g < n3; g++) ax.a[np3++] = 3 * g;
+            for (int a = 3 * n3; a + 1 < naxes; a += 2) ax.a[np3++] = a;
+            const int K = line_item;
+            const int nitems = (M + K - 1) / K;
+            PHL_HIP(phl_lat_alloc(lat->nbr3, (size_t)M * np3 * 8));
+            PHL_HIP(phl_lat_alloc(lat->lines, (size_t)M * n3));
+            PHL_HIP(phl_lat_alloc(lat->line_items, (size_t)(nitems + 1) * n3));
+            const int2 *nbr = reinterpret_cast<const int2 *>(lat->nbr);
+            int *const len = reinterpret_cast<int *>(line_tmp), *const pos = len + (size_t)M * n3, *const tile_sums = pos + (size_t)M * n3 + 1;
+            const int64_t tot3 = (int64_t)M * n3;
+            const unsigned g3 = (unsigned)((tot3 + 255) / 256);
+            hipLaunchKernelGGL(k_compose_pairs_at, dim3((unsigned)(((int64_t)M * np3 + 255) / 256)), dim3(256), 0, st, nbr, M, np3, ax,
+                               reinterpret_cast<int4 *>(lat->nbr3));
+            hipLaunchKernelGGL(k_line_len, dim3(g3), dim3(256), 0, st, nbr, M, n3, len);
+            hipLaunchKernelGGL(k_fill_i32, dim3(256), dim3(256), 0, st, lat->line_items, (int64_t)(nitems + 1) * n3, 0x7FFFFFFF);
+            PHL_TRY(exclusive_scan(len, pos, (int)tot3, tile_sums, st));
+            hipLaunchKernelGGL(k_line_fill, dim3(g3), dim3(256), 0, st, nbr, M, n3, K, nitems, len, pos, lat->lines, lat->line_items);
+            hipLaunchKernelGGL(k_line_items_finish, dim3((unsigned)(((int64_t)(nitems + 1) * n3 + 255) / 256)), dim3(256), 0, st, M, n3, K,
+                               nitems, lat->line_items);
+            lat->n3 = n3;
+            lat->np3 = np3;
+            lat->nitems3 = nitems;
+            lat->line_item_size = K;
+        }
     }
     PHL_HIP(hipGetLastError());
     return PHL_OK;

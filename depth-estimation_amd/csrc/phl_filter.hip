@@ -291,6 +291,97 @@ __global__ __launch_bounds__(256) void k_blur2(const float *__restrict__ vin, fl
 }
 
 // ------------------------------------------------------------------------------------------
+// Three consecutive blur axes (a, b | c) in one pass, one wave per vertex row (vd >= 64 * VEC).  The wave walks a work
+// item of the line list of axis c (phl_internal.h: lines / line_items): T(u) = blur_b(blur_a(in))[u] is formed once per
+// entry with k_blur2's own expression, the last three T stay in registers, and
+//   out[u_i] = blur3(T(u_i-1), T(u_i), T(u_i+1))
+// where an outer operand is zero (no neighbour), the neighbouring entry's T (PHL_LINE_SLIDE) or, at an item cut inside
+// a line and at the rare one-sided link, T(nbr[c][u]) evaluated from that vertex's stencil.  Axis-by-axis Jacobi with
+// the same blur3 association: bit-identical to k_blur2 + k_blur, with the gathers of a pair pass.
+// the eight composed ids of a wave-uniform vertex, in scalar registers
+struct pair_ids_t {
+    int id[8];
+};
+__device__ __forceinline__ pair_ids_t load_pair_ids(const int4 *__restrict__ nb2, int u)
+{
+    const int4 i0 = nb2[(int64_t)u * 2], i1 = nb2[(int64_t)u * 2 + 1];
+    const int raw[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+    pair_ids_t r;
+#pragma unroll
+    for (int k = 0; k < 8; k++) r.id[k] = __builtin_amdgcn_readfirstlane(raw[k]);
+    return r;
+}
+// T(u) from its ids: k_blur2's expression, absent ids skipped by a scalar branch (see there)
+template <int VEC>
+__device__ __forceinline__ typename vec_of<VEC>::type blur2_value(const float *__restrict__ vin, const pair_ids_t &I, int u, int vd, int c)
+{
+    using V = typename vec_of<VEC>::type;
+    V x[8];
+    const V s = vload(vin + (int64_t)u * vd + c, V());
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        x[k] = vzero<VEC>();
+        if (I.id[k] >= 0) x[k] = vload(vin + (int64_t)I.id[k] * vd + c, V());
+    }
+    const V tm = I.id[1] >= 0 ? blur3(x[0], x[1], x[2]) : vzero<VEC>();
+    const V t0 = blur3(x[3], s, x[4]);
+    const V tp = I.id[6] >= 0 ? blur3(x[5], x[6], x[7]) : vzero<VEC>();
+    return blur3(tm, t0, tp);
+}
+
+// An item has fewer than 2 * item size entries: at most 64, so one vector load fetches its whole piece of the line list
+// (lane i holds entry e0 + i) and the walk reads entries by lane.  Three things are in flight per step of the walk: the
+// rows of entry e+1, the ids of entry e+2 (scalar loads, issued behind the row loads so that their latency runs under
+// them) and the output of entry e.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_blur3(const float *__restrict__ vin, float *__restrict__ vout,
+                                               const int4 *__restrict__ nb2, const int2 *__restrict__ nbc,
+                                               const uint32_t *__restrict__ lines, const int *__restrict__ items, int nitems,
+                                               int M, int vd, int xcd_chunk)
+{
+    using V = typename vec_of<VEC>::type;
+    const int lane = threadIdx.x & 63;
+    const int lb = xcd_chunk > 0 ? (int)(blockIdx.x & 7) * xcd_chunk + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int wv = lb * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (wv >= nitems) return;
+    const int e0 = __builtin_amdgcn_readfirstlane(items[wv]);
+    const int cnt = __builtin_amdgcn_readfirstlane(items[wv + 1]) - e0;
+    if (e0 < 0 || cnt <= 0 || cnt > 64 || e0 + cnt > M) return;
+    uint32_t my_ent = lines[e0 + (lane < cnt ? lane : cnt - 1)];
+    if ((int)(my_ent & PHL_LINE_VERTEX) >= M) my_ent = (my_ent & ~PHL_LINE_VERTEX) | (uint32_t)(M - 1);     // (never: keeps every row inside the array)
+    for (int c = lane * VEC; c < vd; c += 64 * VEC) {       // column blocks outermost: a row is written once
+        uint32_t ent = __builtin_amdgcn_readlane(my_ent, 0);
+        int u = (int)(ent & PHL_LINE_VERTEX);
+        int u1 = (int)(__builtin_amdgcn_readlane(my_ent, cnt > 1 ? 1 : 0) & PHL_LINE_VERTEX);
+        pair_ids_t I1 = load_pair_ids(nb2, u);
+        V t_prev = vzero<VEC>(), t_cur = blur2_value<VEC>(vin, I1, u, vd, c), t_next = vzero<VEC>();
+        I1 = load_pair_ids(nb2, u1);
+        for (int i = 0; i < cnt; i++) {
+            const uint32_t ent1 = __builtin_amdgcn_readlane(my_ent, i + 1 < cnt ? i + 1 : i);
+            if (i + 1 < cnt) t_next = blur2_value<VEC>(vin, I1, u1, vd, c);
+            const int u2 = (int)(__builtin_amdgcn_readlane(my_ent, i + 2 < cnt ? i + 2 : i) & PHL_LINE_VERTEX);
+            if (i + 2 < cnt) I1 = load_pair_ids(nb2, u2);
+            const uint32_t fm = (ent >> 28) & 3u, fp = ent >> 30;
+            V tm = vzero<VEC>(), tp = vzero<VEC>();
+            if (fm == PHL_LINE_SLIDE) tm = t_prev;
+            if (fp == PHL_LINE_SLIDE) tp = t_next;
+            if (fm == PHL_LINE_EVAL || fp == PHL_LINE_EVAL) {
+                const int2 nc = nbc[u];
+                const int um = __builtin_amdgcn_readfirstlane(nc.x), up = __builtin_amdgcn_readfirstlane(nc.y);
+                if (fm == PHL_LINE_EVAL && um >= 0) tm = blur2_value<VEC>(vin, load_pair_ids(nb2, um), um, vd, c);
+                if (fp == PHL_LINE_EVAL && up >= 0) tp = blur2_value<VEC>(vin, load_pair_ids(nb2, up), up, vd, c);
+            }
+            vstore(vout + (int64_t)u * vd + c, blur3(tm, t_cur, tp));
+            t_prev = t_cur;
+            t_cur = t_next;
+            ent = ent1;
+            u = u1;
+            u1 = u2;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // slice: out[p][:] = sum_{r<=d} w_r * vert[v_r][:] / (1 + 2^-d)   [ - sub[p][:] ]
 template <int VEC, int LPR, bool EXACT>
 __global__ __launch_bounds__(256) void k_slice(const float *__restrict__ vert, int vd,
@@ -536,13 +627,63 @@ int phl_launch_rows(bool scatter, float *vert, int vd, const int64_t *idx, int64
     return PHL_OK;
 }
 
+static int launch_blur2_table(const phl_lattice *lat, const int4 *nb2, const blur_rows_t &rr, const float *vin, float *vout, int vd,
+                              hipStream_t st);
+
 int phl_launch_blur2(const phl_lattice *lat, int pair, const float *vin, float *vout, int vd, hipStream_t st, bool restricted)
 {
     const int M = (int)lat->M;
     if (M == 0 || vd == 0) return PHL_OK;
     const blur_rows_t rr = rows_of(lat, 2 * pair + 1, restricted);      // out = blur_b(blur_a(in)): the rows axis b's output is read at
     if (rr.total == 0) return PHL_OK;
-    const int4 *nb2 = reinterpret_cast<const int4 *>(lat->nbr2) + (int64_t)pair * M * 2;
+    return launch_blur2_table(lat, reinterpret_cast<const int4 *>(lat->nbr2) + (int64_t)pair * M * 2, rr, vin, vout, vd, st);
+}
+
+// a pair of the three-axes route: the same kernel on the pair table of slot `slot` of nbr3, all rows
+int phl_launch_blur2_slot(const phl_lattice *lat, int slot, const float *vin, float *vout, int vd, hipStream_t st)
+{
+    const int M = (int)lat->M;
+    if (M == 0 || vd == 0) return PHL_OK;
+    if (!lat->nbr3 || slot < 0 || slot >= lat->np3) { phl_set_error("phl_launch_blur2_slot: no pair table %d", slot); return PHL_ERR_INVALID; }
+    const blur_rows_t rr = rows_of(lat, 0, false);
+    return launch_blur2_table(lat, reinterpret_cast<const int4 *>(lat->nbr3) + (int64_t)slot * M * 2, rr, vin, vout, vd, st);
+}
+
+// k_blur3 is written for one wave per row: vd >= 256 on the 16-byte grid, vd >= 64 off it.  Narrower rows (several
+// vertices per wave, where items of unequal length would diverge) stay on the pair route.
+bool phl_blur3_takes(const phl_lattice *lat, const float *vin, const float *vout, int vd)
+{
+    if (!lat->lines || !lat->nbr3 || !lat->line_items || lat->n3 <= 0 || lat->blur_rows_set) return false;
+    const bool v4 = (vd % 4 == 0) && phl_al16(vin) && phl_al16(vout);
+    return pick_lpr(vd, v4 ? 4 : 1) == 64;
+}
+
+int phl_launch_blur3(const phl_lattice *lat, int group, const float *vin, float *vout, int vd, hipStream_t st)
+{
+    const int M = (int)lat->M;
+    if (M == 0 || vd == 0) return PHL_OK;
+    if (!phl_blur3_takes(lat, vin, vout, vd) || group < 0 || group >= lat->n3) {
+        phl_set_error("phl_launch_blur3: no line lists for group %d at vd = %d", group, vd);
+        return PHL_ERR_INVALID;
+    }
+    const int nitems = (int)lat->nitems3;
+    const int4 *nb2 = reinterpret_cast<const int4 *>(lat->nbr3) + (int64_t)group * M * 2;
+    const int2 *nbc = reinterpret_cast<const int2 *>(lat->nbr) + (int64_t)(3 * group + 2) * M;
+    const uint32_t *lines = lat->lines + (int64_t)group * M;
+    const int *items = lat->line_items + (int64_t)group * (nitems + 1);
+    const bool v4 = (vd % 4 == 0) && phl_al16(vin) && phl_al16(vout);
+    int xcd_chunk;
+    const unsigned grid = phl_xcd_grid(((int64_t)nitems + 3) / 4, &xcd_chunk);
+    if (v4) k_blur3<4><<<dim3(grid), dim3(256), 0, st>>>(vin, vout, nb2, nbc, lines, items, nitems, M, vd, xcd_chunk);
+    else k_blur3<1><<<dim3(grid), dim3(256), 0, st>>>(vin, vout, nb2, nbc, lines, items, nitems, M, vd, xcd_chunk);
+    PHL_HIP(hipGetLastError());
+    return PHL_OK;
+}
+
+static int launch_blur2_table(const phl_lattice *lat, const int4 *nb2, const blur_rows_t &rr, const float *vin, float *vout, int vd,
+                              hipStream_t st)
+{
+    const int M = (int)lat->M;
     const bool v4 = (vd % 4 == 0) && phl_al16(vin) && phl_al16(vout);
     constexpr int U2 = 1;   // row groups in flight per wave: 9 row loads each; 1 measured best (2: +3 %, 4: +15 %)
     const row_launch rl = launch_rows(rr.total, vd, v4, U2);

@@ -13,6 +13,12 @@
 #define PHL_WAVE 64
 #define PHL_MAX_HIDDEN 64   // duplicate vertices of the reference-table mode (<= 2 per table doubling)
 #define PHL_EMPTY 0x7FFFFFFF  // empty hash slot (larger than any candidate index)
+// line-list flags (phl_lattice::lines): an outer operand of the third blur is zero (no neighbour on axis c), the T of the
+// neighbouring list entry (the wave has it in registers), or T(nbr[c][v]) evaluated from that vertex's own stencil
+#define PHL_LINE_ABSENT 0u
+#define PHL_LINE_SLIDE 1u
+#define PHL_LINE_EVAL 2u
+#define PHL_LINE_VERTEX 0x0FFFFFFFu   // vertex bits of an entry: line lists are made for M <= 2^28
 
 // thread-local error message
 void phl_set_error(const char *fmt, ...);
@@ -51,6 +57,19 @@ struct phl_lattice {
     phl_contrib_t *csr;     // [N] grouped by vertex, pixel-ascending inside a group
     int32_t *nbr;           // [d+1][M][2]
     int32_t *nbr2;          // [(d+1)/2][M][8] composed neighbour ids of axis pairs (2p, 2p+1), see k_blur2
+    // Three axes per pass (k_blur3; phl_rebuild_table_and_neighbors makes them, nothing where d + 1 < 3 or d + 1 == 4 and
+    // nothing for a lattice with ghost vertices).  The d+1 axes go as n3 triples (3g, 3g+1 | 3g+2) and then pairs:
+    //   nbr3       [np3][M][8]  composed ids (layout of nbr2): slot j < n3 is the pair (3j, 3j+1) of triple j, the
+    //                           slots behind them the pairs (3 n3, 3 n3 + 1), (3 n3 + 2, 3 n3 + 3) that end the route
+    //   lines      [n3][M]      every vertex once, in line order along axis c = 3g+2: vertex | minus << 28 | plus << 30
+    //                           (PHL_LINE_*: where the two outer operands of the last blur come from)
+    //   line_items [n3][nitems3 + 1]  first entry of every per-wave work item; item i of group g is
+    //                           lines[g][line_items[g][i] .. line_items[g][i+1])
+    int32_t *nbr3;
+    uint32_t *lines;
+    int32_t *line_items;
+    int n3, np3, line_item_size;
+    int64_t nitems3;
     int *table;             // open-addressing key -> -(vid+1), PHL_EMPTY = free; kept for phl_add_vertices
     uint32_t table_mask;
     int64_t M_local;        // vertices created by this lattice's own pixels (ghosts come after)
@@ -143,7 +162,7 @@ inline void phl_lat_free_all(T *&...member) { ((void)phl_lat_free(member), ...);
 inline void phl_lat_free_persistent(phl_lattice *lat)
 {
     phl_lat_free_all(lat->vkeys, lat->replay, lat->csr_ptr, lat->csr, lat->nbr, lat->nbr2, lat->table, lat->ft_of_int, lat->int_of_ft,
-                     lat->vfirst);
+                     lat->vfirst, lat->nbr3, lat->lines, lat->line_items);
 }
 inline void phl_tiles_free(phl_lattice *lat)
 {
@@ -454,6 +473,11 @@ int phl_launch_splat(phl_lattice *lat, const float *src, int64_t src_rs, int vd,
 // (restricted: only the rows phl_set_blur_rows named for the pass's last axis are computed)
 int phl_launch_blur(const phl_lattice *lat, int axis, const float *vin, float *vout, int vd, hipStream_t st, bool restricted = false);
 int phl_launch_blur2(const phl_lattice *lat, int pair, const float *vin, float *vout, int vd, hipStream_t st, bool restricted = false);
+// the three-axes route (all rows; never on a row-band lattice): does k_blur3 take rows of this width and alignment (one
+// wave per row), triple `group` in one pass, and the pair in slot `slot` of nbr3 through k_blur2
+bool phl_blur3_takes(const phl_lattice *lat, const float *vin, const float *vout, int vd);
+int phl_launch_blur3(const phl_lattice *lat, int group, const float *vin, float *vout, int vd, hipStream_t st);
+int phl_launch_blur2_slot(const phl_lattice *lat, int slot, const float *vin, float *vout, int vd, hipStream_t st);
 int phl_launch_rows(bool scatter, float *vert, int vd, const int64_t *idx, int64_t k, float *buf, int64_t buf_rs, hipStream_t st);
 int phl_launch_slice(const phl_lattice *lat, const float *vert, int vd, float *out, int64_t out_rs,
                      const float *sub, int64_t sub_rs, unsigned flags, hipStream_t st);

@@ -129,6 +129,7 @@ _ABI = (
     ("phl_get_keys", "i", "PP"),
     ("phl_get_replay", "i", "PPP"),
     ("phl_get_neighbors", "i", "PP"),
+    ("phl_get_blur_lines", "i", "PiPPPP"),
     ("phl_get_splat_lists", "i", "PPPP"),
     ("phl_debug_reference_table", "i", "PPqiqPqPPPiPP"),
     ("phl_debug_probe_paths", "i", "PqiPiPiQPiiP"),
@@ -523,6 +524,22 @@ class Lattice:
         out = np.empty((self.d + 1, self.M, 2), np.int32)
         _call("phl_get_neighbors", self._h, _host(out))
         return out
+
+    def blur_lines(self, group=None):
+        """Line lists of the three-axes-per-pass blur (phl_get_blur_lines in include/phl.h).  Without ``group``: the dict
+        {groups, items, item_size} (all 0 where the lattice has none).  With it: (vertex [M] first-touch ids in line
+        order along axis 3*group+2, minus [M], plus [M] flags -- 0 absent, 1 sliding, 2 evaluate --, item_start
+        [items + 1])."""
+        info = np.zeros(3, np.int64)
+        if group is None:
+            _call("phl_get_blur_lines", self._h, 0, None, None, None, _host(info))
+            return dict(zip(("groups", "items", "item_size"), (int(x) for x in info)))
+        items = self.blur_lines()["items"]
+        vertex = np.empty(self.M, np.int32)
+        flags = np.empty(self.M, np.int32)
+        start = np.empty(items + 1, np.int32)
+        _call("phl_get_blur_lines", self._h, int(group), _host(vertex), _host(flags), _host(start), _host(info))
+        return vertex, flags & 3, (flags >> 2) & 3, start
 
     def splat_lists(self):
         ptr = np.empty(self.M + 1, np.int32)

@@ -648,6 +648,14 @@ int phl_get_pixel_order(phl_lattice *lat, int32_t *pix_order_host /* [n] */);
 int phl_get_keys(phl_lattice *lat, int16_t *keys_host /* [M][d] */);
 int phl_get_replay(phl_lattice *lat, int32_t *vid_host /* [n][d+1] */, float *w_host /* [n][d+1] */);
 int phl_get_neighbors(phl_lattice *lat, int32_t *nbr_host /* [d+1][M][2], -1 = absent */);
+/* The line lists of the three-axes-per-pass blur (axis groups (3g, 3g+1 | 3g+2), built where the blur runs at least one
+ * triple and the lattice has no ghost vertices).  info = { groups, work items per group, nominal item size }, all 0
+ * where there are none; with the three arrays null only info is filled.  Group `group`: vertex_host[i] = first-touch
+ * id of list entry i (every vertex once, in line order along axis 3g+2); flags_host[i] = minus | plus << 2, where the
+ * two outer operands of the last blur come from: 0 absent (zero), 1 the neighbouring entry's value, 2 evaluated from
+ * neighbors()[3g+2][v]; work item k is entries [item_start_host[k], item_start_host[k+1]). */
+int phl_get_blur_lines(phl_lattice *lat, int group, int32_t *vertex_host /* [M] */, int32_t *flags_host /* [M] */,
+                       int32_t *item_start_host /* [items + 1] */, int64_t info[3]);
 int phl_get_splat_lists(phl_lattice *lat, int32_t *ptr_host /* [M+1] */, int32_t *pixel_host /* [n(d+1)] */,
                         float *w_host /* [n(d+1)] */);
 
