@@ -30,6 +30,8 @@ SIDE = 48
 
 # case 1: every d -- (d, L)
 EVERY_D = [(d, L) for d in (8, 9, 14, 15, 16) for L in (4, 36, 64)] + [(d, 20) for d in (10, 11, 12, 13)]
+# ... and d = 10 .. 13 at the one L whose wide rows ((cols + 1) * 64 = 320 .. 448 channels) take the three-axes blur route
+EVERY_D += [(d, 64) for d in (10, 11, 12, 13)]
 # case 2: smooth centred features
 SMOOTH = [(8, 64), (16, 64)]
 # case 6: the staged forms of the contracting slice at d >= 8.  (d, L, scale of the image features, form of the worst

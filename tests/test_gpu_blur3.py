@@ -1,12 +1,19 @@
-"""Three lattice axes per blur pass (k_blur3: the third axis by walking lattice lines).
+"""Three lattice axes per blur pass (k_blur3: the third axis by walking lattice lines), d = 2 ... 6.
 
 The arithmetic is axis-by-axis Jacobi with the same blur3 association as the single-axis kernel, so every check here is
 bitwise: there are no tolerances.  Narrow rows (several vertices per wave) and d = 3 keep the pair route; they are in the
 matrix all the same, so a change of the routing rule cannot leave a width untested.
+
+The feature families and the check of the line lists live in tests/_blur3_util.py, shared with
+tests/test_gpu_blur3_every_d.py: every d up to 16 (all tail layouts of triples and pairs), long lines in the later groups,
+the numpy model of the blur as a reference from outside the library (pinned to the CPU oracle by
+tests/test_blur3_model_cpu.py), other item sizes and the lattices on which the route is declined.
 """
 import numpy as np
 import pytest
 import torch
+
+from _blur3_util import _axis_by_axis, _axis_direction, _bits, _check_line_lists, _features, _lines_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,101 +29,6 @@ def phl():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     _phl.load_library()
     return _phl
-
-
-def _axis_direction(d, c):
-    """A feature-space direction whose elevation is the lattice's axis-c direction (1, .., 1, -d at c, 1, .., 1): pixels
-    on a ramp along it walk one lattice line of axis c."""
-    from oracle import phl_oracle as po
-
-    sf = po.scale_factors(d).astype(np.float64)
-    E = np.zeros((d + 1, d))
-    for k in range(d):                  # the elevation's column of feature k: +1 at 0..k, -(k+1) at k+1, times the scale
-        E[: k + 1, k] = 1
-        E[k + 1, k] = -(k + 1)
-    E *= sf[None, :]
-    a = np.ones(d + 1)
-    a[c] = -d
-    f = np.linalg.lstsq(E, a, rcond=None)[0]
-    assert np.allclose(E @ f, a)
-    return f
-
-
-def _features(kind, d):
-    rng = np.random.default_rng(1000 + d)
-    if kind == "smooth":                # a 48 x 64 image: position over 4 px, smooth colours
-        y, x = np.mgrid[0:48, 0:64].astype(np.float32)
-        cols = [x / 4, y / 4] + [np.sin(x / (7 + 3 * k)) * np.cos(y / (5 + 2 * k)) * 2 + k for k in range(d - 2)]
-        return np.stack(cols[:d], -1).reshape(-1, d).astype(np.float32)
-    if kind == "iid":                   # almost every line has length 1
-        return (rng.random((3000, d), dtype=np.float32) * 40).astype(np.float32)
-    if kind == "constant":              # d + 1 vertices
-        return np.full((500, d), 0.37, np.float32)
-    if kind == "single_pixel":
-        return np.full((1, d), 0.37, np.float32)
-    if kind == "feature_ramp":          # 1 x 4096, one feature varies
-        ref = np.full((4096, d), 0.37, np.float32)
-        ref[:, d - 1] += np.arange(4096, dtype=np.float32) * np.float32(0.25)
-        return ref
-    if kind == "axis_ramp":             # 1 x 4096 along lattice axis 2: one line of ~1025 vertices per remainder
-        t = np.arange(4096, dtype=np.float64) * 0.25
-        return (t[:, None] * _axis_direction(d, 2)[None, :] + 0.37).astype(np.float32)
-    raise AssertionError(kind)
-
-
-def _axis_by_axis(lat, v0):
-    a, b = v0.clone(), torch.empty_like(v0)
-    for axis in range(lat.d + 1):
-        lat.blur_axis(axis, a, b)
-        a, b = b, a
-    return a
-
-
-def _bits(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _lines_of(vertex, nbr_c):
-    """Line id of every list entry: consecutive entries belong together iff they are mutual neighbours."""
-    prev, cur = vertex[:-1], vertex[1:]
-    joined = (nbr_c[prev, 1] == cur) & (nbr_c[cur, 0] == prev)
-    return np.concatenate([[0], np.cumsum(~joined)]), joined
-
-
-def _check_line_lists(lat):
-    """Every vertex once; sliding only between consecutive mutual neighbours inside one work item; absent exactly where
-    nbr[c] is -1; evaluate for everything else.  Returns the longest line over all groups."""
-    info = lat.blur_lines()
-    if info["groups"] == 0:
-        assert info == {"groups": 0, "items": 0, "item_size": 0}
-        return 0
-    nbr = lat.neighbors()
-    M, K = lat.M, info["item_size"]
-    assert info["items"] == (M + K - 1) // K
-    longest = 0
-    for g in range(info["groups"]):
-        c = 3 * g + 2
-        vertex, minus, plus, start = lat.blur_lines(g)
-        assert np.array_equal(np.sort(vertex), np.arange(M))
-        assert start[0] == 0 and start[-1] == M and np.all(np.diff(start) >= 1) and np.all(np.diff(start) < 2 * K)
-        is_start = np.zeros(M + 1, bool)
-        is_start[start] = True
-        line, joined = _lines_of(vertex, nbr[c])
-        slide_minus = np.concatenate([[False], joined & ~is_start[1:M]])
-        slide_plus = np.concatenate([joined & ~is_start[1:M], [False]])
-        for flag, side, slide in ((minus, 0, slide_minus), (plus, 1, slide_plus)):
-            absent = nbr[c][vertex, side] < 0
-            assert np.array_equal(flag == 0, absent)
-            assert np.array_equal(flag == 1, slide & ~absent)
-            assert np.array_equal(flag == 2, ~absent & ~slide)
-        # lines in the order of their first member: the starts' first-touch ids need not ascend (rows do), but every
-        # line is whole and an item is cut inside a line only where that line fills the whole bucket of K entries (the
-        # list's last bucket may be shorter)
-        length = np.bincount(line)
-        inside = 1 + np.nonzero(is_start[1:M] & joined)[0]
-        assert np.all(inside % K == 0) and np.all(line[inside] == line[np.minimum(inside + K, M) - 1])
-        longest = max(longest, int(length.max()))
-    return longest
 
 
 KINDS = ("smooth", "iid", "constant", "single_pixel", "feature_ramp", "axis_ramp")
