@@ -461,18 +461,23 @@ class CRFasRNN(nn.Module):
     covariance of the guide channels (crf.guided; its recorded forward is the torch form, or with ``full_cov_grad=True``
     phl.GuidedFilterFullFn, which trains that W on the library's kernels for up to four guide channels).  ``mode`` is the
     guided W's interpolation (FastGuidedFilter); ``mode='bilinear'`` with ``fused_bilinear=True`` puts its unrecorded
-    forward on phl.guided_filter_bilinear.  Everything else -- CPU tensors, float64,
+    forward on phl.guided_filter_bilinear, and with ``bilinear_grad=True`` as well its recorded forward on
+    phl.GuidedFilterBilinearFn, which trains that W on the library's kernels (the diagonal model).  Everything else -- CPU tensors, float64,
     another Mu, a label count out of a route's range -- is the plain NCHW loop, with the bits it always had.
     ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with; on
     the step routes the loop itself ends in the expected label, and the logits are never written."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
-                 fused_grad=False, fused_step=False, full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False):
+                 fused_grad=False, fused_step=False, full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False,
+                 bilinear_grad=False):
         super().__init__()
         if lattice and full_cov:
             raise ValueError("CRFasRNN: full_cov belongs to the guided-filter W; lattice=True has no covariance model")
-        if lattice and (mode != "nearest" or fused_bilinear):
-            raise ValueError("CRFasRNN: mode and fused_bilinear belong to the guided-filter W; lattice=True does not interpolate")
+        if lattice and (mode != "nearest" or fused_bilinear or bilinear_grad):
+            raise ValueError("CRFasRNN: mode, fused_bilinear and bilinear_grad belong to the guided-filter W; lattice=True does "
+                             "not interpolate")
+        if bilinear_grad and not fused_bilinear:
+            raise ValueError("CRFasRNN: bilinear_grad=True is the backward of the fused_bilinear W: it needs fused_bilinear=True")
         if full_cov_grad and not full_cov:
             raise ValueError("CRFasRNN: full_cov_grad=True is the backward of the full-covariance W: it needs full_cov=True")
         self.Mu, self.niters = mu_init, niters
@@ -483,7 +488,8 @@ class CRFasRNN(nn.Module):
         self.W = BatchedAdjacency() if lattice else BatchedGuidedAdjacency(gchannels, r, eps, gaussian=gaussian,
                                                                              fused_grad=fused_grad and not gaussian,
                                                                              full_cov=full_cov, full_cov_grad=full_cov_grad,
-                                                                             mode=mode, fused_bilinear=fused_bilinear)
+                                                                             mode=mode, fused_bilinear=fused_bilinear,
+                                                                             bilinear_grad=bilinear_grad)
         self.fused_grad, self.fused_step = fused_grad, fused_step
 
     def forward(self, refs, logits, confidence=None, labels=None, energies=None):

@@ -26,7 +26,11 @@ torch form as before.
 ``mode='bilinear'`` of FastGuidedFilter / BatchedGuidedAdjacency (coefficients solved on the bilinearly down-sampled
 images and interpolated back up) reaches the kernels under the keyword ``fused_bilinear=True``: a forward that autograd
 does not record is then phl.guided_filter_bilinear (either model; the taps are computed on the device).  Without the
-keyword, and for every recorded forward, the mode keeps the torch form.
+keyword, and for every recorded forward, the mode keeps the torch form -- unless the keyword ``bilinear_grad=True`` is
+given as well (it needs ``fused_bilinear=True``, and has the diagonal model only): a recorded forward is then
+phl.GuidedFilterBilinearFn, whose backward (phl.guided_filter_bilinear_grad) recomputes the model from y, x and eps and
+gives y, x and omega their gradients.  At subsample_ratio 1 that is phl.GuidedFilterFn; more than 16 guide channels, CPU
+tensors and float64 stay on the torch form.
 
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
@@ -223,17 +227,22 @@ class GuidedFilter(nn.Module):
         softplus(omega) keeps its graph); ``subtract`` is None or y itself.  FastGuidedFilter's ``mode='bilinear'`` with
         ``fused_bilinear=True`` is phl.guided_filter_bilinear for a forward that autograd does not record (at subsample 1
         both interpolations are the identity: the nearest route); a recorded one keeps the torch form, ``fused_grad`` /
-        ``full_cov_grad`` or not."""
+        ``full_cov_grad`` or not, unless ``bilinear_grad=True``: then it is phl.GuidedFilterBilinearFn (at subsample 1
+        phl.GuidedFilterFn, the same function there)."""
         mode = getattr(self, "mode", "nearest")
         bilinear = mode == "bilinear" and getattr(self, "fused_bilinear", False)
+        bilinear_grad = bilinear and getattr(self, "bilinear_grad", False)
         if self.gaussian or not (mode == "nearest" or bilinear) or not (_hip_ok(y) and _hip_ok(x)):
             return None
         if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
             return None
         recording = torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad)
-        if recording and (bilinear or not (self.full_cov_grad if self.full_cov else self.fused_grad)):
+        if recording and not bilinear_grad and (bilinear or not (self.full_cov_grad if self.full_cov else self.fused_grad)):
             return None
         try:
+            if bilinear_grad and recording:
+                fn = phl.GuidedFilterBilinearFn if subsample >= 2 else phl.GuidedFilterFn
+                return fn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             if bilinear and subsample >= 2:
                 return phl.guided_filter_bilinear(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract,
                                                   full_cov=self.full_cov)
@@ -261,16 +270,21 @@ class GuidedFilter(nn.Module):
 class FastGuidedFilter(GuidedFilter):
     """Coefficients solved at 1/subsample_ratio resolution and upsampled (:234-253)."""
 
-    def __init__(self, *args, subsample_ratio=2, mode="nearest", fused_bilinear=False, **kwargs):
+    def __init__(self, *args, subsample_ratio=2, mode="nearest", fused_bilinear=False, bilinear_grad=False, **kwargs):
         super().__init__(*args, **kwargs)
         if self.gaussian:
             # the reference's constructor reads self._r, which its gaussian form never sets (AttributeError, :238)
             raise NotImplementedError("FastGuidedFilter(gaussian=True) does not construct in the reference either")
         if fused_bilinear and mode != "bilinear":
             raise ValueError(f"fused_bilinear=True is the kernel route of mode='bilinear', got mode={mode!r}")
+        if bilinear_grad and not fused_bilinear:
+            raise ValueError("bilinear_grad=True is the backward of the fused_bilinear route: it needs fused_bilinear=True")
+        if bilinear_grad and self.full_cov:
+            raise NotImplementedError("bilinear_grad=True with full_cov=True: the fused bilinear backward has the diagonal model only")
         self.subsample_ratio = subsample_ratio
         self.mode = mode
         self.fused_bilinear = fused_bilinear
+        self.bilinear_grad = bilinear_grad
 
     def _window(self):
         return self._r // self.subsample_ratio

@@ -23,7 +23,8 @@
 // (phl_guided_filter_full, the model over the whole covariance matrix of the guide channels: k_guide_stats_full and
 // k_guide_coef_full in the places of the first two, after run() below; its backward after run_grad().
 // phl_guided_filter_bilinear, FastGuidedFilter(mode='bilinear'): the first two kernels of either model with a four-tap
-// tile fill, then k_guide_mean and k_guide_up in the place of k_guide_apply, after run_full().)
+// tile fill, then k_guide_mean and k_guide_up in the place of k_guide_apply, after run_full(); its backward is
+// run_grad<true>.)
 // Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
 // routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.  The
 // kernels of both directions reach the two forms through one front end (plane_sums, square_sums, product_sums).
@@ -878,10 +879,74 @@ int run_bilinear(const Plan &p, const float *y, const float *x, const float *src
 //   k_grad_x        per (image, tile), channels in a loop: gxs into LDS -> grad_x over the tile's full-resolution pixels
 //   k_grad_eps1/2   grad_eps: a fixed-order two-stage fp64 reduction of gvar_c
 // No atomics anywhere; every gradient is rounded to fp32 once.
+//
+// BL, the backward of phl_guided_filter_bilinear (the diagonal model): ys = D(y), xs = D(x) and out_l = scale (sum_c
+// U(mean A_lc) x_c + U(mean b_l)) - src_l.  Everything between gA and gys, gxs, gvar above is the same code on the same
+// low-resolution planes; the four places that connect the two resolutions take their bilinear form:
+//   k_grad_gather<true>   ys / xs = the four-tap samples, bil_tap / bil_mix and the one rounding to fp32 of the forward's
+//                         tile fill, so that k_guide_stats and k_grad_coef on these planes (identity maps) recompute
+//                         the forward's model bit for bit
+//   k_grad_down<true>     gAbar_lc = scale U^T(g_l x_c), gbbar_l = scale U^T(g_l): U's first tap is non-decreasing in the
+//                         output index, so the full-resolution rows (columns) that tap a low-resolution row (column)
+//                         are one range (up_lower_bound); the thread of a low-resolution pixel sums its rectangle
+//                         with the weights of up_weight, rows then columns, fp64
+//   scatter_tile<true>    D^T: with H >= 2h the first taps of D are at least 2 apart, so a full-resolution row is a tap
+//                         of at most one low-resolution row (down_owner; columns likewise) and D^T is a gather of one
+//                         low-resolution pixel with the product of the two axis weights, 0 where there is none
+//   k_grad_direct<true>   scale sum_l g_l[p] U(mean A_lc)[p] with the four taps of k_guide_up
+// The entry point refuses 2h > H and 2w > W, which the single owner of scatter_tile<true> rests on.
 constexpr int NE = 256;             // threads of the pointwise kernels
 constexpr int NEB = 128;            // first-stage workgroups per channel of the grad_eps reduction
 enum { PART_VAR = 0, PART_MX = 1, PART_YU = 2, NPART = kGradParts };
 
+// U (n low -> N full, sc = (double)n / N) along an axis: the first full index whose first tap is >= v (the first tap is
+// non-decreasing in the full index), and the weight of low index i in the sample at full index I (both taps the same
+// index at a clamped edge: their sum)
+__device__ __forceinline__ int up_lower_bound(int N, double sc, int n, int v)
+{
+    int lo = 0, hi = N;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        int a, b;
+        double l;
+        bil_tap(mid, sc, n, a, b, l);
+        if (a < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ double up_weight(int I, double sc, int n, int i)
+{
+    int a, b;
+    double l;
+    bil_tap(I, sc, n, a, b, l);
+    return (a == i ? 1.0 - l : 0.0) + (b == i ? l : 0.0);
+}
+// D (N full -> n low, sc = (double)N / n >= 2) along an axis: the first tap of low index i, and the one low index whose
+// sample takes full index I with its weight (-1 and 0 where I is nobody's tap).  The first taps are strictly increasing
+// and at least 2 apart, so the owner is the last i whose first tap is <= I: an estimate from the inverse map, corrected
+// with the taps themselves.
+__device__ __forceinline__ int down_first_tap(int i, double sc, int N)
+{
+    int a, b;
+    double l;
+    bil_tap(i, sc, N, a, b, l);
+    return a;
+}
+__device__ __forceinline__ int down_owner(int I, double sc, int N, int n, double &wgt)
+{
+    int i = clampi((int)floor(((double)I + 1.5) / sc - 0.5), 0, n - 1);
+    while (i + 1 < n && down_first_tap(i + 1, sc, N) <= I) i++;
+    while (i >= 0 && down_first_tap(i, sc, N) > I) i--;
+    wgt = 0.0;
+    if (i < 0) return -1;
+    int a, b;
+    double l;
+    bil_tap(i, sc, N, a, b, l);
+    wgt = (a == I ? 1.0 - l : 0.0) + (b == I ? l : 0.0);
+    return i;
+}
+
+template <bool BL = false>
 __global__ __launch_bounds__(NE) void k_grad_gather(const float *__restrict__ src, float *__restrict__ dst,
                                                    const int *__restrict__ rmap, const int *__restrict__ cmap, int H, int W, int h,
                                                    int w)
@@ -890,9 +955,19 @@ __global__ __launch_bounds__(NE) void k_grad_gather(const float *__restrict__ sr
     if (q >= hw) return;
     const int64_t pl = (int64_t)blockIdx.z * gridDim.y + blockIdx.y;
     const int i = (int)(q / w), j = (int)(q % w);
-    dst[pl * hw + q] = src[pl * H * W + (int64_t)clampi(rmap[i], 0, H - 1) * W + clampi(cmap[j], 0, W - 1)];
+    if constexpr (BL) {                                              // Tile::ld<true>: the sample the forward's tiles hold
+        int i0, i1, j0, j1;
+        double ly, lx;
+        bil_tap(i, (double)H / (double)h, H, i0, i1, ly);
+        bil_tap(j, (double)W / (double)w, W, j0, j1, lx);
+        const float *p0 = src + pl * H * W + (int64_t)i0 * W, *p1 = src + pl * H * W + (int64_t)i1 * W;
+        dst[pl * hw + q] = (float)bil_mix(p0[j0], p0[j1], p1[j0], p1[j1], ly, lx);
+    } else {
+        dst[pl * hw + q] = src[pl * H * W + (int64_t)clampi(rmap[i], 0, H - 1) * W + clampi(cmap[j], 0, W - 1)];
+    }
 }
 
+template <bool BL = false>
 __global__ __launch_bounds__(NE) void k_grad_down(const float *__restrict__ g, const float *__restrict__ x, float *__restrict__ P,
                                                  const int *__restrict__ rlow, const int *__restrict__ clow, int n0, int cy, int cx,
                                                  int H, int W, int h, int w, int r, float scale)
@@ -901,18 +976,26 @@ __global__ __launch_bounds__(NE) void k_grad_down(const float *__restrict__ g, c
     if (q >= hw) return;
     const int z = blockIdx.y, n = n0 + z, b = n / cy;
     const int i = (int)(q / w), j = (int)(q % w);
-    const int I0 = lower_bound(rlow, H, i), I1 = lower_bound(rlow, H, i + 1);
-    const int J0 = lower_bound(clow, W, j), J1 = lower_bound(clow, W, j + 1);
+    // the full-resolution rows and columns that reach the pixel: its pre-image under the nearest maps, or (BL) those
+    // whose taps of U include it, first tap i - 1 or i
+    const double sy = (double)h / (double)H, sx = (double)w / (double)W;
+    const int I0 = BL ? up_lower_bound(H, sy, h, i - 1) : lower_bound(rlow, H, i);
+    const int I1 = BL ? up_lower_bound(H, sy, h, i + 1) : lower_bound(rlow, H, i + 1);
+    const int J0 = BL ? up_lower_bound(W, sx, w, j - 1) : lower_bound(clow, W, j);
+    const int J1 = BL ? up_lower_bound(W, sx, w, j + 1) : lower_bound(clow, W, j + 1);
     const double k = (double)scale / ((double)win_count(i, r, h) * (double)win_count(j, r, w));
     const float *gp = g + (int64_t)n * HWf;
     for (int c = 0; c <= cx; c++) {
         const float *xp = c < cx ? x + ((int64_t)b * cx + c) * HWf : nullptr;
         double acc = 0.0;
-        for (int I = I0; I < I1; I++)
+        for (int I = I0; I < I1; I++) {
+            const double wy = BL ? up_weight(I, sy, h, i) : 1.0;
             for (int J = J0; J < J1; J++) {
                 const int64_t o = (int64_t)I * W + J;
-                acc += xp ? (double)gp[o] * (double)xp[o] : (double)gp[o];
+                const double v = xp ? (double)gp[o] * (double)xp[o] : (double)gp[o];
+                if constexpr (BL) acc += wy * up_weight(J, sx, w, j) * v; else acc += v;
             }
+        }
         P[((int64_t)z * (cx + 1) + c) * hw + q] = (float)(acc * k);
     }
 }
@@ -964,11 +1047,33 @@ __global__ __launch_bounds__(NT) void k_grad_coef(const float *__restrict__ ys, 
 // the sample (rmapS[i], cmapS[j]) of the tile's low-resolution pixel (i, j), 0 at the others.  The shares partition the
 // image: the rows from the sample row of the tile's first row up to that of the next tile's (strictly increasing maps),
 // columns likewise -- a sample need not lie in the pre-image of its own low-resolution pixel under the upsampling maps.
-template <typename F>
+// BL: the samples are D's; the value is G at the one low-resolution pixel whose taps include the pixel (down_owner per
+// axis), times the product of the two axis weights, and the shares run between the first taps of the tiles' first rows
+// and columns (no maps).
+template <bool BL = false, typename F>
 __device__ __forceinline__ void scatter_tile(const Tile &t, const double *__restrict__ G, const int *__restrict__ rmapS,
                                              const int *__restrict__ cmapS, int H, int W, F f)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if constexpr (BL) {
+        const double sy = (double)H / (double)t.h, sx = (double)W / (double)t.w;
+        const int I0 = t.ti == 0 ? 0 : clampi(down_first_tap(t.ti, sy, H), 0, H);
+        const int I1 = t.ti + TH >= t.h ? H : clampi(down_first_tap(t.ti + TH, sy, H), 0, H);
+        const int J0 = t.tj == 0 ? 0 : clampi(down_first_tap(t.tj, sx, W), 0, W);
+        const int J1 = t.tj + TW >= t.w ? W : clampi(down_first_tap(t.tj + TW, sx, W), 0, W);
+        for (int I = I0 + wave; I < I1; I += 4) {
+            double wy;
+            const int i = down_owner(I, sy, H, t.h, wy);
+            const bool ri = i >= t.ti && i < t.ti + TH && i < t.h;
+            for (int J = J0 + lane; J < J1; J += 64) {
+                double wx;
+                const int j = down_owner(J, sx, W, t.w, wx);
+                const bool hit = ri && j >= t.tj && j < t.tj + TW && j < t.w;
+                f((int64_t)I * W + J, hit ? wy * wx * G[(i - t.ti) * TW + (j - t.tj)] : 0.0);
+            }
+        }
+        return;
+    }
     const int I0 = t.ti == 0 ? 0 : clampi(rmapS[t.ti], 0, H), I1 = t.ti + TH >= t.h ? H : clampi(rmapS[t.ti + TH], 0, H);
     const int J0 = t.tj == 0 ? 0 : clampi(cmapS[t.tj], 0, W), J1 = t.tj + TW >= t.w ? W : clampi(cmapS[t.tj + TW], 0, W);
     for (int I = I0 + wave; I < I1; I += 4) {
@@ -982,7 +1087,7 @@ __device__ __forceinline__ void scatter_tile(const Tile &t, const double *__rest
     }
 }
 
-template <bool ST>
+template <bool ST, bool BL = false>
 __global__ __launch_bounds__(NT) void k_grad_apply(const float *__restrict__ Q, const float *__restrict__ A,
                                                   const float *__restrict__ ys, const float *__restrict__ xs,
                                                   const float *__restrict__ g, float *__restrict__ grad_y, float *__restrict__ mA,
@@ -1017,8 +1122,8 @@ __global__ __launch_bounds__(NT) void k_grad_apply(const float *__restrict__ Q, 
     __syncthreads();
     const float *gp = g + (int64_t)n * HWf;
     float *op = grad_y + (int64_t)n * HWf;
-    scatter_tile(t, G, rmapS, cmapS, H, W,
-                 [&](int64_t o, double v) { op[o] = (float)(subtract_is_y ? v - (double)gp[o] : v); });
+    scatter_tile<BL>(t, G, rmapS, cmapS, H, W,
+                     [&](int64_t o, double v) { op[o] = (float)(subtract_is_y ? v - (double)gp[o] : v); });
 }
 
 // acc[sel][b][c] (+)= sum over the chunk's labels of image b, in index order, of part[label][sel][c]; a label has
@@ -1039,6 +1144,8 @@ __global__ __launch_bounds__(NE) void k_grad_reduce(const double *__restrict__ p
 }
 
 // D[b][c][p] (+)= sum over the chunk's labels of image b, in index order, of g_l[p] mean(A_lc)[lo(p)]
+// (BL: of g_l[p] U(mean(A_lc))[p], the four taps and the mix of k_guide_up)
+template <bool BL = false>
 __global__ __launch_bounds__(NE) void k_grad_direct(const float *__restrict__ g, const float *__restrict__ mA, double *__restrict__ D,
                                                    const int *__restrict__ rlow, const int *__restrict__ clow, int n0, int nz, int cy,
                                                    int cx, int H, int W, int h, int w)
@@ -1047,9 +1154,21 @@ __global__ __launch_bounds__(NE) void k_grad_direct(const float *__restrict__ g,
     if (p >= HWf) return;
     const int c = blockIdx.y, b = n0 / cy + blockIdx.z;
     const int na = max(n0, b * cy), nb = min(n0 + nz, (b + 1) * cy);
-    const int64_t lo = (int64_t)clampi(rlow[p / W], 0, h - 1) * w + clampi(clow[p % W], 0, w - 1);
     double s = 0.0;
-    for (int n = na; n < nb; n++) s += (double)g[(int64_t)n * HWf + p] * (double)mA[((int64_t)(n - n0) * cx + c) * hw + lo];
+    if constexpr (BL) {
+        int i0, i1, j0, j1;
+        double ly, lx;
+        bil_tap((int)(p / W), (double)h / (double)H, h, i0, i1, ly);
+        bil_tap((int)(p % W), (double)w / (double)W, w, j0, j1, lx);
+        const int64_t q0 = (int64_t)i0 * w, q1 = (int64_t)i1 * w;
+        for (int n = na; n < nb; n++) {
+            const float *m = mA + ((int64_t)(n - n0) * cx + c) * hw;
+            s += (double)g[(int64_t)n * HWf + p] * bil_mix(m[q0 + j0], m[q0 + j1], m[q1 + j0], m[q1 + j1], ly, lx);
+        }
+    } else {
+        const int64_t lo = (int64_t)clampi(rlow[p / W], 0, h - 1) * w + clampi(clow[p % W], 0, w - 1);
+        for (int n = na; n < nb; n++) s += (double)g[(int64_t)n * HWf + p] * (double)mA[((int64_t)(n - n0) * cx + c) * hw + lo];
+    }
     double *d = D + ((int64_t)b * cx + c) * HWf + p;
     *d = na == b * cy ? s : *d + s;
 }
@@ -1065,7 +1184,7 @@ __global__ __launch_bounds__(NE) void k_grad_finish(const double *__restrict__ a
     F[(bc * 2 + 1) * hw + q] = (float)gv;
 }
 
-template <bool ST>
+template <bool ST, bool BL = false>
 __global__ __launch_bounds__(NT) void k_grad_x(const float *__restrict__ F, const double *__restrict__ YU,
                                               const float *__restrict__ xs, const double *__restrict__ D, float *__restrict__ grad_x,
                                               const int *__restrict__ rmapS, const int *__restrict__ cmapS, int cx, int H, int W,
@@ -1093,7 +1212,7 @@ __global__ __launch_bounds__(NT) void k_grad_x(const float *__restrict__ F, cons
         __syncthreads();
         const double *dp = D + bc * HWf;
         float *op = grad_x + bc * HWf;
-        scatter_tile(t, G, rmapS, cmapS, H, W, [&](int64_t o, double v) { op[o] = (float)((double)scale * dp[o] + v); });
+        scatter_tile<BL>(t, G, rmapS, cmapS, H, W, [&](int64_t o, double v) { op[o] = (float)((double)scale * dp[o] + v); });
         // (the next channel's first write to G comes after the barriers of its plane_sums)
     }
 }
@@ -1131,19 +1250,23 @@ __global__ void k_grad_eps2(const double *__restrict__ partial, float *__restric
     grad_eps[c] = (float)s;
 }
 
+// BL: the backward of run_bilinear's diagonal model (no maps; the four pieces named above in their bilinear form).  The
+// per-label planes are those of the nearest form below full resolution, so Plan::per_backward(full = false) sizes the
+// chunks of both.
+template <bool BL = false>
 int run_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B, int cy, int cx,
              int H, int W, int h, int w, int re, const int *row_of_low, const int *col_of_low, const int *low_of_row,
              const int *low_of_col, const float *eps, float scale, int subtract_is_y, hipStream_t st)
 {
     const Plan p(re, h, w);
-    const bool full = h == H && w == W;                 // strictly increasing maps onto the same size: the identity
+    const bool full = !BL && h == H && w == W;          // strictly increasing maps onto the same size: the identity
     const bool need_x = grad_x != nullptr, need_xe = need_x || grad_eps != nullptr, need_apply = need_x || grad_y != nullptr;
     const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, nimg = (int64_t)B * cy;
     const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
     auto stats = p.tiled ? k_guide_stats<false> : k_guide_stats<true>;
     auto coefk = p.tiled ? k_grad_coef<false> : k_grad_coef<true>;
-    auto apply = p.tiled ? k_grad_apply<false> : k_grad_apply<true>;
-    auto gxk = p.tiled ? k_grad_x<false> : k_grad_x<true>;
+    auto apply = p.tiled ? k_grad_apply<false, BL> : k_grad_apply<true, BL>;
+    auto gxk = p.tiled ? k_grad_x<false, BL> : k_grad_x<true, BL>;
     if (int rc = phl_allow_lds(stats, p.lds_stats)) return rc;
     if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
     if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
@@ -1166,17 +1289,20 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
     int &rc = tmp.rc;
     const float *xs = full ? x : xsb;
     if (rc == PHL_OK) {
-        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
         if (!full)
-            k_grad_gather<<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
+            k_grad_gather<BL><<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
+        if constexpr (BL)       // on the samples, which are what the forward's four-tap tile fill holds: the same sums
+            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(xsb, nullptr, nullptr, eps, mx, inv, cx, h, w, h, w, re);
+        else
+            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
         phl_launched(rc, "k_guide_stats / k_grad_gather");
     }
     for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
         const unsigned nz = (unsigned)min(chunk, nimg - n0);
         const unsigned nb = (unsigned)((n0 + nz - 1) / cy - n0 / cy + 1);          // images the chunk touches
         const float *ys = full ? y + n0 * HWf : ysb;
-        if (!full) k_grad_gather<<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
-        k_grad_down<<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, P, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h, w, re, scale);
+        if (!full) k_grad_gather<BL><<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
+        k_grad_down<BL><<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, P, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h, w, re, scale);
         coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(ys, xs, P, mx, inv, Q, A, part, (int)n0, cy, cx, h, w, re);
         if (need_apply)
             apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low, col_of_low,
@@ -1185,8 +1311,8 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
             k_grad_reduce<<<dim3(nblo, (unsigned)cx, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, cx, B, need_x ? NPART : 2,
                                                                             NPART * cx, hw);
         if (need_x)
-            k_grad_direct<<<dim3(nbfull, (unsigned)cx, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy, cx,
-                                                                              H, W, h, w);
+            k_grad_direct<BL><<<dim3(nbfull, (unsigned)cx, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy,
+                                                                                  cx, H, W, h, w);
         phl_launched(rc, "the backward's chunk kernels");
     }
     if (need_x && rc == PHL_OK) {
@@ -1443,6 +1569,20 @@ int check_guided_args(const char *who, const void *y, const void *x, const void 
     return PHL_OK;
 }
 
+// ... and of the three backwards: no gradient is an input or another gradient
+int check_grad_aliasing(const char *who, const void *y, const void *x, const void *g, const void *eps, const void *grad_y,
+                        const void *grad_x, const void *grad_eps)
+{
+    const void *ins[4] = {y, x, g, eps}, *outs[3] = {grad_y, grad_x, grad_eps};
+    for (int o = 0; o < 3; o++)
+        for (int i = 0; i < 4; i++)
+            if (outs[o] && (outs[o] == ins[i] || (i < o && outs[o] == outs[i]))) {
+                phl_set_error("%s: a gradient aliases an input or another gradient", who);
+                return PHL_ERR_INVALID;
+            }
+    return PHL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1516,13 +1656,7 @@ int phl_guided_filter_grad(const float *y, const float *x, const float *g, float
                                    low_of_col, eps, scale))
         return rc;
     if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
-    const void *ins[4] = {y, x, g, eps}, *outs[3] = {grad_y, grad_x, grad_eps};
-    for (int o = 0; o < 3; o++)
-        for (int i = 0; i < 4; i++)
-            if (outs[o] && (outs[o] == ins[i] || (i < o && outs[o] == outs[i]))) {
-                phl_set_error("phl_guided_filter_grad: a gradient aliases an input or another gradient");
-                return PHL_ERR_INVALID;
-            }
+    if (int rc = check_grad_aliasing("phl_guided_filter_grad", y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
     const int re = min(r, max(h, w));
     return run_grad(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps,
                     scale, subtract_is_y, (hipStream_t)stream);
@@ -1542,13 +1676,7 @@ int phl_guided_filter_full_grad(const float *y, const float *x, const float *g, 
                       PHL_GUIDED_FULL_MAX_CX);
         return PHL_ERR_UNSUPPORTED;
     }
-    const void *ins[4] = {y, x, g, eps}, *outs[3] = {grad_y, grad_x, grad_eps};
-    for (int o = 0; o < 3; o++)
-        for (int i = 0; i < 4; i++)
-            if (outs[o] && (outs[o] == ins[i] || (i < o && outs[o] == outs[i]))) {
-                phl_set_error("phl_guided_filter_full_grad: a gradient aliases an input or another gradient");
-                return PHL_ERR_INVALID;
-            }
+    if (int rc = check_grad_aliasing("phl_guided_filter_full_grad", y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
     static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
     using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, float *, float *, int, int, int, int, int, int,
                         int, const int *, const int *, const int *, const int *, const float *, float, int, hipStream_t);
@@ -1604,6 +1732,28 @@ int phl_guided_filter_bilinear_labels_per_chunk(int B, int cy, int cx, int h, in
 {
     if (B < 1 || cy < 1 || cx < 1 || h < 1 || w < 1) return 0;
     return (int)Plan::chunk((int64_t)B * cy, Plan::per_bilinear(cx, (int64_t)h * w));
+}
+
+int phl_guided_filter_bilinear_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps,
+                                    int B, int cy, int cx, int H, int W, int h, int w, int r, const float *eps, float scale,
+                                    int subtract_is_y, unsigned flags, phl_stream stream)
+{
+    if (int rc = check_guided_args("phl_guided_filter_bilinear_grad", y, x, g, "g", B, cy, cx, H, W, h, w, r, nullptr, nullptr, nullptr,
+                                   nullptr, eps, scale, false))
+        return rc;
+    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
+    if (flags) {
+        phl_set_error("phl_guided_filter_bilinear_grad: flags 0x%x (the full-covariance form has no fused backward)", flags);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (2 * (int64_t)h > H || 2 * (int64_t)w > W) {       // below a ratio of 2 two samples of D may share a tap
+        phl_set_error("phl_guided_filter_bilinear_grad: %d x %d is more than half of %d x %d", h, w, H, W);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (int rc = check_grad_aliasing("phl_guided_filter_bilinear_grad", y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
+    const int re = min(r, max(h, w));
+    return run_grad<true>(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, nullptr, nullptr, nullptr, nullptr, eps, scale,
+                          subtract_is_y, (hipStream_t)stream);
 }
 
 }  // extern "C"

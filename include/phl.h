@@ -601,7 +601,7 @@ int phl_guided_filter_full_grad(const float *y_dev, const float *x_dev, const fl
  * other arguments as phl_guided_filter_labels_per_chunk.  0 for sizes below 1, cx > PHL_GUIDED_FULL_MAX_CX or another needs. */
 int phl_guided_filter_full_grad_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs);
 
-/* FastGuidedFilter(mode='bilinear'), forward only: the tensors, eps, the window sums and the status rules of
+/* FastGuidedFilter(mode='bilinear'), the forward (backward: phl_guided_filter_bilinear_grad): the tensors, eps, the window sums and the status rules of
  * phl_guided_filter, but no index maps -- with D = F.interpolate(., size=(h, w), mode='bilinear') and
  * U = F.interpolate(., size=(H, W), mode='bilinear') (align_corners=False, no antialias)
  *   (mean(A), mean(b)) = the model of phl_guided_filter on D(y), D(x), r the radius at h x w
@@ -622,6 +622,27 @@ int phl_guided_filter_bilinear(const float *y_dev, const float *x_dev, const flo
 /* Labels per chunk of a phl_guided_filter_bilinear call (the window-mean planes join the coefficient planes in the
  * budget); host arithmetic only.  0 for sizes below 1. */
 int phl_guided_filter_bilinear_labels_per_chunk(int B, int cy, int cx, int h, int w);
+/* Backward of phl_guided_filter_bilinear (the diagonal model, flags = 0) with src = NULL (subtract_is_y = 0) or src = y
+ * (subtract_is_y != 0): g, the three gradients (each may be NULL, all NULL is PHL_OK with nothing launched), the
+ * recomputation from y, x and eps, the fp64 sums in a fixed order without atomics and the single rounding of every
+ * gradient are those of phl_guided_filter_grad.  D(y) and D(x) are taken again with the forward's taps, weights and
+ * rounding, so the model is the forward's bit for bit; the gradients of mean(A) and mean(b) are scale * U^T(g x_c) and
+ * scale * U^T(g), gathered per low-resolution pixel over the one range of rows and columns whose taps of U include it;
+ * grad_x gets scale * sum_l g_l U(mean(A_lc)) with U's four taps; and the gradients of D(y), D(x) return through D^T.
+ * D^T is a gather as well, and that rests on one assumption: with H >= 2 h the source coordinates of consecutive
+ * samples of D are at least 2 apart, so a full-resolution row is a tap of at most one low-resolution row (columns
+ * likewise with W >= 2 w), and every full-resolution pixel is written once, with 0 where it is nobody's tap.  Hence
+ * 2 h <= H and 2 w <= W are required.
+ * Status, before any HIP call: as phl_guided_filter_bilinear (g must not be NULL); then, after the zero-element return,
+ * PHL_ERR_UNSUPPORTED for cx > PHL_GUIDED_MAX_CX, for any flag bit (PHL_GUIDED_BILINEAR_FULL_COV included: the
+ * full-covariance form has no fused backward; the caller keeps its torch path) and for 2 h > H or 2 w > W; then
+ * PHL_ERR_INVALID for a gradient aliasing an input or another gradient.  The tiled radius is
+ * phl_guided_filter_grad_max_r().  The per-label temporaries are those of phl_guided_filter_grad below full resolution,
+ * so phl_guided_filter_labels_per_chunk(B, cy, cx, h, w, 0, needs) gives the labels per chunk of this call too. */
+int phl_guided_filter_bilinear_grad(const float *y_dev, const float *x_dev, const float *g_dev, float *grad_y_dev,
+                                    float *grad_x_dev, float *grad_eps_dev, int B, int cy, int cx, int H, int W, int h, int w,
+                                    int r, const float *eps_dev, float scale, int subtract_is_y, unsigned flags,
+                                    phl_stream stream);
 
 /* Plain float4 streaming copy dst <- src (n_floats % 4 == 0, 16-byte aligned): measures the
  * HBM read+write ceiling of the box that the roofline fractions are compared with. */
