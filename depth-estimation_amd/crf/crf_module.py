@@ -462,22 +462,28 @@ class CRFasRNN(nn.Module):
     phl.GuidedFilterFullFn, which trains that W on the library's kernels for up to four guide channels).  ``mode`` is the
     guided W's interpolation (FastGuidedFilter); ``mode='bilinear'`` with ``fused_bilinear=True`` puts its unrecorded
     forward on phl.guided_filter_bilinear, and with ``bilinear_grad=True`` as well its recorded forward on
-    phl.GuidedFilterBilinearFn, which trains that W on the library's kernels (the diagonal model).  Everything else -- CPU tensors, float64,
+    phl.GuidedFilterBilinearFn, which trains that W on the library's kernels (the diagonal model); with ``full_cov=True``
+    the keyword for that is ``bilinear_full_grad=True`` (it needs ``fused_bilinear=True`` and ``full_cov=True``, and neither
+    ``full_cov_grad`` nor ``fused_grad``), and the recorded forward is phl.GuidedFilterBilinearFullFn, for up to four
+    guide channels.  Everything else -- CPU tensors, float64,
     another Mu, a label count out of a route's range -- is the plain NCHW loop, with the bits it always had.
     ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with; on
     the step routes the loop itself ends in the expected label, and the logits are never written."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
                  fused_grad=False, fused_step=False, full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False,
-                 bilinear_grad=False):
+                 bilinear_grad=False, *, bilinear_full_grad=False):
         super().__init__()
         if lattice and full_cov:
             raise ValueError("CRFasRNN: full_cov belongs to the guided-filter W; lattice=True has no covariance model")
-        if lattice and (mode != "nearest" or fused_bilinear or bilinear_grad):
-            raise ValueError("CRFasRNN: mode, fused_bilinear and bilinear_grad belong to the guided-filter W; lattice=True does "
-                             "not interpolate")
+        if lattice and (mode != "nearest" or fused_bilinear or bilinear_grad or bilinear_full_grad):
+            raise ValueError("CRFasRNN: mode, fused_bilinear, bilinear_grad and bilinear_full_grad belong to the guided-filter W; "
+                             "lattice=True does not interpolate")
         if bilinear_grad and not fused_bilinear:
             raise ValueError("CRFasRNN: bilinear_grad=True is the backward of the fused_bilinear W: it needs fused_bilinear=True")
+        if bilinear_full_grad and not (fused_bilinear and full_cov):
+            raise ValueError("CRFasRNN: bilinear_full_grad=True is the backward of the fused_bilinear W with the full covariance: "
+                             "it needs fused_bilinear=True and full_cov=True")
         if full_cov_grad and not full_cov:
             raise ValueError("CRFasRNN: full_cov_grad=True is the backward of the full-covariance W: it needs full_cov=True")
         self.Mu, self.niters = mu_init, niters
@@ -489,7 +495,8 @@ class CRFasRNN(nn.Module):
                                                                              fused_grad=fused_grad and not gaussian,
                                                                              full_cov=full_cov, full_cov_grad=full_cov_grad,
                                                                              mode=mode, fused_bilinear=fused_bilinear,
-                                                                             bilinear_grad=bilinear_grad)
+                                                                             bilinear_grad=bilinear_grad,
+                                                                             bilinear_full_grad=bilinear_full_grad)
         self.fused_grad, self.fused_step = fused_grad, fused_step
 
     def forward(self, refs, logits, confidence=None, labels=None, energies=None):

@@ -30,7 +30,12 @@ keyword, and for every recorded forward, the mode keeps the torch form -- unless
 given as well (it needs ``fused_bilinear=True``, and has the diagonal model only): a recorded forward is then
 phl.GuidedFilterBilinearFn, whose backward (phl.guided_filter_bilinear_grad) recomputes the model from y, x and eps and
 gives y, x and omega their gradients.  At subsample_ratio 1 that is phl.GuidedFilterFn; more than 16 guide channels, CPU
-tensors and float64 stay on the torch form.
+tensors and float64 stay on the torch form.  The full-covariance model of the mode trains on the kernels under a keyword
+of its own, ``bilinear_full_grad=True`` (it needs ``fused_bilinear=True`` and ``full_cov=True``; ``full_cov_grad`` and
+``fused_grad`` are neither needed nor enough, and ``bilinear_grad=True`` with ``full_cov=True`` stays an error): a
+recorded forward is then phl.GuidedFilterBilinearFullFn, whose backward is phl.guided_filter_bilinear_full_grad; at
+subsample_ratio 1 it is phl.GuidedFilterFullFn, and more than phl.GUIDED_FULL_MAX_CX guide channels, CPU tensors and
+float64 stay on the torch form.
 
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
@@ -228,10 +233,12 @@ class GuidedFilter(nn.Module):
         ``fused_bilinear=True`` is phl.guided_filter_bilinear for a forward that autograd does not record (at subsample 1
         both interpolations are the identity: the nearest route); a recorded one keeps the torch form, ``fused_grad`` /
         ``full_cov_grad`` or not, unless ``bilinear_grad=True``: then it is phl.GuidedFilterBilinearFn (at subsample 1
-        phl.GuidedFilterFn, the same function there)."""
+        phl.GuidedFilterFn, the same function there); or, with ``full_cov``, unless ``bilinear_full_grad=True``: then it
+        is phl.GuidedFilterBilinearFullFn (at subsample 1 phl.GuidedFilterFullFn)."""
         mode = getattr(self, "mode", "nearest")
         bilinear = mode == "bilinear" and getattr(self, "fused_bilinear", False)
-        bilinear_grad = bilinear and getattr(self, "bilinear_grad", False)
+        # (the constructor admits bilinear_grad without full_cov only, and bilinear_full_grad with it only)
+        bilinear_grad = bilinear and (getattr(self, "bilinear_grad", False) or getattr(self, "bilinear_full_grad", False))
         if self.gaussian or not (mode == "nearest" or bilinear) or not (_hip_ok(y) and _hip_ok(x)):
             return None
         if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
@@ -241,7 +248,10 @@ class GuidedFilter(nn.Module):
             return None
         try:
             if bilinear_grad and recording:
-                fn = phl.GuidedFilterBilinearFn if subsample >= 2 else phl.GuidedFilterFn
+                if self.full_cov:
+                    fn = phl.GuidedFilterBilinearFullFn if subsample >= 2 else phl.GuidedFilterFullFn
+                else:
+                    fn = phl.GuidedFilterBilinearFn if subsample >= 2 else phl.GuidedFilterFn
                 return fn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             if bilinear and subsample >= 2:
                 return phl.guided_filter_bilinear(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract,
@@ -270,7 +280,8 @@ class GuidedFilter(nn.Module):
 class FastGuidedFilter(GuidedFilter):
     """Coefficients solved at 1/subsample_ratio resolution and upsampled (:234-253)."""
 
-    def __init__(self, *args, subsample_ratio=2, mode="nearest", fused_bilinear=False, bilinear_grad=False, **kwargs):
+    def __init__(self, *args, subsample_ratio=2, mode="nearest", fused_bilinear=False, bilinear_grad=False,
+                 bilinear_full_grad=False, **kwargs):
         super().__init__(*args, **kwargs)
         if self.gaussian:
             # the reference's constructor reads self._r, which its gaussian form never sets (AttributeError, :238)
@@ -280,11 +291,16 @@ class FastGuidedFilter(GuidedFilter):
         if bilinear_grad and not fused_bilinear:
             raise ValueError("bilinear_grad=True is the backward of the fused_bilinear route: it needs fused_bilinear=True")
         if bilinear_grad and self.full_cov:
-            raise NotImplementedError("bilinear_grad=True with full_cov=True: the fused bilinear backward has the diagonal model only")
+            raise NotImplementedError("bilinear_grad=True with full_cov=True: this keyword has the diagonal model only "
+                                      "(the full covariance: bilinear_full_grad=True)")
+        if bilinear_full_grad and not (fused_bilinear and self.full_cov):
+            raise ValueError("bilinear_full_grad=True is the backward of the fused_bilinear route with the full covariance: it needs "
+                             "fused_bilinear=True and full_cov=True")
         self.subsample_ratio = subsample_ratio
         self.mode = mode
         self.fused_bilinear = fused_bilinear
         self.bilinear_grad = bilinear_grad
+        self.bilinear_full_grad = bilinear_full_grad
 
     def _window(self):
         return self._r // self.subsample_ratio

@@ -6,7 +6,8 @@ permutohedral BatchedAdjacency, ``full_cov=True`` gives the guided-filter W the 
 (crf.guided; on the kernels for up to four of them, the upsampler's RGB guide among those; ``full_cov_grad=True`` also
 trains it on them), ``mode='bilinear'`` interpolates the guided W's coefficients instead of repeating them over blocks
 (``fused_bilinear=True``: its unrecorded forward on phl.guided_filter_bilinear; ``bilinear_grad=True`` as well: its
-recorded forward on phl.GuidedFilterBilinearFn, which trains it on the kernels).  The trainer classes (:14-60, :105-136) and ``__main__`` need the
+recorded forward on phl.GuidedFilterBilinearFn, which trains it on the kernels; with ``full_cov=True`` that keyword is
+``bilinear_full_grad=True`` and the Function phl.GuidedFilterBilinearFullFn).  The trainer classes (:14-60, :105-136) and ``__main__`` need the
 un-vendored ``oil`` package and Middlebury data and are not mirrored."""
 import os
 
@@ -53,11 +54,13 @@ class _CoordConv(nn.Module):
 
 class CRFdepthRefiner(nn.Module):
     def __init__(self, d_in=64, d_guide=16, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False, fused_step=False,
-                 full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False):
+                 full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False, *,
+                 bilinear_full_grad=False):
         super().__init__()
         self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
                             fused_grad=fused_grad, fused_step=fused_step, full_cov=full_cov, full_cov_grad=full_cov_grad,
-                            mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad)
+                            mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad,
+                            bilinear_full_grad=bilinear_full_grad)
         self.projection = nn.Conv2d(d_in, d_guide - 3, kernel_size=1)
 
     def _guide(self, imgrgb, features):
@@ -98,11 +101,13 @@ def _scalar_unaries_routable(disp, mu):
 
 class CRFdepthUpsampler(nn.Module):
     def __init__(self, d_in=64, d_guide=3, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False, fused_step=False,
-                 full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False):
+                 full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False, *,
+                 bilinear_full_grad=False):
         super().__init__()
         self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
                             fused_grad=fused_grad, fused_step=fused_step, full_cov=full_cov, full_cov_grad=full_cov_grad,
-                            mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad)
+                            mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad,
+                            bilinear_full_grad=bilinear_full_grad)
 
     def forward(self, inputs):
         """fp32 CUDA inputs (_scalar_unaries_routable) get E0 and the labels from phl.nchw_scalar_unaries -- two launches,

@@ -24,7 +24,7 @@
 // k_guide_coef_full in the places of the first two, after run() below; its backward after run_grad().
 // phl_guided_filter_bilinear, FastGuidedFilter(mode='bilinear'): the first two kernels of either model with a four-tap
 // tile fill, then k_guide_mean and k_guide_up in the place of k_guide_apply, after run_full(); its backward is
-// run_grad<true>.)
+// run_grad<true>, and run_full_grad<ST, CX, true> for the full covariance.)
 // Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
 // routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.  The
 // kernels of both directions reach the two forms through one front end (plane_sums, square_sums, product_sums).
@@ -1343,7 +1343,8 @@ int run_grad(const float *y, const float *x, const float *g, float *grad_y, floa
 //                       gcv_lc / N and gmy_l / N (the Q planes of k_grad_apply), A_lc (for grad_x), and as fp64 planes this
 //                       label's terms of gSig_cd / N (pair_plane order) and of gm_c / N without its gSig term
 //   k_grad_finish_full  once: gm_c / N with its - 2 sum_d gSig_cd m_d term and the gSig_cd / N, as fp32 planes
-//   k_grad_x_full       per (image, tile): gxs_c (cx + 1 window sums per channel) into LDS -> grad_x as k_grad_x
+//   k_grad_x_full       per (image, tile): gxs_c (cx + 1 window sums per channel) into LDS -> grad_x as k_grad_x (BL: through
+//                       D^T, scatter_tile<true>)
 // A label's fp64 planes: [npairs gSig][cx gm][cx ys_l U_lc]; k_grad_reduce sums them into acc [B][npairs + 2 cx][h][w].
 template <bool ST, int CX>
 __global__ __launch_bounds__(NT) void k_grad_coef_full(const float *__restrict__ ys, const float *__restrict__ xs,
@@ -1424,7 +1425,7 @@ __global__ __launch_bounds__(NE) void k_grad_finish_full(const double *__restric
     for (int i = 0; i < np; i++) fb[(int64_t)(cx + i) * hw] = (float)ab[(int64_t)i * hw];
 }
 
-template <bool ST>
+template <bool ST, bool BL = false>
 __global__ __launch_bounds__(NT) void k_grad_x_full(const float *__restrict__ F, const double *__restrict__ acc,
                                                    const float *__restrict__ xs, const double *__restrict__ D,
                                                    float *__restrict__ grad_x, const int *__restrict__ rmapS,
@@ -1457,25 +1458,31 @@ __global__ __launch_bounds__(NT) void k_grad_x_full(const float *__restrict__ F,
         __syncthreads();
         const double *dp = D + ((int64_t)b * cx + c) * HWf;
         float *op = grad_x + ((int64_t)b * cx + c) * HWf;
-        scatter_tile(t, G, rmapS, cmapS, H, W, [&](int64_t o, double v) { op[o] = (float)((double)scale * dp[o] + v); });
+        scatter_tile<BL>(t, G, rmapS, cmapS, H, W, [&](int64_t o, double v) { op[o] = (float)((double)scale * dp[o] + v); });
         // (the next channel's first write to G comes after the barriers of its plane_sums)
     }
 }
 
-template <bool ST, int CX>
+// BL: the backward of run_bilinear's full-covariance model (no maps), with the same four bilinear pieces as run_grad<true>
+// and k_grad_x_full<ST, true> for D^T of gxs.  The statistics run on the stored samples xs with identity maps:
+// k_guide_stats_full<ST, CX> forms its window sums (plane, square, product; channel c, then d > c) in the order of the
+// forward's k_guide_stats_full<ST, CX, true>, whose only difference is the four-tap tile fill that k_grad_gather<true>
+// repeats, so mx and P are the forward's bit for bit.  The per-label planes are those of the nearest form below full
+// resolution: Plan::per_backward_full(full = false) sizes the chunks of both.
+template <bool ST, int CX, bool BL = false>
 int run_full_grad(const Plan &p, const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B,
                   int cy, int H, int W, int h, int w, int re, const int *row_of_low, const int *col_of_low, const int *low_of_row,
                   const int *low_of_col, const float *eps, float scale, int subtract_is_y, hipStream_t st)
 {
     constexpr int NP = npairs(CX), NPL = NP + 2 * CX;
-    const bool full = h == H && w == W;
+    const bool full = !BL && h == H && w == W;
     const bool need_x = grad_x != nullptr, need_xe = need_x || grad_eps != nullptr, need_apply = need_x || grad_y != nullptr;
     const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, nimg = (int64_t)B * cy;
     const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
     auto stats = k_guide_stats_full<ST, CX>;
     auto coefk = k_grad_coef_full<ST, CX>;
-    auto apply = k_grad_apply<ST>;
-    auto gxk = k_grad_x_full<ST>;
+    auto apply = k_grad_apply<ST, BL>;
+    auto gxk = k_grad_x_full<ST, BL>;
     if (int rc = phl_allow_lds(stats, p.lds_coef)) return rc;
     if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
     if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
@@ -1498,17 +1505,20 @@ int run_full_grad(const Plan &p, const float *y, const float *x, const float *g,
     int &rc = tmp.rc;
     const float *xs = full ? x : xsb;
     if (rc == PHL_OK) {
-        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(x, row_of_low, col_of_low, eps, mx, Pm, H, W, h, w, re);
         if (!full)
-            k_grad_gather<<<dim3(nblo, (unsigned)CX, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
+            k_grad_gather<BL><<<dim3(nblo, (unsigned)CX, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
+        if constexpr (BL)       // on the samples, as run_grad<true>
+            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(xsb, nullptr, nullptr, eps, mx, Pm, h, w, h, w, re);
+        else
+            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(x, row_of_low, col_of_low, eps, mx, Pm, H, W, h, w, re);
         phl_launched(rc, "k_guide_stats_full / k_grad_gather");
     }
     for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
         const unsigned nz = (unsigned)min(chunk, nimg - n0);
         const unsigned nb = (unsigned)((n0 + nz - 1) / cy - n0 / cy + 1);          // images the chunk touches
         const float *ys = full ? y + n0 * HWf : ysb;
-        if (!full) k_grad_gather<<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
-        k_grad_down<<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, Pd, low_of_row, low_of_col, (int)n0, cy, CX, H, W, h, w, re, scale);
+        if (!full) k_grad_gather<BL><<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
+        k_grad_down<BL><<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, Pd, low_of_row, low_of_col, (int)n0, cy, CX, H, W, h, w, re, scale);
         coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(ys, xs, Pd, mx, Pm, Q, A, part, (int)n0, cy, h, w, re);
         if (need_apply)
             apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low, col_of_low,
@@ -1516,8 +1526,8 @@ int run_full_grad(const Plan &p, const float *y, const float *x, const float *g,
         if (need_xe)
             k_grad_reduce<<<dim3(nblo, (unsigned)nred, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, NPL, B, 1, NPL, hw);
         if (need_x)
-            k_grad_direct<<<dim3(nbfull, (unsigned)CX, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy, CX,
-                                                                              H, W, h, w);
+            k_grad_direct<BL><<<dim3(nbfull, (unsigned)CX, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy,
+                                                                                  CX, H, W, h, w);
         phl_launched(rc, "the full backward's chunk kernels");
     }
     if (need_x && rc == PHL_OK) {
@@ -1743,7 +1753,8 @@ int phl_guided_filter_bilinear_grad(const float *y, const float *x, const float 
         return rc;
     if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
     if (flags) {
-        phl_set_error("phl_guided_filter_bilinear_grad: flags 0x%x (the full-covariance form has no fused backward)", flags);
+        phl_set_error("phl_guided_filter_bilinear_grad: flags 0x%x (the full-covariance backward is phl_guided_filter_bilinear_full_grad)",
+                      flags);
         return PHL_ERR_UNSUPPORTED;
     }
     if (2 * (int64_t)h > H || 2 * (int64_t)w > W) {       // below a ratio of 2 two samples of D may share a tap
@@ -1754,6 +1765,35 @@ int phl_guided_filter_bilinear_grad(const float *y, const float *x, const float 
     const int re = min(r, max(h, w));
     return run_grad<true>(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, nullptr, nullptr, nullptr, nullptr, eps, scale,
                           subtract_is_y, (hipStream_t)stream);
+}
+
+int phl_guided_filter_bilinear_full_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps,
+                                         int B, int cy, int cx, int H, int W, int h, int w, int r, const float *eps, float scale,
+                                         int subtract_is_y, phl_stream stream)
+{
+    const char *who = "phl_guided_filter_bilinear_full_grad";
+    if (int rc = check_guided_args(who, y, x, g, "g", B, cy, cx, H, W, h, w, r, nullptr, nullptr, nullptr, nullptr, eps, scale, false))
+        return rc;
+    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
+    if (cx > PHL_GUIDED_FULL_MAX_CX) {
+        phl_set_error("%s: %d guide channels, at most %d (PHL_GUIDED_FULL_MAX_CX)", who, cx, PHL_GUIDED_FULL_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (2 * (int64_t)h > H || 2 * (int64_t)w > W) {       // below a ratio of 2 two samples of D may share a tap
+        phl_set_error("%s: %d x %d is more than half of %d x %d", who, h, w, H, W);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (int rc = check_grad_aliasing(who, y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
+    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
+    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, float *, float *, int, int, int, int, int, int,
+                        int, const int *, const int *, const int *, const int *, const float *, float, int, hipStream_t);
+    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX] = {
+        {run_full_grad<false, 1, true>, run_full_grad<false, 2, true>, run_full_grad<false, 3, true>, run_full_grad<false, 4, true>},
+        {run_full_grad<true, 1, true>, run_full_grad<true, 2, true>, run_full_grad<true, 3, true>, run_full_grad<true, 4, true>}};
+    const int re = min(r, max(h, w));
+    const Plan p(re, h, w);
+    return runs[p.tiled ? 0 : 1][cx - 1](p, y, x, g, grad_y, grad_x, grad_eps, B, cy, H, W, h, w, re, nullptr, nullptr, nullptr, nullptr,
+                                        eps, scale, subtract_is_y, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -122,6 +122,7 @@ _ABI = (
     ("phl_guided_filter_bilinear", "i", "PPPPiiiiiiiiPfIS"),
     ("phl_guided_filter_bilinear_labels_per_chunk", "i", "iiiii"),
     ("phl_guided_filter_bilinear_grad", "i", "PPPPPPiiiiiiiiPfiIS"),
+    ("phl_guided_filter_bilinear_full_grad", "i", "PPPPPPiiiiiiiiPfiS"),
     ("phl_stream_copy", "i", "PPqS"),
     ("phl_copy2d", "i", "PqqPqqqiS"),
     ("phl_tile_stats", "i", "PiP"),
@@ -1451,8 +1452,9 @@ def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False,
     """Labels (of the B * cy planes of y) that one chunk of a guided_filter call holds at the solving resolution h x w,
     or, with any ``need_*`` flag or ``grad=True``, of the guided_filter_grad call that is asked for those gradients
     (``full``: subsample == 1; ``full_cov``: of the guided_filter_full_grad call -- the forward's chunks do not depend on
-    the model).  A guided_filter_bilinear_grad call holds the labels of the guided_filter_grad call with ``full=False``:
-    the same per-label planes.  Host arithmetic of the library (phl_guided_filter_labels_per_chunk,
+    the model).  A guided_filter_bilinear_grad call holds the labels of the guided_filter_grad call with ``full=False``,
+    and a guided_filter_bilinear_full_grad call those of the guided_filter_full_grad call with ``full=False``: the same
+    per-label planes.  Host arithmetic of the library (phl_guided_filter_labels_per_chunk,
     phl_guided_filter_full_grad_labels_per_chunk), no device needed."""
     needs = (1 if need_y else 0) | (2 if need_x else 0) | (4 if need_eps else 0)
     if grad is None:
@@ -1465,7 +1467,8 @@ def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False,
 
 
 def guided_filter_bilinear(y, x, r, eps, *, subsample, scale=1.0, subtract=None, out=None, full_cov=False):
-    """FastGuidedFilter(mode='bilinear') (phl_guided_filter_bilinear; its backward: guided_filter_bilinear_grad):
+    """FastGuidedFilter(mode='bilinear') (phl_guided_filter_bilinear; its backward: guided_filter_bilinear_grad, with ``full_cov``
+    guided_filter_bilinear_full_grad):
     guided_filter with the linear model solved on ``F.interpolate(., size=(H // s, W // s), mode='bilinear')`` of y and x, radius r // s, and its window means
     interpolated back to (H, W) the same way, ``out = (sum_c U(mean_A_c) x_c + U(mean_b)) * scale - subtract``.  The taps
     are computed on the device (no index maps).  Tensor rules of guided_filter; ``subsample`` >= 2 (at 1 both
@@ -1552,12 +1555,23 @@ def guided_filter_bilinear_grad(y, x, g, r, eps, *, subsample, scale=1.0, subtra
     if int(subsample) < 2:
         raise ValueError(f"guided_filter_bilinear_grad: needs subsample >= 2, got {subsample}")
     return _guided_grad("guided_filter_bilinear_grad", "phl_guided_filter_bilinear_grad", y, x, g, r, eps, subsample, scale,
+                        subtract_is_y, need_y, need_x, need_eps, maps=False, flags=0)
+
+
+def guided_filter_bilinear_full_grad(y, x, g, r, eps, *, subsample, scale=1.0, subtract_is_y=False, need_y=True, need_x=False,
+                                     need_eps=False):
+    """Backward of ``guided_filter_bilinear(..., full_cov=True)`` (phl_guided_filter_bilinear_full_grad): arguments, return
+    value and rules of guided_filter_bilinear_grad; PhlError status 7 for more than GUIDED_FULL_MAX_CX guide channels.  The
+    labels per chunk are ``guided_filter_labels_per_chunk(B, cy, cx, h, w, full_cov=True, need_y=, need_x=, need_eps=)``."""
+    if int(subsample) < 2:
+        raise ValueError(f"guided_filter_bilinear_full_grad: needs subsample >= 2, got {subsample}")
+    return _guided_grad("guided_filter_bilinear_full_grad", "phl_guided_filter_bilinear_full_grad", y, x, g, r, eps, subsample, scale,
                         subtract_is_y, need_y, need_x, need_eps, maps=False)
 
 
-def _guided_grad(name, entry, y, x, g, r, eps, subsample, scale, subtract_is_y, need_y, need_x, need_eps, maps=True):
-    """guided_filter_grad, guided_filter_full_grad and (no ``maps``, a flags word at the end) guided_filter_bilinear_grad:
-    one argument list, three entry points."""
+def _guided_grad(name, entry, y, x, g, r, eps, subsample, scale, subtract_is_y, need_y, need_x, need_eps, maps=True, flags=None):
+    """guided_filter_grad, guided_filter_full_grad and (no ``maps``) guided_filter_bilinear_grad (a ``flags`` word at the
+    end) and guided_filter_bilinear_full_grad: one argument list, four entry points."""
     cx, e, dims, maps = _guided_launch_args(name, y, x, g, "g", r, eps, subsample, need_y or need_x or need_eps, maps)
     new = torch.zeros if y.numel() == 0 else torch.empty
     gy = new(y.shape, dtype=torch.float32, device=y.device) if need_y else None
@@ -1568,7 +1582,7 @@ def _guided_grad(name, entry, y, x, g, r, eps, subsample, scale, subtract_is_y, 
     yc, xc, gc = y.contiguous(), x.contiguous(), g.contiguous()         # (named: a copy must outlive the launch)
     _launch(y.device, entry, _ptr(yc), _ptr(xc), _ptr(gc), _ptr(gy), _ptr(gx), _ptr(ge), *dims,
             *(() if maps is None else (_ptr(m) for m in maps)), _ptr(e), C.c_float(float(scale)), 1 if subtract_is_y else 0,
-            *((0,) if maps is None else ()))
+            *(() if flags is None else (flags,)))
     return gy, gx, ge
 
 
@@ -1639,6 +1653,31 @@ class GuidedFilterBilinearFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         gy, gx, ge = guided_filter_bilinear_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0],
                                                  need_x=need[1], need_eps=need[2])
+        if ge is not None:
+            ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
+        return gy, gx, ge, None, None, None, None
+
+
+class GuidedFilterBilinearFullFn(torch.autograd.Function):
+    """GuidedFilterBilinearFn for the full-covariance model: ``guided_filter_bilinear(y, x, r, eps, subsample=,
+    full_cov=True) * scale - (y if subtract_is_y else 0)`` with its backward on guided_filter_bilinear_full_grad.  Only y, x
+    and eps are saved, one backward call computes the gradients that are asked for.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, y, x, eps, r, subsample, scale, subtract_is_y):
+        ctx.save_for_backward(y, x, eps)
+        ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
+        return guided_filter_bilinear(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None,
+                                      full_cov=True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        y, x, eps = ctx.saved_tensors
+        r, s, scale, sub = ctx.args
+        need = ctx.needs_input_grad
+        gy, gx, ge = guided_filter_bilinear_full_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0],
+                                                      need_x=need[1], need_eps=need[2])
         if ge is not None:
             ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
         return gy, gx, ge, None, None, None, None

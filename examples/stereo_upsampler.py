@@ -6,7 +6,7 @@ left image at full resolution go through the head's forward, then one training s
     E0, labels = phl.nchw_scalar_unaries(disp_lowres, (H, W), 18, gamma, s)      -> phl_nchw_scalar_unaries, two launches
     depth      = CRFasRNN(charb(.05), niters=2, r, gchannels=3).expected_depth(img, None, energies=E0, labels=labels, values=labels)
 
-    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8] [--fused-step] [--full-cov [--full-cov-grad]] [--bilinear [--bilinear-grad]]
+    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8] [--fused-step] [--full-cov [--full-cov-grad]] [--bilinear [--bilinear-grad | --full-cov --bilinear-full-grad]]
 
 --fused-step runs the training step with ``CRFdepthUpsampler(fused_grad=True, fused_step=True)``: W on phl.GuidedFilterFn
 and everything between two W calls on phl.NchwStepTrain.  --full-cov gives W the full covariance of the RGB guide
@@ -14,7 +14,8 @@ and everything between two W calls on phl.NchwStepTrain.  --full-cov gives W the
 or, with --full-cov-grad (``full_cov_grad=True``), on phl.GuidedFilterFullFn, the model's backward kernels.  --bilinear
 gives W ``mode='bilinear', fused_bilinear=True``: coefficients interpolated from the half-resolution solve instead of
 repeated over 2 x 2 blocks, the forward on phl.guided_filter_bilinear, the training step on the torch form -- or, with --bilinear-grad
-(``bilinear_grad=True``), on phl.GuidedFilterBilinearFn, the mode's backward kernels.
+(``bilinear_grad=True``), on phl.GuidedFilterBilinearFn, the mode's backward kernels; with --bilinear --full-cov the switch is
+--bilinear-full-grad (``bilinear_full_grad=True``): phl.GuidedFilterBilinearFullFn.
 
 Prints the mean absolute disparity error of the plain bilinear enlargement and of the head's output against the known
 disparity, and the loss before and after the step.
@@ -32,7 +33,7 @@ from stereo_crf import synthetic_pair  # noqa: E402
 
 
 def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=False, full_cov=False, full_cov_grad=False,
-        bilinear=False, bilinear_grad=False):
+        bilinear=False, bilinear_grad=False, bilinear_full_grad=False):
     import torch
     import torch.nn.functional as F
 
@@ -46,7 +47,7 @@ def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=Fals
     low[:, :, 2:6, 3:9] = 0                                                   # no measurement there
     net = CRFdepthUpsampler(r=r, niters=2, fused_grad=fused_step, fused_step=fused_step, full_cov=full_cov,
                             full_cov_grad=full_cov_grad, mode="bilinear" if bilinear else "nearest", fused_bilinear=bilinear,
-                            bilinear_grad=bilinear_grad).to(dev)
+                            bilinear_grad=bilinear_grad, bilinear_full_grad=bilinear_full_grad).to(dev)
     torch.cuda.synchronize()
     t0 = time.time()
     with torch.no_grad():
@@ -86,9 +87,11 @@ if __name__ == "__main__":
     ap.add_argument("--full-cov-grad", action="store_true", help="with --full-cov: train that W on phl.GuidedFilterFullFn")
     ap.add_argument("--bilinear", action="store_true", help="W interpolates its coefficients (mode='bilinear', fused_bilinear=True)")
     ap.add_argument("--bilinear-grad", action="store_true", help="with --bilinear: train that W on phl.GuidedFilterBilinearFn")
+    ap.add_argument("--bilinear-full-grad", action="store_true",
+                    help="with --bilinear --full-cov: train that W on phl.GuidedFilterBilinearFullFn")
     a = ap.parse_args()
     kw = dict(fused_step=a.fused_step, full_cov=a.full_cov, full_cov_grad=a.full_cov_grad, bilinear=a.bilinear,
-              bilinear_grad=a.bilinear_grad)
+              bilinear_grad=a.bilinear_grad, bilinear_full_grad=a.bilinear_full_grad)
     run(a.h, a.w, a.r, a.factor, **kw)     # first run of the process: library load, first launches, first allocations
     t1 = time.time()
     run(a.h, a.w, a.r, a.factor, quiet=True, **kw)

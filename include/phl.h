@@ -635,7 +635,7 @@ int phl_guided_filter_bilinear_labels_per_chunk(int B, int cy, int cx, int h, in
  * 2 h <= H and 2 w <= W are required.
  * Status, before any HIP call: as phl_guided_filter_bilinear (g must not be NULL); then, after the zero-element return,
  * PHL_ERR_UNSUPPORTED for cx > PHL_GUIDED_MAX_CX, for any flag bit (PHL_GUIDED_BILINEAR_FULL_COV included: the
- * full-covariance form has no fused backward; the caller keeps its torch path) and for 2 h > H or 2 w > W; then
+ * full-covariance backward is phl_guided_filter_bilinear_full_grad below) and for 2 h > H or 2 w > W; then
  * PHL_ERR_INVALID for a gradient aliasing an input or another gradient.  The tiled radius is
  * phl_guided_filter_grad_max_r().  The per-label temporaries are those of phl_guided_filter_grad below full resolution,
  * so phl_guided_filter_labels_per_chunk(B, cy, cx, h, w, 0, needs) gives the labels per chunk of this call too. */
@@ -643,6 +643,24 @@ int phl_guided_filter_bilinear_grad(const float *y_dev, const float *x_dev, cons
                                     float *grad_x_dev, float *grad_eps_dev, int B, int cy, int cx, int H, int W, int h, int w,
                                     int r, const float *eps_dev, float scale, int subtract_is_y, unsigned flags,
                                     phl_stream stream);
+/* Backward of phl_guided_filter_bilinear(..., flags = PHL_GUIDED_BILINEAR_FULL_COV) with src = NULL (subtract_is_y = 0)
+ * or src = y (subtract_is_y != 0): the gradients of phl_guided_filter_full_grad (gcov, gS, grad_eps_c = sum gS_cc, gS
+ * entering grad_x through all cx (cx + 1) / 2 products) on the low-resolution planes, connected to the full resolution
+ * by the four bilinear pieces of phl_guided_filter_bilinear_grad: D(y) and D(x) taken again with the forward's taps,
+ * weights and rounding, so that mx, P and A are the forward's bit for bit; scale * U^T(g x_c) and scale * U^T(g) as
+ * gathers; scale * sum_l g_l U(mean(A_lc)) with U's four taps in grad_x; and D^T as the gather of the one
+ * low-resolution pixel that taps a full-resolution one, which requires 2 h <= H and 2 w <= W as there.  fp64 window
+ * sums, labels summed in index order, a fixed two-stage grad_eps reduction, no atomics, every gradient rounded once.
+ * Status, before any HIP call: as phl_guided_filter_bilinear_grad up to the zero-element and nothing-asked-for returns
+ * (there are no flags); then PHL_ERR_UNSUPPORTED for cx > PHL_GUIDED_FULL_MAX_CX, then for 2 h > H or 2 w > W; then
+ * PHL_ERR_INVALID for a gradient aliasing an input or another gradient.  The tiled radius is
+ * phl_guided_filter_grad_max_r().  The per-label temporaries are those of phl_guided_filter_full_grad below full
+ * resolution, so phl_guided_filter_full_grad_labels_per_chunk(B, cy, cx, h, w, 0, needs) gives the labels per chunk of
+ * this call too. */
+int phl_guided_filter_bilinear_full_grad(const float *y_dev, const float *x_dev, const float *g_dev, float *grad_y_dev,
+                                         float *grad_x_dev, float *grad_eps_dev, int B, int cy, int cx, int H, int W, int h,
+                                         int w, int r, const float *eps_dev, float scale, int subtract_is_y,
+                                         phl_stream stream);
 
 /* Plain float4 streaming copy dst <- src (n_floats % 4 == 0, 16-byte aligned): measures the
  * HBM read+write ceiling of the box that the roofline fractions are compared with. */

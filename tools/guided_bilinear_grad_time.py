@@ -3,7 +3,7 @@ the kernels (phl.GuidedFilterBilinearFn behind ``fused_bilinear=True, bilinear_g
 the mode -- what the same call runs without ``bilinear_grad`` -- and against the nearest ``fused_grad`` route at the same
 shape, on one GPU, in one process.  The method is that of tools/guided_bilinear_time.py.
 
-    python tools/guided_bilinear_grad_time.py [--reps N] [--only NAME] [--no-torch] [--list]
+    python tools/guided_bilinear_grad_time.py [--reps N] [--only NAME] [--no-torch] [--list] [--full-cov]
 
 cx = 3, r = 15, eps = 1e-2, at [1, 18, 1110, 1390] and [1, 64, 1110, 1390] with subsample 2 and 4.  After one warm-up call
 of each route the routes take turns, call by call, event-timed; each reports the median of its --reps (default 9) calls.
@@ -25,12 +25,25 @@ Per case one JSON line:
 The case ``crfasrnn5_18x1110x1390`` is one training step (forward + backward, no optimiser) of a 5-iteration
 CRFasRNN(charb(.05), gchannels=3, r=15, mode='bilinear', fused_bilinear=True), with ``bilinear_grad`` and without
 (flag_ms, torch_ms, and torch's allocator peaks of both).
+--full-cov times the full-covariance model of the mode instead (``full_cov=True``; phl.GuidedFilterBilinearFullFn behind
+``bilinear_full_grad=True``), at the same shapes, on the same tensors, the routes taking turns as above.  Per case:
+    keyword_ms, torch_ms                              forward + backward with ``bilinear_full_grad`` and without it (fp32
+                                                      torch autograd of the mode: what the call ran before the keyword)
+    *_min_ms, *_max_ms, torch_spread_ms               the extremes of the --reps calls; the torch form's max - min
+    faster_by_ms, meets_time_bar                      torch_ms - keyword_ms, and whether it exceeds torch_spread_ms
+    keyword_peak_MiB, torch_peak_MiB, meets_memory_bar   as *_peak_MiB above (the kernel route: plus the temporaries of
+                                                      run_full_grad), and keyword < torch
+    diagonal_ms, nearest_full_ms (+ _peak_MiB)        for context, no bar: the diagonal ``bilinear_grad`` route and the
+                                                      nearest ``full_cov_grad`` route
+and the CRFasRNN case with ``full_cov=True, bilinear_full_grad=flag``.  One image per call and r = 15 only: more images
+and other radii are not measured.
 Event times include launch gaps; for per-kernel times run `rocprofv3 --kernel-trace --stats -- python
 tools/guided_bilinear_grad_time.py --only NAME --no-torch` in a run of its own.
 """
 import argparse
 import json
 import os
+import statistics
 import sys
 
 import torch
@@ -41,7 +54,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import phl  # noqa: E402
 from crf import guided  # noqa: E402
-from guided_bilinear_time import CASES, CX, R, _peak, _time  # noqa: E402
+from guided_bilinear_time import CASES, CX, R, _once, _peak, _time  # noqa: E402
 
 LOOP = "crfasrnn5_18x1110x1390"
 
@@ -94,7 +107,74 @@ def run(name, reps, with_torch):
     print(json.dumps(row), flush=True)
 
 
-def run_loop(reps, with_torch):
+def _time_all(fns, reps):
+    """_time with the extremes kept: (median, min, max) of ``reps`` calls for every callable, the callables taking turns,
+    after two warm-up calls each."""
+    for _ in range(2):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            times[k].append(_once(fn))
+    return [(statistics.median(t), min(t), max(t)) for t in times]
+
+
+def _full_temps_MiB(cy, H, W, s):
+    """The stream-ordered temporaries of run_full_grad below full resolution (phl_guided.hip)."""
+    hw, npairs = (H // s) * (W // s), CX * (CX + 1) // 2
+    npl = npairs + 2 * CX
+    chunk = phl.guided_filter_labels_per_chunk(1, cy, CX, H // s, W // s, need_y=True, need_x=True, need_eps=True, full_cov=True)
+    per = hw * (4 + 8 * (CX + 1) + 8 * CX + 8 * npl)
+    once = hw * (8 * CX + 8 * npairs + 4 * CX + 8 * npl + 4 * (CX + npairs)) + 8 * CX * H * W
+    return chunk, (chunk * per + once) / 2 ** 20
+
+
+def _stats(row, key, t):
+    row.update({key + "_ms": round(t[0], 3), key + "_min_ms": round(t[1], 3), key + "_max_ms": round(t[2], 3)})
+
+
+def _bars(row, key_t, tor_t):
+    spread = tor_t[2] - tor_t[1]
+    row.update(torch_spread_ms=round(spread, 3), faster_by_ms=round(tor_t[0] - key_t[0], 3),
+               torch_over_keyword=round(tor_t[0] / key_t[0], 2), meets_time_bar=bool(tor_t[0] - key_t[0] > spread))
+
+
+def run_full(name, reps, with_torch):
+    cy, H, W, s = CASES[name]
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    y = torch.rand((1, cy, H, W), device=dev, generator=gen).requires_grad_(True)
+    x = torch.rand((1, CX, H, W), device=dev, generator=gen).requires_grad_(True)
+    g = torch.rand((1, cy, H, W), device=dev, generator=gen) * 2 - 1
+    make = lambda **kw: guided.BatchedGuidedAdjacency(CX, R, 1e-2, subsample_ratio=s, **kw).to(dev)      # noqa: E731
+    key = make(mode="bilinear", fused_bilinear=True, full_cov=True, bilinear_full_grad=True)
+    diag = make(mode="bilinear", fused_bilinear=True, bilinear_grad=True)
+    nfull = make(full_cov=True, full_cov_grad=True)
+    tor = make(mode="bilinear", fused_bilinear=True, full_cov=True)
+    chunk, temps = _full_temps_MiB(cy, H, W, s)
+    _, dtemps = _temps_MiB(cy, H, W, s)
+    fns = [_train_call(key, y, x, g), _train_call(diag, y, x, g), _train_call(nfull, y, x, g)]
+    fns += [_train_call(tor, y, x, g)] if with_torch else []
+    t = _time_all(fns, reps)
+    row = dict(case=name, model="full_cov", reps=reps, labels_per_chunk=chunk)
+    _stats(row, "keyword", t[0])
+    _stats(row, "diagonal", t[1])
+    _stats(row, "nearest_full", t[2])
+    for k, (fn, extra) in zip(("keyword", "diagonal", "nearest_full"), zip(fns, (temps, dtemps, temps))):
+        y.grad = x.grad = None
+        row[k + "_peak_MiB"] = round(_peak(fn) + extra, 1)
+    if with_torch:
+        _stats(row, "torch", t[3])
+        _bars(row, t[0], t[3])
+        y.grad = x.grad = None
+        row["torch_peak_MiB"] = round(_peak(fns[3]), 1)
+        row["meets_memory_bar"] = bool(row["keyword_peak_MiB"] < row["torch_peak_MiB"])
+    print(json.dumps(row), flush=True)
+
+
+def run_loop(reps, with_torch, full_cov=False):
     from crf.crf_module import CRFasRNN, charb
 
     dev = torch.device("cuda", 0)
@@ -110,9 +190,23 @@ def run_loop(reps, with_torch):
             (net(refs, logits) * up).sum().backward()
         return f
 
-    nets = [CRFasRNN(charb(.05), niters=5, r=R, gchannels=CX, mode="bilinear", fused_bilinear=True, bilinear_grad=flag).to(dev)
+    kw = (lambda flag: dict(full_cov=True, bilinear_full_grad=flag)) if full_cov else (lambda flag: dict(bilinear_grad=flag))
+    nets = [CRFasRNN(charb(.05), niters=5, r=R, gchannels=CX, mode="bilinear", fused_bilinear=True, **kw(flag)).to(dev)
             for flag in ((True, False) if with_torch else (True,))]
     fns = [step(net) for net in nets]
+    if full_cov:
+        t = _time_all(fns, reps)
+        row = dict(case=LOOP, model="full_cov", reps=reps)
+        _stats(row, "keyword", t[0])
+        refs.grad = logits.grad = None
+        row["keyword_torch_peak_MiB"] = round(_peak(fns[0]), 1)
+        if with_torch:
+            _stats(row, "torch", t[1])
+            _bars(row, t[0], t[1])
+            refs.grad = logits.grad = None
+            row["torch_peak_MiB"] = round(_peak(fns[1]), 1)
+        print(json.dumps(row), flush=True)
+        return
     ms = _time(fns, reps)
     refs.grad = logits.grad = None
     row = dict(case=LOOP, flag_ms=round(ms[0], 3), flag_torch_peak_MiB=round(_peak(fns[0]), 1))
@@ -128,15 +222,16 @@ def main():
     ap.add_argument("--only")
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--list", action="store_true")
+    ap.add_argument("--full-cov", action="store_true", help="the full-covariance model: bilinear_full_grad against the torch form")
     a = ap.parse_args()
     if a.list:
         print(" ".join(list(CASES) + [LOOP]))
         return
     for name in ([a.only] if a.only else list(CASES) + [LOOP]):
         if name == LOOP:
-            run_loop(a.reps, not a.no_torch)
+            run_loop(a.reps, not a.no_torch, a.full_cov)
         else:
-            run(name, a.reps, not a.no_torch)
+            (run_full if a.full_cov else run)(name, a.reps, not a.no_torch)
 
 
 if __name__ == "__main__":
