@@ -183,8 +183,11 @@ __global__ __launch_bounds__(256, 2) void k_compat_wide(const float *__restrict_
     load_e0(acc);                          // E = E0 + X @ Mu: E0 added to the finished product
     if (!LOGITS) {
         // softmax(-E) of the lane's pixel: shift by the row MINIMUM of E; exp(-(E - min)) = exp2((E - min) * -log2e), the
-        // difference taken first -- at a few hundred labels E reaches the hundreds, and the one-fma form of the 256-label
-        // kernels (exp2(min log2e - E log2e)) puts the rounding of |min log2e| into every exponent (~3e-5 relative in Q)
+        // difference taken first.  The one-fma form of the 256-label kernels, exp2(fma(E, -log2e, min log2e)), is as
+        // accurate: the fma is fused, and the rounding of min log2e is common to the row and cancels in the normalisation
+        // (measured up to |E| = 7.65e4: those kernels' Q equals an exact softmax of their own E to the printed digits,
+        // tests/test_gpu_energy_range.py).  The ~3e-5 = ulp(300) relative in Q they lose at energies in the hundreds comes
+        // from accumulating the product ON TOP OF E0; here E0 is added to the finished product
         float m = acc[0][0];
         m = vmin3(m, acc[0][1], acc[0][2]);
 #pragma unroll

@@ -403,6 +403,36 @@ __global__ __launch_bounds__(512) void k_compat_softmax(const float *__restrict_
     // next to the other group's MFMA stream a wave gets a VALU issue slot about once per MFMA -- the ~400 instructions
     // below took 17k cycles there, and the slot waited for them; here they take their own 3-4k, with the matrix pipe
     // idle and the other group in the one slot of its epilogue half that has nothing else to do.
+    // The accumulation starts from E0 - s_p, s_p the row minimum of E0 over its finite entries (0 where there is none): the
+    // softmax is the same function for any per-pixel shift, and every step of the chain then rounds at the magnitude of the
+    // row's own spread, not of an offset all its labels share.  The logits epilogue adds s_p back.
+    float s_p[2] = {0.f, 0.f};
+    auto shift_e0 = [&]() {
+        if (valid) {
+#pragma unroll
+            for (int pg = 0; pg < 2; pg++) {
+                float m = acc[pg][0][0];
+                m = vmin3(m, acc[pg][0][1], acc[pg][0][2]);
+#pragma unroll
+                for (int T = 1; T < NL; T++) {
+                    m = vmin3(m, acc[pg][T][0], acc[pg][T][1]);
+                    m = vmin3(m, acc[pg][T][2], acc[pg][T][3]);
+                }
+                m = vmin3(m, acc[pg][0][3], acc[pg][0][3]);
+                float ma = m, mb = m;
+                PHL_ROW_SWAP(ma, mb);
+                m = vmin3(ma, mb, mb);
+                ma = m; mb = m;
+                PHL_HALF_SWAP(ma, mb);
+                m = vmin3(ma, mb, mb);
+                m = __builtin_fabsf(m) < INFINITY ? m : 0.f;
+                s_p[pg] = m;
+#pragma unroll
+                for (int T = 0; T < NL; T++) acc[pg][T] -= (f32x4)m;
+            }
+        }
+    };
+
     auto softmax_in_place = [&]() {
     if (valid && !LOGITS) {
         // softmax(-E) of this lane's two pixels: 4 NL registers each here, the rest of the rows in lanes i + 16 g4.
@@ -450,7 +480,7 @@ __global__ __launch_bounds__(512) void k_compat_softmax(const float *__restrict_
 #pragma unroll
         for (int pg = 0; pg < 2; pg++)
 #pragma unroll
-            for (int T = 0; T < NL; T++) acc[pg][T] = -acc[pg][T];
+            for (int T = 0; T < NL; T++) acc[pg][T] = -(acc[pg][T] + (f32x4)s_p[pg]);
     }
     };
 
@@ -517,6 +547,7 @@ __global__ __launch_bounds__(512) void k_compat_softmax(const float *__restrict_
             asm volatile("" ::"v"(acc[1][NL - 1]));
 #endif
             pad_e0();
+            shift_e0();
             for (int kc = 0; kc < NT; kc++) chunk(kc);
         }
         CS_STAMP(2 * it + 1);
@@ -620,6 +651,9 @@ __global__ __launch_bounds__(512) void k_compat_softmax(const float *__restrict_
 //    that it is not hoisted out of the slot loop (its registers would spill).
 //  * a wave that goes from its epilogue half to the matrix cores still has the DMAs of its last two slots in flight
 //    (they feed slots 1 and 2 of the half it enters): counted waits at the end of its first two slots there.
+//  * the accumulation starts at E0 itself, not at E0 - s_p (k_compat_softmax's shift_e0): the same shift here measured
+//    1.3 % slower at C3 (2.347 against 2.316 ms, the parent's spread 0.013 ms), so energies with a large common offset lose
+//    ulp(|E0|) per accumulation in this kernel.
 constexpr int CSP_PIECE = 24576;                 // bytes of one slot's piece of the planes
 #ifndef PHL_CSP_XR
 #define PHL_CSP_XR 3
@@ -1009,8 +1043,8 @@ __global__ __launch_bounds__(512) void k_compat_split(const float *__restrict__ 
 
 // The last n % 128 pixels of phl_compat_softmax (the tile kernel takes whole tiles only): one workgroup per pixel,
 // thread c owns label c -- an fmaf chain over k straight from the transposed compatibility matrix, then the row
-// softmax through LDS.  At most 127 pixels: its speed does not matter, its arithmetic is the tile kernel's
-// (f32 fma chain from E0, exp2 of the log2e-scaled difference to the row minimum).
+// softmax through LDS.  At most 127 pixels: its speed does not matter, its arithmetic is k_compat_softmax's
+// (f32 fma chain from E0 - s_p, exp2 of the log2e-scaled difference to the row minimum).
 template <bool LOGITS>
 __global__ __launch_bounds__(256) void k_compat_tail(const float *__restrict__ E0, int64_t e_rs, const float *__restrict__ X,
                                                      int64_t x_rs, const float *__restrict__ MuT, int Lp,
@@ -1021,13 +1055,21 @@ __global__ __launch_bounds__(256) void k_compat_tail(const float *__restrict__ E
     const int c = threadIdx.x;
     xs[c] = c < L ? X[p * x_rs + c] : 0.f;
     __syncthreads();
-    float e = INFINITY;
+    float e = c < L ? E0[p * e_rs + c] : INFINITY;
+    red[c] = e;                                  // the chain starts from E0 - s_p, as in k_compat_softmax (shift_e0)
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (c < o) red[c] = fminf(red[c], red[c + o]);
+        __syncthreads();
+    }
+    const float s_p = __builtin_fabsf(red[0]) < INFINITY ? red[0] : 0.f;
+    __syncthreads();
     if (c < L) {
-        e = E0[p * e_rs + c];
+        e -= s_p;
         for (int k = 0; k < L; k++) e = __builtin_fmaf(xs[k], MuT[(int64_t)c * Lp + k], e);
     }
     if (LOGITS) {
-        if (c < L) out[p * o_rs + c] = -e;
+        if (c < L) out[p * o_rs + c] = -(e + s_p);
         return;
     }
     red[c] = e;

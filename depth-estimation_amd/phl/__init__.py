@@ -697,7 +697,15 @@ def compat_softmax(E0, X, Mu, out=None, logits=False, structure=True, arith=None
     128 < L <= 256, a row of L rounded up to 32 for 256 < L <= 512; the same accuracy against float64, 3/8 of the matrix
     time).  Default: "split" for L > 176 -- below that the f32 kernel is bound by its bytes as well and computes no
     padding -- unless PHL_COMPAT_ARITH names one of the two.  Above 256 labels "f32" keeps the library GEMM route.
-    uniform: see _compat_route."""
+    uniform: see _compat_route.
+    Accuracy contract of arith="split" up to 256 labels (k_compat_split): its fp32 accumulators START AT E0, so every
+    accumulation rounds at ulp(|E0|), where ``E0 + X @ Mu`` in torch rounds once.  With |E0| of the size of |X @ Mu| that
+    is the error of an fp32 dot product; with an offset on E0 it is not -- measured (tests/test_gpu_energy_range.py,
+    DESIGN.md 7.14) 4e-5 in Q at |E0| ~ 3e2 and 6e-3 at 7.65e4 (an 8-bit cost volume), 15 to 20 times torch's fp32 form.
+    The softmax is shift-invariant per pixel: a caller with such energies subtracts a per-pixel constant (the row
+    minimum) from E0 first, or asks for arith="f32", whose kernels start from E0 minus the row minimum themselves and
+    keep torch's accuracy at any offset, as every other route does.  +inf energies (masked labels) give exactly 0
+    (logits: -inf) on every route."""
     if arith is None:
         arith = os.environ.get("PHL_COMPAT_ARITH") or ("split" if E0.shape[-1] > 176 else "f32")
     if arith not in ("f32", "split"):
