@@ -224,45 +224,38 @@ class GuidedFilter(nn.Module):
         return mean_A, mean(b)
 
     def _fused(self, y, x, subsample=1, scale=1.0, subtract=None):
-        """The forward on the HIP kernels (phl.guided_filter), or None where the torch form has to run: a Gaussian
-        window, an interpolation other than nearest, tensors that are not fp32 CUDA, autograd recording without
-        ``fused_grad`` (with ``full_cov``: without ``full_cov_grad``), or a shape the kernels do not take
-        (PHL_ERR_UNSUPPORTED: more than 16 guide channels, with ``full_cov`` more than phl.GUIDED_FULL_MAX_CX).  With
-        ``fused_grad`` a recorded forward is phl.GuidedFilterFn, with ``full_cov_grad`` phl.GuidedFilterFullFn (eps =
-        softplus(omega) keeps its graph); ``subtract`` is None or y itself.  FastGuidedFilter's ``mode='bilinear'`` with
-        ``fused_bilinear=True`` is phl.guided_filter_bilinear for a forward that autograd does not record (at subsample 1
-        both interpolations are the identity: the nearest route); a recorded one keeps the torch form, ``fused_grad`` /
-        ``full_cov_grad`` or not, unless ``bilinear_grad=True``: then it is phl.GuidedFilterBilinearFn (at subsample 1
-        phl.GuidedFilterFn, the same function there); or, with ``full_cov``, unless ``bilinear_full_grad=True``: then it
-        is phl.GuidedFilterBilinearFullFn (at subsample 1 phl.GuidedFilterFullFn)."""
+        """The forward on the HIP kernels, or None where the torch form has to run: a Gaussian window, an interpolation
+        other than nearest or FastGuidedFilter's ``mode='bilinear'`` with ``fused_bilinear=True``, tensors that are not
+        fp32 CUDA, a forward that autograd records without the keyword of its backward, or a shape the kernels do not take
+        (PHL_ERR_UNSUPPORTED: more than 16 guide channels, with ``full_cov`` more than phl.GUIDED_FULL_MAX_CX).  At
+        subsample 1 both interpolations are the identity, so bilinear takes the nearest kernels there.  A recorded forward
+        is the route's phl Function (eps = softplus(omega) keeps its graph); ``subtract`` is None or y itself."""
         mode = getattr(self, "mode", "nearest")
         bilinear = mode == "bilinear" and getattr(self, "fused_bilinear", False)
-        # (the constructor admits bilinear_grad without full_cov only, and bilinear_full_grad with it only)
-        bilinear_grad = bilinear and (getattr(self, "bilinear_grad", False) or getattr(self, "bilinear_full_grad", False))
         if self.gaussian or not (mode == "nearest" or bilinear) or not (_hip_ok(y) and _hip_ok(x)):
             return None
         if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
             return None
         recording = torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad)
-        if recording and not bilinear_grad and (bilinear or not (self.full_cov_grad if self.full_cov else self.fused_grad)):
+        # The keyword of a recorded forward: nearest has fused_grad (with full_cov: full_cov_grad); bilinear has its own
+        # two, whatever those say (the constructor admits bilinear_grad without full_cov only, bilinear_full_grad with).
+        if bilinear:
+            may_record = getattr(self, "bilinear_grad", False) or getattr(self, "bilinear_full_grad", False)
+        else:
+            may_record = self.full_cov_grad if self.full_cov else self.fused_grad
+        if recording and not may_record:
             return None
+        full_cov = bool(self.full_cov)
+        # (bilinear kernels, full_cov) -> the forward and the Function of a recorded one
+        routes = {(False, False): (phl.guided_filter, phl.GuidedFilterFn),
+                  (False, True): (phl.guided_filter, phl.GuidedFilterFullFn),
+                  (True, False): (phl.guided_filter_bilinear, phl.GuidedFilterBilinearFn),
+                  (True, True): (phl.guided_filter_bilinear, phl.GuidedFilterBilinearFullFn)}
+        forward, recorded = routes[bool(bilinear and subsample >= 2), full_cov]
         try:
-            if bilinear_grad and recording:
-                if self.full_cov:
-                    fn = phl.GuidedFilterBilinearFullFn if subsample >= 2 else phl.GuidedFilterFullFn
-                else:
-                    fn = phl.GuidedFilterBilinearFn if subsample >= 2 else phl.GuidedFilterFn
-                return fn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
-            if bilinear and subsample >= 2:
-                return phl.guided_filter_bilinear(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract,
-                                                  full_cov=self.full_cov)
-            if self.full_cov and recording:
-                return phl.GuidedFilterFullFn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
-            if self.full_cov:
-                return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract, full_cov=True)
             if recording:
-                return phl.GuidedFilterFn.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
-            return phl.guided_filter(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract)
+                return recorded.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
+            return forward(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract, full_cov=full_cov)
         except phl.PhlError as e:
             if e.status != phl.ERR_UNSUPPORTED:
                 raise

@@ -21,10 +21,13 @@
 //                   the full-resolution pixels that map into the tile: fp64 sum over the channels, * scale - src, one
 //                   rounding into out (with more than four planes the partial sum passes through out between groups)
 // (phl_guided_filter_full, the model over the whole covariance matrix of the guide channels: k_guide_stats_full and
-// k_guide_coef_full in the places of the first two, after run() below; its backward after run_grad().
-// phl_guided_filter_bilinear, FastGuidedFilter(mode='bilinear'): the first two kernels of either model with a four-tap
-// tile fill, then k_guide_mean and k_guide_up in the place of k_guide_apply, after run_full(); its backward is
-// run_grad<true>, and run_full_grad<ST, CX, true> for the full covariance.)
+// k_guide_coef_full in the places of the first two, in the section after k_guide_apply; its backward's kernels after the
+// diagonal backward's.  phl_guided_filter_bilinear, FastGuidedFilter(mode='bilinear'): the first two kernels of either
+// model with a four-tap tile fill (BL), then k_guide_mean and k_guide_up in the place of k_guide_apply; its backwards are
+// the BL forms of the two nearest ones.)
+// The kernels come first, model by model; the host side is the last section of the file: one argument record (Args), one
+// trait for the two models (Model<CX>, CX = 0 the diagonal one), forward<ST, CX, BL> and backward<ST, CX, BL> for every
+// variant, one dispatch over (tiled, CX, BL), and one checked front (checked()) that every entry point calls.
 // Above the radius whose halo tiles fit LDS (phl_guided_filter_max_r) the same kernels run a streamed form of the tile
 // routine (tile_sums_stream): strips of image rows, horizontal sums straight from memory, LDS independent of r.  The
 // kernels of both directions reach the two forms through one front end (plane_sums, square_sums, product_sums).
@@ -490,79 +493,13 @@ __global__ __launch_bounds__(NT) void k_guide_apply(const float *__restrict__ co
     }
 }
 
-// ---- host: what the forward and the backward derive from (re, h, w) -------------------------------------------------
-inline bool fits_tiled(int r) { return max_lds(r) <= kMaxLds && halo_stride(r) <= 64 * NCO; }
-
 constexpr int npairs(int cx) { return cx * (cx + 1) / 2; }     // elements of the upper triangle of a cx x cx matrix
-
-// The tiled form while its LDS fits the radius, else the streamed form; the tile grid; the dynamic LDS of the three
-// layouts (one halo tile, two, one + the window means); the labels of a chunk.
-struct Plan {
-    bool tiled;
-    dim3 tiles;
-    size_t lds_stats, lds_coef, lds_apply;
-    Plan(int re, int h, int w)
-        : tiled(fits_tiled(re)), tiles((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH)),
-          lds_stats(tiled ? tile_lds(re, 1, false) : stream_lds(false)), lds_coef(tiled ? tile_lds(re, 2, false) : stream_lds(false)),
-          lds_apply(tiled ? tile_lds(re, 1, true) : stream_lds(true))
-    {
-    }
-    dim3 grid(unsigned nz) const { return dim3(tiles.x, tiles.y, nz); }
-    // labels per chunk: the per-label planes of a chunk (`per` bytes a label) stay within kChunkBytes (and gridDim.y / z)
-    static int64_t chunk(int64_t nimg, int64_t per) { return max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per)); }
-    // `per` of the forward (the cx + 1 coefficient planes) and of the backward (ys unless full resolution, P and Q, A and
-    // mA for grad_x, the NPART fp64 terms for grad_x / grad_eps): run(), run_grad() and the query below all come here
-    static int64_t per_forward(int cx, int64_t hw) { return (int64_t)(cx + 1) * hw * (int64_t)sizeof(float); }
-    // ... of the bilinear forward: the cx + 1 window-mean planes beside the cx + 1 coefficient planes
-    static int64_t per_bilinear(int cx, int64_t hw) { return 2 * per_forward(cx, hw); }
-    static int64_t per_backward(int cx, int64_t hw, bool full, bool need_x, bool need_xe)
-    {
-        return hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * kGradParts * cx : 0));
-    }
-    // ... and of the full-covariance backward: npairs(cx) + 2 cx fp64 terms a label in the place of NPART * cx
-    static int64_t per_backward_full(int cx, int64_t hw, bool full, bool need_x, bool need_xe)
-    {
-        return hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * (npairs(cx) + 2 * cx) : 0));
-    }
-};
-
-int run(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h, int w, int re,
-        const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col, const float *eps, float scale,
-        hipStream_t st)
-{
-    const Plan p(re, h, w);
-    const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
-    auto stats = p.tiled ? k_guide_stats<false> : k_guide_stats<true>;
-    auto coefk = p.tiled ? k_guide_coef<false> : k_guide_coef<true>;
-    auto apply = p.tiled ? k_guide_apply<false> : k_guide_apply<true>;
-    if (int rc = phl_allow_lds(stats, p.lds_stats)) return rc;
-    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
-    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
-
-    const int64_t chunk = Plan::chunk(nimg, Plan::per_forward(cx, hw));
-    const size_t nstat = (size_t)B * cx * hw;
-    phl_temps tmp(st);
-    double *mx = tmp.get<double>(nstat);
-    float *inv = tmp.get<float>(nstat), *coef = tmp.get<float>((size_t)chunk * (cx + 1) * hw);
-    int &rc = tmp.rc;
-    if (rc == PHL_OK) {
-        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
-        phl_launched(rc, "k_guide_stats");
-    }
-    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
-        const unsigned nz = (unsigned)min(chunk, nimg - n0);
-        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, row_of_low, col_of_low, mx, inv, coef, (int)n0, cy, cx, H, W, h, w, re);
-        apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(coef, x, src, out, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h, w, re, scale);
-        phl_launched(rc, "k_guide_coef / k_guide_apply");
-    }
-    return tmp.release();
-}
 
 // ---- full covariance: the forward ------------------------------------------------------------------------------------
 // The model the reference kept as commented lines (crf/gaussian_matrix.py:204-212): the guide channels are solved for
 // together, through their whole covariance matrix instead of its diagonal.  At the solving resolution:
 //   S_cd = mean(x_c x_d) - mx_c mx_d      P = (S + diag(eps))^-1 (symmetric)      A_lc = sum_d cov_ld P_dc
-// b_l and out as in the header, so k_guide_apply and the chunks are those of run().  P belongs to the image, not to the
+// b_l and out as in the header, so k_guide_apply and the chunks are those of the diagonal model.  P belongs to the image, not to the
 // label: the two kernels below take the places of k_guide_stats and k_guide_coef, the channel count a template parameter
 // (1 .. PHL_GUIDED_FULL_MAX_CX), so that every matrix element is a register of a constant index.
 //   k_guide_stats_full  per (image, tile): mx_c and the window sums of the cx (cx + 1) / 2 products x_c x_d (two halo
@@ -708,38 +645,6 @@ __global__ __launch_bounds__(NT) void k_guide_coef_full(const float *__restrict_
     });
 }
 
-template <bool ST, int CX>
-int run_full(const Plan &p, const float *y, const float *x, const float *src, float *out, int B, int cy, int H, int W, int h, int w,
-             int re, const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col, const float *eps,
-             float scale, hipStream_t st)
-{
-    const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
-    auto stats = k_guide_stats_full<ST, CX>;
-    auto coefk = k_guide_coef_full<ST, CX>;
-    auto apply = k_guide_apply<ST>;
-    if (int rc = phl_allow_lds(stats, p.lds_coef)) return rc;
-    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
-    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
-
-    const int64_t chunk = Plan::chunk(nimg, Plan::per_forward(CX, hw));
-    phl_temps tmp(st);
-    double *mx = tmp.get<double>((size_t)B * CX * hw), *P = tmp.get<double>((size_t)B * npairs(CX) * hw);
-    float *coef = tmp.get<float>((size_t)chunk * (CX + 1) * hw);
-    int &rc = tmp.rc;
-    if (rc == PHL_OK) {
-        stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(x, row_of_low, col_of_low, eps, mx, P, H, W, h, w, re);
-        phl_launched(rc, "k_guide_stats_full");
-    }
-    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
-        const unsigned nz = (unsigned)min(chunk, nimg - n0);
-        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, row_of_low, col_of_low, mx, P, coef, (int)n0, cy, H, W, h, w, re);
-        apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(coef, x, src, out, low_of_row, low_of_col, (int)n0, cy, CX, H, W, h, w, re,
-                                                        scale);
-        phl_launched(rc, "k_guide_coef_full / k_guide_apply");
-    }
-    return tmp.release();
-}
-
 // ---- bilinear: FastGuidedFilter(mode='bilinear'), forward ----------------------------------------------------------
 // D = F.interpolate(., (h, w), mode='bilinear'), U = F.interpolate(., (H, W), mode='bilinear') (align_corners=False):
 //   (mean_A, mean_b) = the model above (either one) on D(y), D(x)      out_l = (sum_c U(mean_A_lc) x_c + U(mean_b_l)) * scale - src_l
@@ -752,7 +657,7 @@ int run_full(const Plan &p, const float *y, const float *x, const float *src, fl
 //                   fp32 as k_guide_apply rounds them) -> cx + 1 low-resolution planes
 //   k_guide_up      per full-resolution pixel (a thread takes UR rows of one column): the four-tap samples of the mean
 //                   planes and the sum over the channels in fp64, * scale - src, one rounding into out
-// Labels per chunk: kChunkBytes / (2 (cx + 1) h w sizeof(float)), at least 1, at most B cy and 65535 (Plan::per_bilinear):
+// Labels per chunk: kChunkBytes / (2 (cx + 1) h w sizeof(float)), at least 1, at most B cy and 65535 (Plan::per_forward):
 // the coefficient and the mean planes of a chunk stay in the Infinity Cache between the three kernels.
 constexpr int UR = 4;               // full-resolution rows per thread of k_guide_up: a workgroup covers 16 x 64 pixels
 
@@ -805,51 +710,6 @@ __global__ __launch_bounds__(NT) void k_guide_up(const float *__restrict__ mean,
         if (sp) acc -= (double)sp[o];
         op[o] = (float)acc;
     }
-}
-
-// CX = 0: the diagonal model with cx guide channels; else the full covariance of CX (= cx) channels
-template <bool ST, int CX>
-int run_bilinear(const Plan &p, const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h,
-                 int w, int re, const float *eps, float scale, hipStream_t st)
-{
-    const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
-    const size_t lds_first = CX ? p.lds_coef : p.lds_stats;
-    auto meank = k_guide_mean<ST>;
-    if constexpr (CX == 0) {
-        if (int rc = phl_allow_lds(k_guide_stats<ST, true>, lds_first)) return rc;
-        if (int rc = phl_allow_lds(k_guide_coef<ST, true>, p.lds_coef)) return rc;
-    } else {
-        if (int rc = phl_allow_lds(k_guide_stats_full<ST, CX, true>, lds_first)) return rc;
-        if (int rc = phl_allow_lds(k_guide_coef_full<ST, CX, true>, p.lds_coef)) return rc;
-    }
-    if (int rc = phl_allow_lds(meank, p.lds_stats)) return rc;
-
-    const int64_t chunk = Plan::chunk(nimg, Plan::per_bilinear(cx, hw));
-    const size_t nstat = (size_t)B * cx * hw;
-    phl_temps tmp(st);
-    double *mx = tmp.get<double>(nstat), *P = CX ? tmp.get<double>((size_t)B * npairs(CX) * hw) : nullptr;
-    float *inv = CX ? nullptr : tmp.get<float>(nstat);
-    float *coef = tmp.get<float>((size_t)chunk * (cx + 1) * hw), *mean = tmp.get<float>((size_t)chunk * (cx + 1) * hw);
-    const int tilesx = (W + 63) / 64, tilesy = (H + 4 * UR - 1) / (4 * UR);
-    int &rc = tmp.rc;
-    if (rc == PHL_OK) {
-        if constexpr (CX == 0)
-            k_guide_stats<ST, true><<<p.grid((unsigned)B), dim3(NT), lds_first, st>>>(x, nullptr, nullptr, eps, mx, inv, cx, H, W, h, w, re);
-        else
-            k_guide_stats_full<ST, CX, true><<<p.grid((unsigned)B), dim3(NT), lds_first, st>>>(x, nullptr, nullptr, eps, mx, P, H, W, h, w, re);
-        phl_launched(rc, "k_guide_stats (bilinear)");
-    }
-    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
-        const unsigned nz = (unsigned)min(chunk, nimg - n0);
-        if constexpr (CX == 0)
-            k_guide_coef<ST, true><<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, nullptr, nullptr, mx, inv, coef, (int)n0, cy, cx, H, W, h, w, re);
-        else
-            k_guide_coef_full<ST, CX, true><<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(y, x, nullptr, nullptr, mx, P, coef, (int)n0, cy, H, W, h, w, re);
-        meank<<<p.grid(nz), dim3(NT), p.lds_stats, st>>>(coef, mean, cx + 1, h, w, re);
-        k_guide_up<<<dim3((unsigned)tilesx * (unsigned)tilesy, 1, nz), dim3(NT), 0, st>>>(mean, x, src, out, (int)n0, cy, cx, H, W, h, w, tilesx, scale);
-        phl_launched(rc, "k_guide_coef / k_guide_mean / k_guide_up (bilinear)");
-    }
-    return tmp.release();
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------
@@ -1250,94 +1110,15 @@ __global__ void k_grad_eps2(const double *__restrict__ partial, float *__restric
     grad_eps[c] = (float)s;
 }
 
-// BL: the backward of run_bilinear's diagonal model (no maps; the four pieces named above in their bilinear form).  The
-// per-label planes are those of the nearest form below full resolution, so Plan::per_backward(full = false) sizes the
-// chunks of both.
-template <bool BL = false>
-int run_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B, int cy, int cx,
-             int H, int W, int h, int w, int re, const int *row_of_low, const int *col_of_low, const int *low_of_row,
-             const int *low_of_col, const float *eps, float scale, int subtract_is_y, hipStream_t st)
-{
-    const Plan p(re, h, w);
-    const bool full = !BL && h == H && w == W;          // strictly increasing maps onto the same size: the identity
-    const bool need_x = grad_x != nullptr, need_xe = need_x || grad_eps != nullptr, need_apply = need_x || grad_y != nullptr;
-    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, nimg = (int64_t)B * cy;
-    const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
-    auto stats = p.tiled ? k_guide_stats<false> : k_guide_stats<true>;
-    auto coefk = p.tiled ? k_grad_coef<false> : k_grad_coef<true>;
-    auto apply = p.tiled ? k_grad_apply<false, BL> : k_grad_apply<true, BL>;
-    auto gxk = p.tiled ? k_grad_x<false, BL> : k_grad_x<true, BL>;
-    if (int rc = phl_allow_lds(stats, p.lds_stats)) return rc;
-    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
-    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
-    if (int rc = phl_allow_lds(gxk, p.lds_apply)) return rc;
-
-    const int64_t chunk = Plan::chunk(nimg, Plan::per_backward(cx, hw, full, need_x, need_xe));
-    const size_t nstat = (size_t)B * cx * hw;
-    phl_temps tmp(st);
-    double *mx = tmp.get<double>(nstat);
-    float *inv = tmp.get<float>(nstat);
-    float *xsb = full ? nullptr : tmp.get<float>(nstat);
-    float *ysb = full ? nullptr : tmp.get<float>((size_t)chunk * hw);
-    float *P = tmp.get<float>((size_t)chunk * (cx + 1) * hw), *Q = tmp.get<float>((size_t)chunk * (cx + 1) * hw);
-    float *A = need_x ? tmp.get<float>((size_t)chunk * cx * hw) : nullptr, *mA = need_x ? tmp.get<float>((size_t)chunk * cx * hw) : nullptr;
-    double *part = need_xe ? tmp.get<double>((size_t)chunk * NPART * cx * hw) : nullptr;
-    double *acc = need_xe ? tmp.get<double>((size_t)NPART * nstat) : nullptr;
-    float *F = need_x ? tmp.get<float>(2 * nstat) : nullptr;
-    double *D = need_x ? tmp.get<double>((size_t)B * cx * HWf) : nullptr;
-    double *epart = grad_eps ? tmp.get<double>((size_t)cx * NEB) : nullptr;
-    int &rc = tmp.rc;
-    const float *xs = full ? x : xsb;
-    if (rc == PHL_OK) {
-        if (!full)
-            k_grad_gather<BL><<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
-        if constexpr (BL)       // on the samples, which are what the forward's four-tap tile fill holds: the same sums
-            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(xsb, nullptr, nullptr, eps, mx, inv, cx, h, w, h, w, re);
-        else
-            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_stats, st>>>(x, row_of_low, col_of_low, eps, mx, inv, cx, H, W, h, w, re);
-        phl_launched(rc, "k_guide_stats / k_grad_gather");
-    }
-    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
-        const unsigned nz = (unsigned)min(chunk, nimg - n0);
-        const unsigned nb = (unsigned)((n0 + nz - 1) / cy - n0 / cy + 1);          // images the chunk touches
-        const float *ys = full ? y + n0 * HWf : ysb;
-        if (!full) k_grad_gather<BL><<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
-        k_grad_down<BL><<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, P, low_of_row, low_of_col, (int)n0, cy, cx, H, W, h, w, re, scale);
-        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(ys, xs, P, mx, inv, Q, A, part, (int)n0, cy, cx, h, w, re);
-        if (need_apply)
-            apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low, col_of_low,
-                                                            (int)n0, cy, cx, H, W, h, w, re, subtract_is_y, NPART * cx, PART_YU * cx);
-        if (need_xe)
-            k_grad_reduce<<<dim3(nblo, (unsigned)cx, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, cx, B, need_x ? NPART : 2,
-                                                                            NPART * cx, hw);
-        if (need_x)
-            k_grad_direct<BL><<<dim3(nbfull, (unsigned)cx, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy,
-                                                                                  cx, H, W, h, w);
-        phl_launched(rc, "the backward's chunk kernels");
-    }
-    if (need_x && rc == PHL_OK) {
-        k_grad_finish<<<dim3(nblo, (unsigned)cx, (unsigned)B), dim3(NE), 0, st>>>(acc, mx, F, B, cx, hw);
-        gxk<<<p.grid((unsigned)B), dim3(NT), p.lds_apply, st>>>(F, acc + (size_t)PART_YU * nstat, xs, D, grad_x, row_of_low, col_of_low, cx,
-                                                               H, W, h, w, re, scale);
-        phl_launched(rc, "k_grad_finish / k_grad_x");
-    }
-    if (grad_eps && rc == PHL_OK) {
-        k_grad_eps1<<<dim3(NEB, (unsigned)cx), dim3(NE), 0, st>>>(acc, epart, B, cx, h, w, re, cx, 0);
-        k_grad_eps2<<<dim3(1), dim3(64), 0, st>>>(epart, grad_eps, cx);
-        phl_launched(rc, "k_grad_eps");
-    }
-    return tmp.release();
-}
-
 // ---- backward of the full-covariance model -------------------------------------------------------------------------
-// With m_c = mx_c, Sig = S (run_full's header), P = (Sig + diag(eps))^-1, cv_ld = cov_ld, and gA, gb, gA' as above:
+// With m_c = mx_c, Sig = S (the full covariance's forward above), P = (Sig + diag(eps))^-1, cv_ld = cov_ld, and gA, gb, gA' as above:
 //   gcv_ld = sum_c gA'_lc P_cd      gSig_cd = -1/2 sum_l (A_lc gcv_ld + A_ld gcv_lc)      gmy_l = gb_l - sum_d gcv_ld m_d
 //   gm_c = -sum_l gb_l A_lc - sum_l gcv_lc my_l - 2 sum_d gSig_cd m_d
 //   U_l0 = S(gmy_l / N)   U_lc = S(gcv_lc / N)   V_cd = S(gSig_cd / N)
 //   gys_l = U_l0 + sum_c xs_c U_lc          gxs_c = sum_l ys_l U_lc + S(gm_c / N) + 2 sum_d xs_d V_cd
 //   grad_y, grad_x from gys, gxs and mean(A) as above          grad_eps_c = sum gSig_cc
 // (the diagonal form is the case of a diagonal P: gvar_c = gSig_cc).  U, gys and mean(A) have the diagonal form's shape, so
-// run_full_grad is run_grad with k_guide_stats_full for the statistics and three kernels of its own:
+// backward() runs the diagonal form's sequence with k_guide_stats_full for the statistics and three kernels of its own:
 //   k_grad_coef_full    per (label, tile), the channel count a template parameter as in the forward: the window sums of ys,
 //                       ys xs_c, gb and gA_c stay in registers; cv, A = cv P, gA', gcv = gA' P, gmy per pixel in fp64 ->
 //                       gcv_lc / N and gmy_l / N (the Q planes of k_grad_apply), A_lc (for grad_x), and as fp64 planes this
@@ -1463,135 +1244,366 @@ __global__ __launch_bounds__(NT) void k_grad_x_full(const float *__restrict__ F,
     }
 }
 
-// BL: the backward of run_bilinear's full-covariance model (no maps), with the same four bilinear pieces as run_grad<true>
-// and k_grad_x_full<ST, true> for D^T of gxs.  The statistics run on the stored samples xs with identity maps:
-// k_guide_stats_full<ST, CX> forms its window sums (plane, square, product; channel c, then d > c) in the order of the
-// forward's k_guide_stats_full<ST, CX, true>, whose only difference is the four-tap tile fill that k_grad_gather<true>
-// repeats, so mx and P are the forward's bit for bit.  The per-label planes are those of the nearest form below full
-// resolution: Plan::per_backward_full(full = false) sizes the chunks of both.
-template <bool ST, int CX, bool BL = false>
-int run_full_grad(const Plan &p, const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B,
-                  int cy, int H, int W, int h, int w, int re, const int *row_of_low, const int *col_of_low, const int *low_of_row,
-                  const int *low_of_col, const float *eps, float scale, int subtract_is_y, hipStream_t st)
-{
-    constexpr int NP = npairs(CX), NPL = NP + 2 * CX;
-    const bool full = !BL && h == H && w == W;
-    const bool need_x = grad_x != nullptr, need_xe = need_x || grad_eps != nullptr, need_apply = need_x || grad_y != nullptr;
-    const int64_t hw = (int64_t)h * w, HWf = (int64_t)H * W, nimg = (int64_t)B * cy;
-    const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
-    auto stats = k_guide_stats_full<ST, CX>;
-    auto coefk = k_grad_coef_full<ST, CX>;
-    auto apply = k_grad_apply<ST, BL>;
-    auto gxk = k_grad_x_full<ST, BL>;
-    if (int rc = phl_allow_lds(stats, p.lds_coef)) return rc;
-    if (int rc = phl_allow_lds(coefk, p.lds_coef)) return rc;
-    if (int rc = phl_allow_lds(apply, p.lds_apply)) return rc;
-    if (int rc = phl_allow_lds(gxk, p.lds_apply)) return rc;
 
-    const int64_t chunk = Plan::chunk(nimg, Plan::per_backward_full(CX, hw, full, need_x, need_xe));
-    const size_t nstat = (size_t)B * CX * hw;
-    const int nred = need_x ? NPL : NP;                // planes of a label that anything reads after the sum over labels
-    phl_temps tmp(st);
-    double *mx = tmp.get<double>(nstat), *Pm = tmp.get<double>((size_t)B * NP * hw);
+// ---- host ----------------------------------------------------------------------------------------------------------
+// One argument record from the entry point to the launches, one trait for the two linear models, forward<ST, CX, BL> and
+// backward<ST, CX, BL> for every variant, one dispatch over (tiled, CX, BL), one checked front per direction.
+inline bool fits_tiled(int r) { return max_lds(r) <= kMaxLds && halo_stride(r) <= 64 * NCO; }
+
+// a label's fp64 planes that the backward sums over labels: NPART per channel, or with the full covariance
+// [npairs gSig][cx gm][cx ys_l U_lc]
+constexpr int grad_planes(bool full_cov, int cx) { return full_cov ? npairs(cx) + 2 * cx : kGradParts * cx; }
+
+// The tiled form while its LDS fits the radius, else the streamed form; the tile grid; the dynamic LDS of the three
+// layouts (one halo tile, two, one + the window means); the labels of a chunk.
+struct Plan {
+    bool tiled;
+    dim3 tiles;
+    size_t lds_stats, lds_coef, lds_apply;
+    Plan(int re, int h, int w)
+        : tiled(fits_tiled(re)), tiles((unsigned)((w + TW - 1) / TW), (unsigned)((h + TH - 1) / TH)),
+          lds_stats(tiled ? tile_lds(re, 1, false) : stream_lds(false)), lds_coef(tiled ? tile_lds(re, 2, false) : stream_lds(false)),
+          lds_apply(tiled ? tile_lds(re, 1, true) : stream_lds(true))
+    {
+    }
+    dim3 grid(unsigned nz) const { return dim3(tiles.x, tiles.y, nz); }
+    // labels per chunk: the per-label planes of a chunk (`per` bytes a label) stay within kChunkBytes (and gridDim.y / z)
+    static int64_t chunk(int64_t nimg, int64_t per) { return max((int64_t)1, min(min(nimg, (int64_t)65535), (int64_t)kChunkBytes / per)); }
+    // `per` of the forward (the cx + 1 coefficient planes; bilinear: the cx + 1 window-mean planes beside them) and of the
+    // backward (ys unless full resolution, P and Q, A and mA for grad_x, the `planes` = grad_planes() fp64 terms for
+    // grad_x / grad_eps; the bilinear backwards hold the planes of the nearest form below full resolution): forward(),
+    // backward() and the three queries all come here
+    static int64_t per_forward(int cx, int64_t hw, bool bilinear) { return (bilinear ? 2 : 1) * (int64_t)(cx + 1) * hw * (int64_t)sizeof(float); }
+    static int64_t per_backward(int cx, int64_t hw, int planes, bool full, bool need_x, bool need_xe)
+    {
+        return hw * (int64_t)((full ? 0 : 4) + 8 * (cx + 1) + (need_x ? 8 * cx : 0) + (need_xe ? 8 * planes : 0));
+    }
+};
+
+struct Args {
+    const char *who;                                // the entry point, for the messages
+    const float *y, *x, *third;                     // third: the forward's src (may be null), the backward's g
+    float *out, *grad_y, *grad_x, *grad_eps;        // the forward's out; the backward's gradients, null where not asked for
+    int B, cy, cx, H, W, h, w, r;                   // r as the caller gave it; past the checks min(r, max(h, w))
+    const int *row_of_low, *col_of_low, *low_of_row, *low_of_col;      // the nearest index maps; all null: bilinear sampling
+    const float *eps;
+    float scale;
+    int subtract_is_y;
+    hipStream_t st;
+    int64_t hw() const { return (int64_t)h * w; }
+    int64_t HWf() const { return (int64_t)H * W; }
+    int64_t nimg() const { return (int64_t)B * cy; }
+};
+
+// The two linear models, in every place where their host paths differ.  Model<0> below is the diagonal one, a model per
+// guide channel, the channel count a run-time argument of its kernels.  Model<CX>, CX = 1 .. PHL_GUIDED_FULL_MAX_CX, is the
+// full covariance of CX = cx channels.  The members that launch take the tile's source planes (`x`, H x W) beside the
+// record: the backward's statistics run on the gathered samples, whatever the sampling, with BL = false.
+template <int CX>
+struct Model {
+    static constexpr int NP = npairs(CX), NPL = grad_planes(true, CX);
+    using Stat = double;                                                      // beside mx: the upper triangle of P, fp64
+    static int stat_planes(int) { return NP; }
+    static size_t lds_stats(const Plan &p) { return p.lds_coef; }            // products of two channels: two halo tiles
+    static int label_planes(int) { return NPL; }                             // grad_planes(); ys_l U_lc from yu_plane on
+    static int yu_plane(int) { return NP + CX; }
+    static int f_planes(int) { return CX + NP; }                             // fp32 planes of an image in F
+    template <bool ST, bool BL> static auto stats_k() { return k_guide_stats_full<ST, CX, BL>; }
+    template <bool ST, bool BL> static auto coef_k() { return k_guide_coef_full<ST, CX, BL>; }
+    template <bool ST> static auto grad_coef_k() { return k_grad_coef_full<ST, CX>; }
+    template <bool ST, bool BL> static auto grad_x_k() { return k_grad_x_full<ST, BL>; }
+    template <bool ST, bool BL>
+    static void stats(const Args &a, const Plan &p, const float *x, int H, int W, double *mx, Stat *P)
+    {
+        stats_k<ST, BL>()<<<p.grid((unsigned)a.B), dim3(NT), lds_stats(p), a.st>>>(x, a.row_of_low, a.col_of_low, a.eps, mx, P, H, W, a.h, a.w, a.r);
+    }
+    template <bool ST, bool BL>
+    static void coef(const Args &a, const Plan &p, int64_t n0, unsigned nz, const double *mx, const Stat *P, float *coef)
+    {
+        coef_k<ST, BL>()<<<p.grid(nz), dim3(NT), p.lds_coef, a.st>>>(
+            a.y, a.x, a.row_of_low, a.col_of_low, mx, P, coef, (int)n0, a.cy, a.H, a.W, a.h, a.w, a.r);
+    }
+    template <bool ST>
+    static void grad_coef(const Args &a, const Plan &p, int64_t n0, unsigned nz, const float *ys, const float *xs, const float *Pd,
+                          const double *mx, const Stat *P, float *Q, float *A, double *part)
+    {
+        grad_coef_k<ST>()<<<p.grid(nz), dim3(NT), p.lds_coef, a.st>>>(ys, xs, Pd, mx, P, Q, A, part, (int)n0, a.cy, a.h, a.w, a.r);
+    }
+    // one selector of NPL "channels"; without grad_x nothing reads past the gSig planes
+    static void reduce(const Args &a, unsigned nblo, unsigned nb, const double *part, double *acc, int64_t n0, unsigned nz, bool need_x)
+    {
+        k_grad_reduce<<<dim3(nblo, (unsigned)(need_x ? NPL : NP), nb), dim3(NE), 0, a.st>>>(
+            part, acc, (int)n0, (int)nz, a.cy, NPL, a.B, 1, NPL, a.hw());
+    }
+    template <bool ST, bool BL>
+    static void finish_x(const Args &a, const Plan &p, unsigned nblo, const double *acc, const double *mx, float *F, const float *xs, const double *D)
+    {
+        k_grad_finish_full<<<dim3(nblo, 1, (unsigned)a.B), dim3(NE), 0, a.st>>>(acc, mx, F, CX, NPL, a.hw());
+        grad_x_k<ST, BL>()<<<p.grid((unsigned)a.B), dim3(NT), p.lds_apply, a.st>>>(
+            F, acc, xs, D, a.grad_x, a.row_of_low, a.col_of_low, CX, NPL, a.H, a.W, a.h, a.w, a.r, a.scale);
+    }
+    static void eps1(const Args &a, const double *acc, double *epart)       // gvar_c = gSig_cc: plane pair_plane(c, c) of NPL
+    {
+        k_grad_eps1<<<dim3(NEB, (unsigned)CX), dim3(NE), 0, a.st>>>(acc, epart, a.B, CX, a.h, a.w, a.r, NPL, 1);
+    }
+};
+
+template <>
+struct Model<0> {
+    using Stat = float;                                                       // beside mx: inv = 1 / (var + eps), fp32
+    static int stat_planes(int cx) { return cx; }
+    static size_t lds_stats(const Plan &p) { return p.lds_stats; }
+    static int label_planes(int cx) { return grad_planes(false, cx); }       // [NPART][cx]; ys_l U_lc is part PART_YU
+    static int yu_plane(int cx) { return PART_YU * cx; }
+    static int f_planes(int cx) { return 2 * cx; }
+    template <bool ST, bool BL> static auto stats_k() { return k_guide_stats<ST, BL>; }
+    template <bool ST, bool BL> static auto coef_k() { return k_guide_coef<ST, BL>; }
+    template <bool ST> static auto grad_coef_k() { return k_grad_coef<ST>; }
+    template <bool ST, bool BL> static auto grad_x_k() { return k_grad_x<ST, BL>; }
+    template <bool ST, bool BL>
+    static void stats(const Args &a, const Plan &p, const float *x, int H, int W, double *mx, Stat *inv)
+    {
+        stats_k<ST, BL>()<<<p.grid((unsigned)a.B), dim3(NT), lds_stats(p), a.st>>>(
+            x, a.row_of_low, a.col_of_low, a.eps, mx, inv, a.cx, H, W, a.h, a.w, a.r);
+    }
+    template <bool ST, bool BL>
+    static void coef(const Args &a, const Plan &p, int64_t n0, unsigned nz, const double *mx, const Stat *inv, float *coef)
+    {
+        coef_k<ST, BL>()<<<p.grid(nz), dim3(NT), p.lds_coef, a.st>>>(
+            a.y, a.x, a.row_of_low, a.col_of_low, mx, inv, coef, (int)n0, a.cy, a.cx, a.H, a.W, a.h, a.w, a.r);
+    }
+    template <bool ST>
+    static void grad_coef(const Args &a, const Plan &p, int64_t n0, unsigned nz, const float *ys, const float *xs, const float *Pd,
+                          const double *mx, const Stat *inv, float *Q, float *A, double *part)
+    {
+        grad_coef_k<ST>()<<<p.grid(nz), dim3(NT), p.lds_coef, a.st>>>(ys, xs, Pd, mx, inv, Q, A, part, (int)n0, a.cy, a.cx, a.h, a.w, a.r);
+    }
+    // NPART selectors of cx channels; without grad_x nothing reads the PART_YU planes
+    static void reduce(const Args &a, unsigned nblo, unsigned nb, const double *part, double *acc, int64_t n0, unsigned nz, bool need_x)
+    {
+        k_grad_reduce<<<dim3(nblo, (unsigned)a.cx, nb), dim3(NE), 0, a.st>>>(
+            part, acc, (int)n0, (int)nz, a.cy, a.cx, a.B, need_x ? NPART : 2, NPART * a.cx, a.hw());
+    }
+    template <bool ST, bool BL>
+    static void finish_x(const Args &a, const Plan &p, unsigned nblo, const double *acc, const double *mx, float *F, const float *xs, const double *D)
+    {
+        k_grad_finish<<<dim3(nblo, (unsigned)a.cx, (unsigned)a.B), dim3(NE), 0, a.st>>>(acc, mx, F, a.B, a.cx, a.hw());
+        grad_x_k<ST, BL>()<<<p.grid((unsigned)a.B), dim3(NT), p.lds_apply, a.st>>>(
+            F, acc + (size_t)PART_YU * a.B * a.cx * a.hw(), xs, D, a.grad_x, a.row_of_low, a.col_of_low, a.cx, a.H, a.W, a.h, a.w, a.r,
+            a.scale);
+    }
+    static void eps1(const Args &a, const double *acc, double *epart)       // gvar_c: plane c of part PART_VAR = 0
+    {
+        k_grad_eps1<<<dim3(NEB, (unsigned)a.cx), dim3(NE), 0, a.st>>>(acc, epart, a.B, a.cx, a.h, a.w, a.r, a.cx, 0);
+    }
+};
+
+// The forward of every variant.  Nearest: the statistics once, then per chunk of labels the coefficients and
+// k_guide_apply.  BL: the first two fill their tiles with the four-tap samples, and k_guide_mean and k_guide_up take the
+// place of k_guide_apply.
+template <bool ST, int CX, bool BL>
+int forward(const Args &a, const Plan &p)
+{
+    using M = Model<CX>;
+    const int cx = a.cx;
+    const int64_t hw = a.hw(), nimg = a.nimg();
+    if (int rc = phl_allow_lds(M::template stats_k<ST, BL>(), M::lds_stats(p))) return rc;
+    if (int rc = phl_allow_lds(M::template coef_k<ST, BL>(), p.lds_coef)) return rc;
+    if (int rc = BL ? phl_allow_lds(k_guide_mean<ST>, p.lds_stats) : phl_allow_lds(k_guide_apply<ST>, p.lds_apply)) return rc;
+
+    const int64_t chunk = Plan::chunk(nimg, Plan::per_forward(cx, hw, BL));
+    phl_temps tmp(a.st);
+    double *mx = tmp.get<double>((size_t)a.B * cx * hw);
+    auto *sp = tmp.get<typename M::Stat>((size_t)a.B * M::stat_planes(cx) * hw);
+    float *coef = tmp.get<float>((size_t)chunk * (cx + 1) * hw), *mean = BL ? tmp.get<float>((size_t)chunk * (cx + 1) * hw) : nullptr;
+    const int tilesx = (a.W + 63) / 64, tilesy = (a.H + 4 * UR - 1) / (4 * UR);        // of k_guide_up
+    int &rc = tmp.rc;
+    if (rc == PHL_OK) {
+        M::template stats<ST, BL>(a, p, a.x, a.H, a.W, mx, sp);
+        phl_launched(rc, "the guided filter's statistics");
+    }
+    for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
+        const unsigned nz = (unsigned)min(chunk, nimg - n0);
+        M::template coef<ST, BL>(a, p, n0, nz, mx, sp, coef);
+        if constexpr (BL) {
+            k_guide_mean<ST><<<p.grid(nz), dim3(NT), p.lds_stats, a.st>>>(coef, mean, cx + 1, a.h, a.w, a.r);
+            k_guide_up<<<dim3((unsigned)tilesx * (unsigned)tilesy, 1, nz), dim3(NT), 0, a.st>>>(
+                mean, a.x, a.third, a.out, (int)n0, a.cy, cx, a.H, a.W, a.h, a.w, tilesx, a.scale);
+        } else {
+            k_guide_apply<ST><<<p.grid(nz), dim3(NT), p.lds_apply, a.st>>>(
+                coef, a.x, a.third, a.out, a.low_of_row, a.low_of_col, (int)n0, a.cy, cx, a.H, a.W, a.h, a.w, a.r, a.scale);
+        }
+        phl_launched(rc, "the guided filter's chunk kernels");
+    }
+    return tmp.release();
+}
+
+// The backward of every variant.  BL (no maps): the four pieces that connect the two resolutions in their bilinear form
+// (k_grad_gather, k_grad_down, scatter_tile in k_grad_apply and the x kernel, k_grad_direct).  The statistics then run on
+// the stored samples xs with identity maps: the BL = false kernel forms its window sums in the order of the forward's
+// BL = true one, whose only difference is the four-tap tile fill that k_grad_gather<true> repeats, so mx and inv / P
+// are the forward's bit for bit.
+template <bool ST, int CX, bool BL>
+int backward(const Args &a, const Plan &p)
+{
+    using M = Model<CX>;
+    const int cx = a.cx, cy = a.cy, npl = M::label_planes(cx);
+    const float *g = a.third;
+    const bool full = !BL && a.h == a.H && a.w == a.W;          // strictly increasing maps onto the same size: the identity
+    const bool need_x = a.grad_x != nullptr, need_xe = need_x || a.grad_eps != nullptr, need_apply = need_x || a.grad_y != nullptr;
+    const int64_t hw = a.hw(), HWf = a.HWf(), nimg = a.nimg();
+    const unsigned nblo = (unsigned)((hw + NE - 1) / NE), nbfull = (unsigned)((HWf + NE - 1) / NE);
+    if (int rc = phl_allow_lds(M::template stats_k<ST, false>(), M::lds_stats(p))) return rc;
+    if (int rc = phl_allow_lds(M::template grad_coef_k<ST>(), p.lds_coef)) return rc;
+    if (int rc = phl_allow_lds(k_grad_apply<ST, BL>, p.lds_apply)) return rc;
+    if (int rc = phl_allow_lds(M::template grad_x_k<ST, BL>(), p.lds_apply)) return rc;
+
+    const int64_t chunk = Plan::chunk(nimg, Plan::per_backward(cx, hw, npl, full, need_x, need_xe));
+    const size_t nstat = (size_t)a.B * cx * hw;
+    phl_temps tmp(a.st);
+    double *mx = tmp.get<double>(nstat);
+    auto *sp = tmp.get<typename M::Stat>((size_t)a.B * M::stat_planes(cx) * hw);
     float *xsb = full ? nullptr : tmp.get<float>(nstat);
     float *ysb = full ? nullptr : tmp.get<float>((size_t)chunk * hw);
-    float *Pd = tmp.get<float>((size_t)chunk * (CX + 1) * hw), *Q = tmp.get<float>((size_t)chunk * (CX + 1) * hw);
-    float *A = need_x ? tmp.get<float>((size_t)chunk * CX * hw) : nullptr, *mA = need_x ? tmp.get<float>((size_t)chunk * CX * hw) : nullptr;
-    double *part = need_xe ? tmp.get<double>((size_t)chunk * NPL * hw) : nullptr;
-    double *acc = need_xe ? tmp.get<double>((size_t)B * NPL * hw) : nullptr;
-    float *F = need_x ? tmp.get<float>((size_t)B * (CX + NP) * hw) : nullptr;
-    double *D = need_x ? tmp.get<double>((size_t)B * CX * HWf) : nullptr;
-    double *epart = grad_eps ? tmp.get<double>((size_t)CX * NEB) : nullptr;
+    float *Pd = tmp.get<float>((size_t)chunk * (cx + 1) * hw), *Q = tmp.get<float>((size_t)chunk * (cx + 1) * hw);
+    float *A = need_x ? tmp.get<float>((size_t)chunk * cx * hw) : nullptr, *mA = need_x ? tmp.get<float>((size_t)chunk * cx * hw) : nullptr;
+    double *part = need_xe ? tmp.get<double>((size_t)chunk * npl * hw) : nullptr;
+    double *acc = need_xe ? tmp.get<double>((size_t)a.B * npl * hw) : nullptr;
+    float *F = need_x ? tmp.get<float>((size_t)a.B * M::f_planes(cx) * hw) : nullptr;
+    double *D = need_x ? tmp.get<double>((size_t)a.B * cx * HWf) : nullptr;
+    double *epart = a.grad_eps ? tmp.get<double>((size_t)cx * NEB) : nullptr;
     int &rc = tmp.rc;
-    const float *xs = full ? x : xsb;
+    const float *xs = full ? a.x : xsb;
     if (rc == PHL_OK) {
         if (!full)
-            k_grad_gather<BL><<<dim3(nblo, (unsigned)CX, (unsigned)B), dim3(NE), 0, st>>>(x, xsb, row_of_low, col_of_low, H, W, h, w);
-        if constexpr (BL)       // on the samples, as run_grad<true>
-            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(xsb, nullptr, nullptr, eps, mx, Pm, h, w, h, w, re);
+            k_grad_gather<BL><<<dim3(nblo, (unsigned)cx, (unsigned)a.B), dim3(NE), 0, a.st>>>(
+                a.x, xsb, a.row_of_low, a.col_of_low, a.H, a.W, a.h, a.w);
+        if constexpr (BL)
+            M::template stats<ST, false>(a, p, xsb, a.h, a.w, mx, sp);
         else
-            stats<<<p.grid((unsigned)B), dim3(NT), p.lds_coef, st>>>(x, row_of_low, col_of_low, eps, mx, Pm, H, W, h, w, re);
-        phl_launched(rc, "k_guide_stats_full / k_grad_gather");
+            M::template stats<ST, false>(a, p, a.x, a.H, a.W, mx, sp);
+        phl_launched(rc, "the guided filter's statistics / k_grad_gather");
     }
     for (int64_t n0 = 0; n0 < nimg && rc == PHL_OK; n0 += chunk) {
         const unsigned nz = (unsigned)min(chunk, nimg - n0);
         const unsigned nb = (unsigned)((n0 + nz - 1) / cy - n0 / cy + 1);          // images the chunk touches
-        const float *ys = full ? y + n0 * HWf : ysb;
-        if (!full) k_grad_gather<BL><<<dim3(nblo, nz, 1), dim3(NE), 0, st>>>(y + n0 * HWf, ysb, row_of_low, col_of_low, H, W, h, w);
-        k_grad_down<BL><<<dim3(nblo, nz), dim3(NE), 0, st>>>(g, x, Pd, low_of_row, low_of_col, (int)n0, cy, CX, H, W, h, w, re, scale);
-        coefk<<<p.grid(nz), dim3(NT), p.lds_coef, st>>>(ys, xs, Pd, mx, Pm, Q, A, part, (int)n0, cy, h, w, re);
+        const float *ys = full ? a.y + n0 * HWf : ysb;
+        if (!full) k_grad_gather<BL><<<dim3(nblo, nz, 1), dim3(NE), 0, a.st>>>(a.y + n0 * HWf, ysb, a.row_of_low, a.col_of_low, a.H, a.W, a.h, a.w);
+        k_grad_down<BL><<<dim3(nblo, nz), dim3(NE), 0, a.st>>>(
+            g, a.x, Pd, a.low_of_row, a.low_of_col, (int)n0, cy, cx, a.H, a.W, a.h, a.w, a.r, a.scale);
+        M::template grad_coef<ST>(a, p, n0, nz, ys, xs, Pd, mx, sp, Q, A, part);
         if (need_apply)
-            apply<<<p.grid(nz), dim3(NT), p.lds_apply, st>>>(Q, A, ys, xs, g, grad_y, mA, need_x ? part : nullptr, row_of_low, col_of_low,
-                                                            (int)n0, cy, CX, H, W, h, w, re, subtract_is_y, NPL, NP + CX);
-        if (need_xe)
-            k_grad_reduce<<<dim3(nblo, (unsigned)nred, nb), dim3(NE), 0, st>>>(part, acc, (int)n0, (int)nz, cy, NPL, B, 1, NPL, hw);
+            k_grad_apply<ST, BL><<<p.grid(nz), dim3(NT), p.lds_apply, a.st>>>(
+                Q, A, ys, xs, g, a.grad_y, mA, need_x ? part : nullptr, a.row_of_low, a.col_of_low, (int)n0, cy, cx, a.H, a.W, a.h, a.w,
+                a.r, a.subtract_is_y, npl, M::yu_plane(cx));
+        if (need_xe) M::reduce(a, nblo, nb, part, acc, n0, nz, need_x);
         if (need_x)
-            k_grad_direct<BL><<<dim3(nbfull, (unsigned)CX, nb), dim3(NE), 0, st>>>(g, mA, D, low_of_row, low_of_col, (int)n0, (int)nz, cy,
-                                                                                  CX, H, W, h, w);
-        phl_launched(rc, "the full backward's chunk kernels");
+            k_grad_direct<BL><<<dim3(nbfull, (unsigned)cx, nb), dim3(NE), 0, a.st>>>(
+                g, mA, D, a.low_of_row, a.low_of_col, (int)n0, (int)nz, cy, cx, a.H, a.W, a.h, a.w);
+        phl_launched(rc, "the guided filter backward's chunk kernels");
     }
     if (need_x && rc == PHL_OK) {
-        k_grad_finish_full<<<dim3(nblo, 1, (unsigned)B), dim3(NE), 0, st>>>(acc, mx, F, CX, NPL, hw);
-        gxk<<<p.grid((unsigned)B), dim3(NT), p.lds_apply, st>>>(F, acc, xs, D, grad_x, row_of_low, col_of_low, CX, NPL, H, W, h, w, re,
-                                                               scale);
-        phl_launched(rc, "k_grad_finish_full / k_grad_x_full");
+        M::template finish_x<ST, BL>(a, p, nblo, acc, mx, F, xs, D);
+        phl_launched(rc, "k_grad_finish / k_grad_x");
     }
-    if (grad_eps && rc == PHL_OK) {
-        k_grad_eps1<<<dim3(NEB, (unsigned)CX), dim3(NE), 0, st>>>(acc, epart, B, CX, h, w, re, NPL, 1);
-        k_grad_eps2<<<dim3(1), dim3(64), 0, st>>>(epart, grad_eps, CX);
+    if (a.grad_eps && rc == PHL_OK) {
+        M::eps1(a, acc, epart);
+        k_grad_eps2<<<dim3(1), dim3(64), 0, a.st>>>(epart, a.grad_eps, cx);
         phl_launched(rc, "k_grad_eps");
     }
     return tmp.release();
 }
 
-// The arguments the forward and the backward share (`third`: out or g; `maps` false: an entry point that takes no index
-// maps); `who` names the entry point in the message.
-// PHL_OK also for zero elements, which the caller then tests for.
-int check_guided_args(const char *who, const void *y, const void *x, const void *third, const char *third_name, int B, int cy, int cx,
-                      int H, int W, int h, int w, int r, const int *row_of_low, const int *col_of_low, const int *low_of_row,
-                      const int *low_of_col, const float *eps, float scale, bool maps = true)
+// (tiled, cx of the full covariance or 0, bilinear) -> f(ST, CX, BL) as integral constants: every instantiation of
+// forward() and backward() comes from here
+template <typename F>
+int dispatch(bool tiled, int CX, bool BL, F f)
 {
-    if (B < 0 || cy < 0 || cx < 1 || H < 0 || W < 0 || h < 0 || w < 0 || r < 0 || h > H || w > W || !isfinite(scale)) {
-        phl_set_error("%s: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", who, B, cy, cx, H, W, h, w, r,
-                      (double)scale);
+    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one instantiation per channel count");
+    int rc = PHL_ERR_INVALID;
+    dispatch_bool(!tiled, [&](auto st) {
+        dispatch_bool(BL, [&](auto bl) { dispatch_int<0, 1, 2, 3, 4>(CX, [&](auto cx) { rc = f(st, cx, bl); }); });
+    });
+    return rc;
+}
+
+// The arguments the forward and the backward share (`need`: out or g).  PHL_OK also for zero elements, which the
+// caller then tests for.
+int check_guided_args(const Args &a, const void *need, const char *need_name, bool maps)
+{
+    if (a.B < 0 || a.cy < 0 || a.cx < 1 || a.H < 0 || a.W < 0 || a.h < 0 || a.w < 0 || a.r < 0 || a.h > a.H || a.w > a.W ||
+        !isfinite(a.scale)) {
+        phl_set_error("%s: bad arguments (B=%d cy=%d cx=%d H=%d W=%d h=%d w=%d r=%d scale=%g)", a.who, a.B, a.cy, a.cx, a.H, a.W, a.h,
+                      a.w, a.r, (double)a.scale);
         return PHL_ERR_INVALID;
     }
-    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
-    if (h == 0 || w == 0) {
-        phl_set_error("%s: empty solving resolution %d x %d for a %d x %d image", who, h, w, H, W);
+    if (a.B == 0 || a.cy == 0 || a.H == 0 || a.W == 0) return PHL_OK;
+    if (a.h == 0 || a.w == 0) {
+        phl_set_error("%s: empty solving resolution %d x %d for a %d x %d image", a.who, a.h, a.w, a.H, a.W);
         return PHL_ERR_INVALID;
     }
-    if (!y || !x || !third || !eps || (maps && (!row_of_low || !col_of_low || !low_of_row || !low_of_col))) {
-        phl_set_error("%s: null y / x / %s / eps / index map", who, third_name);
+    if (!a.y || !a.x || !need || !a.eps || (maps && (!a.row_of_low || !a.col_of_low || !a.low_of_row || !a.low_of_col))) {
+        phl_set_error("%s: null y / x / %s / eps / index map", a.who, need_name);
         return PHL_ERR_INVALID;
     }
-    const int64_t HWf = (int64_t)H * W, lim = INT64_MAX / 64;      // byte counts of the fp64 temporaries stay in int64
-    const int64_t nimg = (int64_t)B * cy;
-    if (HWf > INT32_MAX || nimg > INT32_MAX || HWf > lim / nimg || HWf > lim / ((int64_t)B * cx) || (h + TH - 1) / TH > 65535 ||
-        B > 65535 || max(H, W) > (1 << 30)) {
-        phl_set_error("%s: %d x %d x (%d | %d) x %d x %d elements are too many", who, B, cy, cx, cy, H, W);
+    const int64_t HWf = a.HWf(), lim = INT64_MAX / 64;      // byte counts of the fp64 temporaries stay in int64
+    const int64_t nimg = a.nimg();
+    if (HWf > INT32_MAX || nimg > INT32_MAX || HWf > lim / nimg || HWf > lim / ((int64_t)a.B * a.cx) || (a.h + TH - 1) / TH > 65535 ||
+        a.B > 65535 || max(a.H, a.W) > (1 << 30)) {
+        phl_set_error("%s: %d x %d x (%d | %d) x %d x %d elements are too many", a.who, a.B, a.cy, a.cx, a.cy, a.H, a.W);
         return PHL_ERR_TOO_LARGE;
     }
-    if (cx > PHL_GUIDED_MAX_CX) {
-        phl_set_error("%s: %d guide channels, at most %d", who, cx, PHL_GUIDED_MAX_CX);
+    if (a.cx > PHL_GUIDED_MAX_CX) {
+        phl_set_error("%s: %d guide channels, at most %d", a.who, a.cx, PHL_GUIDED_MAX_CX);
         return PHL_ERR_UNSUPPORTED;
     }
     return PHL_OK;
 }
 
-// ... and of the three backwards: no gradient is an input or another gradient
-int check_grad_aliasing(const char *who, const void *y, const void *x, const void *g, const void *eps, const void *grad_y,
-                        const void *grad_x, const void *grad_eps)
+// What every entry point checks, in this order: the shared arguments; nothing to do (zero elements, no gradient asked
+// for: PHL_OK); the flags word (`known`: the bits this entry point takes); the channels of the full covariance; the
+// bilinear backward's ratio; aliasing.  Then the window is clipped and the variant dispatched.  `bilinear`: no index maps.
+int checked(Args a, bool grad, bool bilinear, bool full_cov, unsigned flags = 0, unsigned known = 0)
 {
-    const void *ins[4] = {y, x, g, eps}, *outs[3] = {grad_y, grad_x, grad_eps};
+    if (int rc = check_guided_args(a, grad ? (const void *)a.third : a.out, grad ? "g" : "out", !bilinear)) return rc;
+    if (a.B == 0 || a.cy == 0 || a.H == 0 || a.W == 0 || (grad && !a.grad_y && !a.grad_x && !a.grad_eps)) return PHL_OK;
+    if (flags & ~known) {
+        phl_set_error("%s: unknown flags 0x%x%s", a.who, flags,
+                      grad ? " (the full-covariance backward is phl_guided_filter_bilinear_full_grad)" : "");
+        return PHL_ERR_UNSUPPORTED;
+    }
+    full_cov = full_cov || (flags & PHL_GUIDED_BILINEAR_FULL_COV) != 0;
+    if (full_cov && a.cx > PHL_GUIDED_FULL_MAX_CX) {
+        phl_set_error("%s: %d guide channels with the full covariance, at most %d (PHL_GUIDED_FULL_MAX_CX)", a.who, a.cx,
+                      PHL_GUIDED_FULL_MAX_CX);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    if (grad && bilinear && (2 * (int64_t)a.h > a.H || 2 * (int64_t)a.w > a.W)) {       // below a ratio of 2 two samples of D may share a tap
+        phl_set_error("%s: %d x %d is more than half of %d x %d", a.who, a.h, a.w, a.H, a.W);
+        return PHL_ERR_UNSUPPORTED;
+    }
+    // the forward's out is no input; no gradient is an input or another gradient
+    const void *ins[4] = {a.y, a.x, a.third, grad ? a.eps : nullptr}, *outs[3] = {grad ? a.grad_y : a.out, a.grad_x, a.grad_eps};
     for (int o = 0; o < 3; o++)
         for (int i = 0; i < 4; i++)
             if (outs[o] && (outs[o] == ins[i] || (i < o && outs[o] == outs[i]))) {
-                phl_set_error("%s: a gradient aliases an input or another gradient", who);
+                phl_set_error(grad ? "%s: a gradient aliases an input or another gradient" : "%s: out aliases an input", a.who);
                 return PHL_ERR_INVALID;
             }
-    return PHL_OK;
+    a.r = min(a.r, max(a.h, a.w));            // a window beyond the image on both axes sums the same pixels
+    const Plan p(a.r, a.h, a.w);
+    return dispatch(p.tiled, full_cov ? a.cx : 0, bilinear, [&](auto st, auto cx, auto bl) {
+        constexpr bool ST = decltype(st)::value, BL = decltype(bl)::value;
+        constexpr int CX = decltype(cx)::value;
+        return grad ? backward<ST, CX, BL>(a, p) : forward<ST, CX, BL>(a, p);
+    });
 }
+
+int checked_forward(const Args &a, bool bilinear, bool full_cov, unsigned flags = 0)
+{
+    return checked(a, false, bilinear, full_cov, flags, bilinear ? PHL_GUIDED_BILINEAR_FULL_COV : 0);
+}
+int checked_backward(const Args &a, bool bilinear, bool full_cov, unsigned flags = 0) { return checked(a, true, bilinear, full_cov, flags); }
 
 }  // namespace
 
@@ -1604,72 +1616,60 @@ int phl_guided_filter_max_r(void)
     return r;
 }
 
+int phl_guided_filter_grad_max_r(void) { return phl_guided_filter_max_r(); }     // the same two LDS layouts as the forward
+
 int phl_guided_filter_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs)
 {
     if (B < 1 || cy < 1 || cx < 1 || h < 1 || w < 1 || needs < -1 || needs > 7) return 0;
     const int64_t hw = (int64_t)h * w, nimg = (int64_t)B * cy;
     const bool need_x = (needs & 2) != 0, need_xe = (needs & 6) != 0;
-    return (int)Plan::chunk(nimg, needs < 0 ? Plan::per_forward(cx, hw) : Plan::per_backward(cx, hw, full != 0, need_x, need_xe));
+    return (int)Plan::chunk(nimg, needs < 0 ? Plan::per_forward(cx, hw, false)
+                                            : Plan::per_backward(cx, hw, grad_planes(false, cx), full != 0, need_x, need_xe));
+}
+
+int phl_guided_filter_full_grad_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs)
+{
+    if (B < 1 || cy < 1 || cx < 1 || cx > PHL_GUIDED_FULL_MAX_CX || h < 1 || w < 1 || needs < 0 || needs > 7) return 0;
+    const bool need_x = (needs & 2) != 0, need_xe = (needs & 6) != 0;
+    return (int)Plan::chunk((int64_t)B * cy, Plan::per_backward(cx, (int64_t)h * w, grad_planes(true, cx), full != 0, need_x, need_xe));
+}
+
+int phl_guided_filter_bilinear_labels_per_chunk(int B, int cy, int cx, int h, int w)
+{
+    if (B < 1 || cy < 1 || cx < 1 || h < 1 || w < 1) return 0;
+    return (int)Plan::chunk((int64_t)B * cy, Plan::per_forward(cx, (int64_t)h * w, true));
 }
 
 int phl_guided_filter(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h, int w,
                       int r, const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col,
                       const float *eps, float scale, phl_stream stream)
 {
-    if (int rc = check_guided_args("phl_guided_filter", y, x, out, "out", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low, low_of_row,
-                                   low_of_col, eps, scale))
-        return rc;
-    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
-    if (out == y || out == x || out == src) {
-        phl_set_error("phl_guided_filter: out aliases an input");
-        return PHL_ERR_INVALID;
-    }
-    const int re = min(r, max(h, w));            // a window beyond the image on both axes sums the same pixels
-    return run(y, x, src, out, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps, scale, (hipStream_t)stream);
+    return checked_forward({"phl_guided_filter", y, x, src, out, nullptr, nullptr, nullptr, B, cy, cx, H, W, h, w, r, row_of_low,
+                            col_of_low, low_of_row, low_of_col, eps, scale, 0, (hipStream_t)stream}, false, false);
 }
 
 int phl_guided_filter_full(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h,
                            int w, int r, const int *row_of_low, const int *col_of_low, const int *low_of_row, const int *low_of_col,
                            const float *eps, float scale, phl_stream stream)
 {
-    if (int rc = check_guided_args("phl_guided_filter_full", y, x, out, "out", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low,
-                                   low_of_row, low_of_col, eps, scale))
-        return rc;
-    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;          // (as check_guided_args: before the channel bound)
-    if (cx > PHL_GUIDED_FULL_MAX_CX) {
-        phl_set_error("phl_guided_filter_full: %d guide channels, at most %d (PHL_GUIDED_FULL_MAX_CX)", cx, PHL_GUIDED_FULL_MAX_CX);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (out == y || out == x || out == src) {
-        phl_set_error("phl_guided_filter_full: out aliases an input");
-        return PHL_ERR_INVALID;
-    }
-    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
-    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, int, int, int, int, int, int, int, const int *,
-                        const int *, const int *, const int *, const float *, float, hipStream_t);
-    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX] = {{run_full<false, 1>, run_full<false, 2>, run_full<false, 3>, run_full<false, 4>},
-                                                        {run_full<true, 1>, run_full<true, 2>, run_full<true, 3>, run_full<true, 4>}};
-    const int re = min(r, max(h, w));
-    const Plan p(re, h, w);
-    return runs[p.tiled ? 0 : 1][cx - 1](p, y, x, src, out, B, cy, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps,
-                                        scale, (hipStream_t)stream);
+    return checked_forward({"phl_guided_filter_full", y, x, src, out, nullptr, nullptr, nullptr, B, cy, cx, H, W, h, w, r, row_of_low,
+                            col_of_low, low_of_row, low_of_col, eps, scale, 0, (hipStream_t)stream}, false, true);
 }
 
-int phl_guided_filter_grad_max_r(void) { return phl_guided_filter_max_r(); }     // the same two LDS layouts as the forward
+int phl_guided_filter_bilinear(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h,
+                               int w, int r, const float *eps, float scale, unsigned flags, phl_stream stream)
+{
+    return checked_forward({"phl_guided_filter_bilinear", y, x, src, out, nullptr, nullptr, nullptr, B, cy, cx, H, W, h, w, r, nullptr,
+                            nullptr, nullptr, nullptr, eps, scale, 0, (hipStream_t)stream}, true, false, flags);
+}
 
 int phl_guided_filter_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B, int cy,
                            int cx, int H, int W, int h, int w, int r, const int *row_of_low, const int *col_of_low,
                            const int *low_of_row, const int *low_of_col, const float *eps, float scale, int subtract_is_y,
                            phl_stream stream)
 {
-    if (int rc = check_guided_args("phl_guided_filter_grad", y, x, g, "g", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low, low_of_row,
-                                   low_of_col, eps, scale))
-        return rc;
-    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
-    if (int rc = check_grad_aliasing("phl_guided_filter_grad", y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
-    const int re = min(r, max(h, w));
-    return run_grad(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, row_of_low, col_of_low, low_of_row, low_of_col, eps,
-                    scale, subtract_is_y, (hipStream_t)stream);
+    return checked_backward({"phl_guided_filter_grad", y, x, g, nullptr, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, r, row_of_low,
+                             col_of_low, low_of_row, low_of_col, eps, scale, subtract_is_y, (hipStream_t)stream}, false, false);
 }
 
 int phl_guided_filter_full_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps, int B,
@@ -1677,123 +1677,25 @@ int phl_guided_filter_full_grad(const float *y, const float *x, const float *g, 
                                 const int *low_of_row, const int *low_of_col, const float *eps, float scale, int subtract_is_y,
                                 phl_stream stream)
 {
-    if (int rc = check_guided_args("phl_guided_filter_full_grad", y, x, g, "g", B, cy, cx, H, W, h, w, r, row_of_low, col_of_low,
-                                   low_of_row, low_of_col, eps, scale))
-        return rc;
-    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
-    if (cx > PHL_GUIDED_FULL_MAX_CX) {
-        phl_set_error("phl_guided_filter_full_grad: %d guide channels, at most %d (PHL_GUIDED_FULL_MAX_CX)", cx,
-                      PHL_GUIDED_FULL_MAX_CX);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (int rc = check_grad_aliasing("phl_guided_filter_full_grad", y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
-    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
-    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, float *, float *, int, int, int, int, int, int,
-                        int, const int *, const int *, const int *, const int *, const float *, float, int, hipStream_t);
-    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX] = {
-        {run_full_grad<false, 1>, run_full_grad<false, 2>, run_full_grad<false, 3>, run_full_grad<false, 4>},
-        {run_full_grad<true, 1>, run_full_grad<true, 2>, run_full_grad<true, 3>, run_full_grad<true, 4>}};
-    const int re = min(r, max(h, w));
-    const Plan p(re, h, w);
-    return runs[p.tiled ? 0 : 1][cx - 1](p, y, x, g, grad_y, grad_x, grad_eps, B, cy, H, W, h, w, re, row_of_low, col_of_low, low_of_row,
-                                        low_of_col, eps, scale, subtract_is_y, (hipStream_t)stream);
+    return checked_backward({"phl_guided_filter_full_grad", y, x, g, nullptr, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, r,
+                             row_of_low, col_of_low, low_of_row, low_of_col, eps, scale, subtract_is_y, (hipStream_t)stream}, false, true);
 }
 
-int phl_guided_filter_full_grad_labels_per_chunk(int B, int cy, int cx, int h, int w, int full, int needs)
-{
-    if (B < 1 || cy < 1 || cx < 1 || cx > PHL_GUIDED_FULL_MAX_CX || h < 1 || w < 1 || needs < 0 || needs > 7) return 0;
-    const bool need_x = (needs & 2) != 0, need_xe = (needs & 6) != 0;
-    return (int)Plan::chunk((int64_t)B * cy, Plan::per_backward_full(cx, (int64_t)h * w, full != 0, need_x, need_xe));
-}
-
-int phl_guided_filter_bilinear(const float *y, const float *x, const float *src, float *out, int B, int cy, int cx, int H, int W, int h,
-                               int w, int r, const float *eps, float scale, unsigned flags, phl_stream stream)
-{
-    if (int rc = check_guided_args("phl_guided_filter_bilinear", y, x, out, "out", B, cy, cx, H, W, h, w, r, nullptr, nullptr, nullptr,
-                                   nullptr, eps, scale, false))
-        return rc;
-    if (B == 0 || cy == 0 || H == 0 || W == 0) return PHL_OK;
-    if (flags & ~PHL_GUIDED_BILINEAR_FULL_COV) {
-        phl_set_error("phl_guided_filter_bilinear: unknown flags 0x%x", flags);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    const bool full = (flags & PHL_GUIDED_BILINEAR_FULL_COV) != 0;
-    if (full && cx > PHL_GUIDED_FULL_MAX_CX) {
-        phl_set_error("phl_guided_filter_bilinear: %d guide channels with the full covariance, at most %d (PHL_GUIDED_FULL_MAX_CX)", cx,
-                      PHL_GUIDED_FULL_MAX_CX);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (out == y || out == x || out == src) {
-        phl_set_error("phl_guided_filter_bilinear: out aliases an input");
-        return PHL_ERR_INVALID;
-    }
-    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
-    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, int, int, int, int, int, int, int, int,
-                        const float *, float, hipStream_t);
-    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX + 1] = {
-        {run_bilinear<false, 0>, run_bilinear<false, 1>, run_bilinear<false, 2>, run_bilinear<false, 3>, run_bilinear<false, 4>},
-        {run_bilinear<true, 0>, run_bilinear<true, 1>, run_bilinear<true, 2>, run_bilinear<true, 3>, run_bilinear<true, 4>}};
-    const int re = min(r, max(h, w));
-    const Plan p(re, h, w);
-    return runs[p.tiled ? 0 : 1][full ? cx : 0](p, y, x, src, out, B, cy, cx, H, W, h, w, re, eps, scale, (hipStream_t)stream);
-}
-
-int phl_guided_filter_bilinear_labels_per_chunk(int B, int cy, int cx, int h, int w)
-{
-    if (B < 1 || cy < 1 || cx < 1 || h < 1 || w < 1) return 0;
-    return (int)Plan::chunk((int64_t)B * cy, Plan::per_bilinear(cx, (int64_t)h * w));
-}
-
+// (non-zero flags: PHL_ERR_UNSUPPORTED; the full covariance has the entry point below)
 int phl_guided_filter_bilinear_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps,
                                     int B, int cy, int cx, int H, int W, int h, int w, int r, const float *eps, float scale,
                                     int subtract_is_y, unsigned flags, phl_stream stream)
 {
-    if (int rc = check_guided_args("phl_guided_filter_bilinear_grad", y, x, g, "g", B, cy, cx, H, W, h, w, r, nullptr, nullptr, nullptr,
-                                   nullptr, eps, scale, false))
-        return rc;
-    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
-    if (flags) {
-        phl_set_error("phl_guided_filter_bilinear_grad: flags 0x%x (the full-covariance backward is phl_guided_filter_bilinear_full_grad)",
-                      flags);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (2 * (int64_t)h > H || 2 * (int64_t)w > W) {       // below a ratio of 2 two samples of D may share a tap
-        phl_set_error("phl_guided_filter_bilinear_grad: %d x %d is more than half of %d x %d", h, w, H, W);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (int rc = check_grad_aliasing("phl_guided_filter_bilinear_grad", y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
-    const int re = min(r, max(h, w));
-    return run_grad<true>(y, x, g, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, re, nullptr, nullptr, nullptr, nullptr, eps, scale,
-                          subtract_is_y, (hipStream_t)stream);
+    return checked_backward({"phl_guided_filter_bilinear_grad", y, x, g, nullptr, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w, r,
+                             nullptr, nullptr, nullptr, nullptr, eps, scale, subtract_is_y, (hipStream_t)stream}, true, false, flags);
 }
 
 int phl_guided_filter_bilinear_full_grad(const float *y, const float *x, const float *g, float *grad_y, float *grad_x, float *grad_eps,
                                          int B, int cy, int cx, int H, int W, int h, int w, int r, const float *eps, float scale,
                                          int subtract_is_y, phl_stream stream)
 {
-    const char *who = "phl_guided_filter_bilinear_full_grad";
-    if (int rc = check_guided_args(who, y, x, g, "g", B, cy, cx, H, W, h, w, r, nullptr, nullptr, nullptr, nullptr, eps, scale, false))
-        return rc;
-    if (B == 0 || cy == 0 || H == 0 || W == 0 || (!grad_y && !grad_x && !grad_eps)) return PHL_OK;
-    if (cx > PHL_GUIDED_FULL_MAX_CX) {
-        phl_set_error("%s: %d guide channels, at most %d (PHL_GUIDED_FULL_MAX_CX)", who, cx, PHL_GUIDED_FULL_MAX_CX);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (2 * (int64_t)h > H || 2 * (int64_t)w > W) {       // below a ratio of 2 two samples of D may share a tap
-        phl_set_error("%s: %d x %d is more than half of %d x %d", who, h, w, H, W);
-        return PHL_ERR_UNSUPPORTED;
-    }
-    if (int rc = check_grad_aliasing(who, y, x, g, eps, grad_y, grad_x, grad_eps)) return rc;
-    static_assert(PHL_GUIDED_FULL_MAX_CX == 4, "one row of instantiations per channel count");
-    using Run = int (*)(const Plan &, const float *, const float *, const float *, float *, float *, float *, int, int, int, int, int, int,
-                        int, const int *, const int *, const int *, const int *, const float *, float, int, hipStream_t);
-    static const Run runs[2][PHL_GUIDED_FULL_MAX_CX] = {
-        {run_full_grad<false, 1, true>, run_full_grad<false, 2, true>, run_full_grad<false, 3, true>, run_full_grad<false, 4, true>},
-        {run_full_grad<true, 1, true>, run_full_grad<true, 2, true>, run_full_grad<true, 3, true>, run_full_grad<true, 4, true>}};
-    const int re = min(r, max(h, w));
-    const Plan p(re, h, w);
-    return runs[p.tiled ? 0 : 1][cx - 1](p, y, x, g, grad_y, grad_x, grad_eps, B, cy, H, W, h, w, re, nullptr, nullptr, nullptr, nullptr,
-                                        eps, scale, subtract_is_y, (hipStream_t)stream);
+    return checked_backward({"phl_guided_filter_bilinear_full_grad", y, x, g, nullptr, grad_y, grad_x, grad_eps, B, cy, cx, H, W, h, w,
+                             r, nullptr, nullptr, nullptr, nullptr, eps, scale, subtract_is_y, (hipStream_t)stream}, true, true);
 }
 
 }  // extern "C"

@@ -1444,15 +1444,8 @@ def guided_filter(y, x, r, eps, *, subsample=1, scale=1.0, subtract=None, out=No
     ``full_cov``: the linear model over the whole covariance matrix of the guide channels, A = cov_yx (cov_xx + diag(eps))^-1
     (phl_guided_filter_full; PhlError status 7 for more than GUIDED_FULL_MAX_CX guide channels), instead of one model per
     channel."""
-    _, e, dims, maps = _guided_launch_args("guided_filter", y, x, subtract, "subtract", r, eps, subsample)
-    out = _out_or_empty("guided_filter", out, y.shape, y.device, "y's shape and device")
-    if dims is None:
-        return out
-    yc, xc = y.contiguous(), x.contiguous()
-    sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
-    _launch(y.device, "phl_guided_filter_full" if full_cov else "phl_guided_filter", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims,
-            *(_ptr(m) for m in maps), _ptr(e), C.c_float(float(scale)))
-    return out
+    return _guided_forward("guided_filter", "phl_guided_filter_full" if full_cov else "phl_guided_filter", y, x, r, eps, subsample,
+                           scale, subtract, out)
 
 
 def guided_filter_labels_per_chunk(B, cy, cx, h, w, *, full=False, need_y=False, need_x=False, need_eps=False, grad=None,
@@ -1484,21 +1477,28 @@ def guided_filter_bilinear(y, x, r, eps, *, subsample, scale=1.0, subtract=None,
     GUIDED_FULL_MAX_CX guide channels (PhlError status 7 above, as above 16 channels without it)."""
     if int(subsample) < 2:
         raise ValueError(f"guided_filter_bilinear: needs subsample >= 2, got {subsample}")
-    _, e, dims, _ = _guided_launch_args("guided_filter_bilinear", y, x, subtract, "subtract", r, eps, subsample, maps=False)
-    out = _out_or_empty("guided_filter_bilinear", out, y.shape, y.device, "y's shape and device")
-    if dims is None:
-        return out
-    yc, xc = y.contiguous(), x.contiguous()
-    sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
-    _launch(y.device, "phl_guided_filter_bilinear", _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims, _ptr(e), C.c_float(float(scale)),
-            GUIDED_BILINEAR_FULL_COV if full_cov else 0)
-    return out
+    return _guided_forward("guided_filter_bilinear", "phl_guided_filter_bilinear", y, x, r, eps, subsample, scale, subtract, out,
+                           maps=False, flags=GUIDED_BILINEAR_FULL_COV if full_cov else 0)
 
 
 def guided_filter_bilinear_labels_per_chunk(B, cy, cx, h, w):
     """Labels per chunk of a guided_filter_bilinear call at the solving resolution h x w
     (phl_guided_filter_bilinear_labels_per_chunk: host arithmetic of the library, no device needed)."""
     return int(_call("phl_guided_filter_bilinear_labels_per_chunk", int(B), int(cy), int(cx), int(h), int(w), value=True))
+
+
+def _guided_forward(name, entry, y, x, r, eps, subsample, scale, subtract, out, maps=True, flags=None):
+    """guided_filter (either model) and (no ``maps``, a ``flags`` word at the end) guided_filter_bilinear: one argument
+    list, three entry points."""
+    _, e, dims, maps = _guided_launch_args(name, y, x, subtract, "subtract", r, eps, subsample, maps=maps)
+    out = _out_or_empty(name, out, y.shape, y.device, "y's shape and device")
+    if dims is None:
+        return out
+    yc, xc = y.contiguous(), x.contiguous()
+    sub = None if subtract is None else (yc if subtract is y else subtract.contiguous())
+    _launch(y.device, entry, _ptr(yc), _ptr(xc), _ptr(sub), _ptr(out), *dims, *(() if maps is None else (_ptr(m) for m in maps)),
+            _ptr(e), C.c_float(float(scale)), *(() if flags is None else (flags,)))
+    return out
 
 
 def _guided_launch_args(name, y, x, third, third_name, r, eps, subsample, launch=True, maps=True):
@@ -1594,101 +1594,79 @@ def _guided_grad(name, entry, y, x, g, r, eps, subsample, scale, subtract_is_y, 
     return gy, gx, ge
 
 
+def _guided_fn_forward(forward, ctx, y, x, eps, r, subsample, scale, subtract_is_y, **model):
+    """forward of the four Functions below: only y, x and eps are saved."""
+    ctx.save_for_backward(y, x, eps)
+    ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
+    return forward(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None, **model)
+
+
+def _guided_fn_backward(grad, ctx, g):
+    """... and their backward: one call of ``grad`` computes the gradients that are asked for; that of eps has eps's shape."""
+    y, x, eps = ctx.saved_tensors
+    r, s, scale, sub = ctx.args
+    need = ctx.needs_input_grad
+    gy, gx, ge = grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0], need_x=need[1], need_eps=need[2])
+    if ge is not None:
+        ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
+    return gy, gx, ge, None, None, None, None
+
+
 class GuidedFilterFn(torch.autograd.Function):
     """``guided_filter(y, x, r, eps) * scale - (y if subtract_is_y else 0)`` with its backward on the library's kernels
     (guided_filter_grad): only y, x and eps are saved, one backward call computes the gradients that are asked for.
     ``eps`` is a tensor of cx values (or one); its gradient has its shape.  No double backward."""
 
     @staticmethod
-    def forward(ctx, y, x, eps, r, subsample, scale, subtract_is_y):
-        ctx.save_for_backward(y, x, eps)
-        ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
-        return guided_filter(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None)
+    def forward(ctx, *args):
+        return _guided_fn_forward(guided_filter, ctx, *args)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        y, x, eps = ctx.saved_tensors
-        r, s, scale, sub = ctx.args
-        need = ctx.needs_input_grad
-        gy, gx, ge = guided_filter_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0], need_x=need[1],
-                                        need_eps=need[2])
-        if ge is not None:
-            ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
-        return gy, gx, ge, None, None, None, None
+        return _guided_fn_backward(guided_filter_grad, ctx, g)
 
 
 class GuidedFilterFullFn(torch.autograd.Function):
     """GuidedFilterFn for the full-covariance model: ``guided_filter(y, x, r, eps, full_cov=True) * scale - (y if
-    subtract_is_y else 0)`` with its backward on guided_filter_full_grad.  Only y, x and eps are saved, one backward call
-    computes the gradients that are asked for.  No double backward."""
+    subtract_is_y else 0)`` with its backward on guided_filter_full_grad."""
 
     @staticmethod
-    def forward(ctx, y, x, eps, r, subsample, scale, subtract_is_y):
-        ctx.save_for_backward(y, x, eps)
-        ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
-        return guided_filter(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None, full_cov=True)
+    def forward(ctx, *args):
+        return _guided_fn_forward(guided_filter, ctx, *args, full_cov=True)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        y, x, eps = ctx.saved_tensors
-        r, s, scale, sub = ctx.args
-        need = ctx.needs_input_grad
-        gy, gx, ge = guided_filter_full_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0],
-                                             need_x=need[1], need_eps=need[2])
-        if ge is not None:
-            ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
-        return gy, gx, ge, None, None, None, None
+        return _guided_fn_backward(guided_filter_full_grad, ctx, g)
 
 
 class GuidedFilterBilinearFn(torch.autograd.Function):
     """GuidedFilterFn for mode='bilinear': ``guided_filter_bilinear(y, x, r, eps, subsample=) * scale - (y if
-    subtract_is_y else 0)`` with its backward on guided_filter_bilinear_grad.  Only y, x and eps are saved, one backward
-    call computes the gradients that are asked for.  No double backward."""
+    subtract_is_y else 0)`` with its backward on guided_filter_bilinear_grad."""
 
     @staticmethod
-    def forward(ctx, y, x, eps, r, subsample, scale, subtract_is_y):
-        ctx.save_for_backward(y, x, eps)
-        ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
-        return guided_filter_bilinear(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None)
+    def forward(ctx, *args):
+        return _guided_fn_forward(guided_filter_bilinear, ctx, *args)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        y, x, eps = ctx.saved_tensors
-        r, s, scale, sub = ctx.args
-        need = ctx.needs_input_grad
-        gy, gx, ge = guided_filter_bilinear_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0],
-                                                 need_x=need[1], need_eps=need[2])
-        if ge is not None:
-            ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
-        return gy, gx, ge, None, None, None, None
+        return _guided_fn_backward(guided_filter_bilinear_grad, ctx, g)
 
 
 class GuidedFilterBilinearFullFn(torch.autograd.Function):
     """GuidedFilterBilinearFn for the full-covariance model: ``guided_filter_bilinear(y, x, r, eps, subsample=,
-    full_cov=True) * scale - (y if subtract_is_y else 0)`` with its backward on guided_filter_bilinear_full_grad.  Only y, x
-    and eps are saved, one backward call computes the gradients that are asked for.  No double backward."""
+    full_cov=True) * scale - (y if subtract_is_y else 0)`` with its backward on guided_filter_bilinear_full_grad."""
 
     @staticmethod
-    def forward(ctx, y, x, eps, r, subsample, scale, subtract_is_y):
-        ctx.save_for_backward(y, x, eps)
-        ctx.args = (int(r), int(subsample), float(scale), bool(subtract_is_y))
-        return guided_filter_bilinear(y, x, r, eps, subsample=subsample, scale=scale, subtract=y if subtract_is_y else None,
-                                      full_cov=True)
+    def forward(ctx, *args):
+        return _guided_fn_forward(guided_filter_bilinear, ctx, *args, full_cov=True)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        y, x, eps = ctx.saved_tensors
-        r, s, scale, sub = ctx.args
-        need = ctx.needs_input_grad
-        gy, gx, ge = guided_filter_bilinear_full_grad(y, x, g, r, eps, subsample=s, scale=scale, subtract_is_y=sub, need_y=need[0],
-                                                      need_x=need[1], need_eps=need[2])
-        if ge is not None:
-            ge = (ge.sum() if eps.numel() == 1 and ge.numel() != 1 else ge).reshape(eps.shape).to(eps.dtype)
-        return gy, gx, ge, None, None, None, None
+        return _guided_fn_backward(guided_filter_bilinear_full_grad, ctx, g)
 
 
 def stream_copy(dst, src):

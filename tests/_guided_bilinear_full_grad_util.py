@@ -1,5 +1,5 @@
 """What the tests of the bilinear full-covariance guided filter's backward share (test_guided_bilinear_full_grad_cpu.py,
-test_gpu_guided_bilinear_full_grad.py): the closed form of the gradients that run_full_grad<ST, CX, true> of phl_guided.hip
+test_gpu_guided_bilinear_full_grad.py): the closed form of the gradients that backward<ST, CX, true> (CX >= 1) of phl_guided.hip
 implements, written as float64 torch ops (closed_form_grads of _guided_full_grad_util.py with the nearest sample /
 upsample replaced by ``F.interpolate(..., mode='bilinear')`` and their adjoints taken as the vector-Jacobian products of
 those two calls; the CPU test pins it to float64 autograd through the torch form), a spy that knows

@@ -1,6 +1,6 @@
-"""The label-chunk loop of phl_guided_filter_bilinear (phl_guided.hip: run_bilinear()) with a chunk boundary inside an
+"""The label-chunk loop of phl_guided_filter_bilinear (phl_guided.hip: forward(), BL) with a chunk boundary inside an
 image, in the manner of test_gpu_guided_chunks.py: the case asks the library how many labels a chunk of that very call
-holds (phl.guided_filter_bilinear_labels_per_chunk, the function run_bilinear() sizes its chunks with; the window-mean
+holds (phl.guided_filter_bilinear_labels_per_chunk, the function forward() sizes its chunks with; the window-mean
 planes count beside the coefficient planes) and asserts more than one chunk and a boundary inside an image.  The accuracy
 rule is that of tests/test_gpu_guided.py, e_hip <= e_torch with no margin under the precondition e_torch >= 8 u; a
 label's output depends on its own plane and on per-image statistics only, so the labels on both sides of the boundary,

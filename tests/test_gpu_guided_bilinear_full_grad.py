@@ -1,6 +1,6 @@
 """The backward of FastGuidedFilter / BatchedGuidedAdjacency with ``mode='bilinear'`` and ``full_cov=True`` on the HIP
 kernels (phl.guided_filter_bilinear_full_grad, phl.GuidedFilterBilinearFullFn, the ``bilinear_full_grad`` keyword of the
-classes; phl_guided.hip: run_full_grad<ST, CX, true>).
+classes; phl_guided.hip: backward<ST, CX, true>, CX >= 1).
 
 Rule of every accuracy check, the one of tests/test_gpu_guided_bilinear_grad.py and tests/test_gpu_guided_full_grad.py
 applied to each gradient (y, x, omega) through _guided_util.report: with g64 the float64 torch autograd gradient of the

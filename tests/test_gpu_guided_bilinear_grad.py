@@ -1,6 +1,6 @@
 """The backward of FastGuidedFilter / BatchedGuidedAdjacency with ``mode='bilinear'`` on the HIP kernels
 (phl.guided_filter_bilinear_grad, phl.GuidedFilterBilinearFn, the ``bilinear_grad`` keyword of the classes; phl_guided.hip:
-run_grad<true>).
+backward<ST, 0, true>).
 
 Rule of every accuracy check, the one of tests/test_gpu_guided_grad.py applied to each gradient (y, x, omega) through
 _guided_util.report: with g64 the float64 gradient (the torch form in float64 on the device, or the reference's fixture),

@@ -1,9 +1,9 @@
-"""The label-chunk loop of the box-window guided filter (phl_guided.hip: run(), run_grad()) with chunk boundaries inside
+"""The label-chunk loop of the box-window guided filter (phl_guided.hip: forward(), backward()) with chunk boundaries inside
 an image.
 
 The labels B * cy of a call are processed in chunks that keep the per-label temporaries within a fixed budget.  Every
 case here first asks the library how many labels a chunk of that very call holds (phl.guided_filter_labels_per_chunk,
-the function run() and run_grad() size their chunks with) and asserts that there is more than one chunk, that a chunk
+the function forward() and backward() size their chunks with) and asserts that there is more than one chunk, that a chunk
 boundary lies inside an image, that some chunk holds labels of two images and that some chunk starts inside an image: the
 `n0 > 0`, `b = n / cy`, `na` / `nb` arithmetic and the accumulate-or-overwrite branch of k_grad_reduce / k_grad_direct.
 

@@ -89,8 +89,8 @@ def test_more_than_four_guide_channels_is_unsupported():
 
 
 def test_labels_per_chunk_by_hand():
-    """Plan::per_backward_full: bytes a label = hw * (4 unless full + 8 (cx + 1) + 8 cx for grad_x + 8 (npairs + 2 cx) for
-    grad_x or grad_eps), within 96 MiB, at least one label and at most B * cy."""
+    """Plan::per_backward with the full covariance's grad_planes(): bytes a label = hw * (4 unless full + 8 (cx + 1) + 8 cx for
+    grad_x + 8 (npairs + 2 cx) for grad_x or grad_eps), within 96 MiB, at least one label and at most B * cy."""
     import phl
 
     budget = 96 << 20

@@ -32,7 +32,7 @@ CRFasRNN(charb(.05), gchannels=3, r=15, mode='bilinear', fused_bilinear=True), w
     *_min_ms, *_max_ms, torch_spread_ms               the extremes of the --reps calls; the torch form's max - min
     faster_by_ms, meets_time_bar                      torch_ms - keyword_ms, and whether it exceeds torch_spread_ms
     keyword_peak_MiB, torch_peak_MiB, meets_memory_bar   as *_peak_MiB above (the kernel route: plus the temporaries of
-                                                      run_full_grad), and keyword < torch
+                                                      the full-covariance backward), and keyword < torch
     diagonal_ms, nearest_full_ms (+ _peak_MiB)        for context, no bar: the diagonal ``bilinear_grad`` route and the
                                                       nearest ``full_cov_grad`` route
 and the CRFasRNN case with ``full_cov=True, bilinear_full_grad=flag``.  One image per call and r = 15 only: more images
@@ -67,7 +67,7 @@ def _train_call(m, y, x, g):
 
 
 def _temps_MiB(cy, H, W, s):
-    """The backward's stream-ordered temporaries of either kernel route below full resolution (phl_guided.hip: run_grad)."""
+    """The backward's stream-ordered temporaries of either kernel route below full resolution (phl_guided.hip: backward)."""
     hw = (H // s) * (W // s)
     chunk = phl.guided_filter_labels_per_chunk(1, cy, CX, H // s, W // s, need_y=True, need_x=True, need_eps=True)
     per = hw * (4 + 8 * (CX + 1) + 8 * CX + 24 * CX)
@@ -122,7 +122,7 @@ def _time_all(fns, reps):
 
 
 def _full_temps_MiB(cy, H, W, s):
-    """The stream-ordered temporaries of run_full_grad below full resolution (phl_guided.hip)."""
+    """The stream-ordered temporaries of the full-covariance backward below full resolution (phl_guided.hip: backward)."""
     hw, npairs = (H // s) * (W // s), CX * (CX + 1) // 2
     npl = npairs + 2 * CX
     chunk = phl.guided_filter_labels_per_chunk(1, cy, CX, H // s, W // s, need_y=True, need_x=True, need_eps=True, full_cov=True)
