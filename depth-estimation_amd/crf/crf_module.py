@@ -370,6 +370,28 @@ def _expect_routable(logits, labels):
             and not labels.requires_grad)
 
 
+def _confidence_routable(logits, confidence):
+    """What phl.nchw_confidence_unaries computes in place of ``-logits * confidence``: fp32 CUDA [B, L, H, W] logits and
+    a fp32 [B, 1, H, W] confidence on the logits' device.  A scalar, a confidence per label, CPU tensors and float64 keep
+    the torch line."""
+    return (torch.is_tensor(logits) and torch.is_tensor(confidence) and logits.is_cuda and logits.dtype == torch.float32
+            and logits.dim() == 4 and confidence.dtype == torch.float32 and confidence.device == logits.device
+            and confidence.dim() == 4 and tuple(confidence.shape) == (logits.shape[0], 1) + tuple(logits.shape[2:]))
+
+
+def _unaries(logits, confidence, fused):
+    """E0 = -logits * confidence (crf_module.py:95-97).  fused (CRFasRNN's ``fused_unaries``) and _confidence_routable
+    operands: one kernel that reads the logits once -- phl.NchwConfidenceUnaries where autograd records and the logits or
+    the confidence ask for a gradient, which saves its two inputs and no ``-logits`` --, with the torch line's bits."""
+    if confidence is None:
+        return -logits
+    if not (fused and _confidence_routable(logits, confidence)):
+        return -logits * confidence
+    if torch.is_grad_enabled() and (logits.requires_grad or confidence.requires_grad):
+        return phl.nchw_confidence_unaries_fn(logits, confidence)
+    return phl.nchw_confidence_unaries(logits, confidence)
+
+
 _nchw_streams = {}
 
 
@@ -467,12 +489,15 @@ class CRFasRNN(nn.Module):
     ``full_cov_grad`` nor ``fused_grad``), and the recorded forward is phl.GuidedFilterBilinearFullFn, for up to four
     guide channels.  Everything else -- CPU tensors, float64,
     another Mu, a label count out of a route's range -- is the plain NCHW loop, with the bits it always had.
+    ``fused_unaries=True`` puts the unaries ``-logits * confidence`` of fp32 CUDA logits and a [B, 1, H, W] confidence
+    (_confidence_routable) on phl.nchw_confidence_unaries, on every route and with the torch line's bits; recorded, on
+    phl.NchwConfidenceUnaries, which keeps no ``-logits`` for the backward and sums the confidence's gradient in float64.
     ``expected_depth`` is ``logits2average_depth(forward(...))``, what every head of crf/mb_stereo_crf.py ends with; on
     the step routes the loop itself ends in the expected label, and the logits are never written."""
 
     def __init__(self, mu_init, niters=5, r=20, eps=1e-5, notrain_mu=False, gaussian=False, gchannels=1, lattice=False,
                  fused_grad=False, fused_step=False, full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False,
-                 bilinear_grad=False, *, bilinear_full_grad=False):
+                 bilinear_grad=False, *, bilinear_full_grad=False, fused_unaries=False):
         super().__init__()
         if lattice and full_cov:
             raise ValueError("CRFasRNN: full_cov belongs to the guided-filter W; lattice=True has no covariance model")
@@ -497,7 +522,7 @@ class CRFasRNN(nn.Module):
                                                                              mode=mode, fused_bilinear=fused_bilinear,
                                                                              bilinear_grad=bilinear_grad,
                                                                              bilinear_full_grad=bilinear_full_grad)
-        self.fused_grad, self.fused_step = fused_grad, fused_step
+        self.fused_grad, self.fused_step, self.fused_unaries = fused_grad, fused_step, fused_unaries
 
     def forward(self, refs, logits, confidence=None, labels=None, energies=None):
         """refs [B, C, H, W], logits [B, L, H, W].  energies: the unaries E0 [B, L, H, W] themselves in place of
@@ -526,7 +551,7 @@ class CRFasRNN(nn.Module):
         ``values``, True).  energies: E0 itself, on every route.  Gathers what _nchw_route decides on, then dispatches."""
         if energies is not None and (logits is not None or confidence is not None):
             raise ValueError("CRFasRNN: energies are E0 itself; logits and confidence must be None with them")
-        E0 = energies if energies is not None else -logits if confidence is None else -logits * confidence
+        E0 = energies if energies is not None else _unaries(logits, confidence, self.fused_unaries)
         L, recording = E0.shape[1], torch.is_grad_enabled()
         grad = recording and (E0.requires_grad or refs.requires_grad or any(p.requires_grad for p in self.Mu.parameters()))
         facts = (isinstance(self.W, BatchedAdjacency), self.niters, E0.is_cuda and E0.dtype == torch.float32, E0.dim() == 4,

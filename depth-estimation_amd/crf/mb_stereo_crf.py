@@ -55,12 +55,12 @@ class _CoordConv(nn.Module):
 class CRFdepthRefiner(nn.Module):
     def __init__(self, d_in=64, d_guide=16, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False, fused_step=False,
                  full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False, *,
-                 bilinear_full_grad=False):
+                 bilinear_full_grad=False, fused_unaries=False):
         super().__init__()
         self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
                             fused_grad=fused_grad, fused_step=fused_step, full_cov=full_cov, full_cov_grad=full_cov_grad,
                             mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad,
-                            bilinear_full_grad=bilinear_full_grad)
+                            bilinear_full_grad=bilinear_full_grad, fused_unaries=fused_unaries)
         self.projection = nn.Conv2d(d_in, d_guide - 3, kernel_size=1)
 
     def _guide(self, imgrgb, features):
@@ -102,12 +102,12 @@ def _scalar_unaries_routable(disp, mu):
 class CRFdepthUpsampler(nn.Module):
     def __init__(self, d_in=64, d_guide=3, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False, fused_step=False,
                  full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False, *,
-                 bilinear_full_grad=False):
+                 bilinear_full_grad=False, fused_unaries=False):
         super().__init__()
         self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
                             fused_grad=fused_grad, fused_step=fused_step, full_cov=full_cov, full_cov_grad=full_cov_grad,
                             mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad,
-                            bilinear_full_grad=bilinear_full_grad)
+                            bilinear_full_grad=bilinear_full_grad, fused_unaries=fused_unaries)
 
     def forward(self, inputs):
         """fp32 CUDA inputs (_scalar_unaries_routable) get E0 and the labels from phl.nchw_scalar_unaries -- two launches,

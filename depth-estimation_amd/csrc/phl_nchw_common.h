@@ -1,8 +1,9 @@
 // What the channel-major ([B][L][n], n = H * W) translation units share: phl_nchw.hip (the mean-field step),
-// phl_nchw_expect.hip (the expected label) and phl_nchw_scalar.hip (the upsampler head's unaries).  Internal: everything
-// sits in an anonymous namespace, so each translation unit gets its own copy.
+// phl_nchw_expect.hip (the expected label), phl_nchw_scalar.hip (the upsampler head's unaries) and phl_nchw_conf.hip (the
+// unaries from logits and a confidence).  Internal: everything sits in an anonymous namespace, so each translation unit
+// gets its own copy.
 //
-// The pixel layout of the streaming kernels (every kernel of the last two files): a workgroup of NT = 256 threads owns
+// The pixel layout of the streaming kernels (every kernel of the last three files): a workgroup of NT = 256 threads owns
 // WGP = 1024 consecutive pixels of one image -- tile t of the ceil(n / WGP) tiles of image b is workgroup b * tiles + t --
 // and a thread owns PX = 4 of them, which it walks through the L planes.
 //   VEC   n % 4 == 0 and every pointer 16-byte aligned: the pixels are 4 t .. 4 t + 3 of the tile, one float4 per plane,

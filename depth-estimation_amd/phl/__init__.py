@@ -99,6 +99,8 @@ _ABI = (
     ("phl_nchw_expected_value_grad", "i", "PPPPPiiqiS"),
     ("phl_nchw_scalar_unaries", "i", "PPPPPiiiiiiddS"),
     ("phl_nchw_scalar_unaries_grad", "i", "PPPPPPiiiiiiddS"),
+    ("phl_nchw_confidence_unaries", "i", "PPPiiqS"),
+    ("phl_nchw_confidence_unaries_grad", "i", "PPPPPiiqS"),
     ("phl_softmax_neg_grad", "i", "PqPqPqqiS"),
     ("phl_uniform_compat_grad", "i", "PqPqffPqPqqiS"),
     ("phl_compat_grad_x", "i", "PqPfPqqiS"),
@@ -1047,6 +1049,78 @@ class NchwScalarUnaries(torch.autograd.Function):
 def nchw_scalar_unaries_fn(disp, size, L, gamma, s, scale=10.0, threshold=1e-2):
     """Differentiable ``nchw_scalar_unaries``: NchwScalarUnaries.apply(disp, size, L, gamma, s, scale, threshold)."""
     return NchwScalarUnaries.apply(disp, size, L, gamma, s, scale, threshold)
+
+
+# ---------------------------------------------------------------------------------------------
+# the unaries from logits and a per-pixel confidence (crf/crf_module.py, CRFasRNN; include/phl.h, phl_nchw_conf.hip)
+NCHW_CONF_PIXELS = 1024              # PHL_NCHW_CONF_PIXELS: pixels of a workgroup of the confidence-unary kernels
+
+
+def _confidence_operands(name, logits, confidence):
+    """(logits, confidence contiguous and cut from their graph, B, L, n) of the confidence-unary entry points: fp32 CUDA
+    logits [B, L, H, W] or [B, L, n] and a confidence [B, 1, H, W] / [B, 1, n] on the same device."""
+    B, L, n = _nchw_operands(name, logits, None, "logits")
+    _fp32_cuda(name, confidence, device=logits.device)
+    if tuple(confidence.shape) != (B, 1) + tuple(logits.shape[2:]):
+        raise ValueError(f"{name}: confidence must be {(B, 1) + tuple(logits.shape[2:])} for logits {tuple(logits.shape)}, "
+                         f"got {tuple(confidence.shape)}")
+    return logits.detach().contiguous(), confidence.detach().contiguous(), B, L, n
+
+
+def nchw_confidence_unaries(logits, confidence, *, out=None):
+    """CRFasRNN's unaries ``-logits * confidence`` in one kernel that reads the logits once (phl_nchw_confidence_unaries),
+    for fp32 CUDA logits [B, L, H, W] (or [B, L, n]) and a confidence [B, 1, H, W] ([B, 1, n]) on the same device: the bits
+    of the torch line on finite inputs, signed zeros included.  Any L >= 1.  Inputs that are not contiguous are made so.
+    out: a contiguous fp32 tensor of the logits' shape, returned."""
+    x, c, B, L, n = _confidence_operands("nchw_confidence_unaries", logits, confidence)
+    out = _out_or_empty("nchw_confidence_unaries", out, logits.shape, logits.device, "the logits' shape and device")
+    _launch(logits.device, "phl_nchw_confidence_unaries", _ptr(x), _ptr(c), _ptr(out), B, L, n)
+    return out
+
+
+def nchw_confidence_unaries_grad(logits, confidence, gE0, *, need_conf=True, need_logits=False):
+    """(grad_conf, grad_logits) of ``nchw_confidence_unaries(logits, confidence)`` for the upstream gradient gE0 of the
+    logits' shape, one kernel (phl_nchw_confidence_unaries_grad): ``grad_conf = -(logits * gE0).sum(1, keepdim=True)`` with
+    the products and the sum in float64, in label order, stored as fp32 once, and ``grad_logits = -(confidence * gE0)``,
+    the bits of fp32 autograd.  need_conf / need_logits: a part that is not needed is neither computed nor stored and comes
+    back as None; the other part's bits do not depend on it.  gE0 is read once, the logits only for grad_conf, the
+    confidence only for grad_logits.  gE0 that is not contiguous is made so.  The same bits on every call."""
+    x, c, B, L, n = _confidence_operands("nchw_confidence_unaries_grad", logits, confidence)
+    _fp32_cuda("nchw_confidence_unaries_grad", gE0, device=logits.device)
+    if gE0.shape != logits.shape:
+        raise ValueError(f"nchw_confidence_unaries_grad: gE0 must have the logits' shape {tuple(logits.shape)}, got {tuple(gE0.shape)}")
+    if not (need_conf or need_logits):
+        raise ValueError("nchw_confidence_unaries_grad: nothing is asked for (need_conf and need_logits are both false)")
+    ge = gE0.detach().contiguous()
+    gc = torch.empty(confidence.shape, dtype=torch.float32, device=logits.device) if need_conf else None
+    gl = torch.empty(logits.shape, dtype=torch.float32, device=logits.device) if need_logits else None
+    _launch(logits.device, "phl_nchw_confidence_unaries_grad", _ptr(x), _ptr(c), _ptr(ge), _ptr(gc), _ptr(gl), B, L, n)
+    return gc, gl
+
+
+class NchwConfidenceUnaries(torch.autograd.Function):
+    """``nchw_confidence_unaries(logits, confidence)`` with its backward on phl_nchw_confidence_unaries_grad.  Saves the
+    logits and the confidence, nothing the forward computed -- no ``-logits`` lives until the backward.  One call per
+    backward computes only what ``ctx.needs_input_grad`` asks for."""
+
+    @staticmethod
+    def forward(ctx, logits, confidence):
+        ctx.save_for_backward(logits, confidence)
+        return nchw_confidence_unaries(logits, confidence)
+
+    @staticmethod
+    def backward(ctx, gE0):
+        logits, confidence = ctx.saved_tensors
+        need_logits, need_conf = ctx.needs_input_grad
+        gc = gl = None
+        if need_conf or need_logits:
+            gc, gl = nchw_confidence_unaries_grad(logits, confidence, gE0, need_conf=need_conf, need_logits=need_logits)
+        return gl, gc
+
+
+def nchw_confidence_unaries_fn(logits, confidence):
+    """Differentiable ``nchw_confidence_unaries``: NchwConfidenceUnaries.apply(logits, confidence)."""
+    return NchwConfidenceUnaries.apply(logits, confidence)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -6,10 +6,13 @@ left image at full resolution go through the head's forward, then one training s
     E0, labels = phl.nchw_scalar_unaries(disp_lowres, (H, W), 18, gamma, s)      -> phl_nchw_scalar_unaries, two launches
     depth      = CRFasRNN(charb(.05), niters=2, r, gchannels=3).expected_depth(img, None, energies=E0, labels=labels, values=labels)
 
-    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8] [--fused-step] [--full-cov [--full-cov-grad]] [--bilinear [--bilinear-grad | --full-cov --bilinear-full-grad]]
+    python examples/stereo_upsampler.py [--h 288 --w 384 --r 8 --factor 8] [--fused-step] [--fused-unaries] [--full-cov [--full-cov-grad]] [--bilinear [--bilinear-grad | --full-cov --bilinear-full-grad]]
 
 --fused-step runs the training step with ``CRFdepthUpsampler(fused_grad=True, fused_step=True)``: W on phl.GuidedFilterFn
-and everything between two W calls on phl.NchwStepTrain.  --full-cov gives W the full covariance of the RGB guide
+and everything between two W calls on phl.NchwStepTrain.  --fused-unaries passes ``fused_unaries=True``: where the head
+runs its torch prologue (PHL_SCALAR_UNARIES=0 in the environment), CRFasRNN's ``-logits * mask`` is phl.nchw_confidence_unaries
+and under autograd phl.NchwConfidenceUnaries; behind the fused prologue, which hands E0 over itself, it changes nothing.
+--full-cov gives W the full covariance of the RGB guide
 (``CRFdepthUpsampler(full_cov=True)``): the forward on phl.guided_filter(full_cov=True), the training step on the torch form --
 or, with --full-cov-grad (``full_cov_grad=True``), on phl.GuidedFilterFullFn, the model's backward kernels.  --bilinear
 gives W ``mode='bilinear', fused_bilinear=True``: coefficients interpolated from the half-resolution solve instead of
@@ -33,7 +36,7 @@ from stereo_crf import synthetic_pair  # noqa: E402
 
 
 def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=False, full_cov=False, full_cov_grad=False,
-        bilinear=False, bilinear_grad=False, bilinear_full_grad=False):
+        bilinear=False, bilinear_grad=False, bilinear_full_grad=False, fused_unaries=False):
     import torch
     import torch.nn.functional as F
 
@@ -47,7 +50,8 @@ def run(h=288, w=384, r=8, factor=8, device="cuda", quiet=False, fused_step=Fals
     low[:, :, 2:6, 3:9] = 0                                                   # no measurement there
     net = CRFdepthUpsampler(r=r, niters=2, fused_grad=fused_step, fused_step=fused_step, full_cov=full_cov,
                             full_cov_grad=full_cov_grad, mode="bilinear" if bilinear else "nearest", fused_bilinear=bilinear,
-                            bilinear_grad=bilinear_grad, bilinear_full_grad=bilinear_full_grad).to(dev)
+                            bilinear_grad=bilinear_grad, bilinear_full_grad=bilinear_full_grad,
+                            fused_unaries=fused_unaries).to(dev)
     torch.cuda.synchronize()
     t0 = time.time()
     with torch.no_grad():
@@ -83,6 +87,8 @@ if __name__ == "__main__":
     ap.add_argument("--r", type=int, default=8)
     ap.add_argument("--factor", type=int, default=8)
     ap.add_argument("--fused-step", action="store_true", help="the training step on phl.NchwStepTrain / phl.GuidedFilterFn")
+    ap.add_argument("--fused-unaries", action="store_true",
+                    help="-logits * confidence on phl.nchw_confidence_unaries (the head's torch prologue: PHL_SCALAR_UNARIES=0)")
     ap.add_argument("--full-cov", action="store_true", help="W with the full covariance of the RGB guide")
     ap.add_argument("--full-cov-grad", action="store_true", help="with --full-cov: train that W on phl.GuidedFilterFullFn")
     ap.add_argument("--bilinear", action="store_true", help="W interpolates its coefficients (mode='bilinear', fused_bilinear=True)")
@@ -91,7 +97,7 @@ if __name__ == "__main__":
                     help="with --bilinear --full-cov: train that W on phl.GuidedFilterBilinearFullFn")
     a = ap.parse_args()
     kw = dict(fused_step=a.fused_step, full_cov=a.full_cov, full_cov_grad=a.full_cov_grad, bilinear=a.bilinear,
-              bilinear_grad=a.bilinear_grad, bilinear_full_grad=a.bilinear_full_grad)
+              bilinear_grad=a.bilinear_grad, bilinear_full_grad=a.bilinear_full_grad, fused_unaries=a.fused_unaries)
     run(a.h, a.w, a.r, a.factor, **kw)     # first run of the process: library load, first launches, first allocations
     t1 = time.time()
     run(a.h, a.w, a.r, a.factor, quiet=True, **kw)

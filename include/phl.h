@@ -419,6 +419,32 @@ int phl_nchw_scalar_unaries(const float *disp_dev, const float *gamma_dev, const
 int phl_nchw_scalar_unaries_grad(const float *disp_dev, const float *labels_dev, const float *gamma_dev, const float *s_dev,
                                  const float *gE0_dev, float *grad_dev, int B, int h, int w, int H, int W, int L, double scale,
                                  double threshold, phl_stream stream);
+/* ---- the unary energies from logits and a per-pixel confidence (crf/crf_module.py, CRFasRNN: -logits * confidence) ----
+ * logits, E0, gE0, grad_logits: contiguous fp32 [B][L][n] on the device, n = H*W; conf, grad_conf: [B][n].
+ *   phl_nchw_confidence_unaries        E0[b,a,p] = -(logits[b,a,p] * conf[b,p])
+ *   phl_nchw_confidence_unaries_grad   for the upstream gradient gE0 of E0:
+ *                                      grad_conf[b,p]     = -sum_a logits[b,a,p] * gE0[b,a,p]
+ *                                      grad_logits[b,a,p] = -(conf[b,p] * gE0[b,a,p])
+ * One kernel each.  A thread owns four pixels, loads their confidences once and walks the label planes, eight planes in
+ * flight: the forward reads the logits once and writes E0 once; the backward reads gE0 once, the logits once where
+ * grad_conf is asked for and the confidences where grad_logits is.  Either of grad_conf / grad_logits may be NULL, and
+ * that part is then neither computed nor stored (nor its operand read); the other part's bits do not depend on it; both
+ * NULL is PHL_ERR_INVALID.  E0 and grad_logits are one correctly rounded fp32 product each, negated: on finite inputs the
+ * bits of torch's (-logits) * confidence and -(gE0 * confidence), signed zeros included.  grad_conf: the products (exact)
+ * and the sum are float64, added in label order a = 0 .. L-1, and stored as fp32 once.  float4 accesses along the pixel
+ * axis when n % 4 == 0 and every pointer is 16-byte aligned, dwords otherwise.  No LDS, no atomics, no scratch: the same
+ * bits on every call.
+ * Status, checked before any HIP call: PHL_ERR_INVALID for negative sizes or L < 1; then zero elements (B == 0 or
+ * n == 0) are PHL_OK with nothing launched; then PHL_ERR_INVALID for a NULL logits / conf / E0 (gE0; both of grad_conf
+ * and grad_logits) or an output that is one of the inputs or the other output; PHL_ERR_TOO_LARGE when B*L*n*4 bytes
+ * leave int64 or the workgroups (PHL_NCHW_CONF_PIXELS pixels each) leave 2^31 - 1.  Every label count is taken: there is
+ * no PHL_ERR_UNSUPPORTED. */
+#define PHL_NCHW_CONF_PIXELS 1024
+int phl_nchw_confidence_unaries(const float *logits_dev, const float *conf_dev, float *E0_dev, int B, int L, int64_t n,
+                                phl_stream stream);
+int phl_nchw_confidence_unaries_grad(const float *logits_dev, const float *conf_dev, const float *gE0_dev,
+                                     float *grad_conf_dev /* [B][n] or NULL */, float *grad_logits_dev /* [B][L][n] or NULL */,
+                                     int B, int L, int64_t n, phl_stream stream);
 /* ---- backward of the compatibility + softmax step (CRF training) ---------------------------------------------
  * Forward: Q = softmax(-E), E = E0 + X Mu.  With the upstream gradient gQ: dE = Q (s - gQ), s[p] = sum_c gQ[p,c] Q[p,c];
  * gE0 = dE, gX = dE Mu^T, gMu = X^T dE.  All entry points: fp32 rows with unit channel stride, row strides % 4 == 0,
