@@ -32,7 +32,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
 import generate as gen  # noqa: E402
-from _guided_util import build_module, load_case  # noqa: E402
+from _guided_fixtures import build_module, load_case  # noqa: E402
 
 PART_BYTES = 900 << 10
 

@@ -14,10 +14,9 @@ import os
 import numpy as np
 import torch
 
-import generate_guided as gg       # (puts tests/ on sys.path for the two imports below)
+import generate_guided as gg       # (puts tests/ on sys.path for the import below)
 
-from _guided_bilinear_util import BIL_CASES, build_module  # noqa: E402
-from _guided_util import load_case  # noqa: E402
+from _guided_fixtures import BIL_CASES, build_module, load_case  # noqa: E402
 
 
 def main():
@@ -44,7 +43,7 @@ def main():
                 omega=omega, y_u8=y_u8, x_u8=x_u8, mode=np.array("bilinear"))
         z = load_case(name)
         with torch.no_grad():
-            mine = build_module(guided, z, torch.float64, "cpu")(torch.from_numpy(z["y"]).double(), torch.from_numpy(z["x"]).double())
+            mine = build_module(guided, z, torch.float64, "cpu", "bilinear")(torch.from_numpy(z["y"]).double(), torch.from_numpy(z["x"]).double())
         diff = float((mine - out).abs().max())
         print(f"{name}: |out| <= {float(out.abs().max()):.4g}, repository torch form vs reference: {diff}")
         assert diff == 0.0, name

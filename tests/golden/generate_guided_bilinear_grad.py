@@ -18,11 +18,9 @@ import os
 import numpy as np
 import torch
 
-import generate_guided as gg       # (puts tests/ on sys.path for the imports below)
+import generate_guided as gg       # (puts tests/ on sys.path for the import below)
 
-from _guided_bilinear_grad_util import _stem, fixture_grads, load_bilinear_grad  # noqa: E402
-from _guided_bilinear_util import BIL_CASES  # noqa: E402
-from _guided_util import load_case  # noqa: E402
+from _guided_fixtures import BIL_CASES, _stem, fixture_grads, load_case, load_grad_case  # noqa: E402
 
 
 def save_parts(stem, key, arr):
@@ -57,8 +55,8 @@ def main():
         np.savez_compressed(os.path.join(gg.HERE, stem + ".npz"), g_i8=g_i8, grad_omega=mod.omega.grad.numpy())
         save_parts(stem, "gy", y.grad.numpy())
         save_parts(stem, "gx", x.grad.numpy())
-        zz = load_bilinear_grad(name)
-        mine = fixture_grads(guided, zz, torch.float64, "cpu")
+        zz = load_grad_case(name, stem)
+        mine = fixture_grads(guided, zz, torch.float64, "cpu", "bilinear")
         gaps = {k: float(np.abs(m.numpy() - zz["grad_" + k]).max() / np.abs(zz["grad_" + k]).max())
                 for k, m in zip(("y", "x", "omega"), mine)}
         print(f"{name}: repository torch form vs reference, relative to each gradient's largest magnitude: {gaps}")

@@ -25,8 +25,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 
 import generate as gen  # noqa: E402
 from generate_guided import PART_BYTES, repo_guided  # noqa: E402
-from _guided_grad_util import GRAD_CASES, load_grad_case, torch_form_grads  # noqa: E402
-from _guided_util import load_case  # noqa: E402
+from _guided_fixtures import GRAD_CASES, fixture_grads, load_case, load_grad_case  # noqa: E402
 
 
 def save_parts(name, key, arr):
@@ -62,7 +61,7 @@ def main():
         save_parts(name, "gy", y.grad.numpy())
         save_parts(name, "gx", x.grad.numpy())
         zz = load_grad_case(name)
-        mine = torch_form_grads(guided, zz, torch.float64, "cpu")
+        mine = fixture_grads(guided, zz, torch.float64, "cpu")
         gaps = {k: float(np.abs(m.numpy() - zz["grad_" + k]).max() / np.abs(zz["grad_" + k]).max())
                 for k, m in zip(("y", "x", "omega"), mine)}
         print(f"{name}: repository torch form vs reference, relative to each gradient's largest magnitude: {gaps}")

@@ -8,7 +8,9 @@ paths.  Both numbers are printed."""
 import pytest
 import torch
 
-from _guided_util import CASES, DEV, END_TO_END, build_module, load_case, spy, torch_form
+import _guided_util as util
+from _guided_fixtures import CASES, END_TO_END, build_module, load_case
+from _guided_util import DEV, NEAREST, route, spy, torch_form
 from _guided_util import report as _report
 from _guided_util import sweep_case as _sweep_case
 
@@ -24,7 +26,7 @@ def test_goldens(name):
     y, x = torch.from_numpy(z["y"]).to(DEV), torch.from_numpy(z["x"]).to(DEV)
     with torch.no_grad(), spy() as calls:
         hip = m(y, x)
-    assert calls == {"hip": 1, "box_sum": 0}
+    assert calls == route(nearest=1)
     with torch.no_grad(), torch_form():
         t32 = m(y, x)
     _report(name, hip, t32, torch.from_numpy(z["out"]).to(DEV))
@@ -41,7 +43,7 @@ def test_golden_crfasrnn_default_w():
     refs, logits, labels = (torch.from_numpy(z[k]).to(DEV) for k in ("x", "logits", "labels"))
     with torch.no_grad(), spy() as calls:
         hip = net(refs, logits, labels=labels)
-    assert calls == {"hip": int(z["niters"]), "box_sum": 0}
+    assert calls == route(nearest=int(z["niters"]))
     with torch.no_grad(), torch_form():
         t32 = net(refs, logits, labels=labels)
     _report("crfasrnn_guided", hip, t32, torch.from_numpy(z["out"]).to(DEV), factor=2)
@@ -59,7 +61,7 @@ def test_golden_mean_field_guided_adjacency():
     E0, Mu = torch.from_numpy(z["E0"]).to(DEV), torch.from_numpy(z["Mu"]).to(DEV)
     with torch.no_grad(), spy() as calls:
         hip = mean_field_infer(E0, W, Mu, int(z["niters"]))
-    assert calls == {"hip": int(z["niters"]), "box_sum": 0}
+    assert calls == route(nearest=int(z["niters"]))
     with torch.no_grad(), torch_form():
         t32 = mean_field_infer(E0, W, Mu, int(z["niters"]))
     _report("meanfield_guided", hip, t32, torch.from_numpy(z["out"]).to(DEV), factor=2)
@@ -105,14 +107,10 @@ def test_sweep_large_image():
 
 
 def test_deterministic():
-    import phl
-
     g = torch.Generator(device=DEV).manual_seed(4)
     y = torch.rand((2, 7, 131, 257), device=DEV, generator=g)
     x = torch.rand((2, 16, 131, 257), device=DEV, generator=g)
-    a = phl.guided_filter(y, x, 20, 1e-5, subsample=2, scale=840.5, subtract=y)
-    b = phl.guided_filter(y, x, 20, 1e-5, subsample=2, scale=840.5, subtract=y)
-    assert torch.equal(a, b)
+    util.check_deterministic(NEAREST, y, x)
 
 
 def test_unsupported_shapes_fall_back_to_torch():
@@ -128,7 +126,7 @@ def test_unsupported_shapes_fall_back_to_torch():
     for m in (guided.GuidedFilter(17, 2, 1e-2).to(DEV), guided.BatchedGuidedAdjacency(17, 2, 1e-2).to(DEV)):
         with torch.no_grad(), spy() as calls:
             out = m(y, x)
-        assert calls["hip"] == 1 and calls["box_sum"] > 0          # one attempt, then the torch form
+        assert calls == route(nearest=1, box_sum=calls["box_sum"]) and calls["box_sum"] > 0          # one attempt, then the torch form
         with torch.no_grad(), torch_form():
             assert torch.equal(out, m(y, x))
 
@@ -138,31 +136,10 @@ def test_autograd_keeps_the_torch_form():
     torch form.  Bound: 1e-3 of each gradient's largest magnitude.  The fp32 forward at this size is 2e-5 relative from
     float64 (prefix sums, measured for the 48 x 64 fixture); the backward passes through the same box sums once more
     and through 1 / (var + eps) twice, and 1e-3 leaves a factor of 50 over the forward's error for that."""
-    from crf import guided
-
     g = torch.Generator(device=DEV).manual_seed(6)
     y = torch.rand((1, 3, 40, 50), device=DEV, generator=g, requires_grad=True)
     x = torch.rand((1, 3, 40, 50), device=DEV, generator=g)
-    m = guided.BatchedGuidedAdjacency(3, 4, 1e-2).to(DEV)
-    with spy() as calls:
-        m(y, x).square().sum().backward()
-    assert calls["hip"] == 0 and calls["box_sum"] > 0
-    y64 = y.detach().double().requires_grad_(True)
-    m64 = guided.BatchedGuidedAdjacency(3, 4, 1e-2).to(DEV).double()
-    with torch.no_grad():
-        m64.omega.copy_(m.omega.double())
-    m64(y64, x.double()).square().sum().backward()
-    for name, got, want in (("y", y.grad, y64.grad), ("omega", m.omega.grad, m64.omega.grad)):
-        err, mag = float((got.double() - want).abs().max()), float(want.abs().max())
-        print(f"grad {name}: |fp32 - float64| = {err:.3e} of {mag:.3e}")
-        assert err <= 1e-3 * mag, (name, err, mag)
-    # omega alone asks for a gradient: still the torch form; with grad mode off, the kernels
-    with spy() as calls:
-        m(y.detach(), x)
-    assert calls["hip"] == 0
-    with torch.no_grad(), spy() as calls:
-        m(y, x)
-    assert calls == {"hip": 1, "box_sum": 0}
+    util.check_autograd_keeps_the_torch_form(NEAREST, y, x, "grad")
 
 
 def test_gaussian_and_bilinear_never_reach_the_kernels():
@@ -177,4 +154,4 @@ def test_gaussian_and_bilinear_never_reach_the_kernels():
         guided.BatchedGuidedAdjacency(1, 4, 1e-2, mode="bilinear").to(DEV)(y, x)
         guided.GuidedFilter(1, 2, 1e-2).double().to(DEV)(y.double(), x.double())
         guided.GuidedFilter(1, 2, 1e-2)(y.cpu(), x.cpu())
-    assert calls["hip"] == 0
+    assert calls == route(box_sum=calls["box_sum"])

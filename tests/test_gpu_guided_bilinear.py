@@ -7,14 +7,19 @@ max|fp32 torch form - g| over all elements, and e_hip <= e_torch with no margin.
 e_torch >= 8 u, u = 2^-24 max|g|: where the fp32 torch form does not err, the rule judges nothing.  Every figure is
 printed.  The whole loop (CRFasRNN) is held to the project's rule for loops: no further from the float64 plain loop than
 twice the plain fp32 loop."""
+import functools
+
 import pytest
 import torch
 
-from _guided_bilinear_util import BIL_CASES, MIN_U, build_module, check, load_bilinear, module, spy
-from _guided_full_util import correlated_guide
-from _guided_util import DEV, report, torch_form
+import _guided_util as util
+from _guided_fixtures import BIL_CASES, build_module, load_case
+from _guided_util import BILINEAR, BILINEAR_FULL, DEV, MIN_U, correlated_guide, report, route, spy, torch_form, torch_route
 
 pytestmark = pytest.mark.gpu
+module = functools.partial(util.module, variant=BILINEAR)
+check = functools.partial(util.check_forward, BILINEAR)
+check_full = functools.partial(util.check_forward, BILINEAR_FULL)
 
 B, CY, EPS = 2, 3, 1e-2
 
@@ -55,33 +60,25 @@ def test_sweep(case):
         r = 2 * (_max_r() + 1)
         assert min(r // s, max(H // s, W // s)) > _max_r()              # the streamed form of the window sums
     y, x = _inputs(cx, H, W, seed=H * W + cx)
-    check(_name(kind, cx, H, W, r, s), module(kind, cx, r, s, EPS, fused_bilinear=True).to(DEV), y, x)
+    check(_name(kind, cx, H, W, r, s), module(kind, cx, r, s, EPS).to(DEV), y, x)
 
 
 @pytest.mark.parametrize("case", FULL, ids=[f"{c[0]}-cx{c[1]}" for c in FULL])
 def test_full_covariance(case):
     kind, cx, H, W, r, s = case
     y, x = _inputs(cx, H, W, seed=7 * H + cx)
-    check(_name(kind, cx, H, W, r, s, "full "), module(kind, cx, r, s, EPS, fused_bilinear=True, full_cov=True).to(DEV), y, x)
+    check_full(_name(kind, cx, H, W, r, s, "full "), module(kind, cx, r, s, EPS, full_cov=True).to(DEV), y, x)
 
 
 def test_full_covariance_off_diagonal_terms_are_live():
     """On the correlated guide: max|full - diagonal| >= 1000 e_hip, the diagonal model on its own kernels (the check of
     test_gpu_guided_full.py)."""
-    import phl
-
     kind, cx, H, W, r, s = FULL[0]
     gen = torch.Generator(device=DEV).manual_seed(11)
     y = torch.rand((B, CY, H, W), device=DEV, generator=gen)
     x = correlated_guide(B, cx, H, W, gen, DEV)
-    m = module(kind, cx, r, s, EPS, fused_bilinear=True, full_cov=True).to(DEV)
-    name = _name(kind, cx, H, W, r, s, "full, correlated guide, ")
-    hip, e_hip = check(name, m, y, x, absolute=True)
-    with torch.no_grad():
-        diag = phl.guided_filter_bilinear(y, x, r, m.eps, subsample=s, scale=0.5 * (2 * r + 1) ** 2, subtract=y)
-    gap = float((hip - diag).abs().max())
-    print(f"{name}: |full - diagonal| = {gap:.3e} = {gap / max(e_hip, 1e-300):.3g} e_hip")
-    assert gap >= 1000 * e_hip, (gap, e_hip)
+    m = module(kind, cx, r, s, EPS, full_cov=True).to(DEV)
+    check_full(_name(kind, cx, H, W, r, s, "full, correlated guide, "), m, y, x, off_diagonal=True)
 
 
 @pytest.mark.parametrize("name", BIL_CASES)
@@ -89,12 +86,12 @@ def test_goldens(name):
     """The reference's own float64 output as the yardstick."""
     from crf import guided
 
-    z = load_bilinear(name)
-    m = build_module(guided, z, torch.float32, DEV, fused_bilinear=True)
+    z = load_case(name)
+    m = build_module(guided, z, torch.float32, DEV, "bilinear", fused_bilinear=True)
     y, x = torch.from_numpy(z["y"]).to(DEV), torch.from_numpy(z["x"]).to(DEV)
     with torch.no_grad(), spy() as calls:
         hip = m(y, x)
-    assert calls == {"bilinear": 1, "nearest": 0, "box_sum": 0}
+    assert calls == route(bilinear=1)
     with torch.no_grad(), torch_form():
         t32 = m(y, x)
     report(name, hip, t32, torch.from_numpy(z["out"]).to(DEV), min_torch_u=MIN_U)
@@ -108,7 +105,7 @@ def test_noncontiguous_out_view_and_determinism():
     y = torch.rand((B, H, W, CY), device=DEV, generator=gen).permute(0, 3, 1, 2)
     x = torch.rand((B, cx, H, 2 * W), device=DEV, generator=gen)[..., ::2]
     assert not y.is_contiguous() and not x.is_contiguous()
-    m = module(kind, cx, r, s, EPS, fused_bilinear=True).to(DEV)
+    m = module(kind, cx, r, s, EPS).to(DEV)
     hip, _ = check(_name(kind, cx, H, W, r, s, "strided "), m, y, x)
     with torch.no_grad():
         assert torch.equal(m(y, x), hip)                                         # the same bits on every call
@@ -130,10 +127,10 @@ def test_subsample_one_is_the_nearest_route():
 
     y, x = _inputs(3, 41, 67, seed=6)
     for full_cov in (False, True):
-        m = module("bga", 3, 4, 1, EPS, fused_bilinear=True, full_cov=full_cov).to(DEV)
+        m = module("bga", 3, 4, 1, EPS, full_cov=full_cov).to(DEV)
         with torch.no_grad(), spy() as calls:
             got = m(y, x)
-        assert calls == {"bilinear": 0, "nearest": 1, "box_sum": 0}
+        assert calls == route(nearest=1)
         with torch.no_grad():
             assert torch.equal(got, phl.guided_filter(y, x, 4, m.eps, scale=0.5 * 81, subtract=y, full_cov=full_cov))
 
@@ -157,34 +154,34 @@ def test_binding_shape_checks():
 def test_routing():
     kind, cx, H, W, r, s = SWEEP[0]
     y, x = _inputs(cx, H, W, seed=9)
-    flagged = module(kind, cx, r, s, EPS, fused_bilinear=True, fused_grad=True).to(DEV)
-    plain = module(kind, cx, r, s, EPS).to(DEV)
+    flagged = module(kind, cx, r, s, EPS, fused_grad=True).to(DEV)
+    plain = module(kind, cx, r, s, EPS, fused_bilinear=False).to(DEV)
     with torch.no_grad(), spy() as calls:
         flagged(y, x)
-    assert calls == {"bilinear": 1, "nearest": 0, "box_sum": 0}
+    assert calls == route(bilinear=1)
     with torch.no_grad(), spy() as calls:                                        # without the keyword: the torch form
         want = plain(y, x)
-    assert calls["bilinear"] == 0 and calls["nearest"] == 0 and calls["box_sum"] > 0
+    assert calls == torch_route(calls)
     # while recording, fused_grad or not: the torch form, with the bits of the flag off
     yy = y.clone().requires_grad_(True)
     with spy() as calls:
         got = flagged(yy, x)
-    assert calls["bilinear"] == 0 and calls["nearest"] == 0 and calls["box_sum"] > 0
+    assert calls == torch_route(calls)
     assert got.requires_grad and torch.equal(got.detach(), want)
     # float64 on the device: the torch form
     with torch.no_grad(), spy() as calls:
         got64 = flagged.double()(y.double(), x.double())
         want64 = plain.double()(y.double(), x.double())
-    assert calls["bilinear"] == 0 and calls["box_sum"] > 0 and torch.equal(got64, want64)
+    assert calls == torch_route(calls) and torch.equal(got64, want64)
 
 
 def test_seventeen_guide_channels_take_the_torch_form():
     y, x = _inputs(17, 20, 30, seed=10)
     with torch.no_grad():
         with spy() as calls:
-            got = module("bga", 17, 4, 2, EPS, fused_bilinear=True).to(DEV)(y, x)
-        assert calls["bilinear"] == 1 and calls["box_sum"] > 0                   # asked, PHL_ERR_UNSUPPORTED, torch form
-        assert torch.equal(got, module("bga", 17, 4, 2, EPS).to(DEV)(y, x))
+            got = module("bga", 17, 4, 2, EPS).to(DEV)(y, x)
+        assert calls == route(bilinear=1, box_sum=calls["box_sum"]) and calls["box_sum"] > 0     # asked, PHL_ERR_UNSUPPORTED, torch form
+        assert torch.equal(got, module("bga", 17, 4, 2, EPS, fused_bilinear=False).to(DEV)(y, x))
 
 
 def test_crfasrnn_loop():
@@ -199,10 +196,10 @@ def test_crfasrnn_loop():
     with torch.no_grad():
         with spy() as calls:
             new = net(refs, logits, labels=labels)
-        assert calls == {"bilinear": 3, "nearest": 0, "box_sum": 0}
+        assert calls == route(bilinear=3)
         with old_loop(), torch_form(), spy() as calls:
             old = net(refs, logits, labels=labels)
-        assert calls["bilinear"] == 0 and calls["box_sum"] > 0
+        assert calls == torch_route(calls)
         with old_loop():
             want = net.double()(refs.double(), logits.double(), labels=labels.double())
         net.float()

@@ -8,8 +8,7 @@ filtered in a call of their own, must match bit for bit.  Every figure is printe
 import pytest
 import torch
 
-from _guided_bilinear_util import check, module
-from _guided_util import DEV
+from _guided_util import BILINEAR, DEV, check_forward, module
 
 pytestmark = pytest.mark.gpu
 
@@ -33,8 +32,8 @@ def test_chunk_boundary_inside_an_image():
     gen = torch.Generator(device=DEV).manual_seed(1)
     y = torch.rand((B, cy, H, W), device=DEV, generator=gen)
     x = torch.rand((B, CX, H, W), device=DEV, generator=gen)
-    m = module(KIND, CX, R, S, EPS, fused_bilinear=True).to(DEV)
-    hip, _ = check(f"bilinear {KIND} B{B} cy{cy} cx{CX} {H}x{W} r{R} s{S}", m, y, x)
+    m = module(KIND, CX, R, S, EPS, BILINEAR).to(DEV)
+    hip, _ = check_forward(BILINEAR, f"bilinear {KIND} B{B} cy{cy} cx{CX} {H}x{W} r{R} s{S}", m, y, x)
     # the labels around the first boundary (of image 0) and labels wholly behind it, each range one chunk of its own
     b, l = per // cy, per % cy
     with torch.no_grad():

@@ -16,15 +16,19 @@ import functools
 import pytest
 import torch
 
-from _guided_bilinear_full_grad_util import bilinear_full_grad_case, module, route, spy
-from _guided_full_grad_util import grad_inputs
-from _guided_full_util import GUIDES
-from _guided_util import DEV, grads, report
+import _guided_util as util
+from _guided_util import ALL, BILINEAR_FULL, DEV, GUIDES, MIN_U, grad_inputs, grads, report, route, spy
 
 pytestmark = pytest.mark.gpu
+module = functools.partial(util.module, variant=BILINEAR_FULL)
 
 B, CY, EPS = 2, 3, 1e-2
-ALL = dict(need_y=True, need_x=True, need_eps=True)
+
+
+def bilinear_full_grad_case(*args, **kw):
+    res = util.full_grad_case(*args, variant=BILINEAR_FULL, min_torch_u=MIN_U, **kw)
+    print(f"{res['name']}: largest e_hip = {res['u']:.2f} u")
+    return res
 
 
 def _max_r():
@@ -59,20 +63,9 @@ def test_sweep(case, guide):
 
 
 def test_noncontiguous_and_determinism():
-    import phl
-
     kind, cx, H, W, r, s = SWEEP[1]
-    res = bilinear_full_grad_case(kind, B, CY, cx, H, W, r, s, EPS, "correlated", seed=5, noncontiguous=True)
-    y, x, g, m = res["y"], res["x"], res["g"], res["m"]
-    assert not y.is_contiguous() and not x.is_contiguous() and not g.is_contiguous()
-    kw = dict(subsample=s, scale=0.5 * (2 * r + 1) ** 2, subtract_is_y=True, **ALL)
-    e = m.eps.detach()
-    a = phl.guided_filter_bilinear_full_grad(y, x, g, r, e, **kw)
-    b = phl.guided_filter_bilinear_full_grad(y, x, g, r, e, **kw)
-    c = phl.guided_filter_bilinear_full_grad(y.contiguous(), x.contiguous(), g.contiguous(), r, e, **kw)
-    for u, v, w_ in zip(a, b, c):
-        assert torch.equal(u, v) and torch.equal(u, w_)                         # the same bits on every call
-    assert torch.equal(a[0], res["hip"][0]) and torch.equal(a[1], res["hip"][1])  # the module made this call
+    util.check_noncontiguous_and_determinism(
+        BILINEAR_FULL, bilinear_full_grad_case(kind, B, CY, cx, H, W, r, s, EPS, "correlated", seed=5, noncontiguous=True))
 
 
 def test_need_combinations():
@@ -80,16 +73,7 @@ def test_need_combinations():
 
     y, x, g = grad_inputs(2, 5, 3, 37, 52, "correlated", 8)
     eps = torch.tensor([1e-2, 2e-2, 3e-2], device=DEV)
-    kw = dict(subsample=2, scale=40.5, subtract_is_y=True)
-    full = phl.guided_filter_bilinear_full_grad(y, x, g, 4, eps, **ALL, **kw)
-    assert all(t is not None and torch.isfinite(t).all() for t in full)
-    for ny in (False, True):
-        for nx in (False, True):
-            for ne in (False, True):
-                got = phl.guided_filter_bilinear_full_grad(y, x, g, 4, eps, need_y=ny, need_x=nx, need_eps=ne, **kw)
-                for want, asked, have in zip(full, (ny, nx, ne), got):
-                    assert (have is None) if not asked else torch.equal(have, want), (ny, nx, ne)
-    assert tuple(t.shape for t in full) == (y.shape, x.shape, (3,))
+    util.check_need_combinations(BILINEAR_FULL, y, x, g, eps)
     with pytest.raises(ValueError):
         phl.guided_filter_bilinear_full_grad(y, x, g, 4, eps, subsample=1)
     with pytest.raises(ValueError):
@@ -107,28 +91,7 @@ def test_function_honours_needs_input_grad():
 
     y, x, g = grad_inputs(1, 3, 2, 30, 44, "correlated", 9)
     eps = torch.tensor([1e-2, 2e-2], device=DEV)
-    seen = []
-    real = phl.guided_filter_bilinear_full_grad
-
-    def f(*a, **k):
-        seen.append((k["need_y"], k["need_x"], k["need_eps"]))
-        return real(*a, **k)
-
-    phl.guided_filter_bilinear_full_grad = f
-    try:
-        for ny, nx, ne in ((True, False, False), (False, True, False), (False, False, True), (True, True, True)):
-            yy, xx, ee = y.clone().requires_grad_(ny), x.clone().requires_grad_(nx), eps.clone().requires_grad_(ne)
-            out = phl.GuidedFilterBilinearFullFn.apply(yy, xx, ee, 4, 2, 1.0, False)
-            assert torch.equal(out, phl.guided_filter_bilinear(y, x, 4, eps, subsample=2, full_cov=True))
-            saved = out.grad_fn.saved_tensors
-            assert len(saved) == 3 and [t.shape for t in saved] == [y.shape, x.shape, eps.shape]
-            (out * g).sum().backward()
-            assert seen[-1] == (ny, nx, ne)
-            assert (yy.grad is not None) == ny and (xx.grad is not None) == nx and (ee.grad is not None) == ne
-            assert ee.grad is None or ee.grad.shape == eps.shape
-    finally:
-        phl.guided_filter_bilinear_full_grad = real
-    assert len(seen) == 4
+    util.check_function_honours_needs_input_grad(BILINEAR_FULL, y, x, g, eps)
     out = phl.GuidedFilterBilinearFullFn.apply(y.clone().requires_grad_(True), x, eps, 4, 2, 40.5, True)
     assert torch.equal(out, phl.guided_filter_bilinear(y, x, 4, eps, subsample=2, scale=40.5, subtract=y, full_cov=True))
 

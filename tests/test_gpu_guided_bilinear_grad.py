@@ -14,14 +14,16 @@ import functools
 import pytest
 import torch
 
-from _guided_bilinear_grad_util import ROUTE, fixture_grads, load_bilinear_grad, spy, sweep_case_grad
-from _guided_bilinear_util import BIL_CASES, MIN_U, module
-from _guided_util import DEV, grads, report
+import _guided_util as util
+from _guided_fixtures import BIL_CASES, fixture_grads, load_grad_case
+from _guided_util import ALL, BILINEAR, DEV, MIN_U, NEAREST, grads, kernel_route, report, route, spy, torch_route
 
 pytestmark = pytest.mark.gpu
+module = functools.partial(util.module, variant=BILINEAR)
+sweep_case_grad = functools.partial(util.sweep_case_grad, variant=BILINEAR, min_torch_u=MIN_U)
+ROUTE = kernel_route(BILINEAR)
 
 B, CY, EPS = 2, 3, 1e-2
-ALL = dict(need_y=True, need_x=True, need_eps=True)
 
 
 def _max_r():
@@ -59,32 +61,20 @@ def test_goldens(name):
     """The reference's own float64 gradients as the yardstick."""
     from crf import guided
 
-    z = load_bilinear_grad(name)
+    z = load_grad_case(name)
     with spy() as calls:
-        hip = fixture_grads(guided, z, torch.float32, DEV, fused_bilinear=True, bilinear_grad=True)
+        hip = fixture_grads(guided, z, torch.float32, DEV, "bilinear", fused_bilinear=True, bilinear_grad=True)
     assert calls == ROUTE
     with spy() as calls:
-        t32 = fixture_grads(guided, z, torch.float32, DEV, fused_bilinear=True)
-    assert calls["bilinear"] == 0 and calls["bilinear_grad"] == 0 and calls["box_sum"] > 0
+        t32 = fixture_grads(guided, z, torch.float32, DEV, "bilinear", fused_bilinear=True)
+    assert calls == torch_route(calls)
     for k, a, b in zip(("y", "x", "omega"), hip, t32):
         report(f"{name} grad_{k}", a, b, torch.from_numpy(z["grad_" + k]).to(DEV), what="grad", min_torch_u=MIN_U)
 
 
 def test_noncontiguous_and_determinism():
-    import phl
-
     kind, cx, H, W, r, s = SWEEP[1]
-    res = sweep_case_grad(kind, B, CY, cx, H, W, r, s, EPS, seed=5, noncontiguous=True)
-    y, x, g, m = res["y"], res["x"], res["g"], res["m"]
-    assert not y.is_contiguous() and not x.is_contiguous() and not g.is_contiguous()
-    kw = dict(subsample=s, scale=0.5 * (2 * r + 1) ** 2, subtract_is_y=True, **ALL)
-    e = m.eps.detach()
-    a = phl.guided_filter_bilinear_grad(y, x, g, r, e, **kw)
-    b = phl.guided_filter_bilinear_grad(y, x, g, r, e, **kw)
-    c = phl.guided_filter_bilinear_grad(y.contiguous(), x.contiguous(), g.contiguous(), r, e, **kw)
-    for u, v, w_ in zip(a, b, c):
-        assert torch.equal(u, v) and torch.equal(u, w_)                         # the same bits on every call
-    assert torch.equal(a[0], res["hip"][0]) and torch.equal(a[1], res["hip"][1])  # the module made this call
+    util.check_noncontiguous_and_determinism(BILINEAR, sweep_case_grad(kind, B, CY, cx, H, W, r, s, EPS, seed=5, noncontiguous=True))
 
 
 def _inputs(shape_y, cx, seed):
@@ -100,16 +90,7 @@ def test_need_combinations():
 
     y, x, g = _inputs((2, 5, 37, 52), 3, 8)
     eps = torch.tensor([1e-2, 2e-2, 3e-2], device=DEV)
-    kw = dict(subsample=2, scale=40.5, subtract_is_y=True)
-    full = phl.guided_filter_bilinear_grad(y, x, g, 4, eps, **ALL, **kw)
-    assert all(t is not None and torch.isfinite(t).all() for t in full)
-    for ny in (False, True):
-        for nx in (False, True):
-            for ne in (False, True):
-                got = phl.guided_filter_bilinear_grad(y, x, g, 4, eps, need_y=ny, need_x=nx, need_eps=ne, **kw)
-                for want, asked, have in zip(full, (ny, nx, ne), got):
-                    assert (have is None) if not asked else torch.equal(have, want), (ny, nx, ne)
-    assert tuple(t.shape for t in full) == (y.shape, x.shape, (3,))
+    util.check_need_combinations(BILINEAR, y, x, g, eps)
     with pytest.raises(ValueError):
         phl.guided_filter_bilinear_grad(y, x, g, 4, eps, subsample=1)
     with pytest.raises(ValueError):
@@ -119,31 +100,7 @@ def test_need_combinations():
 def test_function_honours_needs_input_grad():
     """GuidedFilterBilinearFn asks guided_filter_bilinear_grad only for the gradients autograd needs, in one call, and
     saves y, x, eps."""
-    import phl
-
-    y, x, g = _inputs((1, 3, 30, 44), 2, 9)
-    eps = torch.tensor([1e-2, 1e-2], device=DEV)
-    seen = []
-    real = phl.guided_filter_bilinear_grad
-
-    def f(*a, **k):
-        seen.append((k["need_y"], k["need_x"], k["need_eps"]))
-        return real(*a, **k)
-
-    phl.guided_filter_bilinear_grad = f
-    try:
-        for ny, nx, ne in ((True, False, False), (False, True, False), (False, False, True), (True, True, True)):
-            yy, xx, ee = y.clone().requires_grad_(ny), x.clone().requires_grad_(nx), eps.clone().requires_grad_(ne)
-            out = phl.GuidedFilterBilinearFn.apply(yy, xx, ee, 4, 2, 1.0, False)
-            assert torch.equal(out, phl.guided_filter_bilinear(y, x, 4, eps, subsample=2))
-            assert len(out.grad_fn.saved_tensors) == 3
-            (out * g).sum().backward()
-            assert seen[-1] == (ny, nx, ne)
-            assert (yy.grad is not None) == ny and (xx.grad is not None) == nx and (ee.grad is not None) == ne
-            assert ee.grad is None or ee.grad.shape == eps.shape
-    finally:
-        phl.guided_filter_bilinear_grad = real
-    assert len(seen) == 4
+    util.check_function_honours_needs_input_grad(BILINEAR, *_inputs((1, 3, 30, 44), 2, 9), torch.tensor([1e-2, 1e-2], device=DEV))
 
 
 # ---- chunks -------------------------------------------------------------------------------------------------------------
@@ -208,7 +165,7 @@ def test_seventeen_guide_channels_take_the_torch_form():
         m = module("bga", 17, 4, 2, EPS, fused_bilinear=True, bilinear_grad=flag).to(DEV)
         with spy() as calls:
             res.append(grads(m, y, x, g, torch.float32))
-        assert calls["bilinear"] == (1 if flag else 0) and calls["bilinear_grad"] == 0 and calls["box_sum"] > 0, calls
+        assert calls == route(bilinear=1 if flag else 0, box_sum=calls["box_sum"]) and calls["box_sum"] > 0, calls
     for a, b in zip(*res):
         assert torch.equal(a, b)
 
@@ -220,7 +177,7 @@ def test_float64_on_the_device_takes_the_torch_form():
         m = module("fast", 3, 4, 2, EPS, fused_bilinear=True, bilinear_grad=flag).to(DEV).double()
         with spy() as calls:
             res.append(grads(m, y, x, g, torch.float64))
-        assert calls["bilinear"] == 0 and calls["bilinear_grad"] == 0 and calls["box_sum"] > 0, calls
+        assert calls == torch_route(calls), calls
     for a, b in zip(*res):
         assert a.dtype == torch.float64 and torch.equal(a, b)
 
@@ -234,7 +191,7 @@ def test_subsample_one_is_the_nearest_pair():
     m = module("bga", 3, 4, 1, EPS, fused_bilinear=True, bilinear_grad=True).to(DEV)
     with spy() as calls:
         got = grads(m, y, x, g, torch.float32)
-    assert calls == {"bilinear": 0, "bilinear_grad": 0, "nearest": 1, "nearest_grad": 1, "box_sum": 0}
+    assert calls == kernel_route(NEAREST)
     want = grads(guided.BatchedGuidedAdjacency(3, 4, EPS, subsample_ratio=1, fused_grad=True).to(DEV), y, x, g, torch.float32)
     for a, b in zip(got, want):
         assert torch.equal(a, b)
@@ -266,12 +223,12 @@ def test_crfasrnn_trains_on_the_kernels(fused_step):
     assert net.W.bilinear_grad
     with spy() as calls:
         hip = run(net, torch.float32)
-    assert calls == {"bilinear": niters, "bilinear_grad": niters, "nearest": 0, "nearest_grad": 0, "box_sum": 0}
+    assert calls == kernel_route(BILINEAR, niters)
     net.W.bilinear_grad = False
     net.fused_step = False
     with spy() as calls:
         t32 = run(net, torch.float32)
-    assert calls["bilinear"] == 0 and calls["bilinear_grad"] == 0 and calls["box_sum"] > 0
+    assert calls == torch_route(calls)
     want = run(net.double(), torch.float64)
     for k in hip:
         report(f"crfasrnn bilinear grad_{k}", hip[k], t32[k], want[k], factor=2, what="grad")

@@ -12,8 +12,9 @@ in u for every case."""
 import pytest
 import torch
 
-from _guided_full_util import GUIDES, affine_inputs, check_full, correlated_guide, full_case
-from _guided_util import DEV, load_case, report, spy, torch_form
+import _guided_util as util
+from _guided_fixtures import load_case
+from _guided_util import DEV, GUIDES, NEAREST_FULL, affine_inputs, correlated_guide, full_case, report, route, spy, torch_form
 
 pytestmark = pytest.mark.gpu
 
@@ -59,7 +60,7 @@ def test_five_channels_fall_back_to_the_torch_form():
     for m in (guided.GuidedFilter(5, 2, 1e-2, full_cov=True).to(DEV), guided.BatchedGuidedAdjacency(5, 2, 1e-2, full_cov=True).to(DEV)):
         with torch.no_grad(), spy() as calls:
             out = m(y, x)
-        assert calls["hip"] == 1 and calls["box_sum"] > 0          # one attempt, then the torch form
+        assert calls == route(nearest=1, box_sum=calls["box_sum"]) and calls["box_sum"] > 0          # one attempt, then the torch form
         with torch.no_grad(), torch_form():
             assert torch.equal(out, m(y, x))
 
@@ -101,7 +102,7 @@ def test_natural_images(name, eps):
     z = load_case(name)
     y, x = torch.from_numpy(z["y"]).to(DEV), torch.from_numpy(z["x"]).to(DEV)
     m = guided.GuidedFilter(int(z["cx"]), int(z["r"]), eps, full_cov=True).to(DEV)
-    check_full(f"full {name} eps{eps:g}", m, y, x, off_diagonal=name == "gf_tsukuba")        # (gf_r4: a random guide)
+    util.check_forward(NEAREST_FULL, f"full {name} eps{eps:g}", m, y, x, off_diagonal=name == "gf_tsukuba")        # (gf_r4: a random guide)
 
 
 def test_affine_reproduction_on_the_kernels():
@@ -119,14 +120,10 @@ def test_affine_reproduction_on_the_kernels():
 
 
 def test_deterministic():
-    import phl
-
     g = torch.Generator(device=DEV).manual_seed(4)
     y = torch.rand((2, 7, 131, 257), device=DEV, generator=g)
     x = correlated_guide(2, 3, 131, 257, g, DEV)
-    a = phl.guided_filter(y, x, 20, 1e-5, subsample=2, scale=840.5, subtract=y, full_cov=True)
-    b = phl.guided_filter(y, x, 20, 1e-5, subsample=2, scale=840.5, subtract=y, full_cov=True)
-    assert torch.isfinite(a).all() and torch.equal(a, b)
+    util.check_deterministic(NEAREST_FULL, y, x)
 
 
 def test_crfasrnn_full_cov_without_grad():
@@ -143,7 +140,7 @@ def test_crfasrnn_full_cov_without_grad():
     net = CRFasRNN(charb(3.), niters=3, gchannels=3, full_cov=True).to(DEV)
     with torch.no_grad(), spy() as calls:
         hip = net(refs, logits, labels=labels)
-    assert calls == {"hip": 3, "box_sum": 0}
+    assert calls == route(nearest=3)
     with torch.no_grad(), torch_form():
         t32 = net(refs, logits, labels=labels)
         want = net.double()(refs.double(), logits.double(), labels=labels.double())
@@ -154,27 +151,7 @@ def test_autograd_keeps_the_torch_form():
     """With autograd recording the torch form runs -- also with fused_grad=True: this model has no backward kernel -- and
     its fp32 gradients are those of the float64 torch form within 1e-3 of each gradient's largest magnitude (the bound and
     the reasoning of tests/test_gpu_guided.py::test_autograd_keeps_the_torch_form)."""
-    from crf import guided
-
     g = torch.Generator(device=DEV).manual_seed(6)
     y = torch.rand((1, 3, 40, 50), device=DEV, generator=g, requires_grad=True)
     x = correlated_guide(1, 3, 40, 50, g, DEV)
-    m = guided.BatchedGuidedAdjacency(3, 4, 1e-2, full_cov=True, fused_grad=True).to(DEV)
-    with spy(grad=True) as calls:
-        m(y, x).square().sum().backward()
-    assert calls["hip"] == 0 and calls["hip_grad"] == 0 and calls["box_sum"] > 0
-    y64 = y.detach().double().requires_grad_(True)
-    m64 = guided.BatchedGuidedAdjacency(3, 4, 1e-2, full_cov=True).to(DEV).double()
-    with torch.no_grad():
-        m64.omega.copy_(m.omega.double())
-    m64(y64, x.double()).square().sum().backward()
-    for name, got, want in (("y", y.grad, y64.grad), ("omega", m.omega.grad, m64.omega.grad)):
-        err, mag = float((got.double() - want).abs().max()), float(want.abs().max())
-        print(f"full_cov grad {name}: |fp32 - float64| = {err:.3e} of {mag:.3e}")
-        assert err <= 1e-3 * mag, (name, err, mag)
-    with spy() as calls:                       # omega alone asks for a gradient: still the torch form
-        m(y.detach(), x)
-    assert calls["hip"] == 0
-    with torch.no_grad(), spy() as calls:
-        m(y, x)
-    assert calls == {"hip": 1, "box_sum": 0}
+    util.check_autograd_keeps_the_torch_form(NEAREST_FULL, y, x, "full_cov grad", fused_grad=True)

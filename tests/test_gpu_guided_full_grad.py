@@ -9,15 +9,18 @@ more than one channel and a window of more than one pixel, each gradient must al
 (phl.guided_filter_grad on the same inputs) by at least 1000 e_hip: a backward without the off-diagonal terms cannot pass.
 The end-to-end CRFasRNN case is held to e_hip <= 2 e_torch: the fp32 compatibility and softmax steps are common to both
 paths."""
+import functools
+
 import pytest
 import torch
 
-from _guided_full_grad_util import ROUTE, check_full_grad, grad_inputs, omega_grad, rule, spy
-from _guided_full_grad_util import full_grad_case as _case
-from _guided_full_util import GUIDES
-from _guided_util import DEV, grads, load_case, module
+import _guided_util as util
+from _guided_fixtures import load_case
+from _guided_util import DEV, GUIDES, NEAREST_FULL, grad_inputs, grads, kernel_route, module, omega_grad, route, rule, spy, torch_route
 
 pytestmark = pytest.mark.gpu
+_case = functools.partial(util.full_grad_case, units=(True, True, True))
+ROUTE = kernel_route(NEAREST_FULL)
 
 
 @pytest.mark.parametrize("guide", GUIDES)
@@ -69,66 +72,23 @@ def test_natural_image(eps):
     y, x = torch.from_numpy(z["y"]).to(DEV), torch.from_numpy(z["x"]).to(DEV)
     g = torch.rand(y.shape, device=DEV, generator=torch.Generator(device=DEV).manual_seed(5)) * 2 - 1
     m = module(kind, int(z["cx"]), int(z["r"]), int(z["s"]), eps, full_cov=True, full_cov_grad=True).to(DEV)
-    check_full_grad(f"full grad tsukuba eps{eps:g}", m, y, x, g)
+    util.check_grad(NEAREST_FULL, f"full grad tsukuba eps{eps:g}", m, y, x, g, units=(True, True, True))
 
 
 def test_need_combinations():
-    import phl
-
-    y, x, g = grad_inputs(2, 5, 3, 37, 52, "correlated", 8)
-    eps = torch.tensor([1e-2, 2e-2, 3e-2], device=DEV)
-    kw = dict(subsample=2, scale=40.5, subtract_is_y=True)
-    full = phl.guided_filter_full_grad(y, x, g, 4, eps, need_y=True, need_x=True, need_eps=True, **kw)
-    assert all(t is not None and torch.isfinite(t).all() for t in full)
-    for ny in (False, True):
-        for nx in (False, True):
-            for ne in (False, True):
-                got = phl.guided_filter_full_grad(y, x, g, 4, eps, need_y=ny, need_x=nx, need_eps=ne, **kw)
-                for want, asked, have in zip(full, (ny, nx, ne), got):
-                    assert (have is None) if not asked else torch.equal(have, want), (ny, nx, ne)
-    assert tuple(t.shape for t in full) == (y.shape, x.shape, (3,))
+    util.check_need_combinations(NEAREST_FULL, *grad_inputs(2, 5, 3, 37, 52, "correlated", 8),
+                                 torch.tensor([1e-2, 2e-2, 3e-2], device=DEV))
 
 
 def test_deterministic():
-    import phl
-
-    y, x, g = grad_inputs(2, 7, 4, 131, 257, "correlated", 4)
-    kw = dict(subsample=2, scale=840.5, subtract_is_y=True, need_y=True, need_x=True, need_eps=True)
-    a = phl.guided_filter_full_grad(y, x, g, 20, 1e-5, **kw)
-    b = phl.guided_filter_full_grad(y, x, g, 20, 1e-5, **kw)
-    for u, v in zip(a, b):
-        assert torch.equal(u, v)
+    util.check_deterministic(NEAREST_FULL, *grad_inputs(2, 7, 4, 131, 257, "correlated", 4))
 
 
 def test_function_honours_needs_input_grad():
     """GuidedFilterFullFn asks guided_filter_full_grad only for the gradients autograd needs, in one call, and saves y, x,
     eps."""
-    import phl
-
-    y, x, g = grad_inputs(1, 3, 2, 30, 44, "correlated", 9)
-    eps = torch.tensor([1e-2, 1e-2], device=DEV)
-    seen = []
-    real = phl.guided_filter_full_grad
-
-    def f(*a, **k):
-        seen.append((k["need_y"], k["need_x"], k["need_eps"]))
-        return real(*a, **k)
-
-    phl.guided_filter_full_grad = f
-    try:
-        for ny, nx, ne in ((True, False, False), (False, True, False), (False, False, True), (True, True, True)):
-            yy, xx, ee = y.clone().requires_grad_(ny), x.clone().requires_grad_(nx), eps.clone().requires_grad_(ne)
-            out = phl.GuidedFilterFullFn.apply(yy, xx, ee, 4, 2, 1.0, False)
-            saved = out.grad_fn.saved_tensors
-            assert len(saved) == 3 and [t.data_ptr() for t in saved] == [yy.data_ptr(), xx.data_ptr(), ee.data_ptr()]
-            with torch.no_grad():
-                assert torch.equal(out, phl.guided_filter(y, x, 4, eps, subsample=2, full_cov=True))
-            (out * g).sum().backward()
-            assert seen[-1] == (ny, nx, ne)
-            assert (yy.grad is not None) == ny and (xx.grad is not None) == nx and (ee.grad is not None) == ne
-    finally:
-        phl.guided_filter_full_grad = real
-    assert len(seen) == 4
+    util.check_function_honours_needs_input_grad(NEAREST_FULL, *grad_inputs(1, 3, 2, 30, 44, "correlated", 9),
+                                                 torch.tensor([1e-2, 1e-2], device=DEV))
 
 
 def test_chunks():
@@ -169,12 +129,12 @@ def test_routing():
     assert calls == ROUTE
     with torch.no_grad(), spy() as calls:      # nothing recorded: the forward alone, as without the keyword
         m(y, x)
-    assert calls == {"hip": 1, "hip_grad": 0, "hip_full_grad": 0, "box_sum": 0}
+    assert calls == route(nearest=1)
     # fused_grad=True does not switch the route on
     m2 = guided.BatchedGuidedAdjacency(3, 4, 1e-2, full_cov=True, fused_grad=True).to(DEV)
     with spy() as calls:
         grads(m2, y, x, g, torch.float32)
-    assert calls["hip"] == 0 and calls["hip_grad"] == 0 and calls["hip_full_grad"] == 0 and calls["box_sum"] > 0
+    assert calls == torch_route(calls)
 
 
 def test_five_guide_channels_run_the_torch_form():
@@ -186,8 +146,8 @@ def test_five_guide_channels_run_the_torch_form():
         m = guided.BatchedGuidedAdjacency(5, 2, 1e-2, full_cov=True, full_cov_grad=flag).to(DEV)
         with spy() as calls:
             res.append(grads(m, y, x, g, torch.float32))
-        assert calls["hip_full_grad"] == 0 and calls["hip_grad"] == 0 and calls["box_sum"] > 0
-        assert calls["hip"] == (1 if flag else 0)              # the attempt that PHL_ERR_UNSUPPORTED ends
+        # (with the keyword the forward is tried once: the attempt that PHL_ERR_UNSUPPORTED ends)
+        assert calls == route(nearest=1 if flag else 0, box_sum=calls["box_sum"]) and calls["box_sum"] > 0, calls
     for a, b in zip(*res):
         assert torch.equal(a, b)
 
@@ -217,11 +177,11 @@ def test_crfasrnn_trains_on_the_kernels():
     assert net.W.full_cov_grad
     with spy() as calls:
         hip = run(net, torch.float32)
-    assert calls == {"hip": niters, "hip_grad": 0, "hip_full_grad": niters, "box_sum": 0}
+    assert calls == kernel_route(NEAREST_FULL, niters)
     net.W.full_cov_grad = False
     with spy() as calls:
         t32 = run(net, torch.float32)
-    assert calls["hip"] == 0 and calls["hip_full_grad"] == 0 and calls["box_sum"] > 0
+    assert calls == torch_route(calls)
     want = run(net.double(), torch.float64)
     for k in hip:
         rule(f"crfasrnn full_cov grad_{k}", hip[k], t32[k], want[k], factor=2)

@@ -12,13 +12,12 @@ import pytest
 import torch
 
 import _guided_util as util
-from _guided_grad_util import GRAD_CASES, load_grad_case, torch_form_grads
-from _guided_util import DEV
+from _guided_fixtures import GRAD_CASES, fixture_grads, load_grad_case
+from _guided_util import DEV, NEAREST, kernel_route, route, spy, torch_route
 from _guided_util import grads as _grads
 from _guided_util import sweep_case_grad as _sweep_case
 
 pytestmark = pytest.mark.gpu
-spy = functools.partial(util.spy, grad=True)
 _report = functools.partial(util.report, what="grad")
 
 
@@ -28,9 +27,9 @@ def test_goldens(name):
 
     z = load_grad_case(name)
     with spy() as calls:
-        hip = torch_form_grads(guided, z, torch.float32, DEV, fused_grad=True)
-    assert calls == {"hip": 1, "hip_grad": 1, "box_sum": 0}
-    t32 = torch_form_grads(guided, z, torch.float32, DEV)
+        hip = fixture_grads(guided, z, torch.float32, DEV, fused_grad=True)
+    assert calls == kernel_route(NEAREST)
+    t32 = fixture_grads(guided, z, torch.float32, DEV)
     for k, a, b in zip(("y", "x", "omega"), hip, t32):
         _report(f"{name} grad_{k}", a, b, torch.from_numpy(z["grad_" + k]).to(DEV))
 
@@ -79,58 +78,16 @@ def _inputs(shape_y, cx, seed):
 
 
 def test_need_combinations():
-    import phl
-
-    y, x, g = _inputs((2, 5, 37, 52), 3, 8)
-    eps = torch.tensor([1e-2, 2e-2, 3e-2], device=DEV)
-    kw = dict(subsample=2, scale=40.5, subtract_is_y=True)
-    full = phl.guided_filter_grad(y, x, g, 4, eps, need_y=True, need_x=True, need_eps=True, **kw)
-    assert all(t is not None and torch.isfinite(t).all() for t in full)
-    for ny in (False, True):
-        for nx in (False, True):
-            for ne in (False, True):
-                got = phl.guided_filter_grad(y, x, g, 4, eps, need_y=ny, need_x=nx, need_eps=ne, **kw)
-                for want, asked, have in zip(full, (ny, nx, ne), got):
-                    assert (have is None) if not asked else torch.equal(have, want), (ny, nx, ne)
-    assert tuple(t.shape for t in full) == (y.shape, x.shape, (3,))
+    util.check_need_combinations(NEAREST, *_inputs((2, 5, 37, 52), 3, 8), torch.tensor([1e-2, 2e-2, 3e-2], device=DEV))
 
 
 def test_deterministic():
-    import phl
-
-    y, x, g = _inputs((2, 7, 131, 257), 16, 4)
-    kw = dict(subsample=2, scale=840.5, subtract_is_y=True, need_y=True, need_x=True, need_eps=True)
-    a = phl.guided_filter_grad(y, x, g, 20, 1e-5, **kw)
-    b = phl.guided_filter_grad(y, x, g, 20, 1e-5, **kw)
-    for u, v in zip(a, b):
-        assert torch.equal(u, v)
+    util.check_deterministic(NEAREST, *_inputs((2, 7, 131, 257), 16, 4))
 
 
 def test_function_honours_needs_input_grad():
     """GuidedFilterFn asks guided_filter_grad only for the gradients autograd needs, in one call, and saves y, x, eps."""
-    import phl
-
-    y, x, g = _inputs((1, 3, 30, 44), 2, 9)
-    eps = torch.tensor([1e-2, 1e-2], device=DEV)
-    seen = []
-    real = phl.guided_filter_grad
-
-    def f(*a, **k):
-        seen.append((k["need_y"], k["need_x"], k["need_eps"]))
-        return real(*a, **k)
-
-    phl.guided_filter_grad = f
-    try:
-        for ny, nx, ne in ((True, False, False), (False, True, False), (False, False, True), (True, True, True)):
-            yy, xx, ee = y.clone().requires_grad_(ny), x.clone().requires_grad_(nx), eps.clone().requires_grad_(ne)
-            out = phl.GuidedFilterFn.apply(yy, xx, ee, 4, 2, 1.0, False)
-            assert len(out.grad_fn.saved_tensors) == 3
-            (out * g).sum().backward()
-            assert seen[-1] == (ny, nx, ne)
-            assert (yy.grad is not None) == ny and (xx.grad is not None) == nx and (ee.grad is not None) == ne
-    finally:
-        phl.guided_filter_grad = real
-    assert len(seen) == 4
+    util.check_function_honours_needs_input_grad(NEAREST, *_inputs((1, 3, 30, 44), 2, 9), torch.tensor([1e-2, 1e-2], device=DEV))
 
 
 def test_crfasrnn_trains_on_the_kernels():
@@ -155,11 +112,11 @@ def test_crfasrnn_trains_on_the_kernels():
     assert net.W.fused_grad
     with spy() as calls:
         hip = run(net, torch.float32)
-    assert calls == {"hip": niters, "hip_grad": niters, "box_sum": 0}
+    assert calls == kernel_route(NEAREST, niters)
     net.W.fused_grad = False
     with spy() as calls:
         t32 = run(net, torch.float32)
-    assert calls["hip"] == 0 and calls["hip_grad"] == 0 and calls["box_sum"] > 0
+    assert calls == torch_route(calls)
     want = run(net.double(), torch.float64)
     for k in hip:
         _report(f"crfasrnn grad_{k}", hip[k], t32[k], want[k], factor=2)
@@ -181,6 +138,6 @@ def test_shapes_the_kernels_do_not_take_run_the_torch_form():
             m = make(flag).to(DEV)
             with spy() as calls:
                 res.append(_grads(m, y, x, g, torch.float32))
-            assert calls["hip_grad"] == 0 and calls["hip"] == (attempts if flag else 0)
+            assert calls == route(nearest=attempts if flag else 0, box_sum=calls["box_sum"])
         for a, b in zip(*res):
             assert torch.equal(a, b)

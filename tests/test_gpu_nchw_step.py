@@ -10,7 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _guided_util import DEV, load_case
+from _guided_fixtures import load_case
+from _guided_util import DEV
 from _nchw_util import (B, LOGITS, PRODUCT, SOFTMAX, UNIFORM, both_loops, check_product, energy, inputs, launch_spy, loop_spy,
                         old_loop, on_float4_path, report_loop, shifted)
 

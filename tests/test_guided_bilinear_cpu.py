@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from _guided_bilinear_util import BIL_CASES, build_module, load_bilinear
+from _guided_fixtures import BIL_CASES, build_module, load_case
 
 BOUND = 1e-12
 
@@ -19,12 +19,12 @@ BOUND = 1e-12
 def test_bilinear_classes_match_reference_float64(name):
     from crf import guided
 
-    z = load_bilinear(name)
+    z = load_case(name)
     assert str(z["mode"]) == "bilinear"
     y, x = torch.from_numpy(z["y"]).double(), torch.from_numpy(z["x"]).double()
     with torch.no_grad():
-        out = build_module(guided, z, torch.float64, "cpu")(y, x)
-        flagged = build_module(guided, z, torch.float64, "cpu", fused_bilinear=True)(y, x)
+        out = build_module(guided, z, torch.float64, "cpu", "bilinear")(y, x)
+        flagged = build_module(guided, z, torch.float64, "cpu", "bilinear", fused_bilinear=True)(y, x)
     err = float(np.abs(out.numpy() - z["out"]).max())
     print(f"{name}: max |torch float64 - reference float64| = {err:.3e}, |out| <= {np.abs(z['out']).max():.4g}")
     assert err <= BOUND * np.abs(z["out"]).max(), (name, err)

@@ -1,6 +1,6 @@
 """The backward of the bilinear full-covariance guided filter without a GPU: the ``bilinear_full_grad`` keyword of the
 classes, of CRFasRNN and of the heads; the closed form that the kernels implement
-(_guided_bilinear_full_grad_util.closed_form_grads) against float64 autograd through the torch form of
+(_guided_util.closed_form_grads with ``mode='bilinear'``) against float64 autograd through the torch form of
 ``mode='bilinear', full_cov=True``; the argument checks of phl_guided_filter_bilinear_full_grad, which return before the
 first HIP call; the ABI row; and the chunk query that answers for the call.
 
@@ -13,8 +13,7 @@ import ctypes
 import pytest
 import torch
 
-from _guided_bilinear_full_grad_util import closed_form_grads, omega_grad
-from _guided_full_util import correlated_guide
+from _guided_util import closed_form_grads, correlated_guide, omega_grad
 from test_guided_full_grad_cpu import BOUND, EPS
 
 KW = dict(mode="bilinear", fused_bilinear=True, full_cov=True)
@@ -120,7 +119,7 @@ def _closed_form_case(kind, cx, H, W, r, s, seed):
     (m(y, x) * g).sum().backward()
     scale = 0.5 * (2 * r + 1) ** 2 if kind == "bga" else 1.0
     with torch.no_grad():
-        gy, gx, ge = closed_form_grads(y, x, g, r, m.eps, s, scale, kind == "bga")
+        gy, gx, ge = closed_form_grads(y, x, g, r, m.eps, s, scale, kind == "bga", "bilinear")
         got = (gy, gx, omega_grad(ge, m.omega))
     name = f"{kind} cx{cx} {H}x{W} r{r} s{s}"
     mag_y = float(y.grad.abs().max())

@@ -11,8 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from _guided_bilinear_grad_util import fixture_grads, load_bilinear_grad
-from _guided_bilinear_util import BIL_CASES
+from _guided_fixtures import BIL_CASES, fixture_grads, load_grad_case
 from test_guided_grad_cpu import BOUND
 
 
@@ -20,8 +19,8 @@ from test_guided_grad_cpu import BOUND
 def test_torch_form_gradients_match_reference_float64(name):
     from crf import guided
 
-    z = load_bilinear_grad(name)
-    got = fixture_grads(guided, z, torch.float64, "cpu")
+    z = load_grad_case(name)
+    got = fixture_grads(guided, z, torch.float64, "cpu", "bilinear")
     for k, mine in zip(("y", "x", "omega"), got):
         want = z["grad_" + k]
         mag = float(np.abs(want).max())

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from _guided_util import CASES, END_TO_END, build_module, load_case
+from _guided_fixtures import CASES, END_TO_END, build_module, load_case
 
 BOUND = 1e-12
 

@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 import torch
 
-from _guided_full_util import affine_inputs, brute_force, correlated_guide
-from _guided_util import build_module, load_case
+from _guided_fixtures import build_module, load_case
+from _guided_util import affine_inputs, brute_force, correlated_guide
 
 
 def _random(shape_y, cx, seed):

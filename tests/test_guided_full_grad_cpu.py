@@ -1,5 +1,5 @@
 """The backward of the full-covariance guided filter without a GPU: the closed form that the kernels implement
-(_guided_full_grad_util.closed_form_grads) against float64 autograd through the torch form, the argument checks of
+(_guided_util.closed_form_grads) against float64 autograd through the torch form, the argument checks of
 phl_guided_filter_full_grad and its chunk query (host code, before the first HIP call), and the ``full_cov_grad`` keyword
 on tensors the kernels do not take.
 
@@ -11,8 +11,7 @@ import ctypes
 import pytest
 import torch
 
-from _guided_full_grad_util import closed_form_grads, omega_grad
-from _guided_full_util import correlated_guide
+from _guided_util import closed_form_grads, correlated_guide, omega_grad
 
 BOUND = 1e-12
 EPS = (1e-2, 2e-2, 5e-3, 3e-2)

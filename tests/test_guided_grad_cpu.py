@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from _guided_grad_util import GRAD_CASES, load_grad_case, torch_form_grads
+from _guided_fixtures import GRAD_CASES, fixture_grads, load_grad_case
 
 BOUND = 1e-12
 
@@ -25,7 +25,7 @@ def test_torch_form_gradients_match_reference_float64(name):
     from crf import guided
 
     z = load_grad_case(name)
-    got = torch_form_grads(guided, z, torch.float64, "cpu")
+    got = fixture_grads(guided, z, torch.float64, "cpu")
     for k, mine in zip(("y", "x", "omega"), got):
         want = z["grad_" + k]
         mag = float(np.abs(want).max())
