@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 import phl
 from crf.gaussian_matrix import BatchedAdjacency, BatchedGuidedAdjacency  # noqa: F401  (crf_module.py:5)
+from crf.guided import _check_guided_keywords
 
 
 def gaussian_weights_u(f):
@@ -479,16 +480,11 @@ class CRFasRNN(nn.Module):
     bias-free 1x1 conv), a call that autograd does not record runs on the fused kernels -- _mean_field_nchw_fused for the
     lattice W, _mean_field_nchw_step for any other (PHL_NCHW_STEP=0 in the environment switches that one off) -- and one
     it records does so on request: ``fused_grad=True`` for the lattice W (_mean_field_nchw_grad; it also puts the guided
-    W itself on phl.GuidedFilterFn), ``fused_step=True`` for any other W.  ``full_cov=True`` gives the guided W the full
-    covariance of the guide channels (crf.guided; its recorded forward is the torch form, or with ``full_cov_grad=True``
-    phl.GuidedFilterFullFn, which trains that W on the library's kernels for up to four guide channels).  ``mode`` is the
-    guided W's interpolation (FastGuidedFilter); ``mode='bilinear'`` with ``fused_bilinear=True`` puts its unrecorded
-    forward on phl.guided_filter_bilinear, and with ``bilinear_grad=True`` as well its recorded forward on
-    phl.GuidedFilterBilinearFn, which trains that W on the library's kernels (the diagonal model); with ``full_cov=True``
-    the keyword for that is ``bilinear_full_grad=True`` (it needs ``fused_bilinear=True`` and ``full_cov=True``, and neither
-    ``full_cov_grad`` nor ``fused_grad``), and the recorded forward is phl.GuidedFilterBilinearFullFn, for up to four
-    guide channels.  Everything else -- CPU tensors, float64,
-    another Mu, a label count out of a route's range -- is the plain NCHW loop, with the bits it always had.
+    W itself on phl.GuidedFilterFn), ``fused_step=True`` for any other W.  ``full_cov``, ``full_cov_grad``, ``mode``,
+    ``fused_bilinear``, ``bilinear_grad`` and ``bilinear_full_grad`` are the guided W's own keywords, handed on to it:
+    crf.guided._guided_route holds the table of the routes they open, crf.guided._check_guided_keywords the rules between
+    them.  Everything else -- CPU tensors, float64, another Mu, a label count out of a route's range -- is the plain NCHW
+    loop, with the bits it always had.
     ``fused_unaries=True`` puts the unaries ``-logits * confidence`` of fp32 CUDA logits and a [B, 1, H, W] confidence
     (_confidence_routable) on phl.nchw_confidence_unaries, on every route and with the torch line's bits; recorded, on
     phl.NchwConfidenceUnaries, which keeps no ``-logits`` for the backward and sums the confidence's gradient in float64.
@@ -499,29 +495,20 @@ class CRFasRNN(nn.Module):
                  fused_grad=False, fused_step=False, full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False,
                  bilinear_grad=False, *, bilinear_full_grad=False, fused_unaries=False):
         super().__init__()
-        if lattice and full_cov:
-            raise ValueError("CRFasRNN: full_cov belongs to the guided-filter W; lattice=True has no covariance model")
-        if lattice and (mode != "nearest" or fused_bilinear or bilinear_grad or bilinear_full_grad):
-            raise ValueError("CRFasRNN: mode, fused_bilinear, bilinear_grad and bilinear_full_grad belong to the guided-filter W; "
-                             "lattice=True does not interpolate")
-        if bilinear_grad and not fused_bilinear:
-            raise ValueError("CRFasRNN: bilinear_grad=True is the backward of the fused_bilinear W: it needs fused_bilinear=True")
-        if bilinear_full_grad and not (fused_bilinear and full_cov):
-            raise ValueError("CRFasRNN: bilinear_full_grad=True is the backward of the fused_bilinear W with the full covariance: "
-                             "it needs fused_bilinear=True and full_cov=True")
-        if full_cov_grad and not full_cov:
-            raise ValueError("CRFasRNN: full_cov_grad=True is the backward of the full-covariance W: it needs full_cov=True")
+        guided = dict(full_cov=full_cov, full_cov_grad=full_cov_grad, mode=mode, fused_bilinear=fused_bilinear,
+                      bilinear_grad=bilinear_grad, bilinear_full_grad=bilinear_full_grad)
+        if lattice and (full_cov or mode != "nearest" or fused_bilinear or bilinear_grad or bilinear_full_grad):
+            raise ValueError("CRFasRNN: full_cov, mode, fused_bilinear, bilinear_grad and bilinear_full_grad belong to the "
+                             "guided-filter W; lattice=True has no covariance model and does not interpolate")
+        # what a keyword needs; every other rule between the guided W's keywords is raised by its constructor
+        _check_guided_keywords(**guided, needs_only=True)
         self.Mu, self.niters = mu_init, niters
         if notrain_mu:
             self.Mu.requires_grad_(False)
         # (fused_grad and the guided W: its box-window filter trains on phl.GuidedFilterFn; the Gaussian window has its own
         # backward, crf.guided.GaussianBlur, and ignores the flag)
         self.W = BatchedAdjacency() if lattice else BatchedGuidedAdjacency(gchannels, r, eps, gaussian=gaussian,
-                                                                             fused_grad=fused_grad and not gaussian,
-                                                                             full_cov=full_cov, full_cov_grad=full_cov_grad,
-                                                                             mode=mode, fused_bilinear=fused_bilinear,
-                                                                             bilinear_grad=bilinear_grad,
-                                                                             bilinear_full_grad=bilinear_full_grad)
+                                                                             fused_grad=fused_grad and not gaussian, **guided)
         self.fused_grad, self.fused_step, self.fused_unaries = fused_grad, fused_step, fused_unaries
 
     def forward(self, refs, logits, confidence=None, labels=None, energies=None):

@@ -3,39 +3,18 @@
 The reference's CRFasRNN defaults to a guided-filter W (crf/gaussian_matrix.py:161-287, crf_module.py:91).  The
 box-window classes (GuidedFilter, FastGuidedFilter, BatchedGuidedAdjacency, GuidedAdjacency) keep the reference's
 constructor / call signatures.  Their torch form below is pinned to the reference run in float64 with its own
-``mBoxFilter`` as the box sum (tests/golden/generate_guided.py, tests/test_guided_cpu.py).  A forward on fp32 CUDA tensors
-that autograd does not record runs on the HIP kernels instead (phl.guided_filter, phl_guided.hip: fp64 window sums over
-LDS tiles, the ``* k - src`` of the adjacency fused); CPU tensors, float64, training, ``mode != 'nearest'`` and
-``gaussian=True`` stay on the torch form.  Around such a forward, CRFasRNN runs the rest of its iteration -- Mu, the add and
-the softmax -- as one channel-major kernel (phl.nchw_softmax_compat, crf_module._mean_field_nchw_step), whichever
-form W itself takes.  Training leaves the torch form only on request: with the keyword ``fused_grad=True`` a forward
-that autograd records goes through phl.GuidedFilterFn, whose backward runs on the library's kernels as well
-(phl.guided_filter_grad: y, x and eps are all that is saved) and gives y, x and omega their gradients.
+``mBoxFilter`` as the box sum (tests/golden/generate_guided.py, tests/test_guided_cpu.py).  On fp32 CUDA tensors the
+forward runs on the HIP kernels instead (phl_guided.hip: fp64 window sums over LDS tiles, the ``* k - src`` of the
+adjacency fused), a forward that autograd records under a keyword only: _guided_route holds the table of the routes
+and their keywords, _check_guided_keywords the rules between the keywords.  Around such a forward, CRFasRNN runs the rest
+of its iteration -- Mu, the add and the softmax -- as one channel-major kernel (phl.nchw_softmax_compat,
+crf_module._mean_field_nchw_step), whichever form W itself takes.
 
 ``full_cov=True`` (keyword of all four classes) solves the guide channels together, A = cov_yx (cov_xx + diag(eps))^-1,
 the model the reference keeps as commented lines (gaussian_matrix.py:204, 209-212) beside a memory print: its torch form
-needs [n, h, w, cx, cx] tensors and a batched inverse.  Here the forward that autograd does not record runs on
-phl.guided_filter(full_cov=True) for up to phl.GUIDED_FULL_MAX_CX guide channels (the inverse once per image, in
-registers); a forward that autograd records runs the torch form of get_coeffs, ``fused_grad`` or not, as do more guide
-channels, CPU tensors, float64 and ``mode != 'nearest'``.  The Gaussian window does not take the flag.  The model trains
-on the kernels under a keyword of its own, ``full_cov_grad=True`` (it needs ``full_cov=True``, and no ``fused_grad``): a
-recorded forward is then phl.GuidedFilterFullFn, whose backward (phl.guided_filter_full_grad) recomputes the statistics
-and the inverse from y, x and eps and gives y, x and omega their gradients; what the kernels do not take stays on the
-torch form as before.
-
-``mode='bilinear'`` of FastGuidedFilter / BatchedGuidedAdjacency (coefficients solved on the bilinearly down-sampled
-images and interpolated back up) reaches the kernels under the keyword ``fused_bilinear=True``: a forward that autograd
-does not record is then phl.guided_filter_bilinear (either model; the taps are computed on the device).  Without the
-keyword, and for every recorded forward, the mode keeps the torch form -- unless the keyword ``bilinear_grad=True`` is
-given as well (it needs ``fused_bilinear=True``, and has the diagonal model only): a recorded forward is then
-phl.GuidedFilterBilinearFn, whose backward (phl.guided_filter_bilinear_grad) recomputes the model from y, x and eps and
-gives y, x and omega their gradients.  At subsample_ratio 1 that is phl.GuidedFilterFn; more than 16 guide channels, CPU
-tensors and float64 stay on the torch form.  The full-covariance model of the mode trains on the kernels under a keyword
-of its own, ``bilinear_full_grad=True`` (it needs ``fused_bilinear=True`` and ``full_cov=True``; ``full_cov_grad`` and
-``fused_grad`` are neither needed nor enough, and ``bilinear_grad=True`` with ``full_cov=True`` stays an error): a
-recorded forward is then phl.GuidedFilterBilinearFullFn, whose backward is phl.guided_filter_bilinear_full_grad; at
-subsample_ratio 1 it is phl.GuidedFilterFullFn, and more than phl.GUIDED_FULL_MAX_CX guide channels, CPU tensors and
-float64 stay on the torch form.
+needs [n, h, w, cx, cx] tensors and a batched inverse; the kernels take up to phl.GUIDED_FULL_MAX_CX guide channels (the
+inverse once per image, in registers).  ``mode='bilinear'`` of FastGuidedFilter / BatchedGuidedAdjacency solves the
+coefficients on the bilinearly down-sampled images and interpolates them back up (the taps are computed on the device).
 
 The learned-width variant, ``GuidedFilter(gaussian=True)``, needs the reference's own separable Gaussian
 (gaussian_matrix.py:86-156), which is provided here with the reference's semantics, quirks included:
@@ -161,6 +140,65 @@ def _box_sum(x, r):
     return c[:, :, k:, k:] - c[:, :, :-k, k:] - c[:, :, k:, :-k] + c[:, :, :-k, :-k]
 
 
+def _check_guided_keywords(*, gaussian=False, full_cov=False, full_cov_grad=False, fast=False, mode="nearest", fused_bilinear=False,
+                           bilinear_grad=False, bilinear_full_grad=False, needs_only=False):
+    """Every rule between the keywords of the guided-filter classes, in the order that decides which exception a call gets
+    that breaks two of them.  GuidedFilter hands over its keywords, FastGuidedFilter (``fast``) its own on top.  needs_only:
+    the "a needs b" rules alone, which CRFasRNN raises ahead of the window and the mode, and for a lattice W too."""
+    rest = not needs_only
+    if rest and gaussian and full_cov:
+        raise NotImplementedError("gaussian=True with full_cov=True: the full covariance has the box window only")
+    if full_cov_grad and not full_cov:
+        raise ValueError("full_cov_grad=True is the backward of the full-covariance model: it needs full_cov=True")
+    if rest and fast and gaussian:
+        # the reference's constructor reads self._r, which its gaussian form never sets (AttributeError, :238)
+        raise NotImplementedError("FastGuidedFilter(gaussian=True) does not construct in the reference either")
+    if rest and fused_bilinear and mode != "bilinear":
+        raise ValueError(f"fused_bilinear=True is the kernel route of mode='bilinear', got mode={mode!r}")
+    if bilinear_grad and not fused_bilinear:
+        raise ValueError("bilinear_grad=True is the backward of the fused_bilinear route: it needs fused_bilinear=True")
+    if rest and bilinear_grad and full_cov:
+        raise NotImplementedError("bilinear_grad=True with full_cov=True: this keyword has the diagonal model only "
+                                  "(the full covariance: bilinear_full_grad=True)")
+    if bilinear_full_grad and not (fused_bilinear and full_cov):
+        raise ValueError("bilinear_full_grad=True is the backward of the fused_bilinear route with the full covariance: it needs "
+                         "fused_bilinear=True and full_cov=True")
+
+
+def _guided_route(gaussian, mode, fused_bilinear, full_cov, subsample, operands_ok, recording, fused_grad, full_cov_grad,
+                  bilinear_grad, bilinear_full_grad):
+    """The route of one guided-filter call, from plain values: "torch", or (bilinear_kernels, full_cov, recorded) -- the key
+    of _KERNELS, and whether the forward is the route's Function (autograd records it) or its plain phl call.
+
+        mode      | further preconditions          | a recorded forward needs            | route
+        nearest   | not full_cov                   | fused_grad                          | (False, False, recording)
+        nearest   | full_cov                       | full_cov_grad                       | (False, True, recording)
+        bilinear  | fused_bilinear, subsample >= 2 | bilinear_grad or bilinear_full_grad | (True, full_cov, recording)
+        bilinear  | fused_bilinear, subsample 1    | bilinear_grad or bilinear_full_grad | (False, full_cov, recording)
+        anything else                                                                    | "torch"
+
+    Every row: the box window (not gaussian) and operands_ok -- y, x and omega fp32 CUDA, y and x 4-D.  Two asymmetries, on
+    purpose: either bilinear keyword admits a recorded bilinear forward whatever full_cov says (the constructor ties each
+    to its model: _check_guided_keywords), and ``fused_grad`` and ``full_cov_grad`` do not; and at subsample 1, where both
+    interpolations are the identity, the bilinear rows land on the nearest kernels and the nearest Function of their
+    model.  More than 16 guide channels (with full_cov: phl.GUIDED_FULL_MAX_CX) are the torch form too: _fused finds out."""
+    bilinear = mode == "bilinear" and fused_bilinear
+    if gaussian or not (mode == "nearest" or bilinear) or not operands_ok:
+        return "torch"
+    keyword = (bilinear_grad or bilinear_full_grad) if bilinear else (full_cov_grad if full_cov else fused_grad)
+    if recording and not keyword:
+        return "torch"
+    return bool(bilinear and subsample >= 2), bool(full_cov), bool(recording)
+
+
+# (bilinear_kernels, full_cov) -> the forward and the Function of a recorded one.  By their names in phl, which _fused looks
+# up at the call: what replaces a function of phl for a while (the call counters of the tests) is then what runs.
+_KERNELS = {(False, False): ("guided_filter", "GuidedFilterFn"),
+            (False, True): ("guided_filter", "GuidedFilterFullFn"),
+            (True, False): ("guided_filter_bilinear", "GuidedFilterBilinearFn"),
+            (True, True): ("guided_filter_bilinear", "GuidedFilterBilinearFullFn")}
+
+
 class GuidedFilter(nn.Module):
     """y filtered by guide x with per-guide-channel (diagonal covariance) linear model,
     eps = softplus(omega) as in the reference's parametrisation (:161-232); with ``full_cov`` one linear model over all
@@ -168,13 +206,10 @@ class GuidedFilter(nn.Module):
 
     def __init__(self, channels=1, r=20, eps=1e-8, gaussian=False, *, fused_grad=False, full_cov=False, full_cov_grad=False):
         super().__init__()
-        if gaussian and full_cov:
-            raise NotImplementedError("GuidedFilter(gaussian=True, full_cov=True): the full covariance has the box window only")
-        if full_cov_grad and not full_cov:
-            raise ValueError("full_cov_grad=True is the backward of the full-covariance model: it needs full_cov=True")
-        self.fused_grad = fused_grad
-        self.full_cov = full_cov
-        self.full_cov_grad = full_cov_grad
+        _check_guided_keywords(gaussian=gaussian, full_cov=full_cov, full_cov_grad=full_cov_grad)
+        self.fused_grad, self.full_cov, self.full_cov_grad = fused_grad, full_cov, full_cov_grad
+        # what FastGuidedFilter overwrites: _guided_route reads them of every class
+        self.subsample_ratio, self.mode, self.fused_bilinear, self.bilinear_grad, self.bilinear_full_grad = 1, "nearest", False, False, False
         self.omega = nn.Parameter(torch.log(torch.expm1(torch.tensor(float(eps)))).expand(channels).clone())
         if gaussian:
             # pinned to the reference (tests/golden/blur_guided.npz): its fp32 log(exp(eps) - 1), not expm1 (:166)
@@ -224,37 +259,20 @@ class GuidedFilter(nn.Module):
         return mean_A, mean(b)
 
     def _fused(self, y, x, subsample=1, scale=1.0, subtract=None):
-        """The forward on the HIP kernels, or None where the torch form has to run: a Gaussian window, an interpolation
-        other than nearest or FastGuidedFilter's ``mode='bilinear'`` with ``fused_bilinear=True``, tensors that are not
-        fp32 CUDA, a forward that autograd records without the keyword of its backward, or a shape the kernels do not take
-        (PHL_ERR_UNSUPPORTED: more than 16 guide channels, with ``full_cov`` more than phl.GUIDED_FULL_MAX_CX).  At
-        subsample 1 both interpolations are the identity, so bilinear takes the nearest kernels there.  A recorded forward
-        is the route's phl Function (eps = softplus(omega) keeps its graph); ``subtract`` is None or y itself."""
-        mode = getattr(self, "mode", "nearest")
-        bilinear = mode == "bilinear" and getattr(self, "fused_bilinear", False)
-        if self.gaussian or not (mode == "nearest" or bilinear) or not (_hip_ok(y) and _hip_ok(x)):
-            return None
-        if y.dim() != 4 or x.dim() != 4 or not _hip_ok(self.omega):
-            return None
+        """The forward on the HIP kernels, or None where the torch form has to run: where _guided_route says so, or at a
+        shape the kernels do not take (PHL_ERR_UNSUPPORTED).  A recorded forward is the route's phl Function (eps =
+        softplus(omega) keeps its graph); ``subtract`` is None or y itself."""
+        operands_ok = _hip_ok(y) and _hip_ok(x) and y.dim() == 4 and x.dim() == 4 and _hip_ok(self.omega)
         recording = torch.is_grad_enabled() and (y.requires_grad or x.requires_grad or self.omega.requires_grad)
-        # The keyword of a recorded forward: nearest has fused_grad (with full_cov: full_cov_grad); bilinear has its own
-        # two, whatever those say (the constructor admits bilinear_grad without full_cov only, bilinear_full_grad with).
-        if bilinear:
-            may_record = getattr(self, "bilinear_grad", False) or getattr(self, "bilinear_full_grad", False)
-        else:
-            may_record = self.full_cov_grad if self.full_cov else self.fused_grad
-        if recording and not may_record:
+        route = _guided_route(self.gaussian, self.mode, self.fused_bilinear, self.full_cov, subsample, operands_ok, recording,
+                              self.fused_grad, self.full_cov_grad, self.bilinear_grad, self.bilinear_full_grad)
+        if route == "torch":
             return None
-        full_cov = bool(self.full_cov)
-        # (bilinear kernels, full_cov) -> the forward and the Function of a recorded one
-        routes = {(False, False): (phl.guided_filter, phl.GuidedFilterFn),
-                  (False, True): (phl.guided_filter, phl.GuidedFilterFullFn),
-                  (True, False): (phl.guided_filter_bilinear, phl.GuidedFilterBilinearFn),
-                  (True, True): (phl.guided_filter_bilinear, phl.GuidedFilterBilinearFullFn)}
-        forward, recorded = routes[bool(bilinear and subsample >= 2), full_cov]
+        bilinear_kernels, full_cov, recorded = route
+        forward, function = (getattr(phl, name) for name in _KERNELS[bilinear_kernels, full_cov])
         try:
-            if recording:
-                return recorded.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
+            if recorded:
+                return function.apply(y, x, self.eps, self._r, subsample, scale, subtract is not None)
             return forward(y, x, self._r, self.eps, subsample=subsample, scale=scale, subtract=subtract, full_cov=full_cov)
         except phl.PhlError as e:
             if e.status != phl.ERR_UNSUPPORTED:
@@ -266,7 +284,7 @@ class GuidedFilter(nn.Module):
         return (mean_A * x[:, None]).sum(2) + mean_b
 
     def forward(self, y, x):
-        out = self._fused(y, x, subsample=getattr(self, "subsample_ratio", 1))
+        out = self._fused(y, x, subsample=self.subsample_ratio)
         return out if out is not None else self._torch_forward(y, x)
 
 
@@ -276,24 +294,10 @@ class FastGuidedFilter(GuidedFilter):
     def __init__(self, *args, subsample_ratio=2, mode="nearest", fused_bilinear=False, bilinear_grad=False,
                  bilinear_full_grad=False, **kwargs):
         super().__init__(*args, **kwargs)
-        if self.gaussian:
-            # the reference's constructor reads self._r, which its gaussian form never sets (AttributeError, :238)
-            raise NotImplementedError("FastGuidedFilter(gaussian=True) does not construct in the reference either")
-        if fused_bilinear and mode != "bilinear":
-            raise ValueError(f"fused_bilinear=True is the kernel route of mode='bilinear', got mode={mode!r}")
-        if bilinear_grad and not fused_bilinear:
-            raise ValueError("bilinear_grad=True is the backward of the fused_bilinear route: it needs fused_bilinear=True")
-        if bilinear_grad and self.full_cov:
-            raise NotImplementedError("bilinear_grad=True with full_cov=True: this keyword has the diagonal model only "
-                                      "(the full covariance: bilinear_full_grad=True)")
-        if bilinear_full_grad and not (fused_bilinear and self.full_cov):
-            raise ValueError("bilinear_full_grad=True is the backward of the fused_bilinear route with the full covariance: it needs "
-                             "fused_bilinear=True and full_cov=True")
-        self.subsample_ratio = subsample_ratio
-        self.mode = mode
-        self.fused_bilinear = fused_bilinear
-        self.bilinear_grad = bilinear_grad
-        self.bilinear_full_grad = bilinear_full_grad
+        _check_guided_keywords(gaussian=self.gaussian, full_cov=self.full_cov, fast=True, mode=mode, fused_bilinear=fused_bilinear,
+                               bilinear_grad=bilinear_grad, bilinear_full_grad=bilinear_full_grad)
+        self.subsample_ratio, self.mode, self.fused_bilinear = subsample_ratio, mode, fused_bilinear
+        self.bilinear_grad, self.bilinear_full_grad = bilinear_grad, bilinear_full_grad
 
     def _window(self):
         return self._r // self.subsample_ratio

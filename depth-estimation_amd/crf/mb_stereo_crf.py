@@ -2,12 +2,9 @@
 reference's crf/mb_stereo_crf.py (:62-66 logits2average_depth, :68-102 CRFdepthRefiner and
 CRFwUncertainty, :138-163 CRFdepthUpsampler).  API surface only: the reference instantiates them
 with the guided-filter W (out of the lattice scope); ``lattice=True`` switches W to the
-permutohedral BatchedAdjacency, ``full_cov=True`` gives the guided-filter W the full covariance of the guide channels
-(crf.guided; on the kernels for up to four of them, the upsampler's RGB guide among those; ``full_cov_grad=True`` also
-trains it on them), ``mode='bilinear'`` interpolates the guided W's coefficients instead of repeating them over blocks
-(``fused_bilinear=True``: its unrecorded forward on phl.guided_filter_bilinear; ``bilinear_grad=True`` as well: its
-recorded forward on phl.GuidedFilterBilinearFn, which trains it on the kernels; with ``full_cov=True`` that keyword is
-``bilinear_full_grad=True`` and the Function phl.GuidedFilterBilinearFullFn).  The trainer classes (:14-60, :105-136) and ``__main__`` need the
+permutohedral BatchedAdjacency.  The other engine keywords (_ENGINE_KEYWORDS) go to CRFasRNN as they are; those of the
+guided-filter W have their table in crf.guided._guided_route (``full_cov=True`` takes up to four guide channels on the
+kernels, the upsampler's RGB guide among those).  The trainer classes (:14-60, :105-136) and ``__main__`` need the
 un-vendored ``oil`` package and Middlebury data and are not mirrored."""
 import os
 
@@ -52,15 +49,23 @@ class _CoordConv(nn.Module):
         return self.conv(torch.cat([x, ii, jj], dim=1))
 
 
+# The keywords that the heads hand on to CRFasRNN as they are: its W and its routes (crf_module.CRFasRNN, crf.guided).
+_ENGINE_KEYWORDS = ("lattice", "fused_grad", "fused_step", "full_cov", "full_cov_grad", "mode", "fused_bilinear", "bilinear_grad",
+                    "bilinear_full_grad", "fused_unaries")
+
+
+def _engine(args):
+    """The CRFasRNN of a head, from the arguments of the head's constructor (its ``locals()``)."""
+    return CRFasRNN(charb(args["gamma"]), niters=args["niters"], r=args["r"], eps=args["eps"], gchannels=args["d_guide"],
+                    **{k: args[k] for k in _ENGINE_KEYWORDS})
+
+
 class CRFdepthRefiner(nn.Module):
     def __init__(self, d_in=64, d_guide=16, r=15, niters=2, eps=1e-2, gamma=.05, lattice=False, fused_grad=False, fused_step=False,
                  full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False, *,
                  bilinear_full_grad=False, fused_unaries=False):
         super().__init__()
-        self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
-                            fused_grad=fused_grad, fused_step=fused_step, full_cov=full_cov, full_cov_grad=full_cov_grad,
-                            mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad,
-                            bilinear_full_grad=bilinear_full_grad, fused_unaries=fused_unaries)
+        self.CRF = _engine(locals())
         self.projection = nn.Conv2d(d_in, d_guide - 3, kernel_size=1)
 
     def _guide(self, imgrgb, features):
@@ -104,10 +109,7 @@ class CRFdepthUpsampler(nn.Module):
                  full_cov=False, full_cov_grad=False, mode="nearest", fused_bilinear=False, bilinear_grad=False, *,
                  bilinear_full_grad=False, fused_unaries=False):
         super().__init__()
-        self.CRF = CRFasRNN(charb(gamma), niters=niters, r=r, eps=eps, gchannels=d_guide, lattice=lattice,
-                            fused_grad=fused_grad, fused_step=fused_step, full_cov=full_cov, full_cov_grad=full_cov_grad,
-                            mode=mode, fused_bilinear=fused_bilinear, bilinear_grad=bilinear_grad,
-                            bilinear_full_grad=bilinear_full_grad, fused_unaries=fused_unaries)
+        self.CRF = _engine(locals())
 
     def forward(self, inputs):
         """fp32 CUDA inputs (_scalar_unaries_routable) get E0 and the labels from phl.nchw_scalar_unaries -- two launches,
